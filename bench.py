@@ -7,8 +7,13 @@ clip + Adam) of the OFASys GeneralistModel on MI355X, BASELINE.json configs[1] (
 
 Contract (driver):  python bench.py --gpus N --steps K --warmup W   (N>1 via torch.distributed.run, one rank per GPU).
 Prints ONE JSON line on rank 0.  `value` is whole-job tokens/s (non-pad encoder + decoder positions, SURVEY.md
-section 8d); `roofline` prices the dominant kernel (the bf16 MFMA GEMM) against the 2.5 PFLOP/s dense bf16 peak;
-`cpu_baseline` times the CPU oracle restatement (oracle/restate.py) on a bounded sample of the same workload.
+section 8d), `ms_per_step` the time of one of the K timed steps.  A plain run sets up, warms up, times the K steps and prints
+the line; its `roofline` prices the step's algorithmic flops against the 2.5 PFLOP/s dense bf16 peak.
+  --full              also measures what takes runs of its own: the dominant kernel (the bf16 MFMA GEMM) bracketed in an
+                      instrumented step (`roofline.achieved` / `frac` and the rocprof figures), the data-parallel exchange
+                      (`dp`, N > 1) and `cpu_baseline`, the CPU oracle restatement (oracle/restate.py) timed on a bounded
+                      sample of the same workload.
+  --dump-outputs DIR  writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -244,7 +249,7 @@ def cpu_baseline(args, model, d):
     bounded size, forward + CE + backward."""
     from oracle import restate
     from oracle.restate import OConfig, OSlot
-    cores = min(os.cpu_count() or 1, 64)
+    cores = int(os.environ.get("OMP_NUM_THREADS") or 0) or min(os.cpu_count() or 1, 64)     # OMP_NUM_THREADS: the CPUs this process may use
     torch.set_num_threads(cores)
     cfgm = model.cfg
     dims = dict(embed_dim=cfgm.encoder.embed_dim, ffn_dim=cfgm.encoder.ffn_embed_dim, heads=cfgm.encoder.attention_heads,
@@ -323,6 +328,29 @@ def source_id():
         return sid(here)
     finally:
         sys.path.pop(0)
+
+
+DUMP_SAMPLE = 1 << 21          # elements of the parameter / gradient arenas written by --dump-outputs (8 MB each as float32)
+
+
+def dump_outputs(trainer, out_dir):
+    """What a caller of the timed path receives from its last step, as out_dir/<name>.npy: TrainStep.train_step's result
+    (stats = [sample_size, loss_sum, ntokens] float64, gnorm, skipped = [skip flag, skipped updates], loss_scale under fp16) and
+    the arenas it updates in place -- the fp32 master weights after the Adam update and the step's gradient -- each as the same
+    fixed, seeded sample of DUMP_SAMPLE positions (the whole arena when it is smaller)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().cpu() for k, v in trainer.last.items()}
+    n = trainer.master.numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(20241016)).sort().values
+        idx = idx.to(trainer.master.device)
+    for name, arena in (("master_params_sample", trainer.master), ("grads_sample", trainer.fp.grad)):
+        arrays[name] = (arena if idx is None else arena[idx]).float().cpu()
+    for name, t in arrays.items():
+        a = t.numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
 
 
 PROFILE_ROUNDS = ("round6", "round5", "round4", "round3", "round2", "round1")
@@ -474,10 +502,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--arch", default=None, help="model size (default: base; large for cfg5)")
     ap.add_argument("--batch", type=int, default=None, help="per-GPU (micro-)batch (default 32; 8 for cfg3; 4 for cfg4 / cfg5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
     ap.add_argument("--cpu-batch", type=int, default=0, help="CPU-leg batch (0: per workload, CPU_SAMPLE)")
     ap.add_argument("--cpu-steps", type=int, default=0, help="CPU-leg timed steps (0: per workload)")
-    ap.add_argument("--profile-gemm", type=int, default=1, help="instrumented steps after the timed region")
+    ap.add_argument("--profile-gemm", type=int, default=1, help="--full: instrumented steps after the timed region")
     ap.add_argument("--profile-park-cycles", type=float, default=1.5e8,
                     help="spin-kernel cycles in front of the instrumented step (the host must finish enqueueing before the GPU starts)")
     ap.add_argument("--workload", default="cfg2", choices=list(WORKLOADS),
@@ -499,7 +527,14 @@ def main():
                          "(its own default trainer precision)")
     ap.add_argument("--launch-check", action="store_true",
                     help="launcher plumbing only: init the process group, one all-reduce, print the JSON skeleton (runs without a GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline: the instrumented GEMM step (--profile-gemm), the data-parallel "
+                         "exchange timings (N > 1) and the CPU oracle baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     _HALF_NOW[0] = HALF[args.dtype]
     if args.batch is None:
         args.batch = {"cfg4": 4, "cfg5": 4, "cfg3": 8}.get(args.workload, 32)
@@ -606,11 +641,13 @@ def main():
         if "graphs" in e:
             graph_mode = {1: "one hipGraph (collectives captured)" if world > 1 else "one hipGraph", 2: "two hipGraphs + eager all-reduce"}[len(e["graphs"])]
     trainer.check()
+    if args.dump_outputs and rank == 0:             # before --full's extra steps change the weights
+        dump_outputs(trainer, args.dump_outputs)
 
     # data-parallel exchange, measured on every rank (the collectives need all of them): each bucket's all-reduce ALONE, and how
     # long the compute stream still waits for the exchange once backward has been enqueued in overlapped eager steps
     dp = None
-    if world > 1:
+    if world > 1 and args.full:
         red = trainer.reducer
         alone = red.time_buckets_alone()
         red.profile, red.exposed_events = True, []
@@ -638,7 +675,7 @@ def main():
 
     # dominant kernel: every MFMA GEMM launch of one step bracketed by HIP events on the launch stream
     prof = None
-    if args.profile_gemm > 0:
+    if args.full and args.profile_gemm > 0:
         K.gemm_profile_begin()
         for _ in range(args.profile_gemm):
             # an eager step is host-bound (~600 launches): park the stream behind a spin kernel first so that every launch and its
@@ -758,7 +795,7 @@ def main():
         }
         if dp is not None:
             out["dp"] = dp
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, model, d)
         print(json.dumps(out))
     if world > 1:

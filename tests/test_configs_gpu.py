@@ -444,7 +444,7 @@ def test_bench_two_ranks_end_to_end_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["OFA_BENCH_DEVICE"] = "0"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--batch", "4", "--steps", "4",
-                        "--warmup", "1", "--no-cpu-baseline", "--profile-gemm", "0"], env=env, capture_output=True, text=True, timeout=900)
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--profile-gemm", "0"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -455,6 +455,35 @@ def test_bench_two_ranks_end_to_end_on_one_gpu():
     dp = out["dp"]                                                   # the exchange describes itself
     assert dp["world_size"] == 2 and dp["backend"] == "gloo" and dp["buckets"] == len(dp["bucket_bytes"]) == len(dp["bucket_allreduce_ms_alone"])
     assert dp["launch_order"] == list(range(dp["buckets"])) and dp["exposed_wait_ms_per_step"] is not None
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run prints the headline line without the --full measurements, and --dump-outputs writes the last timed
+    step's results (float32 / float64, under 64 MB); two runs with the same arguments see the same inputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for i in range(2):
+        out_dir = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch", "4", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["dtype"] == "bf16"
+        assert out["unit"] == "tokens/s" and out["higher_is_better"] is True
+        assert "cpu_baseline" not in out and "launches_per_step" not in out["roofline"]
+        files = {f: np.load(out_dir / f) for f in sorted(os.listdir(out_dir))}
+        assert set(files) == {"stats.npy", "gnorm.npy", "skipped.npy", "master_params_sample.npy", "grads_sample.npy"}, files.keys()
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert files["stats.npy"][0] > 0 and files["skipped.npy"][0] == 0 and np.abs(files["grads_sample.npy"]).max() > 0
+        dumps.append(files)
+    assert dumps[0]["stats.npy"][0] == dumps[1]["stats.npy"][0] and dumps[0]["stats.npy"][2] == dumps[1]["stats.npy"][2]
 
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs (RCCL over xGMI); the one-GPU lease runs the gloo variant above")
@@ -469,7 +498,7 @@ def test_bench_two_ranks_rccl_full_graph():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--batch", "8", "--steps", "6", "--warmup", "2",
-                        "--no-cpu-baseline", "--profile-gemm", "0"], env=env, capture_output=True, text=True, timeout=1200)
+                        "--full", "--no-cpu-baseline", "--profile-gemm", "0"], env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert out["n_gpus"] == 2 and out["config"]["step_mode"] == "one hipGraph (collectives captured)"

@@ -39,13 +39,13 @@ cd $R
 python tools/build_id.py > $O/round${N}_source_id.txt
 # the bench lines below quote the kernel-trace / PMC summaries of THIS run (bench.py reads them from profiles/)
 cp $O/round${N}_rocprof_kernel_stats.json $O/round${N}_rocprof_cfg2b_kernel_stats.json $O/round${N}_rocprof_cfg4_kernel_stats.json $O/round${N}_rocprof_cfg3_kernel_stats.json $O/round${N}_rocprof_cfg5_kernel_stats.json $O/round${N}_pmc_traffic.json $O/round${N}_pmc_traffic_cfg2b.json $R/profiles/
-T 600 python bench.py > $O/round${N}_bench.json 2> $O/bench_run.log
+T 600 python bench.py --full > $O/round${N}_bench.json 2> $O/bench_run.log
 tail -c 1200 $O/round${N}_bench.json
-T 600 python bench.py --workload cfg2b --steps 30 --warmup 5 > $O/round${N}_bench_cfg2b.json 2> $O/bench_cfg2b_run.log
-T 600 python bench.py --workload cfg4 --steps 30 --warmup 5 > $O/round${N}_bench_cfg4.json 2> $O/bench_cfg4_run.log
-T 600 python bench.py --workload cfg3 --steps 30 --warmup 5 > $O/round${N}_bench_cfg3.json 2> $O/bench_cfg3_run.log
-T 600 python bench.py --workload cfg5 --steps 10 --warmup 3 > $O/round${N}_bench_cfg5.json 2> $O/bench_cfg5_run.log
-T 600 python bench.py --workload cfg2b --no-pack --steps 30 --warmup 5 --no-cpu-baseline > $O/round${N}_bench_cfg2b_padded.json 2> $O/bench_cfg2b_padded_run.log
+T 600 python bench.py --full --workload cfg2b --steps 30 --warmup 5 > $O/round${N}_bench_cfg2b.json 2> $O/bench_cfg2b_run.log
+T 600 python bench.py --full --workload cfg4 --steps 30 --warmup 5 > $O/round${N}_bench_cfg4.json 2> $O/bench_cfg4_run.log
+T 600 python bench.py --full --workload cfg3 --steps 30 --warmup 5 > $O/round${N}_bench_cfg3.json 2> $O/bench_cfg3_run.log
+T 600 python bench.py --full --workload cfg5 --steps 10 --warmup 3 > $O/round${N}_bench_cfg5.json 2> $O/bench_cfg5_run.log
+T 600 python bench.py --full --workload cfg2b --no-pack --steps 30 --warmup 5 --no-cpu-baseline > $O/round${N}_bench_cfg2b_padded.json 2> $O/bench_cfg2b_padded_run.log
 T 300 python tools/attn_bench.py > $O/round${N}_attn_bench.txt 2>&1
 for w in cfg2b cfg4 dec cross; do T 300 python tools/attn_sbias_bench.py $w 2>&1 | grep -v amdgpu.ids >> $O/round${N}_attn_sbias_bench.txt; done
 for w in cfg2 cfg2b cfg4; do T 300 python tools/native_glue_trace.py $w 2>&1 | grep -v amdgpu.ids > $O/round${N}_native_glue_$w.txt; done

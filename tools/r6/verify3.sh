@@ -6,7 +6,7 @@ PAT="fault|round|TOTAL|COMPLETE|Error" run v_audit_cfg2b python tools/capture_au
 PAT="fault|round|TOTAL|COMPLETE|Error" run v_audit_cfg3 python tools/capture_audit.py --workload cfg3 --stress
 T=1500 PAT="MEASURED|passed|failed|Error|error" TAIL=40 run v_newtests python -m pytest tests/test_bench_parity_gpu.py tests/test_packing_gpu.py -q -s -x -k "cfg2b or behind_lse"
 for w in cfg2 cfg2b cfg3 cfg4 cfg5; do
-  timeout -k 10 420 python bench.py --workload $w --steps 20 --warmup 5 --no-cpu-baseline > $O/q_$w.json 2> $O/q_$w.err
+  timeout -k 10 420 python bench.py --full --workload $w --steps 20 --warmup 5 --no-cpu-baseline > $O/q_$w.json 2> $O/q_$w.err
   python - <<PY
 import json
 try:
