@@ -541,6 +541,31 @@ int ofa_layernorm_bwd_slots(int64_t rows, int cols, int dtype, int gelu);
 int ofa_colsum_slots(int64_t rows);
 int ofa_gemm_splits(int M, int N, int K, int transA, int transB, int batch, int flags, int dtype, int64_t ws_bytes);
 
+/* ---- beam search (csrc/beam_search.hip): the policy of SequenceGenerator.generate / BeamSearch.step
+ * (generator/sequence_generator.py:283-492, finalize_hypos :530-627; utils/search.py:107-142) in two launches per decoding
+ * step that take fixed device addresses and the step number only, so they are recorded inside the per-step hipGraph.
+ * Rows are bsz sentences x K beams (K <= 16, K * V < 2^24).  ws: ofa_beam_ws_bytes(rows, V, K) bytes, written by
+ * ofa_beam_topk and read by ofa_beam_select of the same step.
+ * ofa_beam_topk: one read of logits [rows, ld] (V valid columns, fp32 / bf16 / fp16): the fp32 log-softmax normaliser of
+ * x / temperature with constraint_range ([4, cstart) and [cend, V) -inf, cstart < 0: off; :724, 742-745) applied first, then
+ * the reference's post-normaliser masks in order (EOS at step < min_len, NaN, PAD, unk_penalty, step >= max_len, n-gram bans over
+ * tokens[row, 0..step] when ngram > 0; :296-343) and each row's best 2K candidates per 4096-column chunk.  done: optional int
+ * [bsz] -- rows of finished sentences are skipped.
+ * ofa_beam_select: one workgroup per sentence.  tokens int64 [rows, tok_ld] (tok_cap valid columns; column 0 = BOS) and scores
+ * fp32 [rows, score_ld] are the histories, gathered in place; the next token goes to column step + 1 and the cumulative score
+ * to column step; reorder int64 [rows] receives the source row of every row (the identity for a finished sentence); ignore int
+ * [bsz, K] is cands_to_ignore; done int [bsz]; nfin int [1] counts finished sentences.  Finalised hypotheses: fin_tok int64
+ * [bsz, K, fin_ld] (tokens 1..step, then EOS), fin_pos fp32 [bsz, K, fin_ld] (positional scores), fin_score fp32 [bsz, K]
+ * (divided by (step + 1)^len_penalty when normalize), fin_len / fin_cnt int [bsz, K] / [bsz]. */
+int64_t ofa_beam_ws_bytes(int rows, int V, int K);
+int ofa_beam_topk(const void* logits, int64_t ld, int rows, int V, int K, float temperature, int cstart, int cend, int step,
+                  int min_len, int max_len, int pad, int unk, int eos, float unk_penalty, int ngram, const int64_t* tokens,
+                  int64_t tok_ld, const int* done, void* ws, int dtype, void* stream);
+int ofa_beam_select(const void* ws, int bsz, int K, int V, int step, int max_len, int eos, int unk, float unk_penalty,
+                    int normalize, float len_penalty, int64_t* tokens, int64_t tok_ld, int tok_cap, float* scores,
+                    int64_t score_ld, int* ignore, int* done, int* nfin, int64_t* reorder, int64_t* fin_tok, float* fin_pos,
+                    int64_t fin_ld, float* fin_score, int* fin_len, int* fin_cnt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,13 +6,24 @@ One decoding step of OFA-base is ~130 small kernels; launched eagerly from Pytho
 are decoded (host-bound).  `StepDecoder` keeps every buffer a step touches at a fixed address -- target tokens, encoder
 output, the KV caches at their final capacity -- and records ONE hipGraph PER STEP LENGTH (the prefix length and the cache
 length are kernel arguments, so each length is its own graph; a sequence of T steps replays T graphs).  Graphs are keyed by
-(rows, source length, step) and reused by every later batch of the same shape.  The beam-search policy itself (scoring,
-length penalty, finalisation) stays out of scope; `greedy` below is the minimal loop used by tests and benchmarks.
+(rows, source length, step) and reused by every later batch of the same shape.  `greedy` below is the minimal loop used
+by tests and benchmarks.
+
+`SequenceGenerator` is the reference's beam search (generator/sequence_generator.py:66-627 with utils/search.py BeamSearch)
+on top of `StepDecoder`: the policy of a step -- normaliser, masks, n-gram bans, top 2K, finalisation, active selection,
+history gather -- is two HIP launches (csrc/beam_search.hip) recorded with the decoder and the self-attention cache reorder
+into the step's graph, so a step has no host synchronisation.  Differences from the reference ("Generation
+(beam search)"):
+the row count stays fixed (finished sentences are masked, not removed; rows are independent, so results are the same),
+the returned tensors are on the CPU, and `attention` is empty (the decoder returns no alignment).
 """
-from typing import Dict, List, Optional
+import math
+from dataclasses import dataclass
+from typing import Any, Dict, List, Optional
 
 import torch
 
+from . import kernels as K
 from .preprocessor import ModalityType, Slot
 
 
@@ -24,6 +35,8 @@ class StepDecoder:
         self._graphs: Dict[int, tuple] = {}
         self._pool = None
         self._seq = 0
+        self._ws: Dict[tuple, torch.Tensor] = {}          # scratch buffers allocated inside this decoder's captures (see step)
+        self._ws_keep: List[torch.Tensor] = []
 
     # ------------------------------------------------------------------ sequence state
     def begin(self, src_slots: List[Slot], beam_order: Optional[torch.Tensor] = None):
@@ -46,6 +59,7 @@ class StepDecoder:
         shape = (out.shape[1], out.shape[0], out.dtype, fingerprint)
         if shape != self._shape:                          # another batch shape: new buffers, new graphs
             self._shape, self._graphs, self._pool, self._seq = shape, {}, None, 0
+            self._ws, self._ws_keep = {}, []
             self.enc = {k: [t.clone() if torch.is_tensor(t) else t for t in v] if isinstance(v, list) else v for k, v in enc.items()}
             self.tokens = torch.zeros(shape[0], self.max_len, dtype=torch.long, device=out.device)
             self.inc = {"__capacity__": self.max_len, "__static__": True}
@@ -63,12 +77,15 @@ class StepDecoder:
         self.t = 0
         return self
 
-    def step(self, next_tokens: torch.Tensor) -> torch.Tensor:
-        """Append one token per row and return the logits of that position: [rows, V]."""
+    def step(self, next_tokens: Optional[torch.Tensor], post=None) -> torch.Tensor:
+        """Append one token per row and return the logits of that position: [rows, V].  next_tokens None: column t of
+        `tokens` was already written on the device (beam search).  post(logits, t): device work recorded into the same
+        step graph after the decoder (the beam-search kernels and the cache reorder)."""
         t = self.t
         if t >= self.max_len:
             raise ValueError(f"StepDecoder: max_len={self.max_len} exceeded")
-        self.tokens[:, t].copy_(next_tokens.reshape(-1))
+        if next_tokens is not None:
+            self.tokens[:, t].copy_(next_tokens.reshape(-1))
         graphed = self.use_graph and self._seq >= self.warmup_sequences
         if graphed and t in self._graphs:
             g, logits = self._graphs[t]
@@ -77,8 +94,23 @@ class StepDecoder:
         elif graphed:
             g = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
-            with torch.no_grad(), torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
-                logits = self._run(t)
+            # kernels.workspace() caches scratch per stream, and every capture runs on torch's one default capture stream: a
+            # buffer allocated inside this capture lives in THIS decoder's private pool.  Left in the shared cache, a later
+            # capture (a TrainStep) would address it without owning it and fault once it is dropped and the pool released.  The
+            # decoder's captures therefore see only their own scratch, kept alive here for as long as its graphs.
+            saved = dict(K._ws_cache)
+            K._ws_cache.clear()
+            K._ws_cache.update(self._ws)
+            try:
+                with torch.no_grad(), torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
+                    logits = self._run(t)
+                    if post is not None:
+                        post(logits, t)
+            finally:
+                self._ws = dict(K._ws_cache)
+                self._ws_keep.extend(v for v in self._ws.values() if all(v is not w for w in self._ws_keep))
+                K._ws_cache.clear()
+                K._ws_cache.update(saved)
             if self._pool is None:
                 self._pool = g.pool()
             self._graphs[t] = (g, logits)
@@ -86,6 +118,8 @@ class StepDecoder:
         else:
             with torch.no_grad():
                 logits = self._run(t)
+                if post is not None:
+                    post(logits, t)
         self.t = t + 1
         return logits
 
@@ -101,13 +135,19 @@ class StepDecoder:
                 c["len"] = n
         return n
 
-    def reorder(self, new_order: torch.Tensor):
-        """Beam reorder between steps: caches, encoder output and the token prefix follow `new_order` (in place)."""
+    def reorder(self, new_order: torch.Tensor, caches_only: bool = False):
+        """Beam reorder between steps: caches, encoder output and the token prefix follow `new_order` (in place).
+        caches_only: the self-attention caches alone -- beams that move within their sentence (beam search) share the encoder
+        output and the cross-attention cache, and the token history is gathered by the beam kernels.  `new_order` is read on
+        the device only (no host synchronisation), so the call can be recorded into a step graph with the index at a fixed
+        address."""
         m = self.model
         if new_order.numel() != self._shape[0]:
             raise ValueError("StepDecoder.reorder keeps the row count (the buffers of the captured steps are fixed): "
                              f"got {new_order.numel()} indices for {self._shape[0]} rows")
         m.decoder.reorder_incremental_state_scripting(self.inc, new_order)
+        if caches_only:
+            return
         enc = m.encoder.reorder_encoder_out(self.enc, new_order)
         for k, v in enc.items():
             if isinstance(v, list):
@@ -129,3 +169,173 @@ class StepDecoder:
             nxt = logits.argmax(-1)
         toks = torch.cat([self.tokens[:, :steps], nxt.view(-1, 1)], 1)
         return toks, torch.stack(logits_all)
+
+
+# ---------------------------------------------------------------------------------------------------------------- beam search
+@dataclass
+class SequenceGeneratorOutput:
+    """One finalised hypothesis (generator/sequence_generator.py:25-40): tokens 1..n ending in EOS, its (length-normalised)
+    score, the positional scores, and the decoded forms a task fills in."""
+    tokens: torch.LongTensor
+    score: torch.FloatTensor
+    attention: torch.FloatTensor
+    positional_scores: torch.FloatTensor
+    text: Optional[str] = None
+    image: Any = None
+    box: Optional[torch.Tensor] = None
+
+
+class SequenceGenerator:
+    """Beam search with the reference's constructor and defaults (generator/sequence_generator.py:66-159).  Unsupported
+    options of the reference raise NotImplementedError: other search strategies, an LM, a constraint trie, match_source_len,
+    prefix tokens and lexical constraints."""
+
+    MAX_BEAM = 16
+
+    def __init__(self, tgt_dict, beam_size: int = 1, return_n_best: int = -1, max_len_a: int = 0, max_len_b: int = 200,
+                 max_len: int = 256, min_len: int = 1, normalize_scores: bool = True, len_penalty: float = 1.0,
+                 unk_penalty: float = 0.0, temperature: float = 1.0, match_source_len: bool = False,
+                 no_repeat_ngram_size: int = 0, search_strategy=None, lm_model=None, lm_weight: float = 1.0,
+                 constraint_trie=None, constraint_range: Optional[str] = None, use_graph: bool = True, **unused_kwargs):
+        if search_strategy is not None:
+            raise NotImplementedError("SequenceGenerator: only plain beam search is implemented (search_strategy must be None; "
+                                      "sampling, diverse beam and constrained search are not)")
+        if lm_model is not None:
+            raise NotImplementedError("SequenceGenerator: LM fusion (lm_model) is not implemented")
+        if constraint_trie is not None:
+            raise NotImplementedError("SequenceGenerator: constraint_trie (a host-side trie walk per step) is not implemented; "
+                                      "constraint_range is")
+        if match_source_len:
+            raise NotImplementedError("SequenceGenerator: match_source_len is not implemented")
+        if not temperature > 0:
+            raise ValueError("--temperature must be greater than 0")
+        self.pad, self.unk, self.bos, self.eos = tgt_dict.pad(), tgt_dict.unk(), tgt_dict.bos(), tgt_dict.eos()
+        self.vocab_size = len(tgt_dict)
+        self.beam_size = min(beam_size, self.vocab_size - 1)
+        if self.beam_size > self.MAX_BEAM:
+            raise NotImplementedError(f"SequenceGenerator: beam_size {beam_size} > {self.MAX_BEAM} (csrc/beam_search.hip)")
+        if return_n_best == -1:
+            return_n_best = self.beam_size
+        self.return_n_best = min(self.beam_size, return_n_best)
+        self.max_len_a, self.max_len_b, self.max_len, self.min_len = max_len_a, max_len_b, max_len, min_len
+        self.normalize_scores, self.len_penalty, self.unk_penalty = normalize_scores, len_penalty, unk_penalty
+        self.temperature, self.no_repeat_ngram_size = temperature, no_repeat_ngram_size
+        self.constraint_start, self.constraint_end = None, None
+        if constraint_range is not None:
+            self.constraint_start, self.constraint_end = (int(v) for v in str(constraint_range).strip("()[] ").split(","))
+        self.use_graph = use_graph
+        self._dec: Optional[StepDecoder] = None
+        self._state: Optional[Dict[str, torch.Tensor]] = None
+        self.steps_run = 0                                # decoding steps launched by the last generate()
+
+    def effective_max_len(self, sample) -> int:
+        """The output length limit the reference applies.  Its source-length rule (min(max_len, max_len_a * src_len + max_len_b),
+        sequence_generator.py:185-217) never fires: the text-slot filter at :180-182 compares `x.modality == ModalityType` -- the
+        enum CLASS -- which is always false, so src_len is None and the limit is max_len.  Reproduced as is."""
+        return self.max_len
+
+    def check_sample(self, sample, **kwargs) -> bool:
+        """Refuse what is not implemented; returns whether the step-0 n-gram bans apply.  A collated batch always carries
+        `prefix_tokens`; for a plain target it is [bsz, 0], which the reference treats as no prefix (`step < prefix_tokens.size(1)`
+        never holds).  A prefix with columns -- even all <pad> -- changes the reference's step (:283-288: no min_len mask while
+        step < its width) and is refused.  One trace of an empty prefix remains: the n-gram blocker skips rows whose prefix is not
+        shorter than step + n - 1 (:319-327), so with n = 1 nothing is banned at step 0."""
+        if kwargs.get("constraints") is not None:
+            raise NotImplementedError("SequenceGenerator: lexical constraints are not implemented")
+        prefix = sample.get("prefix_tokens")
+        if prefix is not None and prefix.dim() == 2 and prefix.size(1) > 0:
+            raise NotImplementedError("SequenceGenerator: prefix_tokens are not implemented (got a prefix of "
+                                      f"{prefix.size(1)} columns)")
+        return not (prefix is not None and self.no_repeat_ngram_size == 1)
+
+    # ------------------------------------------------------------------ device state
+    def _buffers(self, rows, bsz, V, max_len, device):
+        key = (rows, V, max_len, device)
+        if self._state is None or self._state["key"] != key:
+            K_ = self.beam_size
+            i32 = dict(dtype=torch.int32, device=device)
+            self._state = {
+                "key": key,
+                "ws": torch.empty((K.beam_ws_bytes(rows, V, K_) + 3) // 4, dtype=torch.float32, device=device),
+                "scores": torch.zeros(rows, max_len + 1, dtype=torch.float32, device=device),
+                "ignore": torch.zeros(bsz, K_, **i32), "done": torch.zeros(bsz, **i32), "nfin": torch.zeros(1, **i32),
+                "reorder": torch.arange(rows, dtype=torch.long, device=device),
+                "fin_tok": torch.zeros(bsz, K_, max_len + 1, dtype=torch.long, device=device),
+                "fin_pos": torch.zeros(bsz, K_, max_len + 1, dtype=torch.float32, device=device),
+                "fin_score": torch.zeros(bsz, K_, dtype=torch.float32, device=device),
+                "fin_len": torch.zeros(bsz, K_, **i32), "fin_cnt": torch.zeros(bsz, **i32),
+                "host": torch.zeros(2, dtype=torch.int32, pin_memory=True),
+            }
+        st = self._state
+        for name in ("scores", "ignore", "done", "nfin", "fin_cnt"):
+            st[name].zero_()
+        st["reorder"].copy_(torch.arange(rows, dtype=torch.long, device=device))
+        return st
+
+    def _step_kernels(self, logits, t, dec, st, max_len, ngram_step0=True):
+        """Everything a step does after the decoder, on the device (recorded into the step graph)."""
+        V = logits.shape[1]
+        ngram = self.no_repeat_ngram_size if (t > 0 or ngram_step0) else 0
+        K.beam_topk(logits, self.beam_size, t, st["ws"], tokens=dec.tokens, done=st["done"], temperature=self.temperature,
+                    constraint_range=None if self.constraint_start is None else (self.constraint_start, self.constraint_end),
+                    min_len=self.min_len, max_len=max_len, pad=self.pad, unk=self.unk, eos=self.eos,
+                    unk_penalty=self.unk_penalty, ngram=ngram)
+        st["tokens"] = dec.tokens
+        K.beam_select(st["ws"], st, self.beam_size, V, t, max_len, eos=self.eos, unk=self.unk, unk_penalty=self.unk_penalty,
+                      normalize=self.normalize_scores, len_penalty=self.len_penalty)
+        dec.reorder(st["reorder"], caches_only=True)
+
+    # ------------------------------------------------------------------ generate
+    @torch.no_grad()
+    def generate(self, model, sample, **kwargs):
+        ngram_step0 = self.check_sample(sample, **kwargs)
+        slots = sample["net_input"]["slots"]
+        source_slots = [s for s in slots if s.is_src]
+        first = source_slots[0].value
+        src = first["fbank"] if isinstance(first, dict) else first
+        bsz, device = src.shape[0], src.device
+        beam = self.beam_size
+        rows = bsz * beam
+        max_len = self.effective_max_len(sample)
+        assert self.min_len <= max_len, "min_len cannot be larger than max_len, please adjust these!"
+        if self._dec is None or self._dec.model is not model:
+            self._dec = StepDecoder(model, max_len + 1, use_graph=self.use_graph)
+        dec = self._dec
+        dec.begin(source_slots, torch.arange(bsz, device=device).repeat_interleave(beam))
+        dec.tokens.fill_(self.pad)
+        dec.tokens[:, 0] = self.bos
+        st = self._buffers(rows, bsz, self.vocab_size, max_len, device)
+        host, events = st["host"], [None, None]
+        post = lambda logits, t: self._step_kernels(logits, t, dec, st, max_len, ngram_step0)   # noqa: E731
+        for step in range(max_len + 1):
+            logits = dec.step(None, post=post)
+            if logits.shape[1] > self.vocab_size:
+                raise ValueError(f"decoder output width {logits.shape[1]} > dictionary size {self.vocab_size}")
+            # the all-finished counter reaches the host one step late, through pinned memory: no synchronisation inside a step
+            host[step % 2].copy_(st["nfin"][0], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            events[step % 2] = ev
+            self.steps_run = step + 1
+            if step > 0:
+                events[(step - 1) % 2].synchronize()
+                if int(host[(step - 1) % 2]) >= bsz:
+                    break
+        torch.cuda.synchronize()
+        return self._collect(st, bsz)
+
+    def _collect(self, st, bsz):
+        cnt, ln = st["fin_cnt"].cpu(), st["fin_len"].cpu()
+        toks, pos, sc = st["fin_tok"].cpu(), st["fin_pos"].cpu(), st["fin_score"].cpu()
+        out = []
+        for b in range(bsz):
+            hyps = [SequenceGeneratorOutput(tokens=toks[b, i, :int(ln[b, i])].clone(), score=sc[b, i].clone(),
+                                            attention=torch.empty(0), positional_scores=pos[b, i, :int(ln[b, i])].clone())
+                    for i in range(int(cnt[b]))]
+            scores = torch.tensor([float(h.score.item()) for h in hyps])
+            _, order = torch.sort(scores, descending=True)
+            if self.return_n_best == 1:
+                out.append(hyps[order[0]])
+            else:
+                out.append([hyps[i] for i in order][: self.return_n_best])
+        return out

@@ -1272,3 +1272,35 @@ def join_bwd(dy, dz, x, y, ga, gb, stats, p, seed, offset, offset_base, grads, f
     else:
         fold.flush_if_large()
     return dres, dx
+
+
+# ------------------------------------------------------------------ beam search (csrc/beam_search.hip)
+def beam_ws_bytes(rows, V, K):
+    return int(lib().cdll.ofa_beam_ws_bytes(int(rows), int(V), int(K)))
+
+
+def beam_topk(logits2d, K, step, ws, tokens=None, done=None, temperature=1.0, constraint_range=None, min_len=1, max_len=256,
+              pad=1, unk=3, eos=2, unk_penalty=0.0, ngram=0):
+    """Row pass of one beam-search step: logits2d [rows, V] (row stride ld, last dim contiguous) -> each row's normaliser parts and
+    best 2K candidates in `ws` (beam_ws_bytes).  tokens: int64 [rows, >= step + 1] history (n-gram bans); done: int32 [bsz] or None."""
+    rows, V = logits2d.shape
+    if logits2d.stride(1) != 1:
+        raise OfaError("beam_topk: the logits' last dimension must be contiguous")
+    cs, ce = (-1, -1) if constraint_range is None else (int(constraint_range[0]), int(constraint_range[1]))
+    tok_ld = tokens.stride(0) if tokens is not None else 0
+    lib().call("ofa_beam_topk", ptr(logits2d), logits2d.stride(0), rows, V, int(K), float(temperature), cs, ce, int(step),
+               int(min_len), int(max_len), int(pad), int(unk), int(eos), float(unk_penalty), int(ngram), ptr(tokens), tok_ld,
+               ptr(done), ptr(ws), dtype_code(logits2d), stream())
+
+
+def beam_select(ws, st, K, V, step, max_len, eos=2, unk=3, unk_penalty=0.0, normalize=False, len_penalty=1.0):
+    """Sentence pass of one beam-search step over the state dict `st` (generator.SequenceGenerator._buffers, plus "tokens": the
+    decoder's token history): finalises, selects the K active candidates, gathers the histories in place and writes the reorder
+    index."""
+    tokens, scores = st["tokens"], st["scores"]
+    bsz = st["done"].numel()
+    lib().call("ofa_beam_select", ptr(ws), bsz, int(K), int(V), int(step), int(max_len), int(eos), int(unk), float(unk_penalty),
+               int(bool(normalize)), float(len_penalty), ptr(tokens), tokens.stride(0), tokens.shape[1], ptr(scores),
+               scores.stride(0), ptr(st["ignore"]), ptr(st["done"]), ptr(st["nfin"]), ptr(st["reorder"]), ptr(st["fin_tok"]),
+               ptr(st["fin_pos"]), st["fin_tok"].stride(1), ptr(st["fin_score"]), ptr(st["fin_len"]), ptr(st["fin_cnt"]),
+               stream())

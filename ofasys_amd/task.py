@@ -4,10 +4,13 @@
     task = Task(name="caption", instruction="[IMAGE:image] what does the image describe? -> [TEXT:caption]", micro_batch_size=4)
     task.add_dataset(rows, "train")            # any sequence of dict rows: datasets.Dataset, list of dicts, ...
 
-What stays out: file / OSS readers, multi-worker prefetch, metrics, generators, checkpoint state.  The
+Generation: `Task.generator` / `Task.inference` run beam search (ofasys_amd/generator.py SequenceGenerator; task/base.py:232-246,
+470-556, 727-793) for TEXT targets.
+What stays out: file / OSS readers, multi-worker prefetch, metrics, non-text generators, checkpoint state.  The
 batch iterator is a plain in-process loop over the bound dataset: micro-batches of `micro_batch_size` rows, each rank of a
 data-parallel job reading its own contiguous shard (io/reader/dataset.py:49-53), reshuffled per epoch with a seeded permutation.
 """
+import json
 import random
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Set, Union
@@ -48,6 +51,11 @@ class CriterionConfig:                                # engine/criterion/label_s
 
 
 @dataclass
+class EvaluationConfig:                               # task/base.py:138-153 (the generator arguments; metrics stay out)
+    generator_args: str = '{"beam":5,"max_len_b":32,"no_repeat_ngram_size":3}'
+
+
+@dataclass
 class ImagePreprocessConfig(PreprocessConfig):        # preprocessor/default/image.py (resize + mean/std 0.5 normalisation)
     patch_image_size: int = 224
     mean: float = 0.5
@@ -59,6 +67,7 @@ class TaskConfig:                                     # task/base.py:157-189
     dataset: DatasetConfig = field(default_factory=DatasetConfig)
     instruction: InstructionConfig = field(default_factory=InstructionConfig)
     criterion: CriterionConfig = field(default_factory=CriterionConfig)
+    evaluation: EvaluationConfig = field(default_factory=EvaluationConfig)
     text: TextPreprocessConfig = field(default_factory=TextPreprocessConfig)
     box: BoxPreprocessConfig = field(default_factory=BoxPreprocessConfig)
     image: ImagePreprocessConfig = field(default_factory=ImagePreprocessConfig)
@@ -121,6 +130,7 @@ class Task:
         self.global_dict = None
         self.general_preprocess: Optional[GeneralPreprocess] = None
         self._iters = {}
+        self._generator = None
 
     # ------------------------------------------------------------------ identity / datasets (task/base.py:256-273)
     @property
@@ -210,6 +220,61 @@ class Task:
         if split not in self._iters:
             self.init_data_iterator(split)
         return next(self._iters[split])
+
+    # ------------------------------------------------------------------ generation (task/base.py:232-246, 470-556, 727-793)
+    def build_generator(self, **gen_kwargs):
+        """SequenceGenerator with the reference's pops and defaults (task/base.py:475-486; normalize_scores defaults to False
+        here, unlike the generator's own default).  Only plain beam search exists: sampling, diverse beam, diverse siblings,
+        match_source_len and lexical constraints raise NotImplementedError."""
+        from .generator import SequenceGenerator
+        if self.global_dict is None:
+            raise ValueError(f"task {self.name}: initialize(global_dict) before building a generator")
+        args = dict(
+            beam_size=gen_kwargs.pop("beam", 5), return_n_best=gen_kwargs.pop("return_n_best", 1),
+            max_len_a=gen_kwargs.pop("max_len_a", 0), max_len_b=gen_kwargs.pop("max_len_b", 200),
+            max_len=gen_kwargs.pop("max_len", 256), min_len=gen_kwargs.pop("min_len", 1),
+            normalize_scores=gen_kwargs.pop("normalize_scores", False), len_penalty=gen_kwargs.pop("lenpen", 1),
+            unk_penalty=gen_kwargs.pop("unkpen", 0), temperature=gen_kwargs.pop("temperature", 1.0),
+            no_repeat_ngram_size=gen_kwargs.pop("no_repeat_ngram_size", 0))
+        unsupported = {"sampling": False, "sampling_topk": -1, "sampling_topp": -1.0, "diverse_beam_groups": -1,
+                       "diversity_rate": -1, "match_source_len": False, "constrained": False, "constraints": None}
+        for k, default in unsupported.items():
+            v = gen_kwargs.pop(k, default)
+            if v != default:
+                raise NotImplementedError(f"build_generator: {k}={v!r} -- only plain beam search is implemented")
+        gen_kwargs.pop("diverse_beam_strength", None)
+        return SequenceGenerator(self.global_dict, **args, **gen_kwargs)
+
+    @property
+    def generator(self):
+        """Built on first use from cfg.evaluation.generator_args (JSON) and cfg.constraint_range (text targets)."""
+        if self._generator is None:
+            gen_args = json.loads(self.cfg.evaluation.generator_args)
+            if self.target_modality == ModalityType.TEXT:
+                # closed-set tasks: the reference constrains every step with the text preprocessor's trie (task/base.py:236-240);
+                # SequenceGenerator refuses a trie rather than generate free text
+                gen_args["constraint_trie"] = self.general_preprocess.name2pre["text"].constraint_trie
+                gen_args["constraint_range"] = self.cfg.constraint_range
+            elif self.target_modality is not None:
+                raise NotImplementedError(f"task {self.name}: generation for {self.target_modality} targets is not implemented")
+            self._generator = self.build_generator(**gen_args)
+        return self._generator
+
+    @generator.setter
+    def generator(self, generator):
+        self._generator = generator
+
+    def inference(self, model, sample, **kwargs):
+        """Beam search on `sample` (a collated batch); for TEXT targets every hypothesis gets `.text` through the task's text
+        tokenizer (preprocessor/default/text.py:340-371).  The model is left in eval mode."""
+        model.eval()
+        outputs = self.generator.generate(model, sample, **kwargs)
+        if self.target_modality == ModalityType.TEXT:
+            pre = self.general_preprocess.name2pre["text"]
+            for single in outputs:
+                for hyp in (single if isinstance(single, list) else [single]):
+                    hyp.text = pre.decode(hyp.tokens)
+        return outputs
 
 
 def collect_adaptor_name_from_tasks(tasks) -> Set[str]:
