@@ -540,6 +540,37 @@ int ofa_copy_batched(const ofa_copy_job* jobs, int njobs, void* stream);
 int ofa_layernorm_bwd_slots(int64_t rows, int cols, int dtype, int gelu);
 int ofa_colsum_slots(int64_t rows);
 int ofa_gemm_splits(int M, int N, int K, int transA, int transB, int batch, int flags, int dtype, int64_t ws_bytes);
+/* Host only: the kernel ofa_gemm launches for this product, written to plan[0 .. OFA_GEMM_PLAN_LEN).  Operands as ofa_gemm_splits
+ * assumes them: dense (lda = transA ? M : K, ldb = transB ? K : N, ldc = N) and 16-byte aligned -- so a zero-padded contraction
+ * (OFA_GEMM_A_KPAD_ZERO) is asked for with K rounded up as its rows are stored.  ws_bytes: the workspace the call passes (0: none). */
+enum {
+  OFA_GEMM_PLAN_KERNEL = 0,      /* OFA_GEMM_KERNEL_* */
+  OFA_GEMM_PLAN_SIMPLE_WHY,      /* kernel SIMPLE: 1 fp32 operands, 2 OFA_GEMM_FORCE_SIMPLE, 3 a shape the MFMA kernels reject; else 0 */
+  OFA_GEMM_PLAN_WAVES_M,         /* waves of a workgroup along M, N */
+  OFA_GEMM_PLAN_WAVES_N,
+  OFA_GEMM_PLAN_WAVE_TM,         /* 32 x 32 accumulator tiles of one wave along M, N */
+  OFA_GEMM_PLAN_WAVE_TN,
+  OFA_GEMM_PLAN_TILE_M,          /* output tile of a workgroup (MIXED: the tall one) */
+  OFA_GEMM_PLAN_TILE_N,
+  OFA_GEMM_PLAN_SPLITS,          /* K-slices (> 1: fp32 partial slabs in ws) */
+  OFA_GEMM_PLAN_KSPLIT,          /* contraction length of a slice */
+  OFA_GEMM_PLAN_K,               /* contraction length the kernel runs (rounded up to whole 64-row tiles where it zero-fills) */
+  OFA_GEMM_PLAN_MIXED_TALL,      /* MIXED: row tiles of 256 ... */
+  OFA_GEMM_PLAN_MIXED_SHORT,     /* ... and of 192 below them */
+  OFA_GEMM_PLAN_COLSTAT_ROWS,    /* rows per column-statistics partial row (ofa_gemm_colstat); 0: the plan cannot write them */
+  OFA_GEMM_PLAN_REDUCE,          /* 1: a split-K reduce launch follows */
+  OFA_GEMM_PLAN_LEN
+};
+enum {
+  OFA_GEMM_KERNEL_SIMPLE = 0,    /* the exact fp32-FMA VALU kernel */
+  OFA_GEMM_KERNEL_REG = 1,       /* register-staged double-buffered loop (gemm_mfma_kernel, GLDS = false) */
+  OFA_GEMM_KERNEL_LDS_DMA = 2,   /* LDS-DMA double-buffered loop (gemm_mfma_kernel, GLDS = true) */
+  OFA_GEMM_KERNEL_RING = 3,      /* four-stage LDS-DMA ring (gemm_ring_kernel) */
+  OFA_GEMM_KERNEL_BIG = 4,       /* eight-wave big tile, lockstep loop (gemm_big_kernel) */
+  OFA_GEMM_KERNEL_PP = 5,        /* eight-wave big tile, ping-pong loop (gemm_pp_kernel) */
+  OFA_GEMM_KERNEL_MIXED = 6      /* 256- and 192-row big tiles in one launch (gemm_big_mixed_kernel) */
+};
+int ofa_gemm_plan(int M, int N, int K, int transA, int transB, int batch, int flags, int dtype, int64_t ws_bytes, int* plan);
 
 /* ---- beam search (csrc/beam_search.hip): the policy of SequenceGenerator.generate / BeamSearch.step
  * (generator/sequence_generator.py:283-492, finalize_hypos :530-627; utils/search.py:107-142) in two launches per decoding

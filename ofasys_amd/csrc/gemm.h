@@ -1,5 +1,7 @@
 // Shared GEMM argument block (exact VALU kernel + MFMA kernel).
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace ofa {
@@ -22,7 +24,15 @@ __host__ __device__ inline int64_t batch_off(int z, int inner, int64_t s_in, int
 int gemm_simple_launch(const GemmArgs& g, int batch, int dtype, hipStream_t st);
 int gemm_mfma_launch(const GemmArgs& g, int batch, void* ws, int64_t ws_bytes, hipStream_t st, bool f16 = false);
 bool gemm_mfma_supported(const GemmArgs& g);
-int gemm_mfma_splits(const GemmArgs& g, int batch, int64_t ws_bytes);
-// gemm_pp.hip: the ping-pong main loop on the 256 x 256 / 192 x 256 tile (tm = 4 / 3); false: shape or variant not built
+// gemm_pp.hip: the ping-pong main loop on the 256 x 256 / 192 x 256 tile (tm = 4 / 3); false: refused, run the lockstep loop
 bool gemm_pp_launch(int variant, const GemmArgs& g, int batch, int tm, int splits, int ksplit, float* ws, hipStream_t st, bool f16);
+// gemm_mfma.hip: sets a GEMM kernel's dynamic-LDS limit to `bytes` once per device (`done`: one bit per device); false: refused
+bool gemm_lds_attr(const void* kern, int bytes, uint64_t& done);
+
+// (A k-major, B k-major, fp32 output, f16) of a product as template arguments: f(ak, bk, of, f16), each a std::integral_constant
+template <class F> auto with_bool(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+template <class F> auto with_layout(const GemmArgs& g, bool f16, F&& f) {
+  return with_bool(!g.transA, [&](auto ak) { return with_bool(g.transB != 0, [&](auto bk) {
+    return with_bool((g.flags & OFA_GEMM_OUT_F32) != 0, [&](auto of) { return with_bool(f16, [&](auto h) { return f(ak, bk, of, h); }); }); }); });
+}
 }  // namespace ofa

@@ -702,10 +702,19 @@ __global__ __launch_bounds__(512) void gemm_big_mixed_kernel(GemmArgs g, int til
   }
 }
 
+// The planner's tile-time model in microseconds (why: gemm_plan; profiles/round2_gemm_eight_wave_sweep.txt is what it was fitted to):
+//     time = rounds x (K-steps x step + per-tile),  a round = `slots` tiles;  step_nt: k-major B
+struct TileTime {
+  int slots;
+  double step, step_nt, per_tile;
+  double tile_us(int nk, bool nt) const { return nk * (nt ? step_nt : step) + per_tile; }
+  double us(int64_t tiles, int nk, bool nt) const { return (double)cdiv(tiles, slots) * tile_us(nk, nt); }
+};
+constexpr TileTime TT_128{512, 0.90, 1.0, 4.2}, TT_256{256, 1.45, 1.45, 7.6}, TT_192{256, 1.13, 1.13, 6.5};
+
 // estimated time of that launch: per XCD its eighth of the tall and of the short tiles, handed to its 32 CUs in order as they free up
-// (tile times from gemm_plan's fitted model: K-steps x 1.45 + 7.6 us for 256 x 256, x 1.13 + 6.5 for 192 x 256)
 static double mixed_time_us(int nbig, int nsmall, int nk) {
-  const double t4 = nk * 1.45 + 7.6, t3 = nk * 1.13 + 6.5;
+  const double t4 = TT_256.tile_us(nk, false), t3 = TT_192.tile_us(nk, false);
   double worst = 0.0;
   for (int x = 0; x < 8; ++x) {
     auto lo = [](int n, int x_) { const int q = n >> 3, r = n & 7; return x_ < r ? x_ * (q + 1) : r * (q + 1) + (x_ - r) * q; };
@@ -722,36 +731,48 @@ static double mixed_time_us(int nbig, int nsmall, int nk) {
   return worst;
 }
 
-template <bool BKM, bool OF, bool F16>
-static void launch_big_mixed(const GemmArgs& g, int rows_big, int rows_small, hipStream_t st) {
-  const int tiles_n = cdiv(g.N, 256), nbig = rows_big * tiles_n, nsmall = rows_small * tiles_n;
-  const size_t lds = 4 * (size_t)256 * BK * sizeof(bf16_t);
-  auto kern = gemm_big_mixed_kernel<BKM, OF, F16>;
-  static bool attr_done = false;   // per instantiation
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done = true;
+constexpr int BIG_LDS = 4 * 256 * BK * sizeof(bf16_t);       // 2 operands x 2 stages x 32 KiB
+
+// dynamic LDS beyond the default needs the attribute on every DEVICE a kernel is launched on (the flag is a bit per device, not one per
+// process: `done`, per kernel); false: refused -- the caller falls back to another plan, or launches anyway so that check_launch reports it
+bool gemm_lds_attr(const void* kern, int bytes, uint64_t& done) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+  if (done >> dev & 1) return true;
+  if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
   }
+  done |= 1ull << dev;
+  return true;
+}
+
+template <bool BKM, bool OF, bool F16>
+static bool launch_big_mixed(const GemmArgs& g, int rows_big, int rows_small, hipStream_t st) {
+  const int tiles_n = cdiv(g.N, 256), nbig = rows_big * tiles_n, nsmall = rows_small * tiles_n;
+  auto kern = gemm_big_mixed_kernel<BKM, OF, F16>;
+  static uint64_t attr_done = 0;
+  if (!gemm_lds_attr((const void*)kern, BIG_LDS, attr_done)) return false;     // (the caller runs the plain plan)
   const int per_xcd = cdiv(nbig, 8) + cdiv(nsmall, 8);              // (an XCD's list is at most this long; shorter lists leave idle workgroups)
-  hipLaunchKernelGGL(kern, dim3(8 * per_xcd), dim3(512), lds, st, g, tiles_n, rows_big, rows_small);
+  hipLaunchKernelGGL(kern, dim3(8 * per_xcd), dim3(512), BIG_LDS, st, g, tiles_n, rows_big, rows_small);
+  return true;
 }
 
 // Grouped weight-gradient products (ofa_gemm_group_tn): up to GROUP_MAX independent  slabs_p[s] = A_p^T B_p over K-slice s
 // in ONE launch of 256 x 256 eight-wave tiles.  A layer's weight gradients are each 9-36 such tiles: alone, a product has
 // to be cut into 3-7 K-slices of 128 x 128 tiles to occupy the chip (short K loops, per-tile overheads every ~30 K-steps,
 // a 3-7 slab reduce); together they fill the 256 CUs with ~2 slices each and K loops of ~100 steps.
-// (GroupItem / GroupArgs: gemm_core.h)
+// (GroupItem / GroupArgs: gemm_core.h.  The unused second template parameter keeps the kernel's name as the profiles record it.)
 
-template <bool F16, bool W4 = false>
-__global__ __launch_bounds__(W4 ? 256 : 512) void gemm_group_tn_kernel(GroupArgs ga) {
+template <bool F16, bool = false>
+__global__ __launch_bounds__(512) void gemm_group_tn_kernel(GroupArgs ga) {
   GemmArgs g;
   int t, ks;
   const GroupItem* itp = group_enter(ga, g, t, ks);
   if (!itp) return;
   const GroupItem& it = *itp;
   // (OUT_F32 = false: the non-slab epilogue of this instantiation is the 16-bit accumulate of a one-slice product)
-  if constexpr (W4) gemm_big_body<4, 4, false, false, false, 2, 2, F16>(g, it.tiles_m, it.tiles_n, it.ksplit, it.ws, t, ks, 0, it.splits, it.out == nullptr);
-  else gemm_big_body<4, 2, false, false, false, 2, 4, F16>(g, it.tiles_m, it.tiles_n, it.ksplit, it.ws, t, ks, 0, it.splits, it.out == nullptr);
+  gemm_big_body<4, 2, false, false, false, 2, 4, F16>(g, it.tiles_m, it.tiles_n, it.ksplit, it.ws, t, ks, 0, it.splits, it.out == nullptr);
 }
 
 template <bool OUT_F32, bool F16 = false>
@@ -791,80 +812,40 @@ bool gemm_mfma_supported(const GemmArgs& g) {
   return true;
 }
 
-template <int WM, int WN, bool AK, bool BKM, bool OF, bool GL, bool F16 = false>
-static void launch_cfg2(const GemmArgs& g, int batch, int splits, int ksplit, float* ws, hipStream_t st) {
-  constexpr int BM = 64 * WM, BN = 64 * WN;
-  const int tiles_m = cdiv(g.M, BM), tiles_n = cdiv(g.N, BN);
-  const size_t lds = GL ? 2 * (size_t)(BM + BN) * BK * sizeof(bf16_t)
-                        : 2 * (size_t)(TileGeom<BM, AK>::ELEMS + TileGeom<BN, BKM>::ELEMS) * sizeof(bf16_t);
-  auto kern = gemm_mfma_kernel<WM, WN, AK, BKM, OF, GL, F16>;
-  static bool attr_done = false;   // per instantiation
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done = true;
-  }
-  dim3 grid(tiles_m * tiles_n, splits, batch), block(WM * WN * 64);
-  hipLaunchKernelGGL(kern, grid, block, lds, st, g, tiles_m, tiles_n, ksplit, ws);
-}
+// Everything a launch of one product needs, decided in one place (gemm_plan); the launchers only dispatch on it.  The fields are those
+// of ofa_gemm_plan (include/ofasys_amd.h).
+struct GemmPlan {
+  int kernel;                // OFA_GEMM_KERNEL_*
+  int wm, wn;                // waves of a workgroup along M / N
+  int tm, tn;                // 32 x 32 accumulator tiles of a wave along M / N
+  int splits, ksplit, K;     // K-slices, their length, the contraction the kernel runs
+  int mixed_a, mixed_b;      // MIXED: row tiles of 256 / 192 (gemm_big_mixed_kernel)
+  int colstat_rows;          // rows per column-statistics partial row (epilogue_lds: a wave's accumulator rows), 0: none
+  bool reduce;               // a split-K reduce launch follows
+  int pp;                    // PP: the ping-pong variant (gemm_pp.hip)
+  int bm() const { return 32 * tm * wm; }
+  int bn() const { return 32 * tn * wn; }
+};
 
-template <int WM, int WN, bool AK, bool BKM, bool OF, int S = 4, bool F16 = false, int TMW = 2, int TNW = 2>
-static void launch_ring(const GemmArgs& g, int batch, int splits, int ksplit, float* ws, hipStream_t st) {
-  constexpr int BM = 32 * TMW * WM, BN = 32 * TNW * WN;
-  const int tiles_m = cdiv(g.M, BM), tiles_n = cdiv(g.N, BN);
-  const size_t lds = S * (size_t)(BM + BN) * BK * sizeof(bf16_t);
-  auto kern = gemm_ring_kernel<WM, WN, AK, BKM, OF, S, F16, TMW, TNW>;
-  static bool attr_done = false;   // per instantiation
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done = true;
-  }
-  dim3 grid(tiles_m * tiles_n, splits, batch), block(WM * WN * 64);
-  hipLaunchKernelGGL(kern, grid, block, lds, st, g, tiles_m, tiles_n, ksplit, ws);
-}
+// Planner knobs.  The product reads no environment variable: it plans with the defaults below.  The DEBUG library (make -C
+// ofasys_amd/csrc debug -> libofasys_amd_dbg.so, -DOFA_DEBUG_SWITCHES: tools/gemm_tile_sweep.py, gemm_split_check.py, gemm_timeline.py,
+// gemm_pp_ab.py, gemm_mixed_bench.py, the forced-tile tests) reads OFA_GEMM_TILE, OFA_GEMM_PP and OFA_GEMM_MIXED on every call -- the tools
+// flip them inside one process -- and OFA_GEMM_SPLIT_MIN_K once.
+struct PlanKnobs {
+  int tile = 0;              // forced tile: 22 / 12 / 11 (128 x 128, 64 x 128, 64 x 64), 44 = 84 (256 x 256), 34 = 83 (192 x 256); 0: planned
+  int pp = -1;               // ping-pong variant of every big tile (0: the lockstep loop); -1: pp_variant decides
+  int mixed = -1;            // mixed tile heights: 0 never, 1 whenever eligible, -1 the time model decides
+  int split_min_k = 2048;    // shortest contraction that is split along K
+};
 
-// small grids take the 4-stage ring (see gemm_ring_kernel)
-static bool use_ring(const GemmArgs& g, int wm, int wn, int64_t blocks, int ksplit) {
-  if ((g.K % BK) != 0 || (ksplit % BK) != 0 || (g.flags & OFA_GEMM_NO_LDS_DMA)) return false;
-  const int64_t cap = (wm == 1 && wn == 1) ? 512 : 256;              // 64 KiB of LDS: two per CU; 96 / 128 KiB: one
-  return blocks <= cap && ksplit >= 4 * BK;
-}
-
-template <int WM, int WN, bool AK, bool BKM, bool OF, bool F16 = false>
-static void launch_cfg(const GemmArgs& g, int batch, int splits, int ksplit, float* ws, hipStream_t st) {
-  if (use_ring(g, WM, WN, (int64_t)cdiv(g.M, 64 * WM) * cdiv(g.N, 64 * WN) * splits * batch, ksplit)) {
-    // the 64 x 64 / 64 x 128 workgroup tiles run as FOUR waves of 32 x 32 / 32 x 64 (see gemm_ring_kernel): in the replayed steps
-    // cfg-2 12.18 -> 12.07 ms, cfg-5 (every product is a small grid) 135.6 -> 130.5 ms, same box (profiles/round4_ring_waves_ab.txt)
-    if constexpr (WM == 1 && WN == 1) launch_ring<2, 2, AK, BKM, OF, 4, F16, 1, 1>(g, batch, splits, ksplit, ws, st);
-    else if constexpr (WM == 1 && WN == 2) launch_ring<2, 2, AK, BKM, OF, 4, F16, 1, 2>(g, batch, splits, ksplit, ws, st);
-    else launch_ring<WM, WN, AK, BKM, OF, 4, F16>(g, batch, splits, ksplit, ws, st);
-    return;
-  }
-  // LDS-DMA staging needs full K tiles (no zero fill); anything else takes the register-staged loop
-  if ((g.K % BK) == 0 && !(g.flags & OFA_GEMM_NO_LDS_DMA)) launch_cfg2<WM, WN, AK, BKM, OF, true, F16>(g, batch, splits, ksplit, ws, st);
-  else launch_cfg2<WM, WN, AK, BKM, OF, false, F16>(g, batch, splits, ksplit, ws, st);
-}
-
-template <bool AK, bool BKM, bool OF, bool F16 = false>
-static void launch_shape(const GemmArgs& g, int batch, int wm, int wn, int splits, int ksplit, float* ws,
-                         hipStream_t st) {
-  if (wm == 2 && wn == 2) launch_cfg<2, 2, AK, BKM, OF, F16>(g, batch, splits, ksplit, ws, st);
-  else if (wm == 1 && wn == 2) launch_cfg<1, 2, AK, BKM, OF, F16>(g, batch, splits, ksplit, ws, st);
-  else launch_cfg<1, 1, AK, BKM, OF, F16>(g, batch, splits, ksplit, ws, st);
-}
-
-template <int TM, int TN, bool AK, bool BKM, bool OF, int WGM = 2, int WGN = 2, bool F16 = false>
-static void launch_big(const GemmArgs& g, int batch, int splits, int ksplit, float* ws, hipStream_t st) {
-  constexpr int BM = 32 * TM * WGM, BN = 32 * TN * WGN;
-  const int tiles_m = cdiv(g.M, BM), tiles_n = cdiv(g.N, BN);
-  const size_t lds = 4 * (size_t)256 * BK * sizeof(bf16_t);     // 2 operands x 2 stages x 32 KiB
-  auto kern = gemm_big_kernel<TM, TN, AK, BKM, OF, WGM, WGN, F16>;
-  static bool attr_done = false;   // per instantiation
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done = true;
-  }
-  dim3 grid(tiles_m * tiles_n, splits, batch), block(64 * WGM * WGN);
-  hipLaunchKernelGGL(kern, grid, block, lds, st, g, tiles_m, tiles_n, ksplit, ws);
+static PlanKnobs plan_knobs() {
+  PlanKnobs k;
+#ifdef OFA_DEBUG_SWITCHES
+  auto env = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+  static const int split_min_k = env("OFA_GEMM_SPLIT_MIN_K", k.split_min_k);
+  k = PlanKnobs{env("OFA_GEMM_TILE", k.tile), env("OFA_GEMM_PP", k.pp), env("OFA_GEMM_MIXED", k.mixed), split_min_k};
+#endif
+  return k;
 }
 
 // Which main loop runs a big tile: 0 = the compiler-scheduled lockstep loop (gemm_big_kernel), 23 = the ping-pong loop (gemm_pp.hip).
@@ -873,32 +854,16 @@ static void launch_big(const GemmArgs& g, int batch, int splits, int ksplit, flo
 // profiles/round5_gemm_pp_ablate.txt, round5_gemm_pp_timeline.txt); with an m-major operand -- fragments are two transposing reads each:
 // twice the LDS read instructions -- and a long contraction the ping-pong loop wins: grouped weight gradients of an encoder layer
 // 209 -> 182 us, input gradients at K = 2304 / 3072 / 9216: 49.2 -> 47.0, 60.9 -> 59.4, 178 -> 169 us.
-static int pp_variant(bool trans_a, bool trans_b, int K) {
-#ifdef OFA_DEBUG_SWITCHES
-  const char* e = getenv("OFA_GEMM_PP");       // (read per call: tools/gemm_pp_ab.py flips it inside one process)
-  if (e) return atoi(e);
-#endif
+static int pp_variant(const PlanKnobs& kn, bool trans_a, bool trans_b, int K) {
+  if (kn.pp >= 0) return kn.pp;
   if (trans_a && !trans_b) return 23;
   if (!trans_a && !trans_b && K >= 2048) return 23;
   return 0;
 }
 
-template <bool AK, bool BKM, bool OF, bool F16 = false>
-static void launch_big_shape(const GemmArgs& g, int batch, int tm, int splits, int ksplit, float* ws, hipStream_t st) {
-  if (const int v = pp_variant(!AK, BKM, g.K)) {
-    if (gemm_pp_launch(v, g, batch, tm, splits, ksplit, ws, st, F16)) return;
-  }
-  if constexpr (AK) {
-    if (tm == 3) { launch_big<3, 2, AK, BKM, OF, 2, 4, F16>(g, batch, splits, ksplit, ws, st); return; }   // 96 x 64 per wave
-  }
-  launch_big<4, 2, AK, BKM, OF, 2, 4, F16>(g, batch, splits, ksplit, ws, st);                              // 128 x 64 per wave
-}
-
-struct GemmPlan { int wm, wn, big_tm, splits, ksplit, K, mixed_a, mixed_b; };   // mixed_a / mixed_b: row tiles of 256 / 192 (gemm_big_mixed_kernel), 0 / 0: not used
-
-// tile / split-K plan of one product (shared by the launcher and ofa_gemm_splits, which tells a caller that defers the
-// split-K reduce how many partial slabs the launch will write)
-static GemmPlan gemm_plan(GemmArgs g, int batch, bool has_ws, int64_t ws_bytes) {
+// The plan of one product: a pure function of the sizes, flags and layout, the batch and the workspace (has_ws: one is passed, ws_bytes:
+// its size), and the knobs.  ofa_gemm_splits tells a caller that defers the split-K reduce how many partial slabs the launch will write.
+static GemmPlan gemm_plan(GemmArgs g, int batch, bool has_ws, int64_t ws_bytes, const PlanKnobs& kn) {
   // zero-padded contraction (vocabulary-logit gradients, lda padded to a multiple of 64): run the LDS-DMA loop over the
   // padded K; A's tail columns are zeros, B's rows past K are clamped reads
   if ((g.flags & OFA_GEMM_A_KPAD_ZERO) && !g.transA && !g.transB && (g.K % BK) != 0 && ((g.K + BK - 1) / BK) * BK <= g.lda)
@@ -906,6 +871,8 @@ static GemmPlan gemm_plan(GemmArgs g, int batch, bool has_ws, int64_t ws_bytes) 
   // weight gradients over a row count that is not a multiple of 64 (both operands m-major): the LDS-DMA loop over the rounded-up K,
   // A's missing rows read as zeros, B's clamped (a_krows / b_krows = the real count, set by the launcher)
   if (g.transA && !g.transB && (g.K % BK) != 0 && !(g.flags & OFA_GEMM_NO_LDS_DMA)) g.K = ((g.K + BK - 1) / BK) * BK;
+  // LDS-DMA staging needs full K tiles (no zero fill); anything else takes the register-staged loop
+  const bool dma = (g.K % BK) == 0 && !(g.flags & OFA_GEMM_NO_LDS_DMA);
   // tile choice: the biggest tile that, together with split-K (when a workspace is given and K is long), still puts
   // >= ~1.5 workgroups on every CU; 128x128 tiles halve the LDS traffic per flop of 64-wide ones.
   const int64_t t22 = (int64_t)cdiv(g.M, 128) * cdiv(g.N, 128) * batch;
@@ -918,55 +885,41 @@ static GemmPlan gemm_plan(GemmArgs g, int batch, bool has_ws, int64_t ws_bytes) 
   // Round 3 (tools/gemm_split_check.py, the ResNet trunk's 1 x 1 / 3 x 3 products): at K = 1024 the split loses too (18432 x 256 x 1024:
   // 31.7 us in two slices + reduce vs 20.2 us as 64 x 128 tiles; 6272 x 256 x 1024: 22.4 vs 14.0 us as 64 x 64 tiles), and so does any
   // split of a product whose 128 x 128 tiles already fill a round of the 256 CUs (18432 x 256 x 2304: 46.6 vs 37.6 us)
-  // Planner overrides for experiments (tools/gemm_tile_sweep.py, gemm_split_check.py, gemm_timeline.py, the forced-tile test) exist in
-  // the DEBUG library only (make -C ofasys_amd/csrc debug -> libofasys_amd_dbg.so, -DOFA_DEBUG_SWITCHES); the shipped library has
-  // one code path and reads no environment variable.
-#ifdef OFA_DEBUG_SWITCHES
-  static const int split_min_k = getenv("OFA_GEMM_SPLIT_MIN_K") ? atoi(getenv("OFA_GEMM_SPLIT_MIN_K")) : 2048;
-  const int force_tile = getenv("OFA_GEMM_TILE") ? atoi(getenv("OFA_GEMM_TILE")) : 0;   // 22 / 12 / 11 / 44 (= 84) / 34 (= 83); read per call
-  static const int64_t nosplit_t11 = getenv("OFA_GEMM_NOSPLIT_T11") ? atoll(getenv("OFA_GEMM_NOSPLIT_T11")) : 256;
-#else
-  constexpr int split_min_k = 2048, force_tile = 0;
-  constexpr int64_t nosplit_t11 = 256;
-#endif
-  if (g.K < split_min_k || t22 >= 256) maxs = 1;
+  if (g.K < kn.split_min_k || t22 >= 256) maxs = 1;
   // Round 4: a forward / input-gradient product whose 64 x 64 tiles alone put a four-wave workgroup on every compute unit is not split
   // either (the decoder-side K = 2304 / 3072 input gradients: 1536 x 768 x 3072 ran as 72 tiles x 5 slices + a reduce launch, 26 + 6.5 us;
   // as 288 ring-staged 64 x 64 tiles it needs no second launch)
-  if (!g.transA && g.K <= 4096 && t11 >= nosplit_t11) maxs = 1;
+  if (!g.transA && g.K <= 4096 && t11 >= 256) maxs = 1;
   const int64_t want = 384;
   int wm, wn;
   int64_t tiles;
   if (t22 * maxs >= want && g.M > 64 && g.N >= 128) { wm = 2; wn = 2; tiles = t22; }
   else if (t12 * maxs >= want && g.N >= 128) { wm = 1; wn = 2; tiles = t12; }
   else { wm = 1; wn = 1; tiles = t11; }
-  if (force_tile == 22) { wm = 2; wn = 2; tiles = t22; }
-  else if (force_tile == 12) { wm = 1; wn = 2; tiles = t12; }
-  else if (force_tile == 11) { wm = 1; wn = 1; tiles = t11; }
+  if (kn.tile == 22) { wm = 2; wn = 2; tiles = t22; }
+  else if (kn.tile == 12) { wm = 1; wn = 2; tiles = t12; }
+  else if (kn.tile == 11) { wm = 1; wn = 1; tiles = t11; }
   // Big tiles: ONE 512-thread workgroup per CU, eight waves of 128 x 64 (256 x 256 tile) or 96 x 64 (192 x 256) -- two waves per
   // SIMD, so one wave's barrier / LDS waits are covered by the other's MFMAs: 1.42 us per K-step of 2048 MFMA-clocks against
   // 0.87 us per 1024 for a pair of 128 x 128 workgroups (tools/gemm_timeline.py, profiles/round2_gemm_timeline.txt).  The
   // price is per tile: first-tile flight, epilogue, store acknowledgement and re-dispatch cost 7.6 us with nothing else
   // on the CU to hide them (4.2 us per pair of 128 x 128 workgroups), and the grid is quantised in rounds of 256 tiles.
-  // The choice is made on that model (microseconds; profiles/round2_gemm_eight_wave_sweep.txt is what it was fitted to):
-  //     time = rounds x (K-steps x step + per-tile)      128 x 128: 512 slots, step 0.90 (1.0 NT), per-tile 4.2
-  //                                                      256 x 256: 256 slots, step 1.45, per-tile 7.6
-  //                                                      192 x 256: 256 slots, step 1.13, per-tile 6.5   (k-major A only)
+  // The choice is made on that model (TT_128, TT_256, TT_192), with a 5 % margin for the big tile:
   // e.g. 13312 x 768 x 3072: 95 / 77 / 61 -> 192 x 256 (measured 81 / 77-83 / 65); 13312 x 2304 x 768: 62 / 50 / 60 -> 256 x 256
   // (62 / 54 / 61); 13312 x 3072 x 768 (NN): 75 / 75 / 80 -> stays on 128 x 128 (76 / 76 / 84).  m-major A (weight gradients)
   // keeps the rule of round 1: one round of <= 256 tiles or K >= 4096, on the 256 x 256 tile.
   int big_tm = 0;                                           // 3: 192 x 256, 4: 256 x 256
-  const bool big_ok = (g.K % BK) == 0 && !(g.flags & OFA_GEMM_NO_LDS_DMA) && g.N >= 256 && g.M >= 192;
-  if (big_ok && force_tile != 22 && force_tile != 12 && force_tile != 11) {
-    const int64_t t4 = (int64_t)cdiv(g.M, 256) * cdiv(g.N, 256) * batch, t3 = (int64_t)cdiv(g.M, 192) * cdiv(g.N, 256) * batch;
-    if (force_tile == 44 || force_tile == 84) big_tm = 4;
-    else if (force_tile == 34 || force_tile == 83) big_tm = g.transA ? 4 : 3;
+  const bool big_ok = dma && g.N >= 256 && g.M >= 192;
+  const bool forced_small = kn.tile == 22 || kn.tile == 12 || kn.tile == 11;
+  const int nk = g.K / BK;
+  const int64_t t4 = (int64_t)cdiv(g.M, 256) * cdiv(g.N, 256) * batch, t3 = (int64_t)cdiv(g.M, 192) * cdiv(g.N, 256) * batch;
+  if (big_ok && !forced_small) {
+    if (kn.tile == 44 || kn.tile == 84) big_tm = 4;
+    else if (kn.tile == 34 || kn.tile == 83) big_tm = g.transA ? 4 : 3;
     else if (!g.transA) {
-      const int nk = g.K / BK;
       if (batch == 1 && nk >= 4 && t22 >= 512 && wm == 2 && wn == 2) {
-        auto est = [&](int64_t t, int slots, double step, double per_tile) { return (double)cdiv(t, slots) * (nk * step + per_tile); };
-        const double e2 = est(t22, 512, g.transB ? 1.0 : 0.90, 4.2);
-        const double e4 = t4 >= 128 ? est(t4, 256, 1.45, 7.6) : 1e30, e3 = t3 >= 128 ? est(t3, 256, 1.13, 6.5) : 1e30;
+        const double e2 = TT_128.us(t22, nk, g.transB);
+        const double e4 = t4 >= 128 ? TT_256.us(t4, nk, false) : 1e30, e3 = t3 >= 128 ? TT_192.us(t3, nk, false) : 1e30;
         if (e4 <= e3 && e4 < 0.95 * e2) big_tm = 4;
         else if (e3 < e4 && e3 < 0.95 * e2) big_tm = 3;
       }
@@ -974,32 +927,22 @@ static GemmPlan gemm_plan(GemmArgs g, int batch, bool has_ws, int64_t ws_bytes) 
       const double f4 = (double)t4 / (double)(cdiv(t4, 256) * 256) * ((double)g.M / (cdiv(g.M, 256) * 256)) * ((double)g.N / (cdiv(g.N, 256) * 256));
       // (round 6: also several well-filled rounds over a medium contraction -- the vocabulary projection's weight gradient, 51272 x 768
       //  over 1536 decoder rows, 603 tiles = 2.36 rounds: 156 us on 128 x 128 tiles, whose transposing fragment reads the time model
-      //  above flatters, 131 us here)
-      if (f4 >= 0.7 && (g.K >= 4096 || t4 <= 256 || g.K >= 1024)) big_tm = 4;
+      //  above flatters, 131 us here.  Open: ADVICE.md's narrower gate for this rule, which would change plans.)
+      if (f4 >= 0.7 && (g.K >= 1024 || t4 <= 256)) big_tm = 4;
     }
-    if (big_tm) {
-      wm = wn = 0;
-      tiles = big_tm == 4 ? t4 : t3;
-    }
+    if (big_tm) tiles = big_tm == 4 ? t4 : t3;
   }
   int splits = 1;
   // Round 6: a k-major-A product with a very long contraction and a handful of output tiles (the vocabulary projection's input gradient,
   // 1536 x 768 x 51328: 72 tiles of 128 x 128 in 6 K-slices ran at 15 % of peak, every tile re-reading its operand panels at 64 flop / B)
   // takes the 256 x 256 tile cut into as many K-slices as fill ONE round of the 256 CUs: twice the flops per operand byte, ~57 K tiles per
   // workgroup, fp32 slabs summed by the reduce launch (tools/gemm_bench.py, profiles/round6_gemm_microbench.txt).
-#ifdef OFA_DEBUG_SWITCHES
-  const bool big_split_on = !(getenv("OFA_GEMM_BIGSPLIT") && atoi(getenv("OFA_GEMM_BIGSPLIT")) == 0);
-#else
-  constexpr bool big_split_on = true;
-#endif
-  if (big_split_on && !big_tm && big_ok && !force_tile && !g.transA && batch == 1 && has_ws && g.K >= 8192) {
-    const int64_t t4 = (int64_t)cdiv(g.M, 256) * cdiv(g.N, 256);
+  if (!big_tm && big_ok && !kn.tile && !g.transA && batch == 1 && has_ws && g.K >= 8192) {
     int s = t4 <= 64 ? (int)(256 / t4) : 1;
     s = s > maxs ? maxs : s;
     while (s > 1 && (int64_t)s * g.M * ((g.N + 3) & ~3) * 4 > ws_bytes) --s;
     if (s >= 4) {
       big_tm = 4;
-      wm = wn = 0;
       tiles = t4;
       splits = s;
     }
@@ -1014,24 +957,40 @@ static GemmPlan gemm_plan(GemmArgs g, int batch, bool has_ws, int64_t ws_bytes) 
     ksplit = cdiv(cdiv(g.K, splits), BK) * BK;
     splits = cdiv(g.K, ksplit);
   }
+  GemmPlan p{};
+  p.splits = splits;
+  p.ksplit = ksplit;
+  p.K = g.K;
+  p.reduce = splits > 1 && !(g.flags & OFA_GEMM_DEFER_REDUCE);
+  if (big_tm) {
+    // eight waves, 2 x 4, of (32 big_tm) x 64.  The ping-pong loop takes 16-bit outputs with a k-major A or two m-major operands
+    p.wm = 2; p.wn = 4; p.tm = big_tm; p.tn = 2;
+    p.pp = pp_variant(kn, g.transA, g.transB, g.K);
+    p.kernel = p.pp && !(g.flags & OFA_GEMM_OUT_F32) && !(g.transA && g.transB) ? OFA_GEMM_KERNEL_PP : OFA_GEMM_KERNEL_BIG;
+  } else if (dma && (int64_t)cdiv(g.M, 64 * wm) * cdiv(g.N, 64 * wn) * splits * batch <= ((wm == 1 && wn == 1) ? 512 : 256) &&
+             ksplit >= 4 * BK) {
+    // small grids take the 4-stage ring (64 KiB of LDS: two workgroups per CU; 96 / 128 KiB: one), its 64 x 64 / 64 x 128 tiles as
+    // FOUR waves of 32 x 32 / 32 x 64 (see gemm_ring_kernel): in the replayed steps cfg-2 12.18 -> 12.07 ms, cfg-5 (every product is a
+    // small grid) 135.6 -> 130.5 ms, same box (profiles/round4_ring_waves_ab.txt)
+    p.kernel = OFA_GEMM_KERNEL_RING;
+    p.wm = 2; p.wn = 2; p.tm = wm; p.tn = wn;
+  } else {
+    p.kernel = dma ? OFA_GEMM_KERNEL_LDS_DMA : OFA_GEMM_KERNEL_REG;
+    p.wm = wm; p.wn = wn; p.tm = 2; p.tn = 2;
+  }
+  p.colstat_rows = splits > 1 || batch != 1 ? 0 : 32 * p.tm;
   // Round 6: two tile heights in one launch (gemm_big_mixed_kernel) where the plan above leaves a partly filled round: k-major A, one
   // K-slice, no batch, plain epilogue (the column statistics and the row bias index rows of the whole product).  The candidates
   // (a tall row tiles, the rest short) are simulated once per shape; the choice has to beat the plan's own estimate by 5 % (tools/gemm_mixed_bench.py, MI355X, replayed graphs:
   // 13312 x 3072 x 768 NT 76.5 -> 68.5 us, its NN twin 78.3 -> 68.6; 13312 x 9216 x 768 -- 4 % by the model -- measured 201 -> 192 alone but
   // nothing inside the step and 200 -> 225 in an eager back-to-back loop, where consecutive launches overlap their tails: not taken).
-  int mixed_a = 0, mixed_b = 0;
-#ifdef OFA_DEBUG_SWITCHES
-  const int mixed_mode = getenv("OFA_GEMM_MIXED") ? atoi(getenv("OFA_GEMM_MIXED")) : -1;     // 0: never, 1: whenever eligible, -1: the model decides
-#else
-  constexpr int mixed_mode = -1;
-#endif
-  if (mixed_mode != 0 && big_ok && !force_tile && !g.transA && batch == 1 && splits == 1 && !g.colstat && !(g.flags & OFA_GEMM_BIAS_ROW) &&
-      g.M >= 1024 && g.N >= 512 && g.K >= 4 * BK && pp_variant(false, g.transB != 0, g.K) == 0) {
+  if (kn.mixed != 0 && big_ok && !kn.tile && !g.transA && batch == 1 && splits == 1 && !g.colstat && !(g.flags & OFA_GEMM_BIAS_ROW) &&
+      g.M >= 1024 && g.N >= 512 && g.K >= 4 * BK && pp_variant(kn, false, g.transB != 0, g.K) == 0) {
     struct Key { int M, N, K, tb; };
     struct Val { int a, b; double t; };
     static std::mutex mu;
     static std::vector<std::pair<Key, Val>> cache;
-    const int nk = g.K / BK, tiles_n = cdiv(g.N, 256);
+    const int tiles_n = cdiv(g.N, 256);
     Val best{0, 0, 1e30};
     bool hit = false;
     {
@@ -1051,81 +1010,98 @@ static GemmPlan gemm_plan(GemmArgs g, int batch, bool has_ws, int64_t ws_bytes) 
       std::lock_guard<std::mutex> lk(mu);
       if (cache.size() < 256) cache.push_back({Key{g.M, g.N, g.K, g.transB}, best});
     }
-    // the plan's own estimate, by the same model
-    double cur;
-    if (big_tm == 4) cur = (double)cdiv(tiles, 256) * (nk * 1.45 + 7.6);
-    else if (big_tm == 3) cur = (double)cdiv(tiles, 256) * (nk * 1.13 + 6.5);
-    else cur = (double)cdiv(tiles, (wm == 2 && wn == 2) ? 512 : 1024) * (nk * (g.transB ? 1.0 : 0.90) + 4.2);
-    const bool modelled = (wm == 2 && wn == 2) || big_tm;               // (the plans the time model above covers)
-    if (best.a > 0 && best.b > 0 && (mixed_mode == 1 || (modelled && best.t < 0.95 * cur))) {
-      mixed_a = best.a;
-      mixed_b = best.b;
+    // the plan's own estimate, by the same model (it covers the 128 x 128 and the big tiles)
+    const bool modelled = (wm == 2 && wn == 2) || big_tm;
+    const double cur = big_tm == 4 ? TT_256.us(tiles, nk, false) : big_tm == 3 ? TT_192.us(tiles, nk, false) : TT_128.us(tiles, nk, g.transB);
+    if (best.a > 0 && best.b > 0 && (kn.mixed == 1 || (modelled && best.t < 0.95 * cur))) {
+      p.kernel = OFA_GEMM_KERNEL_MIXED;
+      p.wm = 2; p.wn = 4; p.tm = 4; p.tn = 2;
+      p.mixed_a = best.a;
+      p.mixed_b = best.b;
     }
   }
-  return GemmPlan{wm, wn, big_tm, splits, ksplit, g.K, mixed_a, mixed_b};
+  return p;
 }
 
-int gemm_mfma_splits(const GemmArgs& g, int batch, int64_t ws_bytes) { return gemm_plan(g, batch, ws_bytes > 0, ws_bytes).splits; }
-
-// rows per column-statistics partial row of the kernel the plan selects (0: that kernel cannot produce them): the accumulator
-// rows of one wave, 32 * TM (epilogue_lds)
-static int plan_colstat_rows(const GemmArgs& g, const GemmPlan& pl, int batch) {
-  if (pl.splits > 1 || batch != 1) return 0;
-  if (pl.big_tm) return pl.big_tm * 32;
-  GemmArgs gp = g;
-  gp.K = pl.K;
-  const int64_t blocks = (int64_t)cdiv(g.M, 64 * pl.wm) * cdiv(g.N, 64 * pl.wn) * pl.splits * batch;
-  return (use_ring(gp, pl.wm, pl.wn, blocks, pl.ksplit) && pl.wm == 1) ? 32 : 64;      // (the four-wave ring forms: 32-row wave blocks)
+// one launch of a tile kernel on the plan's grid: output tiles x K-slices x batch
+template <auto KERN>
+static void launch_tiles(int lds, const GemmArgs& g, int batch, const GemmPlan& p, float* ws, hipStream_t st) {
+  static uint64_t attr_done = 0;
+  (void)gemm_lds_attr((const void*)KERN, lds, attr_done);       // (refused: the launch fails and check_launch reports it)
+  const int tiles_m = cdiv(g.M, p.bm()), tiles_n = cdiv(g.N, p.bn());
+  hipLaunchKernelGGL(KERN, dim3(tiles_m * tiles_n, p.splits, batch), dim3(64 * p.wm * p.wn), lds, st, g, tiles_m, tiles_n, p.ksplit, ws);
 }
 
-int gemm_mfma_colstat_groups(const GemmArgs& g_in, void* ws, int64_t ws_bytes) {
-  GemmArgs g = g_in;
-  if ((g.flags & (OFA_GEMM_OUT_F32 | OFA_GEMM_ACCUM)) || (g.N & 7)) return 0;
-  const GemmPlan pl = gemm_plan(g, 1, ws != nullptr, ws_bytes);
-  const int rows = plan_colstat_rows(g, pl, 1);
-  return rows ? cdiv(g.M, rows) : 0;
+template <int WM, int WN, bool AK, bool BKM, bool OF, bool F16>
+static void launch_cfg2(const GemmArgs& g, int batch, const GemmPlan& p, float* ws, hipStream_t st) {
+  constexpr int BM = 64 * WM, BN = 64 * WN;
+  if (p.kernel == OFA_GEMM_KERNEL_LDS_DMA)
+    launch_tiles<gemm_mfma_kernel<WM, WN, AK, BKM, OF, true, F16>>(2 * (BM + BN) * BK * sizeof(bf16_t), g, batch, p, ws, st);
+  else
+    launch_tiles<gemm_mfma_kernel<WM, WN, AK, BKM, OF, false, F16>>(2 * (TileGeom<BM, AK>::ELEMS + TileGeom<BN, BKM>::ELEMS) * sizeof(bf16_t),
+                                                                    g, batch, p, ws, st);
+}
+
+template <bool AK, bool BKM, bool OF, bool F16>
+static int launch_plan(const GemmArgs& g, int batch, const GemmPlan& p, float* ws, hipStream_t st) {
+  switch (p.kernel) {
+    case OFA_GEMM_KERNEL_PP:
+      if (gemm_pp_launch(p.pp, g, batch, p.tm, p.splits, p.ksplit, ws, st, F16)) break;
+      [[fallthrough]];                                          // (refused: the lockstep loop on the same tile)
+    case OFA_GEMM_KERNEL_BIG:
+      if constexpr (AK) {
+        if (p.tm == 3) { launch_tiles<gemm_big_kernel<3, 2, AK, BKM, OF, 2, 4, F16>>(BIG_LDS, g, batch, p, ws, st); break; }
+      }
+      launch_tiles<gemm_big_kernel<4, 2, AK, BKM, OF, 2, 4, F16>>(BIG_LDS, g, batch, p, ws, st);
+      break;
+    case OFA_GEMM_KERNEL_RING: {
+      const int lds = 4 * (p.bm() + p.bn()) * BK * sizeof(bf16_t);
+      if (p.tm == 1 && p.tn == 1) launch_tiles<gemm_ring_kernel<2, 2, AK, BKM, OF, 4, F16, 1, 1>>(lds, g, batch, p, ws, st);
+      else if (p.tm == 1) launch_tiles<gemm_ring_kernel<2, 2, AK, BKM, OF, 4, F16, 1, 2>>(lds, g, batch, p, ws, st);
+      else launch_tiles<gemm_ring_kernel<2, 2, AK, BKM, OF, 4, F16, 2, 2>>(lds, g, batch, p, ws, st);
+      break;
+    }
+    default:                                                    // REG / LDS_DMA
+      if (p.wm == 2) launch_cfg2<2, 2, AK, BKM, OF, F16>(g, batch, p, ws, st);
+      else if (p.wn == 2) launch_cfg2<1, 2, AK, BKM, OF, F16>(g, batch, p, ws, st);
+      else launch_cfg2<1, 1, AK, BKM, OF, F16>(g, batch, p, ws, st);
+  }
+  int rc = check_launch("gemm_mfma");
+  if (rc || !p.reduce) return rc;
+  const int64_t quads = (int64_t)g.M * ((g.N + 3) / 4);
+  dim3 grid((unsigned)((quads + 255) / 256 > 2048 ? 2048 : (quads + 255) / 256), batch), block(256);
+  hipLaunchKernelGGL((splitk_reduce_kernel<OF, F16>), grid, block, 0, st, g, (const float*)ws, p.splits);
+  return check_launch("gemm_splitk_reduce");
 }
 
 int gemm_mfma_launch(const GemmArgs& g_in, int batch, void* ws, int64_t ws_bytes, hipStream_t st, bool f16) {
+  const PlanKnobs kn = plan_knobs();
+  GemmPlan p = gemm_plan(g_in, batch, ws != nullptr, ws_bytes, kn);
   GemmArgs g = g_in;
   g.a_krows = g.b_krows = g.K;
-  const GemmPlan pl = gemm_plan(g, batch, ws != nullptr, ws_bytes);
-  if (g.colstat) g.colstat_rows = plan_colstat_rows(g, pl, batch);
-  g.K = pl.K;
-  const int wm = pl.wm, wn = pl.wn, big_tm = pl.big_tm, splits = pl.splits, ksplit = pl.ksplit;
-  const bool ak = !g.transA, bk = g.transB != 0, of = (g.flags & OFA_GEMM_OUT_F32) != 0;
-  if (pl.mixed_a > 0) {                                     // (k-major A, one K-slice, no batch: gemm_plan)
-    if (bk) { if (of) { if (f16) launch_big_mixed<true, true, true>(g, pl.mixed_a, pl.mixed_b, st); else launch_big_mixed<true, true, false>(g, pl.mixed_a, pl.mixed_b, st); }
-              else { if (f16) launch_big_mixed<true, false, true>(g, pl.mixed_a, pl.mixed_b, st); else launch_big_mixed<true, false, false>(g, pl.mixed_a, pl.mixed_b, st); } }
-    else { if (of) { if (f16) launch_big_mixed<false, true, true>(g, pl.mixed_a, pl.mixed_b, st); else launch_big_mixed<false, true, false>(g, pl.mixed_a, pl.mixed_b, st); }
-           else { if (f16) launch_big_mixed<false, false, true>(g, pl.mixed_a, pl.mixed_b, st); else launch_big_mixed<false, false, false>(g, pl.mixed_a, pl.mixed_b, st); } }
-    return check_launch("gemm_big_mixed");
+  g.K = p.K;
+  if (g.colstat) g.colstat_rows = p.colstat_rows;
+  if (p.kernel == OFA_GEMM_KERNEL_MIXED) {                   // (k-major A, one K-slice, no batch: gemm_plan)
+    if (with_layout(g, f16, [&](auto, auto bk, auto of, auto h) { return launch_big_mixed<bk, of, h>(g, p.mixed_a, p.mixed_b, st); }))
+      return check_launch("gemm_big_mixed");
+    p = gemm_plan(g_in, batch, ws != nullptr, ws_bytes, PlanKnobs{kn.tile, kn.pp, 0, kn.split_min_k});   // refused: the plain plan
   }
-#define GEMM_DISPATCH(AK, BKM, OF)                                                                      \
-  do {                                                                                                  \
-    if (f16) {                                                                                          \
-      if (big_tm) launch_big_shape<AK, BKM, OF, true>(g, batch, big_tm, splits, ksplit, (float*)ws, st);  \
-      else launch_shape<AK, BKM, OF, true>(g, batch, wm, wn, splits, ksplit, (float*)ws, st);           \
-    } else if (big_tm) launch_big_shape<AK, BKM, OF>(g, batch, big_tm, splits, ksplit, (float*)ws, st); \
-    else launch_shape<AK, BKM, OF>(g, batch, wm, wn, splits, ksplit, (float*)ws, st);                   \
-  } while (0)
-  if (ak && bk) { if (of) GEMM_DISPATCH(true, true, true); else GEMM_DISPATCH(true, true, false); }
-  else if (ak && !bk) { if (of) GEMM_DISPATCH(true, false, true); else GEMM_DISPATCH(true, false, false); }
-  else if (!ak && !bk) { if (of) GEMM_DISPATCH(false, false, true); else GEMM_DISPATCH(false, false, false); }
-  else { if (of) GEMM_DISPATCH(false, true, true); else GEMM_DISPATCH(false, true, false); }
-#undef GEMM_DISPATCH
-  int rc = check_launch("gemm_mfma");
-  if (rc) return rc;
-  if (splits > 1 && !(g.flags & OFA_GEMM_DEFER_REDUCE)) {
-    const int64_t quads = (int64_t)g.M * ((g.N + 3) / 4);
-    dim3 grid((unsigned)((quads + 255) / 256 > 2048 ? 2048 : (quads + 255) / 256), batch), block(256);
-    if (of && f16) hipLaunchKernelGGL((splitk_reduce_kernel<true, true>), grid, block, 0, st, g, (const float*)ws, splits);
-    else if (of) hipLaunchKernelGGL(splitk_reduce_kernel<true>, grid, block, 0, st, g, (const float*)ws, splits);
-    else if (f16) hipLaunchKernelGGL((splitk_reduce_kernel<false, true>), grid, block, 0, st, g, (const float*)ws, splits);
-    else hipLaunchKernelGGL(splitk_reduce_kernel<false>, grid, block, 0, st, g, (const float*)ws, splits);
-    rc = check_launch("gemm_splitk_reduce");
-  }
-  return rc;
+  return with_layout(g, f16, [&](auto ak, auto bk, auto of, auto h) { return launch_plan<ak, bk, of, h>(g, batch, p, (float*)ws, st); });
+}
+
+// rows of the column-statistics partial rows of the product's plan (0: it cannot produce them)
+static int gemm_mfma_colstat_groups(const GemmArgs& g, void* ws, int64_t ws_bytes) {
+  if ((g.flags & (OFA_GEMM_OUT_F32 | OFA_GEMM_ACCUM)) || (g.N & 7)) return 0;
+  const int rows = gemm_plan(g, 1, ws != nullptr, ws_bytes, plan_knobs()).colstat_rows;
+  return rows ? cdiv(g.M, rows) : 0;
+}
+
+// the product as ofa_gemm_splits / ofa_gemm_plan see it: dense leading dimensions, aligned operands
+static GemmArgs dense_args(int M, int N, int K, int transA, int transB, int flags) {
+  GemmArgs g{};
+  g.M = M; g.N = N; g.K = K; g.transA = transA; g.transB = transB; g.flags = flags;
+  g.lda = transA ? M : K; g.ldb = transB ? K : N; g.ldc = N;
+  return g;
 }
 
 }  // namespace ofa
@@ -1134,10 +1110,20 @@ using namespace ofa;
 
 extern "C" int ofa_gemm_splits(int M, int N, int K, int transA, int transB, int batch, int flags, int dtype, int64_t ws_bytes) {
   if ((dtype != OFA_BF16 && dtype != OFA_F16) || (flags & OFA_GEMM_FORCE_SIMPLE) || M <= 0 || N <= 0 || K <= 0 || batch <= 0) return 1;
-  GemmArgs g{};
-  g.M = M; g.N = N; g.K = K; g.transA = transA; g.transB = transB; g.flags = flags;
-  g.lda = transA ? M : K; g.ldb = transB ? K : N; g.ldc = N;
-  return gemm_mfma_splits(g, batch, ws_bytes);
+  return gemm_plan(dense_args(M, N, K, transA, transB, flags), batch, ws_bytes > 0, ws_bytes, plan_knobs()).splits;
+}
+
+extern "C" int ofa_gemm_plan(int M, int N, int K, int transA, int transB, int batch, int flags, int dtype, int64_t ws_bytes, int* plan) {
+  OFA_REQUIRE(plan && OFA_DT_OK(dtype) && M > 0 && N > 0 && K > 0 && batch > 0, OFA_ERR_INVALID, "gemm_plan: bad argument");
+  memset(plan, 0, OFA_GEMM_PLAN_LEN * sizeof(int));
+  const GemmArgs g = dense_args(M, N, K, transA, transB, flags);
+  const int why = dtype == OFA_F32 ? 1 : (flags & OFA_GEMM_FORCE_SIMPLE) ? 2 : !gemm_mfma_supported(g) ? 3 : 0;
+  if (why) { plan[OFA_GEMM_PLAN_SIMPLE_WHY] = why; return 0; }          // (OFA_GEMM_KERNEL_SIMPLE = 0)
+  const GemmPlan p = gemm_plan(g, batch, ws_bytes > 0, ws_bytes, plan_knobs());
+  const int v[] = {p.kernel, 0, p.wm, p.wn, p.tm, p.tn, p.bm(), p.bn(), p.splits, p.ksplit, p.K, p.mixed_a, p.mixed_b, p.colstat_rows, p.reduce};
+  static_assert(sizeof(v) / sizeof(v[0]) == OFA_GEMM_PLAN_LEN, "one value per plan field");
+  memcpy(plan, v, sizeof(v));
+  return 0;
 }
 
 // ---- grouped weight-gradient products
@@ -1267,31 +1253,14 @@ extern "C" int ofa_gemm_group_tn(const ofa_gemm_group_item* items, int n, int dt
   }
   for (int p = n; p < GROUP_MAX; ++p) ga.it[p] = ga.it[0];
   ga.n = n; ga.total = first;
-  const size_t lds = 4 * (size_t)256 * BK * sizeof(bf16_t);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)gemm_group_tn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)gemm_group_tn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done = true;
-  }
   hipStream_t st = (hipStream_t)stream;
-#ifdef OFA_DEBUG_SWITCHES
-  static const bool w4 = getenv("OFA_GROUP_W4") && atoi(getenv("OFA_GROUP_W4"));     // experiment: four waves of 128 x 128
-  if (w4 && dtype != OFA_F16) {
-    static bool attr4 = false;
-    if (!attr4) {
-      (void)hipFuncSetAttribute((const void*)gemm_group_tn_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr4 = true;
-    }
-    hipLaunchKernelGGL((gemm_group_tn_kernel<false, true>), dim3(ga.total), dim3(256), lds, st, ga);
-    return check_launch("gemm_group_tn_w4");
-  }
-#endif
-  if (const int v = pp_variant(true, false, 0)) {
+  if (const int v = pp_variant(plan_knobs(), true, false, 0)) {
     if (gemm_group_pp_launch(v, ga, dtype == OFA_F16, st)) return check_launch("gemm_group_tn_pp");
   }
-  if (dtype == OFA_F16) hipLaunchKernelGGL(gemm_group_tn_kernel<true>, dim3(ga.total), dim3(512), lds, st, ga);
-  else hipLaunchKernelGGL(gemm_group_tn_kernel<false>, dim3(ga.total), dim3(512), lds, st, ga);
+  auto kern = dtype == OFA_F16 ? gemm_group_tn_kernel<true> : gemm_group_tn_kernel<false>;
+  static uint64_t attr_done[2] = {0, 0};                                    // (bf16, f16)
+  (void)gemm_lds_attr((const void*)kern, BIG_LDS, attr_done[dtype == OFA_F16]);
+  hipLaunchKernelGGL(kern, dim3(ga.total), dim3(512), BIG_LDS, st, ga);
   return check_launch("gemm_group_tn");
 }
 

@@ -299,27 +299,13 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs g, int tiles_m, i
                                                                         (int)gridDim.y, false);
 }
 
-// 160 KiB of dynamic LDS needs the attribute on every DEVICE the kernel is launched on (the flag is a bit per device, not one per
-// process), and a refused attribute must not leave a launch that cannot start: false -> the planner's lockstep kernel.
-static bool pp_lds_attr(const void* kern, uint64_t& done) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  if (done >> dev & 1) return true;
-  if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  done |= 1ull << dev;
-  return true;
-}
-
 template <int TM, bool AK, bool BKM, bool OF, bool F16, int NKS, bool STAGGER, bool PRIO, int ABL = 0, int NDL = 4>
 static bool launch_pp(const GemmArgs& g, int batch, int splits, int ksplit, float* ws, hipStream_t st) {
   constexpr int BM = 64 * TM, BN = 256;
   const int tiles_m = cdiv(g.M, BM), tiles_n = cdiv(g.N, BN);
   auto kern = gemm_pp_kernel<TM, AK, BKM, OF, F16, NKS, STAGGER, PRIO, ABL, NDL>;
   static uint64_t attr_done = 0;   // per instantiation, one bit per device
-  if (!pp_lds_attr((const void*)kern, attr_done)) return false;    // (the caller falls back to the lockstep loop)
+  if (!gemm_lds_attr((const void*)kern, PP_LDS, attr_done)) return false;    // (the caller falls back to the lockstep loop)
   dim3 grid(tiles_m * tiles_n, splits, batch), block(512);
   hipLaunchKernelGGL(kern, grid, block, PP_LDS, st, g, tiles_m, tiles_n, ksplit, ws);
   return true;
@@ -366,23 +352,22 @@ static bool launch_pp_variant(int variant, const GemmArgs& g, int batch, int spl
   }
 }
 
-// Same tile / split-K / batch contract as launch_big_shape (gemm_mfma.hip); false: not a shape or variant this loop is built for (fp32
-// outputs and the k-major-B / m-major-A layout stay on the lockstep loop)
-bool gemm_pp_launch(int variant, const GemmArgs& g, int batch, int tm, int splits, int ksplit, float* ws, hipStream_t st, bool f16) {
-  const bool ak = !g.transA, bk = g.transB != 0, of = (g.flags & OFA_GEMM_OUT_F32) != 0;
-  if (of || (!ak && bk)) return false;
-  if (!ak) tm = 4;
-#define PP_DISPATCH(TMV, AK, BKM) \
-  (f16 ? launch_pp_variant<TMV, AK, BKM, false, true>(variant, g, batch, splits, ksplit, ws, st) \
-       : launch_pp_variant<TMV, AK, BKM, false, false>(variant, g, batch, splits, ksplit, ws, st))
+// Same tile / split-K / batch contract as the lockstep loop (launch_plan, gemm_mfma.hip).  gemm_plan sends 16-bit outputs with a k-major A
+// or two m-major operands; the all-k-major form is built in the debug library only (measured level with the lockstep loop: experiments).
+// false: refused (the LDS attribute, or a variant this build does not have) -- the caller runs the lockstep loop.
 #ifdef OFA_DEBUG_SWITCHES
-  if (ak && bk) return tm == 3 ? PP_DISPATCH(3, true, true) : PP_DISPATCH(4, true, true);     // (NT: measured level with the lockstep loop; experiments only)
+constexpr bool PP_NT = true;
 #else
-  if (ak && bk) return false;
+constexpr bool PP_NT = false;
 #endif
-  if (ak && !bk) return tm == 3 ? PP_DISPATCH(3, true, false) : PP_DISPATCH(4, true, false);
-  return PP_DISPATCH(4, false, false);
-#undef PP_DISPATCH
+bool gemm_pp_launch(int variant, const GemmArgs& g, int batch, int tm, int splits, int ksplit, float* ws, hipStream_t st, bool f16) {
+  return with_layout(g, f16, [&](auto ak, auto bk, auto of, auto h) {
+    if constexpr (of || (!ak && bk) || (ak && bk && !PP_NT)) return false;
+    else if constexpr (ak) {
+      if (tm == 3) return launch_pp_variant<3, ak, bk, false, h>(variant, g, batch, splits, ksplit, ws, st);
+      return launch_pp_variant<4, ak, bk, false, h>(variant, g, batch, splits, ksplit, ws, st);
+    } else return launch_pp_variant<4, false, false, false, h>(variant, g, batch, splits, ksplit, ws, st);
+  });
 }
 
 // Grouped weight gradients (ofa_gemm_group_tn) on the same loop: both operands m-major, 256 x 256 tiles
@@ -400,7 +385,7 @@ template <bool F16, int NKS, bool STAGGER, bool PRIO, int NDL = 4>
 static bool launch_group_pp(const GroupArgs& ga, hipStream_t st) {
   auto kern = gemm_group_tn_pp_kernel<F16, NKS, STAGGER, PRIO, NDL>;
   static uint64_t attr_done = 0;   // per instantiation, one bit per device
-  if (!pp_lds_attr((const void*)kern, attr_done)) return false;    // (the caller launches gemm_group_tn_kernel)
+  if (!gemm_lds_attr((const void*)kern, PP_LDS, attr_done)) return false;    // (the caller launches gemm_group_tn_kernel)
   hipLaunchKernelGGL(kern, dim3(ga.total), dim3(512), PP_LDS, st, ga);
   return true;
 }
