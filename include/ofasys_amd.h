@@ -597,6 +597,29 @@ int ofa_beam_select(const void* ws, int bsz, int K, int V, int step, int max_len
                     int64_t score_ld, int* ignore, int* done, int* nfin, int64_t* reorder, int64_t* fin_tok, float* fin_pos,
                     int64_t fin_ld, float* fin_score, int* fin_len, int* fin_cnt, void* stream);
 
+/* ---- closed-set scoring (csrc/closed_set_score.hip): TraverseTask.inference (task/traverse_task.py:63-110) without the
+ * full-vocabulary projection.  The answer trie arrives as flat int arrays (ofasys_amd/traverse.py TraversePlan): N nodes, E edges
+ * grouped by node (node_edge_off [N + 1], edge_token [E], edge_node [E]), per node the (answer, position) whose decoder row
+ * holds its hidden state (rep_ans / rep_pos [N]), per answer its path (path_off [C + 1], path_edge [P]) and the work items
+ * ([n_items, 3]: node, first edge, one past the last; a few edges of one node each).
+ * h: decoder features, row (b * chunk + (answer - c0)) * T + position, ld_h elements apart, D valid; W: output projection rows
+ * [V, ld_w]; bias [V] or NULL; h, W and bias share `dtype`; rows 16-byte aligned.  ws: ofa_closed_set_ws_bytes(bsz, E, N) bytes
+ * (edge logits fp32 [bsz, E], then node log-sum-exps fp32 [bsz, N]).
+ * ofa_closed_set_edge_logits: z[b, e] = h[b, rep(node(e))] . W[edge_token[e]] (+ bias), fp32 accumulation, for the items given
+ * whose node's representative answer lies in [c0, c0 + chunk) -- callable once per chunk of answers.
+ * ofa_closed_set_reduce: the node log-sum-exps and scores[b, c] = sum over path(c) of (z - lse), fp32 [bsz, C] (two launches).
+ * ofa_closed_set_score: both, for features that hold every answer (chunk = C, c0 = 0): three launches, no host synchronisation. */
+int64_t ofa_closed_set_ws_bytes(int bsz, int E, int N);
+int ofa_closed_set_edge_logits(const void* h, int64_t ld_h, int dtype, const void* W, int64_t ld_w, const void* bias, int D, int V,
+                               int bsz, int chunk, int T, int c0, const int* items, int n_items, const int* edge_token,
+                               const int* rep_ans, const int* rep_pos, int N, int E, void* ws, void* stream);
+int ofa_closed_set_reduce(int bsz, int C, int N, int E, int P, const int* node_edge_off, const int* edge_node, const int* path_off,
+                          const int* path_edge, void* ws, float* scores, void* stream);
+int ofa_closed_set_score(const void* h, int64_t ld_h, int dtype, const void* W, int64_t ld_w, const void* bias, int D, int V,
+                         int bsz, int C, int Tmax, int N, int E, int P, const int* items, int n_items, const int* node_edge_off,
+                         const int* edge_token, const int* edge_node, const int* rep_ans, const int* rep_pos, const int* path_off,
+                         const int* path_edge, void* ws, float* scores, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1304,3 +1304,54 @@ def beam_select(ws, st, K, V, step, max_len, eos=2, unk=3, unk_penalty=0.0, norm
                scores.stride(0), ptr(st["ignore"]), ptr(st["done"]), ptr(st["nfin"]), ptr(st["reorder"]), ptr(st["fin_tok"]),
                ptr(st["fin_pos"]), st["fin_tok"].stride(1), ptr(st["fin_score"]), ptr(st["fin_len"]), ptr(st["fin_cnt"]),
                stream())
+
+
+# ------------------------------------------------------------------ closed-set scoring (csrc/closed_set_score.hip)
+def closed_set_ws_bytes(bsz, E, N):
+    return int(lib().cdll.ofa_closed_set_ws_bytes(int(bsz), int(E), int(N)))
+
+
+def _closed_set_proj(h2d, weight, bias):
+    if h2d.dim() != 2 or weight.dim() != 2 or h2d.stride(1) != 1 or weight.stride(1) != 1:
+        raise OfaError("closed_set: features [rows, D] and projection rows [V, D] must have a contiguous last dimension")
+    if weight.dtype != h2d.dtype or (bias is not None and bias.dtype != h2d.dtype):
+        raise OfaError(f"closed_set: features ({h2d.dtype}), projection ({weight.dtype}) and bias must share one dtype")
+    if weight.shape[1] != h2d.shape[1] or (bias is not None and (bias.numel() != weight.shape[0] or not bias.is_contiguous())):
+        raise OfaError("closed_set: projection [V, D] / bias [V] do not match the features' width")
+
+
+def closed_set_edge_logits(h2d, weight, bias, plan, bsz, chunk, T, c0, items, ws):
+    """Stage 1 for one chunk of answers: h2d [bsz * chunk * T, D] holds the decoder features of answers c0 .. c0 + chunk - 1
+    (row (b * chunk + c - c0) * T + t); `items` int32 [n, 3] is the slice of the plan's work items whose nodes are represented in
+    the chunk; `plan`: the device arrays of a traverse.TraversePlan; ws: closed_set_ws_bytes(bsz, E, N) bytes."""
+    _closed_set_proj(h2d, weight, bias)
+    if h2d.shape[0] != bsz * chunk * T:
+        raise OfaError(f"closed_set_edge_logits: {h2d.shape[0]} feature rows for bsz={bsz} x chunk={chunk} x T={T}")
+    lib().call("ofa_closed_set_edge_logits", ptr(h2d), h2d.stride(0), dtype_code(h2d), ptr(weight), weight.stride(0), ptr(bias),
+               h2d.shape[1], weight.shape[0], int(bsz), int(chunk), int(T), int(c0), ptr(items), items.shape[0],
+               ptr(plan["edge_token"]), ptr(plan["rep_ans"]), ptr(plan["rep_pos"]), plan["N"], plan["E"], ptr(ws), stream())
+
+
+def closed_set_reduce(plan, bsz, ws, scores):
+    """Stages 2 and 3 over the edge logits in `ws`: scores fp32 [bsz, C] (contiguous)."""
+    if scores.dtype != torch.float32 or not scores.is_contiguous() or scores.numel() != bsz * plan["C"]:
+        raise OfaError("closed_set_reduce: scores must be a contiguous float32 [bsz, C]")
+    lib().call("ofa_closed_set_reduce", int(bsz), plan["C"], plan["N"], plan["E"], plan["P"], ptr(plan["node_edge_off"]),
+               ptr(plan["edge_node"]), ptr(plan["path_off"]), ptr(plan["path_edge"]), ptr(ws), ptr(scores), stream())
+
+
+def closed_set_score(h2d, weight, bias, plan, bsz, ws=None):
+    """All three stages for features that hold every answer: h2d [bsz * C * Tmax, D] -> scores fp32 [bsz, C]."""
+    _closed_set_proj(h2d, weight, bias)
+    C, T = plan["C"], plan["Tmax"]
+    if h2d.shape[0] != bsz * C * T:
+        raise OfaError(f"closed_set_score: {h2d.shape[0]} feature rows for bsz={bsz} x C={C} x Tmax={T}")
+    if ws is None:
+        ws = torch.empty((closed_set_ws_bytes(bsz, plan["E"], plan["N"]) + 3) // 4, dtype=torch.float32, device=h2d.device)
+    scores = torch.empty(bsz, C, dtype=torch.float32, device=h2d.device)
+    items = plan["items"]
+    lib().call("ofa_closed_set_score", ptr(h2d), h2d.stride(0), dtype_code(h2d), ptr(weight), weight.stride(0), ptr(bias),
+               h2d.shape[1], weight.shape[0], int(bsz), C, T, plan["N"], plan["E"], plan["P"], ptr(items), items.shape[0],
+               ptr(plan["node_edge_off"]), ptr(plan["edge_token"]), ptr(plan["edge_node"]), ptr(plan["rep_ans"]),
+               ptr(plan["rep_pos"]), ptr(plan["path_off"]), ptr(plan["path_edge"]), ptr(ws), ptr(scores), stream())
+    return scores

@@ -1,0 +1,214 @@
+"""Closed-set inference (reference: task/traverse_task.py, exported as `ofasys.task.TraverseTask`): score every answer of a
+closed set under teacher forcing, each position's distribution restricted to the answer trie's next layer, and return the best
+answer.  The route for the tasks `Task.generator` refuses (an instruction whose target carries `closed_set`: VQA with an answer
+list, classification, SNLI-VE).
+
+The reference projects every (answer, position) onto the vocabulary, masks, takes a full log-softmax and gathers.  Here the trie is
+flattened once on the host (`TraversePlan`) and the device computes one dot product per trie EDGE, one log-sum-exp per trie NODE
+and one short sum per answer (csrc/closed_set_score.hip); the [rows, T, V] logits never exist.  The decoder still runs per answer
+(features only), in chunks of answers so that memory does not grow with the size of the closed set.
+"""
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import kernels as K
+from .preprocessor import ModalityType, Slot
+from .task import Task
+
+
+class TraversePlan:
+    """The answer trie as flat int32 arrays.  `answers`: token-id sequences without BOS / EOS, in label order.
+
+    nodes        distinct prefixes [bos] + answer[:t], t = 0 .. len, numbered in order of first appearance (node 0 = [bos]); so the
+                 nodes first reached by answers c0 .. c1 - 1 are one contiguous range, and so are their edges and work items
+    edges        CSR by node: node_edge_off [N + 1], edge_token [E], edge_node [E]; an answer's last edge is EOS
+    rep_ans/pos  [N] the lowest answer index passing through the node and the position t: the decoder row holding its state
+    paths        path_off [C + 1], path_edge [P]: the len + 1 edges of every answer
+    items        [I, 3] (node, first edge, one past the last): the edges in pieces of at most ITEM_EDGES edges of one node -- the
+                 unit of work of the edge kernel (the root's ~C edges spread over C / ITEM_EDGES workgroups)
+    prev_output_tokens / target   [C, Tmax] as traverse_task.py:32-61 pads them (BOS first / EOS last, <pad> after)
+    """
+
+    ITEM_EDGES = 8
+
+    def __init__(self, answers: Sequence[Sequence[int]], bos: int, eos: int, pad: int):
+        answers = [[int(t) for t in a] for a in answers]
+        if len(answers) == 0:
+            raise ValueError("TraversePlan: the closed set is empty")
+        self.C = C = len(answers)
+        self.bos, self.eos, self.pad = int(bos), int(eos), int(pad)
+        self.lengths = np.array([len(a) + 1 for a in answers], np.int32)
+        self.Tmax = T = int(self.lengths.max())
+        self.prev_output_tokens = np.full((C, T), pad, np.int64)
+        self.target = np.full((C, T), pad, np.int64)
+        node_of = {(): 0}
+        rep = [(0, 0)]
+        children: List[Dict[int, int]] = [{}]                # node -> {token: child node or -1 (EOS)}, insertion order as Trie
+        for c, a in enumerate(answers):
+            self.prev_output_tokens[c, :len(a) + 1] = [bos] + a
+            self.target[c, :len(a) + 1] = a + [eos]
+            for t in range(1, len(a) + 1):
+                key = tuple(a[:t])
+                if key not in node_of:
+                    node_of[key] = len(rep)
+                    rep.append((c, t))
+                    children.append({})
+                children[node_of[tuple(a[:t - 1])]].setdefault(a[t - 1], node_of[key])
+            children[node_of[tuple(a)]].setdefault(eos, -1)
+        self.N = N = len(rep)
+        self.rep_ans = np.array([r[0] for r in rep], np.int32)
+        self.rep_pos = np.array([r[1] for r in rep], np.int32)
+        self.node_edge_off = np.zeros(N + 1, np.int32)
+        self.node_edge_off[1:] = np.cumsum([len(ch) for ch in children])
+        self.E = E = int(self.node_edge_off[-1])
+        self.edge_token = np.array([tok for ch in children for tok in ch], np.int32)
+        self.edge_node = np.repeat(np.arange(N, dtype=np.int32), np.diff(self.node_edge_off))
+        edge_of = [{tok: int(self.node_edge_off[n]) + i for i, tok in enumerate(ch)} for n, ch in enumerate(children)]
+        self.path_off = np.zeros(C + 1, np.int32)
+        self.path_off[1:] = np.cumsum(self.lengths)
+        path = []
+        for a in answers:
+            for t, tok in enumerate(a + [eos]):
+                path.append(edge_of[node_of[tuple(a[:t])]][tok])
+        self.path_edge = np.array(path, np.int32)
+        self.P = len(path)
+        items = []
+        for n in range(N):
+            lo, hi = int(self.node_edge_off[n]), int(self.node_edge_off[n + 1])
+            items.extend((n, e, min(e + self.ITEM_EDGES, hi)) for e in range(lo, hi, self.ITEM_EDGES))
+        self.items = np.array(items, np.int32).reshape(-1, 3)
+        assert E == len(self.edge_token) == len(self.edge_node) and int(self.path_off[-1]) == self.P
+
+    def allowed(self, c: int, t: int) -> List[int]:
+        """The tokens position t of answer c may take: Trie.get_next_layer(prev_output_tokens[c, :t + 1])."""
+        n = self.node_of(c, t)
+        return self.edge_token[self.node_edge_off[n]:self.node_edge_off[n + 1]].tolist()
+
+    def node_of(self, c: int, t: int) -> int:
+        """The node reached by the first t tokens of answer c (t <= its length): the node of its t-th path edge."""
+        return int(self.edge_node[self.path_edge[self.path_off[c] + t]])
+
+    def chunk_items(self, c0: int, c1: int):
+        """The rows [i0, i1) of `items` whose node is represented by an answer in [c0, c1), and the chunk's longest row."""
+        n0, n1 = np.searchsorted(self.rep_ans, [c0, c1], side="left")        # rep_ans is non-decreasing
+        i0, i1 = np.searchsorted(self.items[:, 0], [n0, n1], side="left")
+        return int(i0), int(i1), int(self.lengths[c0:c1].max())
+
+    def to_device(self, device) -> Dict[str, object]:
+        """The arrays the kernels read (kernels.closed_set_*), on `device`, plus the padded decoder inputs."""
+        d = {k: torch.from_numpy(getattr(self, k)).to(device) for k in
+             ("node_edge_off", "edge_token", "edge_node", "rep_ans", "rep_pos", "path_off", "path_edge", "items",
+              "prev_output_tokens")}
+        d.update(C=self.C, N=self.N, E=self.E, P=self.P, Tmax=self.Tmax)
+        return d
+
+
+class TraverseTask(Task):
+    """`Task` for closed-set targets.  `max_rows`: cap on the decoder rows (sentences x answers) of one chunk; the answers are
+    processed `max(1, max_rows // bsz)` at a time, so device memory follows the cap and not the size of the closed set.  The
+    default, 2048 rows, keeps the decoder's GEMMs at a few thousand rows x Tmax -- large enough to fill the device at OFA-base
+    size, while activations stay in the tens of MB."""
+
+    def __init__(self, cfg=None, max_rows: int = 2048, **kwargs):
+        super().__init__(cfg, **kwargs)
+        if max_rows < 1:
+            raise ValueError("TraverseTask: max_rows must be >= 1")
+        self.max_rows = int(max_rows)
+        self.plan: Optional[TraversePlan] = None
+        self.index2ans: Dict[int, object] = {}
+        self._dev: Dict[torch.device, Dict[str, object]] = {}
+        self._buf: Dict[tuple, Dict[str, torch.Tensor]] = {}
+
+    def initialize(self, global_dict, closed_set=None, **kwargs):
+        """As Task.initialize, then the plan of the text preprocessor's closed set: `closed_set` (answer strings or token-id
+        sequences, a list or a dict answer -> label), else cfg.text.ans2label, else what an earlier initialize + the text
+        preprocessor's prepare_for_generation left."""
+        before = self.general_preprocess.name2pre["text"].ans2label_dict if self.general_preprocess is not None else None
+        super().initialize(global_dict, **kwargs)
+        pre = self.general_preprocess.name2pre["text"]
+        if closed_set is None and not pre.ans2label_dict:
+            closed_set = before
+        if closed_set is not None:
+            pre.prepare_for_generation(closed_set)
+        if not pre.ans2label_dict:
+            raise ValueError(f"task {self.name}: TraverseTask needs a closed set -- pass initialize(global_dict, closed_set=[...]), "
+                             "set cfg.text.ans2label to the JSON of an answer -> label dict, or call the text preprocessor's "
+                             "prepare_for_generation(closed_set) and initialize again")
+        self.build_plan()
+
+    def build_plan(self):
+        pre, d = self.general_preprocess.name2pre["text"], self.global_dict
+        answers = list(pre.ans2label_dict.keys() if isinstance(pre.ans2label_dict, dict) else pre.ans2label_dict)
+        self.index2ans = dict(enumerate(answers))
+        ids = [pre.encode(a).tolist() if isinstance(a, str) else [int(t) for t in a] for a in answers]
+        if any(t < 0 or t >= len(d) for a in ids for t in a):
+            raise ValueError(f"task {self.name}: the closed set holds token ids outside the dictionary (size {len(d)})")
+        self.plan = TraversePlan(ids, d.bos(), d.eos(), d.pad())
+        self._dev, self._buf = {}, {}
+
+    # ------------------------------------------------------------------ device state
+    def _plan_on(self, device):
+        if device not in self._dev:
+            self._dev[device] = self.plan.to_device(device)
+        return self._dev[device]
+
+    def _buffers(self, bsz, device):
+        key = (bsz, device)
+        if key not in self._buf:                              # the pass's own scratch: allocated eagerly, never inside a capture
+            n = (K.closed_set_ws_bytes(bsz, self.plan.E, self.plan.N) + 3) // 4
+            self._buf[key] = {"ws": torch.empty(n, dtype=torch.float32, device=device),
+                              "scores": torch.empty(bsz, self.plan.C, dtype=torch.float32, device=device)}
+        return self._buf[key]
+
+    @staticmethod
+    def output_projection(model):
+        """(weight [V, D], bias or None) of the decoder's text output projection: the tied token embedding, or the adaptor's own
+        Linear (adaptor/text.py:72)."""
+        ga = model.decoder.adaptor
+        text = ga.name2adaptor["text"]
+        if text.share_input_output_embed:
+            return ga.embed_tokens.weight, None
+        proj = text.output_projection
+        return proj.weight, getattr(proj, "bias", None)
+
+    # ------------------------------------------------------------------ scoring (traverse_task.py:63-110)
+    @torch.no_grad()
+    def score(self, model, sample) -> torch.Tensor:
+        """log p(answer | source) under the trie constraint for every answer: float32 [bsz, C] on the CPU."""
+        if self.plan is None:
+            raise ValueError(f"task {self.name}: initialize(global_dict) first")
+        model.eval()
+        plan = self.plan
+        src = [s for s in sample["net_input"]["slots"] if s.is_src]
+        enc = model.encoder(src)
+        out = enc["encoder_out"][0]
+        bsz, device = out.shape[1], out.device
+        dev, buf = self._plan_on(device), self._buffers(bsz, device)
+        weight, bias = self.output_projection(model)
+        if int(plan.edge_token.max()) >= weight.shape[0]:
+            raise ValueError(f"the closed set holds token id {int(plan.edge_token.max())}, the output projection has {weight.shape[0]} rows")
+        per = max(1, self.max_rows // bsz)
+        for c0 in range(0, plan.C, per):
+            c1 = min(plan.C, c0 + per)
+            i0, i1, T = plan.chunk_items(c0, c1)
+            if i1 == i0:                                      # only repeats of earlier answers: no new node
+                continue
+            n = c1 - c0
+            # rows ordered (sentence, answer) as the reference: encoder rows repeat_interleave'd, answers tiled
+            enc_c = model.encoder.reorder_encoder_out(enc, torch.arange(bsz, device=device).repeat_interleave(n))
+            prev = dev["prev_output_tokens"][c0:c1, :T].repeat(bsz, 1)
+            h, _ = model.decoder([Slot(ModalityType.TEXT, False, prev)], encoder_out=enc_c, features_only=True)
+            h2d = h.reshape(bsz * n * T, h.shape[-1])
+            if h2d.dtype != weight.dtype:
+                h2d = h2d.to(weight.dtype)
+            K.closed_set_edge_logits(h2d, weight, bias, dev, bsz, n, T, c0, dev["items"][i0:i1], buf["ws"])
+        K.closed_set_reduce(dev, bsz, buf["ws"], buf["scores"])
+        return buf["scores"].cpu()
+
+    def inference(self, model, sample, **kwargs) -> List[object]:
+        """The best answer of the closed set per sentence (ties to the lower answer index).  The model is left in eval mode."""
+        scores = self.score(model, sample)
+        best = np.argmax(scores.numpy(), axis=1)              # numpy: the first maximum
+        return [self.index2ans[int(i)] for i in best]
