@@ -620,6 +620,31 @@ int ofa_closed_set_score(const void* h, int64_t ld_h, int dtype, const void* W, 
                          const int* edge_token, const int* edge_node, const int* rep_ans, const int* rep_pos, const int* path_off,
                          const int* path_edge, void* ws, float* scores, void* stream);
 
+/* ---- trie-constrained beam search (csrc/trie_beam.hip): a beam-search step whose rows are restricted to the children of the
+ * answer trie's node they have reached (generator/sequence_generator.py:729-741), without the [rows, V] output projection.
+ * The trie is a TraversePlan's flat arrays (N nodes, E edges: node_edge_off [N + 1], edge_token [E], edge_child [E]: the node an
+ * edge leads to, -1 for an EOS edge; max_degree: the largest number of edges of one node).  node int [rows]: the trie node of every
+ * row, -1 = dead (its whole distribution is -inf).
+ * ofa_trie_beam_topk replaces ofa_beam_topk: h [rows, ld_h] are the decoder's last-position features, W [V, ld_w] / bias [V] or NULL
+ * the output projection (one dtype, rows 16-byte aligned); per row one dot product per child edge of node[row] (fp32 accumulation,
+ * + bias, / temperature), the fp32 normaliser parts and the best 2K FINITE candidates after the post-normaliser masks of
+ * ofa_beam_topk, written in ofa_beam_topk's layout of ws (ofa_beam_ws_bytes(rows, V, K) bytes) for ofa_beam_select of the same
+ * step.  Grid (ofa_trie_beam_splits(max_degree, V), rows); a row with fewer than 2K finite candidates is completed with -inf
+ * candidates at the lowest token ids not listed, as torch.topk breaks the reference's ties.  At step 0 only beam 0 of a sentence
+ * is computed (the sentence pass reads no other).
+ * ofa_trie_beam_advance runs after ofa_beam_select: node[row] <- the child of node[reorder[row]] through tokens[row, step + 1]
+ * (dead: dead parent, score -inf, EOS edge); a sentence whose K slots are all ignored or at -inf gets done = 1 and bumps nfin.
+ * ofa_trie_beam_splits: the grid's x extent for a plan (0: invalid arguments). */
+int ofa_trie_beam_splits(int max_degree, int V);
+int ofa_trie_beam_topk(const void* h, int64_t ld_h, int dtype, const void* W, int64_t ld_w, const void* bias, int D, int V,
+                       int rows, int K, const int* node, const int* node_edge_off, const int* edge_token, int N, int E,
+                       int max_degree, float temperature, int step, int min_len, int max_len, int pad, int unk, int eos,
+                       float unk_penalty, int ngram, const int64_t* tokens, int64_t tok_ld, const int* done, void* ws,
+                       void* stream);
+int ofa_trie_beam_advance(int* node, const int* node_edge_off, const int* edge_token, const int* edge_child, int N, int E,
+                          int bsz, int K, int step, const int64_t* tokens, int64_t tok_ld, int tok_cap, const float* scores,
+                          int64_t score_ld, const int* ignore, const int64_t* reorder, int* done, int* nfin, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,437 @@
+// Trie-constrained beam-search step for gfx950: the reference's generator with a `constraint_trie`
+// (generator/sequence_generator.py:729-741: every row's logits are masked to the children of the trie node its prefix has
+// reached, then log-softmax) without the [rows, V] output projection.  After the mask a row's distribution is a log-softmax over
+// the CHILDREN OF ONE TRIE NODE, so the only logits that have to exist are one dot product per child edge (the algebra of
+// closed_set_score.hip, per decoding step instead of under teacher forcing).  The trie arrives as the flat arrays of
+// ofasys_amd/traverse.py TraversePlan; next to the beam state lives one trie node per row (int32 [rows], -1 = dead: off the
+// trie, past an EOS edge, or at a score of -inf).
+//
+// 1. ofa_trie_beam_topk -- the row pass, replacing ofa_beam_topk.  Grid (Su, rows): workgroup `split` of a row takes edges
+//    [split * epw, (split + 1) * epw) of the row's node, epw = 256 * p edges per workgroup and Su = ceil(max_degree / epw) fixed per
+//    plan (p the smallest count for which Su fits the sentence pass's layout, below), so a captured grid never changes.  The
+//    hidden row is staged once in LDS as raw 16-byte vectors; 16 lanes share an edge: they gather W[edge_token[e]] with 16-byte
+//    loads, accumulate in fp32 and reduce with DPP inside their row of 16 lanes (four edges per wave in flight); + bias,
+//    / temperature.  The workgroup then writes IN ofa_beam_topk'S WORKSPACE LAYOUT AND ORDER (value descending, token ascending)
+//      - its (max, sum exp) part of the fp32 normaliser -- NaN for a dead row or a NaN logit, which ofa_beam_select turns into an
+//        all -inf row;
+//      - its best 2K candidates after the reference's post-normaliser masks in order (:296-343: EOS below min_len, NaN, PAD, unk
+//        penalty, step >= max_len, n-gram bans).
+//    so that ofa_beam_select (beam_search.hip) consumes them unchanged; the layout's parts Su .. splits(V) - 1 are written empty.
+//    Only FINITE candidates are listed.  Everything else of the row is -inf in the reference (non-children by the mask, children
+//    by the masks above), and torch.topk breaks those ties towards the lower index: split 0 completes its list to 2K entries with
+//    -inf candidates at the lowest token ids it has not listed (fewer than 2K finite candidates in split 0 means a node of fewer
+//    than epw edges, i.e. the other splits are empty; with a larger node a refill can repeat a token another split lists as
+//    finite -- only the token of a -inf beam can differ from the reference then, which nothing observes).
+// 2. ofa_beam_select runs as it is.
+// 3. ofa_trie_beam_advance -- one workgroup per sentence, after the sentence pass: every new active row takes the child of its
+//    parent's node (read through `reorder`; all K old nodes are read into LDS before any is written) through the chosen token;
+//    dead if the parent was dead, the score is -inf or the edge is EOS.  A sentence whose K active slots are all ignored or at
+//    -inf is marked done and the all-finished counter bumped: nothing can be finalised from such slots (:361 finalises finite
+//    scores only), so the results are the reference's without the max_len + 1 - depth empty steps it runs.
+// No host synchronisation, fixed addresses, workspace passed in.  Every index read from the plan or the state is range-checked
+// before it addresses memory (an invalid node is a dead row, an invalid token a NaN logit).
+#include "common.h"
+
+namespace ofa {
+
+constexpr int TB_MAX_K = 16;              // = BEAM_MAX_K of beam_search.hip
+constexpr int TB_THREADS = 256;
+constexpr int TB_CHUNK = 4096;            // = BEAM_CHUNK: vocabulary columns per part of the sentence pass's layout
+constexpr int TB_BAN_MAX = 256;           // n-gram bans of one row: at most step + 1
+constexpr int TB_LDS_MAX = 65536;
+
+static inline int tb_layout_splits(int V) { return (V + TB_CHUNK - 1) / TB_CHUNK; }
+// edges per workgroup: the smallest multiple of 256 for which ceil(max_degree / epw) parts fit the layout (max_degree <= V: <= 4096)
+static inline int tb_edges_per_wg(int max_degree, int V) {
+  const int S = tb_layout_splits(V);
+  int p = 1;
+  while (cdiv(max_degree, TB_THREADS * p) > S) ++p;
+  return TB_THREADS * p;
+}
+
+// sum over the 16 lanes of a DPP row; every lane of the row receives it
+__device__ __forceinline__ float row16_sum(float v) {
+#ifndef OFA_WAVE_REDUCE_SHFL
+  v += dpp_f<0xB1, 0xf>(0.f, v);          // quad_perm [1,0,3,2]
+  v += dpp_f<0x4E, 0xf>(0.f, v);          // quad_perm [2,3,0,1]
+  v += dpp_f<0x141, 0xf>(0.f, v);         // row_half_mirror
+  v += dpp_f<0x140, 0xf>(0.f, v);         // row_mirror
+#else
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 16);
+#endif
+  return v;
+}
+
+// wave arg-max of (key desc, idx asc) over the lanes; NaN keys are empty.  Returns false when every lane is empty.
+__device__ __forceinline__ bool tb_wave_argmax(float key, int idx, float& mx, int& mi) {
+  mx = wave_max(key);
+  if (mx != mx) return false;
+  const float neg = (key == mx) ? -(float)idx : -INFINITY;     // indices < 2^24: exact as float
+  mi = (int)(-wave_max(neg));
+  return true;
+}
+
+struct TrieTopkArgs {
+  const void* h; int64_t ld_h;
+  const void* W; int64_t ld_w; const void* bias;
+  int D, V, rows, K, S, Su, epw;
+  const int* node; const int* node_edge_off; const int* edge_token; int N, E;
+  float temperature; int step, min_len, max_len, pad, unk, eos; float unk_pen;
+  int ngram; const int64_t* tokens; int64_t tok_ld;
+  const int* done;
+  float* stats; float* cval; int* ctok;        // [rows, S, 2] / [rows, S, 2K] / [rows, S, 2K]
+};
+
+struct TrieTopkScratch {                  // the row pass's fixed LDS scratch, at the start of its dynamic region
+  int banl[TB_BAN_MAX];
+  float lkey[4][2 * TB_MAX_K], lval[4][2 * TB_MAX_K];
+  int ltok[4][2 * TB_MAX_K];
+  int mtok[2 * TB_MAX_K];
+  float red_m[4], red_s[4];
+  int red_nan[4];
+  int nban, ngot;
+  float unk_val;
+  int pad_;
+};
+static_assert(sizeof(TrieTopkScratch) % 16 == 0, "the staged row behind the scratch is read with 16-byte LDS loads");
+
+template <typename T>
+__global__ __launch_bounds__(TB_THREADS) void trie_beam_topk_kernel(TrieTopkArgs a) {
+  constexpr int NV = Vec<T>::N;
+  const int split = blockIdx.x, row = blockIdx.y;
+  if (a.done && a.done[row / a.K]) return;
+  if (a.step == 0 && row % a.K != 0) return;                  // the sentence pass reads beam 0 only at step 0
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K2 = 2 * a.K, nv = a.D / NV;
+  // all LDS scratch lives in the dynamic region, so its base -- and with it the 16-byte reads of the staged row -- stays 16-byte
+  // aligned whatever the fixed scratch adds up to (static __shared__ in front of an extern region shifts its base unpadded)
+  extern __shared__ __attribute__((aligned(16))) uint4 tb_smem[];
+  TrieTopkScratch& sh = *(TrieTopkScratch*)tb_smem;
+  uint4* hrow = tb_smem + sizeof(TrieTopkScratch) / 16;       // [D / NV] the hidden row, raw
+  float* key = (float*)(hrow + nv);                           // [epw] logits, then ordering keys (NaN: no candidate)
+  int* tokl = (int*)(key + a.epw);                            // [epw] their tokens
+  int (&banl)[TB_BAN_MAX] = sh.banl;
+  int& nban = sh.nban;
+  int& ngot = sh.ngot;
+  float& unk_val = sh.unk_val;
+  float (&red_m)[4] = sh.red_m;
+  float (&red_s)[4] = sh.red_s;
+  int (&red_nan)[4] = sh.red_nan;
+  float (&lkey)[4][2 * TB_MAX_K] = sh.lkey;
+  float (&lval)[4][2 * TB_MAX_K] = sh.lval;
+  int (&ltok)[4][2 * TB_MAX_K] = sh.ltok;
+  int (&mtok)[2 * TB_MAX_K] = sh.mtok;
+
+  const int64_t part = (int64_t)row * a.S + split;
+  float* st = a.stats + part * 2;
+  float* ov = a.cval + part * K2;
+  int* ot = a.ctok + part * K2;
+  // ---- the layout's parts this plan never uses: empty
+  if (split == 0) {
+    for (int e = tid; e < (a.S - a.Su) * K2; e += TB_THREADS) {
+      const int64_t o = ((int64_t)row * a.S + a.Su) * K2 + e;
+      a.cval[o] = -INFINITY;
+      a.ctok[o] = -1;
+    }
+    for (int s = a.Su + tid; s < a.S; s += TB_THREADS) {
+      a.stats[((int64_t)row * a.S + s) * 2] = -INFINITY;
+      a.stats[((int64_t)row * a.S + s) * 2 + 1] = 0.f;
+    }
+  }
+  // ---- the row's node and this workgroup's slice of its edges (all uniform)
+  const int nd = a.node[row];
+  int e0 = 0, e1 = 0;
+  bool live = (unsigned)nd < (unsigned)a.N;
+  if (live) {
+    e0 = a.node_edge_off[nd];
+    e1 = a.node_edge_off[nd + 1];
+    live = e0 >= 0 && e1 > e0 && e1 <= a.E;
+  }
+  const int b0 = e0 + split * a.epw;
+  const int cnt = live ? max(0, min(a.epw, e1 - b0)) : 0;
+  if (cnt == 0) {                                             // a dead row (NaN normaliser: the whole row is -inf) or an empty slice
+    if (tid == 0) {
+      st[0] = (!live && split == 0) ? __int_as_float(0x7fc00000) : -INFINITY;
+      st[1] = 0.f;
+    }
+    for (int r = tid; r < K2; r += TB_THREADS) { ov[r] = -INFINITY; ot[r] = -1; }
+    return;
+  }
+  const uint4* hsrc = (const uint4*)((const T*)a.h + (int64_t)row * a.ld_h);
+  for (int v = tid; v < nv; v += TB_THREADS) hrow[v] = hsrc[v];
+  if (tid == 0) { nban = 0; unk_val = 0.f; }
+  __syncthreads();
+  // ---- n-gram bans of this row (history tokens[row, 0..step]): every earlier occurrence of the last n-1 tokens bans its successor
+  const int ng = a.ngram;
+  if (ng > 0 && a.step + 2 - ng >= 0) {
+    const int64_t* hist = a.tokens + (int64_t)row * a.tok_ld;
+    const int last = a.step - ng + 2;
+    for (int i = tid; i + ng - 1 <= a.step; i += TB_THREADS) {
+      bool match = true;
+      for (int q = 0; q < ng - 1; ++q) match = match && (hist[i + q] == hist[last + q]);
+      if (match) {
+        const int q = atomicAdd(&nban, 1);
+        if (q < TB_BAN_MAX) banl[q] = (int)hist[i + ng - 1];
+      }
+    }
+  }
+  // ---- one dot product per edge: 16 lanes per edge, four edges per wave at a time
+  const int grp = lane >> 4, gl = lane & 15;
+  for (int base = wave * 4; base < cnt; base += 16) {         // (wave-uniform bound: all 64 lanes reach the DPP reduction)
+    const int i = base + grp;
+    const int tok = i < cnt ? a.edge_token[b0 + i] : -1;
+    const bool ok = (unsigned)tok < (unsigned)a.V;
+    float acc = 0.f;
+    if (ok) {
+      const uint4* w = (const uint4*)((const T*)a.W + (int64_t)tok * a.ld_w);
+      for (int v = gl; v < nv; v += 16) {
+        float wf[NV], hf[NV];
+        unpack16<T>(w[v], wf);
+        unpack16<T>(hrow[v], hf);
+#pragma unroll
+        for (int q = 0; q < NV; ++q) acc = fmaf(wf[q], hf[q], acc);
+      }
+    }
+    acc = row16_sum(acc);
+    if (gl == 0 && i < cnt) {
+      float z = __int_as_float(0x7fc00000);
+      if (ok) {
+        z = acc;
+        if (a.bias) z += ld1<T>((const T*)a.bias + tok);
+        if (a.temperature != 1.f) z = z / a.temperature;
+      }
+      key[i] = z;
+      tokl[i] = tok;
+    }
+  }
+  __syncthreads();
+  // ---- this slice's part of the normaliser
+  float m = -INFINITY;
+  int has_nan = 0;
+  for (int i = tid; i < cnt; i += TB_THREADS) {
+    const float v = key[i];
+    if (v != v) has_nan = 1;
+    else m = fmaxf(m, v);
+  }
+  m = wave_max(m);
+  float s = 0.f;
+  if (m != -INFINITY)
+    for (int i = tid; i < cnt; i += TB_THREADS) {
+      const float v = key[i];
+      if (v == v) s += expf(v - m);
+    }
+  s = wave_sum(s);
+  has_nan = __any(has_nan) ? 1 : 0;
+  if (lane == 0) { red_m[wave] = m; red_s[wave] = s; red_nan[wave] = has_nan; }
+  __syncthreads();
+  if (tid == 0) {
+    const float M = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
+    float S = 0.f;
+    for (int w = 0; w < 4; ++w)
+      if (red_m[w] != -INFINITY) S += red_s[w] * expf(red_m[w] - M);
+    const bool bad = red_nan[0] | red_nan[1] | red_nan[2] | red_nan[3];
+    st[0] = bad ? __int_as_float(0x7fc00000) : M;
+    st[1] = S;
+  }
+  // ---- post-normaliser masks -> ordering keys; -inf is no candidate (entry i is read and written by thread i % 256 only)
+  const int nb = min(nban, TB_BAN_MAX);
+  for (int i = tid; i < cnt; i += TB_THREADS) {
+    float v = key[i];
+    const int c = tokl[i];
+    if (c == a.eos && a.step < a.min_len) v = -INFINITY;
+    if (v != v) v = -INFINITY;
+    if (c == a.pad) v = -INFINITY;
+    if (a.step >= a.max_len && c != a.eos) v = -INFINITY;
+    for (int q = 0; q < nb; ++q)
+      if (banl[q] == c) v = -INFINITY;
+    if (c == a.unk) { unk_val = v; v = v - a.unk_pen; }
+    key[i] = v == -INFINITY ? __int_as_float(0x7fc00000) : v;
+  }
+  // ---- per-wave top 2K, sorted by (key desc, token asc)
+  for (int it = 0; it < K2; ++it) {
+    float lb = __int_as_float(0x7fc00000);
+    int lc = 0x7fffffff, li = -1;
+    for (int i = tid; i < cnt; i += TB_THREADS) {
+      const float v = key[i];
+      if (v == v) {
+        const int c = tokl[i];
+        if (li < 0 || v > lb || (v == lb && c < lc)) { lb = v; lc = c; li = i; }
+      }
+    }
+    float mx; int mc;
+    if (!tb_wave_argmax(lb, lc, mx, mc)) {
+      if (lane == 0) for (int r = it; r < K2; ++r) { lkey[wave][r] = __int_as_float(0x7fc00000); ltok[wave][r] = -1; }
+      break;
+    }
+    if (li >= 0 && lc == mc) {
+      lkey[wave][it] = lb;
+      lval[wave][it] = mc == a.unk ? unk_val : lb;
+      ltok[wave][it] = mc;
+      key[li] = __int_as_float(0x7fc00000);
+    }
+  }
+  __syncthreads();
+  // ---- wave 0 merges the four sorted lists (<= 128 entries: two per lane)
+  if (wave == 0) {
+    float k0 = __int_as_float(0x7fc00000), k1 = k0;
+    int t0 = 0x7fffffff, t1 = 0x7fffffff;
+    const int x0 = lane, x1 = lane + 64;
+    if (x0 < 4 * K2 && ltok[x0 / K2][x0 % K2] >= 0) { k0 = lkey[x0 / K2][x0 % K2]; t0 = ltok[x0 / K2][x0 % K2]; }
+    if (x1 < 4 * K2 && ltok[x1 / K2][x1 % K2] >= 0) { k1 = lkey[x1 / K2][x1 % K2]; t1 = ltok[x1 / K2][x1 % K2]; }
+    int got = 0;
+    for (int it = 0; it < K2; ++it) {
+      const bool use0 = k0 == k0 && (!(k1 == k1) || k0 > k1 || (k0 == k1 && t0 < t1));
+      const float lb = use0 ? k0 : k1;
+      const int lt = use0 ? t0 : t1;
+      float mx; int mt;
+      if (!tb_wave_argmax(lb, lt, mx, mt)) break;
+      if (lb == lb && lt == mt) {
+        const int x = use0 ? x0 : x1;
+        ov[it] = lval[x / K2][x % K2];
+        ot[it] = mt;
+        mtok[it] = mt;
+        if (use0) k0 = __int_as_float(0x7fc00000); else k1 = __int_as_float(0x7fc00000);
+      }
+      ++got;
+    }
+    if (lane == 0) ngot = got;
+  }
+  __syncthreads();
+  // ---- fewer than 2K finite candidates: split 0 refills with -inf at the lowest token ids it has not listed, the others stay empty
+  if (tid == 0) {
+    const int got = ngot;
+    int t = 0;
+    for (int r = got; r < K2; ++r) {
+      int tok = -1;
+      if (split == 0) {
+        for (; t < a.V; ++t) {
+          bool used = false;
+          for (int q = 0; q < got; ++q) used = used || mtok[q] == t;
+          if (!used) break;
+        }
+        if (t < a.V) tok = t++;
+      }
+      ov[r] = -INFINITY;
+      ot[r] = tok;
+    }
+  }
+}
+
+struct TrieAdvanceArgs {
+  int* node; const int* node_edge_off; const int* edge_token; const int* edge_child; int N, E;
+  int bsz, K, step;
+  const int64_t* tokens; int64_t tok_ld; int tok_cap;
+  const float* scores; int64_t score_ld;
+  const int* ignore; const int64_t* reorder; int* done; int* nfin;
+};
+
+__global__ __launch_bounds__(TB_THREADS) void trie_beam_advance_kernel(TrieAdvanceArgs a) {
+  const int sent = blockIdx.x;
+  if (a.done[sent]) return;                                   // finished (possibly by this step's sentence pass): its nodes are not read again
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K = a.K, r0 = sent * K;
+  __shared__ int old[TB_MAX_K];
+  __shared__ int alive;
+  if (tid < K) old[tid] = a.node[r0 + tid];
+  if (tid == 0) alive = 0;
+  __syncthreads();                                            // every old node is read before any is written
+  for (int b = wave; b < K; b += 4) {
+    const int64_t row = r0 + b;
+    const int64_t parent = a.reorder[row] - r0;
+    const float sc = a.scores[row * a.score_ld + a.step];
+    const bool finite = sc == sc && sc != -INFINITY;
+    int child = -1;
+    if (finite && parent >= 0 && parent < K && a.step + 1 < a.tok_cap) {
+      const int pn = old[parent];
+      if ((unsigned)pn < (unsigned)a.N) {
+        const int64_t tok = a.tokens[row * a.tok_ld + a.step + 1];
+        const int e0 = max(a.node_edge_off[pn], 0), e1 = min(a.node_edge_off[pn + 1], a.E);
+        float found = -1.f;                                   // node ids < 2^24: exact as float
+        for (int e = e0 + lane; e < e1; e += WAVE)
+          if ((int64_t)a.edge_token[e] == tok) found = fmaxf(found, (float)a.edge_child[e]);
+        child = (int)wave_max(found);
+        if (child >= a.N) child = -1;
+      }
+    }
+    if (lane == 0) {
+      a.node[row] = child;
+      if (finite && !a.ignore[row]) atomicOr(&alive, 1);
+    }
+  }
+  __syncthreads();
+  if (tid == 0 && !alive) {                                   // every slot ignored or at -inf: nothing more can be finalised
+    a.done[sent] = 1;
+    atomicAdd(a.nfin, 1);
+  }
+}
+
+static inline bool tb_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace ofa
+
+using namespace ofa;
+
+extern "C" int ofa_trie_beam_splits(int max_degree, int V) {
+  if (max_degree <= 0 || V <= 1 || max_degree > V) return 0;
+  return cdiv(max_degree, tb_edges_per_wg(max_degree, V));
+}
+
+extern "C" int ofa_trie_beam_topk(const void* h, int64_t ld_h, int dtype, const void* W, int64_t ld_w, const void* bias, int D, int V,
+                                  int rows, int K, const int* node, const int* node_edge_off, const int* edge_token, int N, int E,
+                                  int max_degree, float temperature, int step, int min_len, int max_len, int pad, int unk, int eos,
+                                  float unk_penalty, int ngram, const int64_t* tokens, int64_t tok_ld, const int* done, void* ws,
+                                  void* stream) {
+  OFA_REQUIRE(h && W && node && node_edge_off && edge_token && ws, OFA_ERR_INVALID, "ofa_trie_beam_topk: null pointer");
+  OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "ofa_trie_beam_topk: bad dtype %d", dtype);
+  OFA_REQUIRE(rows > 0 && V > 1 && D > 0 && step >= 0 && N > 0 && E > 0, OFA_ERR_INVALID,
+              "ofa_trie_beam_topk: rows=%d V=%d D=%d step=%d N=%d E=%d", rows, V, D, step, N, E);
+  OFA_REQUIRE(K >= 1 && K <= TB_MAX_K, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: beam size %d outside [1, %d]", K, TB_MAX_K);
+  OFA_REQUIRE(rows % K == 0, OFA_ERR_INVALID, "ofa_trie_beam_topk: rows %d not a multiple of the beam size %d", rows, K);
+  OFA_REQUIRE((int64_t)K * V < (1 << 24), OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: beam * vocabulary must stay below 2^24");
+  OFA_REQUIRE(max_degree >= 1 && max_degree <= V && max_degree <= E, OFA_ERR_INVALID,
+              "ofa_trie_beam_topk: max_degree %d outside [1, min(V, E)]", max_degree);
+  OFA_REQUIRE(temperature > 0.f, OFA_ERR_INVALID, "ofa_trie_beam_topk: temperature must be > 0");
+  OFA_REQUIRE(ngram <= 0 || (tokens && tok_ld > step), OFA_ERR_INVALID, "ofa_trie_beam_topk: n-gram bans need the token history");
+  OFA_REQUIRE(ngram <= 0 || step < TB_BAN_MAX, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: n-gram bans beyond step %d", TB_BAN_MAX);
+  const int vn = dt_vecn(dtype);
+  OFA_REQUIRE(D % vn == 0 && ld_h % vn == 0 && ld_w % vn == 0 && ld_h >= D && ld_w >= D && tb_aligned16(h) && tb_aligned16(W),
+              OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: rows must be 16-byte aligned (D=%d ld_h=%lld ld_w=%lld)", D, (long long)ld_h,
+              (long long)ld_w);
+  TrieTopkArgs a{h, ld_h, W, ld_w, bias, D, V, rows, K, tb_layout_splits(V), 0, tb_edges_per_wg(max_degree, V), node, node_edge_off,
+                 edge_token, N, E, temperature, step, min_len, max_len, pad, unk, eos, unk_penalty, ngram, tokens, tok_ld, done,
+                 nullptr, nullptr, nullptr};
+  a.Su = cdiv(max_degree, a.epw);
+  const size_t smem = sizeof(TrieTopkScratch) + (size_t)D * (dtype == OFA_F32 ? 4 : 2) + (size_t)a.epw * 8;
+  OFA_REQUIRE(smem <= TB_LDS_MAX, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: D=%d with %d edges per workgroup needs %zu bytes of LDS",
+              D, a.epw, smem);
+  OFA_REQUIRE(rows <= 65535, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: %d rows", rows);
+  const int64_t S = a.S;
+  a.stats = (float*)ws;
+  a.cval = a.stats + (int64_t)rows * S * 2;
+  a.ctok = (int*)(a.cval + (int64_t)rows * S * 2 * K);
+  dim3 grid(a.Su, rows);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == OFA_F32) hipLaunchKernelGGL(trie_beam_topk_kernel<float>, grid, dim3(TB_THREADS), smem, st, a);
+  else if (dtype == OFA_BF16) hipLaunchKernelGGL(trie_beam_topk_kernel<bf16_t>, grid, dim3(TB_THREADS), smem, st, a);
+  else hipLaunchKernelGGL(trie_beam_topk_kernel<f16_t>, grid, dim3(TB_THREADS), smem, st, a);
+  return check_launch("ofa_trie_beam_topk");
+}
+
+extern "C" int ofa_trie_beam_advance(int* node, const int* node_edge_off, const int* edge_token, const int* edge_child, int N, int E,
+                                     int bsz, int K, int step, const int64_t* tokens, int64_t tok_ld, int tok_cap,
+                                     const float* scores, int64_t score_ld, const int* ignore, const int64_t* reorder, int* done,
+                                     int* nfin, void* stream) {
+  OFA_REQUIRE(node && node_edge_off && edge_token && edge_child && tokens && scores && ignore && reorder && done && nfin,
+              OFA_ERR_INVALID, "ofa_trie_beam_advance: null pointer");
+  OFA_REQUIRE(bsz > 0 && step >= 0 && N > 0 && E > 0 && N < (1 << 24), OFA_ERR_INVALID, "ofa_trie_beam_advance: bsz=%d step=%d N=%d E=%d",
+              bsz, step, N, E);
+  OFA_REQUIRE(K >= 1 && K <= TB_MAX_K, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_advance: beam size %d outside [1, %d]", K, TB_MAX_K);
+  OFA_REQUIRE(tok_cap >= step + 1 && tok_ld >= tok_cap && score_ld > step, OFA_ERR_INVALID,
+              "ofa_trie_beam_advance: history buffers too short for step %d (tok_cap=%d tok_ld=%lld score_ld=%lld)", step, tok_cap,
+              (long long)tok_ld, (long long)score_ld);
+  TrieAdvanceArgs a{node, node_edge_off, edge_token, edge_child, N, E, bsz, K, step, tokens, tok_ld, tok_cap, scores, score_ld,
+                    ignore, reorder, done, nfin};
+  hipLaunchKernelGGL(trie_beam_advance_kernel, dim3(bsz), dim3(TB_THREADS), 0, (hipStream_t)stream, a);
+  return check_launch("ofa_trie_beam_advance");
+}

@@ -7,7 +7,8 @@ are decoded (host-bound).  `StepDecoder` keeps every buffer a step touches at a 
 output, the KV caches at their final capacity -- and records ONE hipGraph PER STEP LENGTH (the prefix length and the cache
 length are kernel arguments, so each length is its own graph; a sequence of T steps replays T graphs).  Graphs are keyed by
 (rows, source length, step) and reused by every later batch of the same shape.  `greedy` below is the minimal loop used
-by tests and benchmarks.
+by tests and benchmarks.  With `features_only` a step returns the last position's features [rows, D] instead of logits (the
+output projection is not run): what `TrieBeamGenerator` consumes.
 
 `SequenceGenerator` is the reference's beam search (generator/sequence_generator.py:66-627 with utils/search.py BeamSearch)
 on top of `StepDecoder`: the policy of a step -- normaliser, masks, n-gram bans, top 2K, finalisation, active selection,
@@ -16,6 +17,11 @@ into the step's graph, so a step has no host synchronisation.  Differences from 
 (beam search)"):
 the row count stays fixed (finished sentences are masked, not removed; rows are independent, so results are the same),
 the returned tensors are on the CPU, and `attention` is empty (the decoder returns no alignment).
+
+`TrieBeamGenerator` is the same search restricted, at every step, to the next layer of a closed set's answer trie (the reference's
+`constraint_trie`, generator/sequence_generator.py:729-741): the row pass computes one dot product per child edge of the row's trie
+node instead of reading a [rows, V] projection (csrc/trie_beam.hip), the sentence pass is unchanged, and a third small launch
+advances every row's node.
 """
 import math
 from dataclasses import dataclass
@@ -28,9 +34,10 @@ from .preprocessor import ModalityType, Slot
 
 
 class StepDecoder:
-    def __init__(self, model, max_len: int, use_graph: bool = True, warmup_sequences: int = 1):
+    def __init__(self, model, max_len: int, use_graph: bool = True, warmup_sequences: int = 1, features_only: bool = False):
         self.model, self.max_len, self.use_graph = model, int(max_len), use_graph
         self.warmup_sequences = warmup_sequences
+        self.features_only = bool(features_only)          # a step returns [rows, D] features; the output projection is skipped
         self._shape = None
         self._graphs: Dict[int, tuple] = {}
         self._pool = None
@@ -78,9 +85,9 @@ class StepDecoder:
         return self
 
     def step(self, next_tokens: Optional[torch.Tensor], post=None) -> torch.Tensor:
-        """Append one token per row and return the logits of that position: [rows, V].  next_tokens None: column t of
-        `tokens` was already written on the device (beam search).  post(logits, t): device work recorded into the same
-        step graph after the decoder (the beam-search kernels and the cache reorder)."""
+        """Append one token per row and return the logits of that position: [rows, V] ([rows, D] features with `features_only`).
+        next_tokens None: column t of `tokens` was already written on the device (beam search).  post(logits, t): device work
+        recorded into the same step graph after the decoder (the beam-search kernels and the cache reorder)."""
         t = self.t
         if t >= self.max_len:
             raise ValueError(f"StepDecoder: max_len={self.max_len} exceeded")
@@ -124,8 +131,9 @@ class StepDecoder:
         return logits
 
     def _run(self, t):
+        kw = {"features_only": True} if self.features_only else {}
         out, _ = self.model.decoder([Slot(ModalityType.TEXT, False, self.tokens[:, :t + 1])], encoder_out=self.enc,
-                                    incremental_state=self.inc)
+                                    incremental_state=self.inc, **kw)
         return out[:, -1]
 
     def _set_lengths(self, n):
@@ -305,12 +313,21 @@ class SequenceGenerator:
         dec.tokens.fill_(self.pad)
         dec.tokens[:, 0] = self.bos
         st = self._buffers(rows, bsz, self.vocab_size, max_len, device)
-        host, events = st["host"], [None, None]
         post = lambda logits, t: self._step_kernels(logits, t, dec, st, max_len, ngram_step0)   # noqa: E731
-        for step in range(max_len + 1):
-            logits = dec.step(None, post=post)
+
+        def check(logits):
             if logits.shape[1] > self.vocab_size:
                 raise ValueError(f"decoder output width {logits.shape[1]} > dictionary size {self.vocab_size}")
+        self._loop(dec, st, bsz, max_len + 1, post, check)
+        return self._collect(st, bsz)
+
+    def _loop(self, dec, st, bsz, nsteps, post, check=None):
+        """At most `nsteps` decoding steps, stopping once every sentence is finished."""
+        host, events = st["host"], [None, None]
+        for step in range(nsteps):
+            out = dec.step(None, post=post)
+            if check is not None:
+                check(out)
             # the all-finished counter reaches the host one step late, through pinned memory: no synchronisation inside a step
             host[step % 2].copy_(st["nfin"][0], non_blocking=True)
             ev = torch.cuda.Event()
@@ -322,7 +339,6 @@ class SequenceGenerator:
                 if int(host[(step - 1) % 2]) >= bsz:
                     break
         torch.cuda.synchronize()
-        return self._collect(st, bsz)
 
     def _collect(self, st, bsz):
         cnt, ln = st["fin_cnt"].cpu(), st["fin_len"].cpu()
@@ -339,3 +355,91 @@ class SequenceGenerator:
             else:
                 out.append([hyps[i] for i in order][: self.return_n_best])
         return out
+
+
+class TrieBeamGenerator(SequenceGenerator):
+    """Beam search over the answer trie of a closed set: `plan` is a traverse.TraversePlan; the options, defaults and refusals are
+    SequenceGenerator's.  Every step is restricted to the children of the trie node a row has reached, as the reference's generator
+    does with a `constraint_trie` -- so `constraint_range` cannot be given as well (the reference asserts it, :730), and a
+    `prefix_tokens` with columns stays refused (its prefix steps need the full-vocabulary normaliser).
+
+    The row pass never forms [rows, V] logits: the decoder returns features and csrc/trie_beam.hip computes one dot product per
+    child edge.  The decoder's capacity and the step loop follow min(max_len, plan.Tmax) -- no hypothesis is longer than the deepest
+    answer -- and a sentence stops as soon as nothing more can be finalised, where the reference runs its remaining steps on
+    all -inf rows.  Beam search is not the exact arg-max over the closed set (TraverseTask.score is)."""
+
+    def __init__(self, tgt_dict, plan, *args, **kwargs):
+        if kwargs.get("constraint_range") is not None:
+            raise ValueError("TrieBeamGenerator: constraint_range cannot be combined with a constraint trie")
+        super().__init__(tgt_dict, *args, **kwargs)
+        if (plan.bos, plan.eos, plan.pad) != (self.bos, self.eos, self.pad):
+            raise ValueError("TrieBeamGenerator: the plan was built with other BOS / EOS / PAD ids than the dictionary's")
+        self.plan = plan
+        self._dev: Dict[torch.device, Dict[str, object]] = {}
+
+    def _plan_on(self, device):
+        if device not in self._dev:
+            self._dev[device] = self.plan.to_device(device)
+        return self._dev[device]
+
+    def _buffers(self, rows, bsz, V, max_len, device):
+        fresh = self._state is None or self._state["key"] != (rows, V, max_len, device)
+        st = super()._buffers(rows, bsz, V, max_len, device)
+        if fresh:
+            st["node"] = torch.zeros(rows, dtype=torch.int32, device=device)
+        st["node"].zero_()                                # every row starts at the root
+        return st
+
+    def _trie_step(self, feats, t, dec, st, dev, weight, bias, max_len, ngram_step0=True):
+        """Everything a step does after the decoder, on the device (recorded into the step graph)."""
+        ngram = self.no_repeat_ngram_size if (t > 0 or ngram_step0) else 0
+        if feats.dtype != weight.dtype:
+            feats = feats.to(weight.dtype)
+        K.trie_beam_topk(feats, weight, bias, dev, st["node"], self.beam_size, t, st["ws"], tokens=dec.tokens, done=st["done"],
+                         temperature=self.temperature, min_len=self.min_len, max_len=max_len, pad=self.pad, unk=self.unk,
+                         eos=self.eos, unk_penalty=self.unk_penalty, ngram=ngram)
+        st["tokens"] = dec.tokens
+        K.beam_select(st["ws"], st, self.beam_size, weight.shape[0], t, max_len, eos=self.eos, unk=self.unk,
+                      unk_penalty=self.unk_penalty, normalize=self.normalize_scores, len_penalty=self.len_penalty)
+        K.trie_beam_advance(dev, st["node"], st, self.beam_size, t)
+        dec.reorder(st["reorder"], caches_only=True)
+
+    @torch.no_grad()
+    def generate(self, model, sample, **kwargs):
+        from .traverse import TraverseTask
+        ngram_step0 = self.check_sample(sample, **kwargs)
+        source_slots = [s for s in sample["net_input"]["slots"] if s.is_src]
+        first = source_slots[0].value
+        src = first["fbank"] if isinstance(first, dict) else first
+        bsz, device = src.shape[0], src.device
+        beam = self.beam_size
+        rows = bsz * beam
+        max_len = self.effective_max_len(sample)
+        assert self.min_len <= max_len, "min_len cannot be larger than max_len, please adjust these!"
+        steps = min(max_len, self.plan.Tmax)              # no hypothesis is longer than the deepest answer (+ EOS)
+        weight, bias = TraverseTask.output_projection(model)
+        V = weight.shape[0]
+        if V > self.vocab_size:
+            raise ValueError(f"decoder output width {V} > dictionary size {self.vocab_size}")
+        if int(self.plan.edge_token.max()) >= V:
+            raise ValueError(f"the closed set holds token id {int(self.plan.edge_token.max())}, the output projection has {V} rows")
+        if self._dec is None or self._dec.model is not model or self._dec.max_len != steps + 1:
+            self._dec = StepDecoder(model, steps + 1, use_graph=self.use_graph, features_only=True)
+        dec = self._dec
+        dec.begin(source_slots, torch.arange(bsz, device=device).repeat_interleave(beam))
+        dec.tokens.fill_(self.pad)
+        dec.tokens[:, 0] = self.bos
+        st = self._buffers(rows, bsz, V, steps, device)
+        dev = self._plan_on(device)
+        post = lambda feats, t: self._trie_step(feats, t, dec, st, dev, weight, bias, max_len, ngram_step0)   # noqa: E731
+        self._loop(dec, st, bsz, steps + 1, post)
+        return self._collect(st, bsz)
+
+    def _collect(self, st, bsz):
+        if self.return_n_best == 1:                       # (the reference indexes an empty list here)
+            empty = (st["fin_cnt"].cpu() == 0).nonzero().flatten().tolist()
+            if empty:
+                raise ValueError(f"TrieBeamGenerator: no finalised hypothesis for sentence {empty[0]} of the batch "
+                                 f"(beam {self.beam_size}, min_len {self.min_len}, max_len {self.max_len}: no answer of the closed "
+                                 "set survives the length limits and the beam)")
+        return super()._collect(st, bsz)

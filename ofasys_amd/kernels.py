@@ -1355,3 +1355,37 @@ def closed_set_score(h2d, weight, bias, plan, bsz, ws=None):
                ptr(plan["node_edge_off"]), ptr(plan["edge_token"]), ptr(plan["edge_node"]), ptr(plan["rep_ans"]),
                ptr(plan["rep_pos"]), ptr(plan["path_off"]), ptr(plan["path_edge"]), ptr(ws), ptr(scores), stream())
     return scores
+
+
+# ------------------------------------------------------------------ trie-constrained beam search (csrc/trie_beam.hip)
+def trie_beam_splits(max_degree, V):
+    """Workgroups per row of trie_beam_topk for a plan (the grid's x extent)."""
+    n = int(lib().cdll.ofa_trie_beam_splits(int(max_degree), int(V)))
+    if n <= 0:
+        raise OfaError(f"trie_beam_splits: max_degree={max_degree} V={V}")
+    return n
+
+
+def trie_beam_topk(h2d, weight, bias, plan, node, K, step, ws, tokens=None, done=None, temperature=1.0, min_len=1, max_len=256,
+                   pad=1, unk=3, eos=2, unk_penalty=0.0, ngram=0):
+    """Row pass of one trie-constrained beam-search step, in place of beam_topk: h2d [rows, D] last-position features, weight
+    [V, D] / bias the output projection, `plan` the device arrays of a traverse.TraversePlan, node int32 [rows] the trie node of
+    every row (-1: dead).  Writes `ws` (beam_ws_bytes(rows, V, K)) for beam_select of the same step."""
+    _closed_set_proj(h2d, weight, bias)
+    rows = h2d.shape[0]
+    if node.dtype != torch.int32 or node.numel() != rows or not node.is_contiguous():
+        raise OfaError("trie_beam_topk: node must be a contiguous int32 [rows]")
+    tok_ld = tokens.stride(0) if tokens is not None else 0
+    lib().call("ofa_trie_beam_topk", ptr(h2d), h2d.stride(0), dtype_code(h2d), ptr(weight), weight.stride(0), ptr(bias),
+               h2d.shape[1], weight.shape[0], rows, int(K), ptr(node), ptr(plan["node_edge_off"]), ptr(plan["edge_token"]),
+               plan["N"], plan["E"], plan["max_degree"], float(temperature), int(step), int(min_len), int(max_len), int(pad),
+               int(unk), int(eos), float(unk_penalty), int(ngram), ptr(tokens), tok_ld, ptr(done), ptr(ws), stream())
+
+
+def trie_beam_advance(plan, node, st, K, step):
+    """After beam_select: every row's trie node follows its parent (st["reorder"]) through the token chosen at `step`; sentences
+    with nothing left to finalise are marked done.  `st`: the state dict beam_select works on."""
+    tokens, scores = st["tokens"], st["scores"]
+    lib().call("ofa_trie_beam_advance", ptr(node), ptr(plan["node_edge_off"]), ptr(plan["edge_token"]), ptr(plan["edge_child"]),
+               plan["N"], plan["E"], st["done"].numel(), int(K), int(step), ptr(tokens), tokens.stride(0), tokens.shape[1],
+               ptr(scores), scores.stride(0), ptr(st["ignore"]), ptr(st["reorder"]), ptr(st["done"]), ptr(st["nfin"]), stream())

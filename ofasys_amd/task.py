@@ -222,13 +222,10 @@ class Task:
         return next(self._iters[split])
 
     # ------------------------------------------------------------------ generation (task/base.py:232-246, 470-556, 727-793)
-    def build_generator(self, **gen_kwargs):
-        """SequenceGenerator with the reference's pops and defaults (task/base.py:475-486; normalize_scores defaults to False
-        here, unlike the generator's own default).  Only plain beam search exists: sampling, diverse beam, diverse siblings,
-        match_source_len and lexical constraints raise NotImplementedError."""
-        from .generator import SequenceGenerator
-        if self.global_dict is None:
-            raise ValueError(f"task {self.name}: initialize(global_dict) before building a generator")
+    def generator_kwargs(self, **gen_kwargs) -> Dict[str, Any]:
+        """The reference's generator arguments (task/base.py:475-486: its pops and defaults; normalize_scores defaults to False
+        here, unlike the generator's own default) as SequenceGenerator keywords.  Only plain beam search exists: sampling, diverse
+        beam, diverse siblings, match_source_len and lexical constraints raise NotImplementedError."""
         args = dict(
             beam_size=gen_kwargs.pop("beam", 5), return_n_best=gen_kwargs.pop("return_n_best", 1),
             max_len_a=gen_kwargs.pop("max_len_a", 0), max_len_b=gen_kwargs.pop("max_len_b", 200),
@@ -243,7 +240,14 @@ class Task:
             if v != default:
                 raise NotImplementedError(f"build_generator: {k}={v!r} -- only plain beam search is implemented")
         gen_kwargs.pop("diverse_beam_strength", None)
-        return SequenceGenerator(self.global_dict, **args, **gen_kwargs)
+        return dict(args, **gen_kwargs)
+
+    def build_generator(self, **gen_kwargs):
+        """SequenceGenerator from the reference's generator arguments (`generator_kwargs`)."""
+        from .generator import SequenceGenerator
+        if self.global_dict is None:
+            raise ValueError(f"task {self.name}: initialize(global_dict) before building a generator")
+        return SequenceGenerator(self.global_dict, **self.generator_kwargs(**gen_kwargs))
 
     @property
     def generator(self):

@@ -1,7 +1,9 @@
 """Closed-set inference (reference: task/traverse_task.py, exported as `ofasys.task.TraverseTask`): score every answer of a
 closed set under teacher forcing, each position's distribution restricted to the answer trie's next layer, and return the best
 answer.  The route for the tasks `Task.generator` refuses (an instruction whose target carries `closed_set`: VQA with an answer
-list, classification, SNLI-VE).
+list, classification, SNLI-VE).  `search="beam"` is the reference's everyday route for the same tasks instead: beam search whose
+every step is restricted to the trie's next layer (generator.TrieBeamGenerator) -- sentences x beam decoder rows for at most
+longest answer + 1 steps whatever the size of the closed set, but not the exact arg-max.
 
 The reference projects every (answer, position) onto the vocabulary, masks, takes a full log-softmax and gathers.  Here the trie is
 flattened once on the host (`TraversePlan`) and the device computes one dot product per trie EDGE, one log-sum-exp per trie NODE
@@ -23,7 +25,9 @@ class TraversePlan:
 
     nodes        distinct prefixes [bos] + answer[:t], t = 0 .. len, numbered in order of first appearance (node 0 = [bos]); so the
                  nodes first reached by answers c0 .. c1 - 1 are one contiguous range, and so are their edges and work items
-    edges        CSR by node: node_edge_off [N + 1], edge_token [E], edge_node [E]; an answer's last edge is EOS
+    edges        CSR by node: node_edge_off [N + 1], edge_token [E], edge_node [E]; an answer's last edge is EOS.  edge_child [E] is
+                 the node an edge leads to (-1 for an EOS edge) and max_degree the largest number of edges of one node: what the
+                 trie-constrained beam search walks (csrc/trie_beam.hip)
     rep_ans/pos  [N] the lowest answer index passing through the node and the position t: the decoder row holding its state
     paths        path_off [C + 1], path_edge [P]: the len + 1 edges of every answer
     items        [I, 3] (node, first edge, one past the last): the edges in pieces of at most ITEM_EDGES edges of one node -- the
@@ -65,6 +69,8 @@ class TraversePlan:
         self.E = E = int(self.node_edge_off[-1])
         self.edge_token = np.array([tok for ch in children for tok in ch], np.int32)
         self.edge_node = np.repeat(np.arange(N, dtype=np.int32), np.diff(self.node_edge_off))
+        self.edge_child = np.array([child for ch in children for child in ch.values()], np.int32)
+        self.max_degree = int(np.diff(self.node_edge_off).max())
         edge_of = [{tok: int(self.node_edge_off[n]) + i for i, tok in enumerate(ch)} for n, ch in enumerate(children)]
         self.path_off = np.zeros(C + 1, np.int32)
         self.path_off[1:] = np.cumsum(self.lengths)
@@ -100,8 +106,8 @@ class TraversePlan:
         """The arrays the kernels read (kernels.closed_set_*), on `device`, plus the padded decoder inputs."""
         d = {k: torch.from_numpy(getattr(self, k)).to(device) for k in
              ("node_edge_off", "edge_token", "edge_node", "rep_ans", "rep_pos", "path_off", "path_edge", "items",
-              "prev_output_tokens")}
-        d.update(C=self.C, N=self.N, E=self.E, P=self.P, Tmax=self.Tmax)
+              "prev_output_tokens", "edge_child")}
+        d.update(C=self.C, N=self.N, E=self.E, P=self.P, Tmax=self.Tmax, max_degree=self.max_degree)
         return d
 
 
@@ -109,13 +115,23 @@ class TraverseTask(Task):
     """`Task` for closed-set targets.  `max_rows`: cap on the decoder rows (sentences x answers) of one chunk; the answers are
     processed `max(1, max_rows // bsz)` at a time, so device memory follows the cap and not the size of the closed set.  The
     default, 2048 rows, keeps the decoder's GEMMs at a few thousand rows x Tmax -- large enough to fill the device at OFA-base
-    size, while activations stay in the tens of MB."""
+    size, while activations stay in the tens of MB.
+    `search`: what `inference` does by default -- "all" scores every answer (exact), "beam" runs the trie-constrained beam search with
+    `beam` beams (`beam_search`)."""
 
-    def __init__(self, cfg=None, max_rows: int = 2048, **kwargs):
+    SEARCHES = ("all", "beam")
+
+    def __init__(self, cfg=None, max_rows: int = 2048, search: str = "all", beam: int = 5, **kwargs):
         super().__init__(cfg, **kwargs)
         if max_rows < 1:
             raise ValueError("TraverseTask: max_rows must be >= 1")
-        self.max_rows = int(max_rows)
+        if search not in self.SEARCHES:
+            raise ValueError(f"TraverseTask: search must be one of {self.SEARCHES}, got {search!r}")
+        if beam < 1:
+            raise ValueError("TraverseTask: beam must be >= 1")
+        self.max_rows, self.search, self.beam = int(max_rows), search, int(beam)
+        self._seq2label: Dict[tuple, int] = {}
+        self._trie_gens: Dict[tuple, object] = {}
         self.plan: Optional[TraversePlan] = None
         self.index2ans: Dict[int, object] = {}
         self._dev: Dict[torch.device, Dict[str, object]] = {}
@@ -146,7 +162,10 @@ class TraverseTask(Task):
         if any(t < 0 or t >= len(d) for a in ids for t in a):
             raise ValueError(f"task {self.name}: the closed set holds token ids outside the dictionary (size {len(d)})")
         self.plan = TraversePlan(ids, d.bos(), d.eos(), d.pad())
-        self._dev, self._buf = {}, {}
+        self._dev, self._buf, self._trie_gens = {}, {}, {}
+        self._seq2label = {}
+        for i, a in enumerate(ids):                           # duplicates go to the lowest label
+            self._seq2label.setdefault(tuple(a), i)
 
     # ------------------------------------------------------------------ device state
     def _plan_on(self, device):
@@ -207,8 +226,53 @@ class TraverseTask(Task):
         K.closed_set_reduce(dev, bsz, buf["ws"], buf["scores"])
         return buf["scores"].cpu()
 
-    def inference(self, model, sample, **kwargs) -> List[object]:
-        """The best answer of the closed set per sentence (ties to the lower answer index).  The model is left in eval mode."""
+    # ------------------------------------------------------------------ trie-constrained beam search (generator.TrieBeamGenerator)
+    def trie_generator(self, **gen_kwargs):
+        """The TrieBeamGenerator for these generator arguments (Task.generator_kwargs: `beam`, `return_n_best`, `max_len`,
+        `normalize_scores` False by default, ...), kept so that its captured step graphs are reused by later batches."""
+        from .generator import TrieBeamGenerator
+        if self.plan is None:
+            raise ValueError(f"task {self.name}: initialize(global_dict) first")
+        kw = self.generator_kwargs(**gen_kwargs)
+        key = tuple(sorted((k, repr(v)) for k, v in kw.items()))
+        if key not in self._trie_gens:
+            self._trie_gens[key] = TrieBeamGenerator(self.global_dict, self.plan, **kw)
+        return self._trie_gens[key]
+
+    def _beam_hypotheses(self, model, sample, beam=None, n_best=1, **generator_options):
+        model.eval()
+        gen = self.trie_generator(beam=self.beam if beam is None else int(beam), return_n_best=int(n_best), **generator_options)
+        return gen.generate(model, sample)
+
+    def beam_search(self, model, sample, beam: Optional[int] = None, n_best: int = 1, **generator_options):
+        """Beam search restricted to the answer trie: per sentence the best hypothesis (n_best = 1) or the list of the n_best best,
+        as Task.inference returns them, `.text` filled through the text preprocessor.  Scores are unnormalised log-probabilities
+        unless normalize_scores=True.  The model is left in eval mode."""
+        outputs = self._beam_hypotheses(model, sample, beam, n_best, **generator_options)
+        pre = self.general_preprocess.name2pre["text"]
+        for single in outputs:
+            for hyp in (single if isinstance(single, list) else [single]):
+                hyp.text = pre.decode(hyp.tokens)
+        return outputs
+
+    def inference(self, model, sample, search: Optional[str] = None, **kwargs) -> List[object]:
+        """The best answer of the closed set per sentence.  search "all" (the default of the constructor): every answer is scored,
+        ties to the lower answer index.  search "beam": the answer spelled by the best hypothesis of `beam_search(**kwargs)`
+        (duplicate answers: the lowest label) -- the reference's route, not necessarily the arg-max.  The model is left in eval
+        mode."""
+        search = self.search if search is None else search
+        if search not in self.SEARCHES:
+            raise ValueError(f"TraverseTask.inference: search must be one of {self.SEARCHES}, got {search!r}")
+        if search == "beam":
+            kwargs.pop("n_best", None)
+            out = []
+            # (the hypotheses are mapped by token sequence: no text decoding, which costs milliseconds per hypothesis on the host)
+            for b, hyp in enumerate(self._beam_hypotheses(model, sample, n_best=1, **kwargs)):
+                seq = tuple(hyp.tokens[:-1].tolist())
+                if seq not in self._seq2label:
+                    raise ValueError(f"task {self.name}: the hypothesis of sentence {b} ({list(seq)}) is not an answer of the closed set")
+                out.append(self.index2ans[self._seq2label[seq]])
+            return out
         scores = self.score(model, sample)
         best = np.argmax(scores.numpy(), axis=1)              # numpy: the first maximum
         return [self.index2ans[int(i)] for i in best]
