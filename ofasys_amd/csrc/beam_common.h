@@ -1,0 +1,156 @@
+// What the two beam-search row passes (beam_search.hip: ofa_beam_topk over [rows, V] logits; trie_beam.hip: ofa_trie_beam_topk over
+// the child edges of a trie node) and the sentence pass (ofa_beam_select) have in common, defined once: the limits, the workspace
+// layout the row passes write and the sentence pass reads, the reference's post-normaliser masks in its order, the tie rules
+// (value descending, token ascending, NaN = empty) and the candidate-list machinery around the per-wave selection loops, which
+// stay with their kernels (one selects over 16 register-held values per lane, the other over an LDS array strided by thread).
+// Device helpers and host helpers only: no kernels, no entry points.
+#pragma once
+#include "common.h"
+
+namespace ofa {
+
+constexpr int BEAM_MAX_K = 16;
+constexpr int BEAM_THREADS = 256;
+constexpr int BEAM_PER_LANE = 16;
+constexpr int BEAM_CHUNK = BEAM_THREADS * BEAM_PER_LANE;   // vocabulary columns per part of the workspace layout
+
+static inline int beam_splits(int V) { return (V + BEAM_CHUNK - 1) / BEAM_CHUNK; }
+
+// ---------------------------------------------------------------- the workspace: S = beam_splits(V) parts per row
+struct BeamWs {
+  float* stats;                           // [rows, S, 2]  (max, sum exp(x - max)) of the part; NaN max: the part holds a NaN
+  float* cval;                            // [rows, S, 2K] the part's best candidates, (value desc, token asc); value before the unk penalty
+  int* ctok;                              // [rows, S, 2K] their tokens, -1: none
+};
+static inline int64_t beam_ws_cval_off(int64_t rows, int64_t S) { return rows * S * 2; }                      // in 4-byte words
+static inline int64_t beam_ws_ctok_off(int64_t rows, int64_t S, int64_t K) { return beam_ws_cval_off(rows, S) + rows * S * 2 * K; }
+static inline int64_t beam_ws_words(int64_t rows, int64_t S, int64_t K) { return beam_ws_ctok_off(rows, S, K) + rows * S * 2 * K; }
+static inline BeamWs beam_ws_carve(const void* ws, int64_t rows, int64_t S, int64_t K) {
+  float* p = (float*)ws;
+  return BeamWs{p, p + beam_ws_cval_off(rows, S), (int*)(p + beam_ws_ctok_off(rows, S, K))};
+}
+
+// ---------------------------------------------------------------- the policy arguments both row passes take
+struct BeamPolicy {
+  float temperature;
+  int step, min_len, max_len, pad, unk, eos; float unk_pen;
+  int ngram; const int64_t* tokens; int64_t tok_ld;
+  const int* done;
+};
+
+// The arguments both row passes share, checked before any launch; `who` is the entry point's name.
+static inline int beam_check_row_pass(const char* who, int rows, int V, int K, float temperature, int step, int ngram,
+                                      const int64_t* tokens, int64_t tok_ld) {
+  OFA_REQUIRE(K >= 1 && K <= BEAM_MAX_K, OFA_ERR_UNSUPPORTED, "%s: beam size %d outside [1, %d]", who, K, BEAM_MAX_K);
+  OFA_REQUIRE(rows % K == 0, OFA_ERR_INVALID, "%s: rows %d not a multiple of the beam size %d", who, rows, K);
+  OFA_REQUIRE((int64_t)K * V < (1 << 24), OFA_ERR_UNSUPPORTED, "%s: beam * vocabulary must stay below 2^24", who);
+  OFA_REQUIRE(temperature > 0.f, OFA_ERR_INVALID, "%s: temperature must be > 0", who);
+  OFA_REQUIRE(ngram <= 0 || (tokens && tok_ld > step), OFA_ERR_INVALID, "%s: n-gram bans need the token history", who);
+  return OFA_OK;
+}
+
+// ---------------------------------------------------------------- device side
+// wave arg-max of (key desc, idx asc) over the lanes; NaN keys are empty.  Returns false when every lane is empty.
+__device__ __forceinline__ bool wave_argmax(float key, int idx, float& mx, int& mi) {
+  mx = wave_max(key);
+  if (mx != mx) return false;
+  const float neg = (key == mx) ? -(float)idx : -INFINITY;     // indices < 2^24: exact as float
+  mi = (int)(-wave_max(neg));
+  return true;
+}
+
+// LDS scratch of the list machinery of one 256-thread workgroup: every wave's sorted list and its part of the normaliser
+struct BeamListScratch {
+  float lkey[4][2 * BEAM_MAX_K], lval[4][2 * BEAM_MAX_K];
+  int ltok[4][2 * BEAM_MAX_K];
+  float red_m[4], red_s[4];
+  int red_nan[4];
+};
+static_assert(sizeof(BeamListScratch) % 16 == 0, "embedded in front of 16-byte aligned LDS data");
+
+// n-gram bans of a row (utils/ngram_repeat_block.py over the history tokens[row, 0..step]): every earlier occurrence of the row's
+// last n-1 tokens bans the token that followed it; ban(token) is called by the thread that found the occurrence.
+template <typename Sink>
+__device__ __forceinline__ void beam_ngram_scan(const BeamPolicy& p, int row, int tid, Sink ban) {
+  const int n = p.ngram;
+  if (n > 0 && p.step + 2 - n >= 0) {
+    const int64_t* h = p.tokens + (int64_t)row * p.tok_ld;
+    const int last = p.step - n + 2;                        // the row's last n-1 tokens start here
+    for (int i = tid; i + n - 1 <= p.step; i += BEAM_THREADS) {
+      bool match = true;
+      for (int q = 0; q < n - 1; ++q) match = match && (h[i + q] == h[last + q]);
+      if (match) ban(h[i + n - 1]);
+    }
+  }
+}
+
+// The workgroup's part of the fp32 normaliser: m = the lane's max over its non-NaN values, has_nan = it saw a NaN,
+// lane_sum(M) = the lane's sum of exp(value - M) given its wave's max.  Thread 0 stores (max, sum) -- NaN max for a part
+// that holds a NaN -- to st.  Contains a workgroup barrier: LDS written before the call is visible to every thread after it.
+template <typename LaneSum>
+__device__ __forceinline__ void beam_normaliser_part(BeamListScratch& sh, int tid, float m, int has_nan, LaneSum lane_sum, float* st) {
+  const int lane = tid & 63, wave = tid >> 6;
+  m = wave_max(m);
+  float s = 0.f;
+  if (m != -INFINITY) s = lane_sum(m);
+  s = wave_sum(s);
+  has_nan = __any(has_nan) ? 1 : 0;
+  if (lane == 0) { sh.red_m[wave] = m; sh.red_s[wave] = s; sh.red_nan[wave] = has_nan; }
+  __syncthreads();
+  if (tid == 0) {
+    const float M = fmaxf(fmaxf(sh.red_m[0], sh.red_m[1]), fmaxf(sh.red_m[2], sh.red_m[3]));
+    float S = 0.f;
+    for (int w = 0; w < 4; ++w)
+      if (sh.red_m[w] != -INFINITY) S += sh.red_s[w] * expf(sh.red_m[w] - M);
+    const bool bad = sh.red_nan[0] | sh.red_nan[1] | sh.red_nan[2] | sh.red_nan[3];
+    st[0] = bad ? NAN : M;
+    st[1] = S;
+  }
+}
+
+// The masks after the normaliser for value v of token c, in the reference's order (sequence_generator.py:296-311, 319-343):
+// EOS at step < min_len, NaN -> -inf, PAD, step >= max_len: all but EOS, n-gram bans, unk -= unk_penalty.  Returns the
+// ordering key; the penalty orders only -- unk_val keeps the value of unk, and the sentence pass subtracts the penalty after
+// the normaliser.
+__device__ __forceinline__ float beam_mask_key(const BeamPolicy& p, float v, int c, bool banned, float& unk_val) {
+  if (c == p.eos && p.step < p.min_len) v = -INFINITY;
+  if (v != v) v = -INFINITY;
+  if (c == p.pad) v = -INFINITY;
+  if (p.step >= p.max_len && c != p.eos) v = -INFINITY;
+  if (banned) v = -INFINITY;
+  if (c == p.unk) { unk_val = v; v = v - p.unk_pen; }
+  return v;
+}
+
+// a wave whose candidates ran out after `it` entries closes its sorted list
+__device__ __forceinline__ void beam_close_list(BeamListScratch& sh, int wave, int lane, int it, int K2) {
+  if (lane == 0) for (int r = it; r < K2; ++r) { sh.lkey[wave][r] = NAN; sh.ltok[wave][r] = -1; }
+}
+
+// Wave 0 merges the four waves' sorted lists (<= 128 entries: two per lane) into ov / ot, (key desc, token asc); returns the
+// number of entries written (< K2: the lists ran out; the caller fills the tail).  listed: if given, an LDS copy of ot.
+__device__ __forceinline__ int beam_merge_lists(const BeamListScratch& sh, int lane, int K2, float* ov, int* ot, int* listed = nullptr) {
+  float k0 = NAN, k1 = NAN;
+  int t0 = 0x7fffffff, t1 = 0x7fffffff;
+  const int e0 = lane, e1 = lane + 64;
+  if (e0 < 4 * K2 && sh.ltok[e0 / K2][e0 % K2] >= 0) { k0 = sh.lkey[e0 / K2][e0 % K2]; t0 = sh.ltok[e0 / K2][e0 % K2]; }
+  if (e1 < 4 * K2 && sh.ltok[e1 / K2][e1 % K2] >= 0) { k1 = sh.lkey[e1 / K2][e1 % K2]; t1 = sh.ltok[e1 / K2][e1 % K2]; }
+  int it = 0;
+  for (; it < K2; ++it) {
+    const bool use0 = k0 == k0 && (!(k1 == k1) || k0 > k1 || (k0 == k1 && t0 < t1));
+    const float lb = use0 ? k0 : k1;
+    const int lt = use0 ? t0 : t1;
+    float mx; int mt;
+    if (!wave_argmax(lb, lt, mx, mt)) break;
+    if (lb == lb && lt == mt) {
+      const int e = use0 ? e0 : e1;
+      ov[it] = sh.lval[e / K2][e % K2];
+      ot[it] = mt;
+      if (listed) listed[it] = mt;
+      if (use0) k0 = NAN; else k1 = NAN;
+    }
+  }
+  return it;
+}
+
+}  // namespace ofa

@@ -19,47 +19,28 @@
 //    (the active_mask topk), carries cands_to_ignore, and gathers the token / score histories in place.  A finished sentence
 //    (K hypotheses or step == max_len) sets its done flag, bumps the all-finished counter and is a no-op afterwards; its rows
 //    keep the identity reorder.
-#include "common.h"
+#include "beam_common.h"
 
 namespace ofa {
-
-constexpr int BEAM_MAX_K = 16;
-constexpr int BEAM_THREADS = 256;
-constexpr int BEAM_PER_LANE = 16;
-constexpr int BEAM_CHUNK = BEAM_THREADS * BEAM_PER_LANE;   // columns per row-pass workgroup
-
-static inline int beam_splits(int V) { return (V + BEAM_CHUNK - 1) / BEAM_CHUNK; }
 
 struct BeamTopkArgs {
   const void* logits; int64_t ld;
   int rows, V, K, S;
-  float temperature; int cstart, cend;
-  int step, min_len, max_len, pad, unk, eos; float unk_pen;
-  int ngram; const int64_t* tokens; int64_t tok_ld;
-  const int* done;
-  float* stats; float* cval; int* ctok;        // [rows, S, 2] / [rows, S, 2K] / [rows, S, 2K]
+  int cstart, cend;
+  BeamPolicy p;
+  BeamWs ws;
 };
-
-// wave arg-max of (key desc, idx asc) over the lanes; NaN keys are empty.  Returns false when every lane is empty.
-__device__ __forceinline__ bool wave_argmax(float key, int idx, float& mx, int& mi) {
-  mx = wave_max(key);
-  if (mx != mx) return false;
-  const float neg = (key == mx) ? -(float)idx : -INFINITY;     // indices < 2^24: exact as float
-  mi = (int)(-wave_max(neg));
-  return true;
-}
 
 template <typename T>
 __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(BeamTopkArgs a) {
   const int split = blockIdx.x, row = blockIdx.y;
-  if (a.done && a.done[row / a.K]) return;
+  const BeamPolicy& p = a.p;
+  if (p.done && p.done[row / a.K]) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int base = split * BEAM_CHUNK, K2 = 2 * a.K;
+  const int64_t part = (int64_t)row * a.S + split;
   __shared__ uint32_t ban[BEAM_CHUNK / 32];
-  __shared__ float red_m[4], red_s[4];
-  __shared__ int red_nan[4];
-  __shared__ float lkey[4][2 * BEAM_MAX_K], lval[4][2 * BEAM_MAX_K];
-  __shared__ int ltok[4][2 * BEAM_MAX_K];
+  __shared__ BeamListScratch sh;
 
   // ---- the row's logits chunk: one read, 16 columns per lane in flight together
   const T* src = (const T*)a.logits + (int64_t)row * a.ld;
@@ -71,20 +52,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(BeamTopkArgs a)
   }
   for (int i = tid; i < BEAM_CHUNK / 32; i += BEAM_THREADS) ban[i] = 0u;
   __syncthreads();
-  // ---- n-gram bans of this row (history tokens[row, 0..step])
-  const int n = a.ngram;
-  if (n > 0 && a.step + 2 - n >= 0) {
-    const int64_t* h = a.tokens + (int64_t)row * a.tok_ld;
-    const int last = a.step - n + 2;                      // the row's last n-1 tokens start here
-    for (int i = tid; i + n - 1 <= a.step; i += BEAM_THREADS) {
-      bool match = true;
-      for (int q = 0; q < n - 1; ++q) match = match && (h[i + q] == h[last + q]);
-      if (match) {
-        const int64_t col = h[i + n - 1] - base;
-        if (col >= 0 && col < BEAM_CHUNK) atomicOr(&ban[col >> 5], 1u << (col & 31));
-      }
-    }
-  }
+  // ---- n-gram bans of this row, as a bitmap over the chunk
+  beam_ngram_scan(p, row, tid, [&](int64_t tok) {
+    const int64_t col = tok - base;
+    if (col >= 0 && col < BEAM_CHUNK) atomicOr(&ban[col >> 5], 1u << (col & 31));
+  });
   // ---- pre-normaliser masks + the chunk's normaliser part
   float m = -INFINITY;
   int has_nan = 0;
@@ -92,7 +64,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(BeamTopkArgs a)
   for (int j = 0; j < BEAM_PER_LANE; ++j) {
     const int c = base + wave * (64 * BEAM_PER_LANE) + j * 64 + lane;
     float v = x[j];
-    if (a.temperature != 1.f) v = v / a.temperature;
+    if (p.temperature != 1.f) v = v / p.temperature;
     if (a.cstart >= 0 && ((c >= 4 && c < a.cstart) || c >= a.cend)) v = -INFINITY;
     x[j] = v;
     if (c < a.V) {
@@ -100,41 +72,22 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(BeamTopkArgs a)
       else m = fmaxf(m, v);
     }
   }
-  m = wave_max(m);
-  float s = 0.f;
-  if (m != -INFINITY) {
+  beam_normaliser_part(sh, tid, m, has_nan, [&](float wm) {
+    float s = 0.f;
 #pragma unroll
     for (int j = 0; j < BEAM_PER_LANE; ++j) {
       const int c = base + wave * (64 * BEAM_PER_LANE) + j * 64 + lane;
-      if (c < a.V && x[j] == x[j]) s += expf(x[j] - m);
+      if (c < a.V && x[j] == x[j]) s += expf(x[j] - wm);
     }
-  }
-  s = wave_sum(s);
-  has_nan = __any(has_nan) ? 1 : 0;
-  if (lane == 0) { red_m[wave] = m; red_s[wave] = s; red_nan[wave] = has_nan; }
-  __syncthreads();                                        // (also orders the ban bitmap)
-  if (tid == 0) {
-    float M = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
-    float S = 0.f;
-    for (int w = 0; w < 4; ++w)
-      if (red_m[w] != -INFINITY) S += red_s[w] * expf(red_m[w] - M);
-    const bool bad = red_nan[0] | red_nan[1] | red_nan[2] | red_nan[3];
-    float* st = a.stats + ((int64_t)row * a.S + split) * 2;
-    st[0] = bad ? NAN : M;
-    st[1] = S;
-  }
-  // ---- post-normaliser masks -> ordering keys (NaN key = no candidate)
+    return s;
+  }, a.ws.stats + part * 2);                                // (its barrier also orders the ban bitmap)
+  // ---- post-normaliser masks -> ordering keys (NaN key = no candidate; -inf stays a candidate)
   float unk_val = 0.f;
 #pragma unroll
   for (int j = 0; j < BEAM_PER_LANE; ++j) {
     const int c = base + wave * (64 * BEAM_PER_LANE) + j * 64 + lane;
-    float v = x[j];
-    if (c == a.eos && a.step < a.min_len) v = -INFINITY;
-    if (v != v) v = -INFINITY;
-    if (c == a.pad) v = -INFINITY;
-    if (a.step >= a.max_len && c != a.eos) v = -INFINITY;
-    if (c < a.V && (ban[(c - base) >> 5] >> ((c - base) & 31)) & 1u) v = -INFINITY;
-    if (c == a.unk) { unk_val = v; v = v - a.unk_pen; }
+    const bool banned = c < a.V && (ban[(c - base) >> 5] >> ((c - base) & 31)) & 1u;
+    const float v = beam_mask_key(p, x[j], c, banned, unk_val);
     x[j] = c < a.V ? v : NAN;
   }
   // ---- per-wave top 2K, sorted
@@ -147,49 +100,29 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(BeamTopkArgs a)
     const int lc = lj < 0 ? 0x7fffffff : base + wave * (64 * BEAM_PER_LANE) + lj * 64 + lane;
     float mx; int mc;
     if (!wave_argmax(lb, lc, mx, mc)) {
-      if (lane == 0) for (int r = it; r < K2; ++r) { lkey[wave][r] = NAN; ltok[wave][r] = -1; }
+      beam_close_list(sh, wave, lane, it, K2);
       break;
     }
     if (lj >= 0 && lc == mc) {
-      lkey[wave][it] = lb;
-      lval[wave][it] = mc == a.unk ? unk_val : lb;
-      ltok[wave][it] = mc;
+      sh.lkey[wave][it] = lb;
+      sh.lval[wave][it] = mc == p.unk ? unk_val : lb;
+      sh.ltok[wave][it] = mc;
 #pragma unroll
       for (int j = 0; j < BEAM_PER_LANE; ++j)
         if (j == lj) x[j] = NAN;
     }
   }
   __syncthreads();
-  // ---- wave 0 merges the four sorted lists (<= 128 entries: two per lane)
   if (wave == 0) {
-    float k0 = NAN, k1 = NAN;
-    int t0 = 0x7fffffff, t1 = 0x7fffffff;
-    const int e0 = lane, e1 = lane + 64;
-    if (e0 < 4 * K2 && ltok[e0 / K2][e0 % K2] >= 0) { k0 = lkey[e0 / K2][e0 % K2]; t0 = ltok[e0 / K2][e0 % K2]; }
-    if (e1 < 4 * K2 && ltok[e1 / K2][e1 % K2] >= 0) { k1 = lkey[e1 / K2][e1 % K2]; t1 = ltok[e1 / K2][e1 % K2]; }
-    float* ov = a.cval + ((int64_t)row * a.S + split) * K2;
-    int* ot = a.ctok + ((int64_t)row * a.S + split) * K2;
-    for (int it = 0; it < K2; ++it) {
-      const bool use0 = k0 == k0 && (!(k1 == k1) || k0 > k1 || (k0 == k1 && t0 < t1));
-      const float lb = use0 ? k0 : k1;
-      const int lt = use0 ? t0 : t1;
-      float mx; int mt;
-      if (!wave_argmax(lb, lt, mx, mt)) {
-        if (lane == 0) for (int r = it; r < K2; ++r) { ov[r] = -INFINITY; ot[r] = -1; }
-        break;
-      }
-      if (lb == lb && lt == mt) {
-        const int e = use0 ? e0 : e1;
-        ov[it] = lval[e / K2][e % K2];
-        ot[it] = mt;
-        if (use0) k0 = NAN; else k1 = NAN;
-      }
-    }
+    float* ov = a.ws.cval + part * K2;
+    int* ot = a.ws.ctok + part * K2;
+    const int got = beam_merge_lists(sh, lane, K2, ov, ot);
+    if (lane == 0) for (int r = got; r < K2; ++r) { ov[r] = -INFINITY; ot[r] = -1; }
   }
 }
 
 struct BeamSelectArgs {
-  const float* stats; const float* cval; const int* ctok;
+  BeamWs ws;
   int bsz, K, V, S, step, max_len, eos, unk; float unk_pen;
   int normalize; float len_pen;
   int64_t* tokens; int64_t tok_ld; int tok_cap;
@@ -221,7 +154,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_select_kernel(BeamSelectArg
 
   // ---- each beam row's normaliser from its splits' parts
   if (tid < nr) {
-    const float* st = a.stats + (int64_t)(r0 + tid) * a.S * 2;
+    const float* st = a.ws.stats + (int64_t)(r0 + tid) * a.S * 2;
     float M = -INFINITY;
     bool isnan_ = false;
     for (int s = 0; s < a.S; ++s) {
@@ -246,9 +179,9 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_select_kernel(BeamSelectArg
       if (s == 0 && j < a.V) { tok = j; sc = -INFINITY; }
     } else {
       const int64_t off = ((int64_t)(r0 + r) * a.S + s) * K2 + j;
-      tok = a.ctok[off];
+      tok = a.ws.ctok[off];
       if (tok >= 0) {
-        float lp = a.cval[off] - lse[r];
+        float lp = a.ws.cval[off] - lse[r];
         if (tok == a.unk) lp = lp - a.unk_pen;
         if (lp != lp) lp = -INFINITY;
         sc = step > 0 ? lp + cum[r] : lp;
@@ -397,8 +330,7 @@ using namespace ofa;
 
 extern "C" int64_t ofa_beam_ws_bytes(int rows, int V, int K) {
   if (rows <= 0 || V <= 0 || K <= 0) return 0;
-  const int64_t S = beam_splits(V);
-  return (int64_t)rows * S * (2 + 2 * (int64_t)K * 2) * 4;
+  return beam_ws_words(rows, beam_splits(V), K) * 4;
 }
 
 extern "C" int ofa_beam_topk(const void* logits, int64_t ld, int rows, int V, int K, float temperature, int cstart, int cend,
@@ -408,18 +340,12 @@ extern "C" int ofa_beam_topk(const void* logits, int64_t ld, int rows, int V, in
   OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "ofa_beam_topk: bad dtype %d", dtype);
   OFA_REQUIRE(rows > 0 && V > 1 && ld >= V && step >= 0, OFA_ERR_INVALID, "ofa_beam_topk: rows=%d V=%d ld=%lld step=%d", rows, V,
               (long long)ld, step);
-  OFA_REQUIRE(K >= 1 && K <= BEAM_MAX_K, OFA_ERR_UNSUPPORTED, "ofa_beam_topk: beam size %d outside [1, %d]", K, BEAM_MAX_K);
-  OFA_REQUIRE(rows % K == 0, OFA_ERR_INVALID, "ofa_beam_topk: rows %d not a multiple of the beam size %d", rows, K);
-  OFA_REQUIRE((int64_t)K * V < (1 << 24), OFA_ERR_UNSUPPORTED, "ofa_beam_topk: beam * vocabulary must stay below 2^24");
-  OFA_REQUIRE(temperature > 0.f, OFA_ERR_INVALID, "ofa_beam_topk: temperature must be > 0");
-  OFA_REQUIRE(ngram <= 0 || (tokens && tok_ld > step), OFA_ERR_INVALID, "ofa_beam_topk: n-gram bans need the token history");
-  BeamTopkArgs a{logits, ld, rows, V, K, beam_splits(V), temperature, cstart, cend, step, min_len, max_len, pad, unk, eos,
-                 unk_penalty, ngram, tokens, tok_ld, done, nullptr, nullptr, nullptr};
-  const int64_t S = a.S;
-  a.stats = (float*)ws;
-  a.cval = a.stats + (int64_t)rows * S * 2;
-  a.ctok = (int*)(a.cval + (int64_t)rows * S * 2 * K);
-  dim3 grid(a.S, rows);
+  if (const int rc = beam_check_row_pass("ofa_beam_topk", rows, V, K, temperature, step, ngram, tokens, tok_ld)) return rc;
+  const int S = beam_splits(V);
+  BeamTopkArgs a{logits, ld, rows, V, K, S, cstart, cend,
+                 BeamPolicy{temperature, step, min_len, max_len, pad, unk, eos, unk_penalty, ngram, tokens, tok_ld, done},
+                 beam_ws_carve(ws, rows, S, K)};
+  dim3 grid(S, rows);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == OFA_F32) hipLaunchKernelGGL(beam_topk_kernel<float>, grid, dim3(BEAM_THREADS), 0, st, a);
   else if (dtype == OFA_BF16) hipLaunchKernelGGL(beam_topk_kernel<bf16_t>, grid, dim3(BEAM_THREADS), 0, st, a);
@@ -444,12 +370,9 @@ extern "C" int ofa_beam_select(const void* ws, int bsz, int K, int V, int step, 
   const size_t smem = select_smem(K, S, step);
   OFA_REQUIRE(smem <= 65536, OFA_ERR_UNSUPPORTED, "ofa_beam_select: beam %d x %d vocabulary splits x step %d needs %zu bytes of LDS",
               K, S, step, smem);
-  const int64_t rows = (int64_t)bsz * K;
-  BeamSelectArgs a{(const float*)ws, nullptr, nullptr, bsz, K, V, S, step, max_len, eos, unk, unk_penalty, normalize, len_penalty,
+  BeamSelectArgs a{beam_ws_carve(ws, (int64_t)bsz * K, S, K), bsz, K, V, S, step, max_len, eos, unk, unk_penalty, normalize, len_penalty,
                    tokens, tok_ld, tok_cap, scores, score_ld, ignore, done, nfin, reorder, fin_tok, fin_pos, fin_ld, fin_score,
                    fin_len, fin_cnt};
-  a.cval = a.stats + rows * S * 2;
-  a.ctok = (const int*)(a.cval + rows * S * 2 * K);
   hipLaunchKernelGGL(beam_select_kernel, dim3(bsz), dim3(BEAM_THREADS), smem, (hipStream_t)stream, a);
   return check_launch("ofa_beam_select");
 }

@@ -78,7 +78,7 @@ __global__ __launch_bounds__(WAVE) void closed_set_edge_kernel(ClosedSetEdgeArgs
       if (lane == j) out = s;
     }
     if (lane < nb) {
-      if (!ok) out = __int_as_float(0x7fc00000);
+      if (!ok) out = NAN;
       else if (a.bias) out += ld1<T>((const T*)a.bias + tok);
       a.z[(int64_t)(b0 + lane) * a.E + e] = out;
     }
@@ -112,12 +112,10 @@ __global__ __launch_bounds__(256) void closed_set_path_kernel(const float* z, co
   for (int p = p0; p < p1; ++p) {
     const int e = path_edge[p];
     const int n = (unsigned)e < (unsigned)E ? edge_node[e] : -1;
-    s += (unsigned)n < (unsigned)N ? z[(int64_t)b * E + e] - lse[(int64_t)b * N + n] : __int_as_float(0x7fc00000);
+    s += (unsigned)n < (unsigned)N ? z[(int64_t)b * E + e] - lse[(int64_t)b * N + n] : NAN;
   }
   scores[idx] = s;
 }
-
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace ofa
 
@@ -136,10 +134,7 @@ extern "C" int ofa_closed_set_edge_logits(const void* h, int64_t ld_h, int dtype
   OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "ofa_closed_set_edge_logits: bad dtype %d", dtype);
   OFA_REQUIRE(D > 0 && V > 0 && bsz > 0 && chunk > 0 && T > 0 && c0 >= 0 && N > 0 && E > 0 && n_items >= 0, OFA_ERR_INVALID,
               "ofa_closed_set_edge_logits: D=%d V=%d bsz=%d chunk=%d T=%d c0=%d E=%d items=%d", D, V, bsz, chunk, T, c0, E, n_items);
-  const int vn = dt_vecn(dtype);
-  OFA_REQUIRE(D % vn == 0 && ld_h % vn == 0 && ld_w % vn == 0 && ld_h >= D && ld_w >= D && aligned16(h) && aligned16(W),
-              OFA_ERR_UNSUPPORTED, "ofa_closed_set_edge_logits: rows must be 16-byte aligned (D=%d ld_h=%lld ld_w=%lld)", D,
-              (long long)ld_h, (long long)ld_w);
+  if (const int rc = check_proj_operands("ofa_closed_set_edge_logits", dtype, D, h, ld_h, W, ld_w)) return rc;
   const size_t smem = (size_t)CS_BT * D * (dtype == OFA_F32 ? 4 : 2);
   OFA_REQUIRE(smem <= CS_LDS_MAX, OFA_ERR_UNSUPPORTED, "ofa_closed_set_edge_logits: D=%d needs %zu bytes of LDS", D, smem);
   if (n_items == 0) return OFA_OK;

@@ -134,11 +134,16 @@ __device__ __forceinline__ float dpp_f(float old, float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v), CTRL,
                                                                ROW_MASK, 0xf, false));
 }
-__device__ __forceinline__ float wave_sum(float v) {
+// sum over the 16 lanes of a DPP row; every lane of the row receives it
+__device__ __forceinline__ float row16_sum(float v) {
   v += dpp_f<0xB1, 0xf>(0.f, v);          // quad_perm [1,0,3,2]
   v += dpp_f<0x4E, 0xf>(0.f, v);          // quad_perm [2,3,0,1]  -> every quad holds its sum
   v += dpp_f<0x141, 0xf>(0.f, v);         // row_half_mirror      -> every 8 lanes
   v += dpp_f<0x140, 0xf>(0.f, v);         // row_mirror           -> every row of 16
+  return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+  v = row16_sum(v);
   v += dpp_f<0x142, 0xa>(0.f, v);         // row_bcast15 into rows 1, 3
   v += dpp_f<0x143, 0xc>(0.f, v);         // row_bcast31 into rows 2, 3 -> lanes 48..63 hold the total
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
@@ -153,6 +158,11 @@ __device__ __forceinline__ float wave_max(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 #else
+__device__ __forceinline__ float row16_sum(float v) {
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 16);
+  return v;
+}
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -225,6 +235,16 @@ template <bool EXACT> __device__ __forceinline__ void gauss_cdf(float x, float& 
 }
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// Feature rows h [*, D] and projection rows W [V, D] that kernels read as 16-byte vectors; `who` is the entry point's name.
+static inline int check_proj_operands(const char* who, int dtype, int D, const void* h, int64_t ld_h, const void* W, int64_t ld_w) {
+  const int vn = dt_vecn(dtype);
+  OFA_REQUIRE(D % vn == 0 && ld_h % vn == 0 && ld_w % vn == 0 && ld_h >= D && ld_w >= D && aligned16(h) && aligned16(W),
+              OFA_ERR_UNSUPPORTED, "%s: rows must be 16-byte aligned (D=%d ld_h=%lld ld_w=%lld)", who, D, (long long)ld_h,
+              (long long)ld_w);
+  return OFA_OK;
+}
 
 // Workgroups are dispatched in linear order (x fastest, then y, then z) round-robin over the 8 XCDs, and each XCD has its own L2.
 // xcd_remap is the bijective "each XCD gets a contiguous chunk of the n logical ids" map: workgroups whose logical ids are

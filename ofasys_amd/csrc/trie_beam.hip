@@ -30,46 +30,19 @@
 //    scores only), so the results are the reference's without the max_len + 1 - depth empty steps it runs.
 // No host synchronisation, fixed addresses, workspace passed in.  Every index read from the plan or the state is range-checked
 // before it addresses memory (an invalid node is a dead row, an invalid token a NaN logit).
-#include "common.h"
+#include "beam_common.h"
 
 namespace ofa {
 
-constexpr int TB_MAX_K = 16;              // = BEAM_MAX_K of beam_search.hip
-constexpr int TB_THREADS = 256;
-constexpr int TB_CHUNK = 4096;            // = BEAM_CHUNK: vocabulary columns per part of the sentence pass's layout
 constexpr int TB_BAN_MAX = 256;           // n-gram bans of one row: at most step + 1
 constexpr int TB_LDS_MAX = 65536;
 
-static inline int tb_layout_splits(int V) { return (V + TB_CHUNK - 1) / TB_CHUNK; }
 // edges per workgroup: the smallest multiple of 256 for which ceil(max_degree / epw) parts fit the layout (max_degree <= V: <= 4096)
 static inline int tb_edges_per_wg(int max_degree, int V) {
-  const int S = tb_layout_splits(V);
+  const int S = beam_splits(V);
   int p = 1;
-  while (cdiv(max_degree, TB_THREADS * p) > S) ++p;
-  return TB_THREADS * p;
-}
-
-// sum over the 16 lanes of a DPP row; every lane of the row receives it
-__device__ __forceinline__ float row16_sum(float v) {
-#ifndef OFA_WAVE_REDUCE_SHFL
-  v += dpp_f<0xB1, 0xf>(0.f, v);          // quad_perm [1,0,3,2]
-  v += dpp_f<0x4E, 0xf>(0.f, v);          // quad_perm [2,3,0,1]
-  v += dpp_f<0x141, 0xf>(0.f, v);         // row_half_mirror
-  v += dpp_f<0x140, 0xf>(0.f, v);         // row_mirror
-#else
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 16);
-#endif
-  return v;
-}
-
-// wave arg-max of (key desc, idx asc) over the lanes; NaN keys are empty.  Returns false when every lane is empty.
-__device__ __forceinline__ bool tb_wave_argmax(float key, int idx, float& mx, int& mi) {
-  mx = wave_max(key);
-  if (mx != mx) return false;
-  const float neg = (key == mx) ? -(float)idx : -INFINITY;     // indices < 2^24: exact as float
-  mi = (int)(-wave_max(neg));
-  return true;
+  while (cdiv(max_degree, BEAM_THREADS * p) > S) ++p;
+  return BEAM_THREADS * p;
 }
 
 struct TrieTopkArgs {
@@ -77,19 +50,14 @@ struct TrieTopkArgs {
   const void* W; int64_t ld_w; const void* bias;
   int D, V, rows, K, S, Su, epw;
   const int* node; const int* node_edge_off; const int* edge_token; int N, E;
-  float temperature; int step, min_len, max_len, pad, unk, eos; float unk_pen;
-  int ngram; const int64_t* tokens; int64_t tok_ld;
-  const int* done;
-  float* stats; float* cval; int* ctok;        // [rows, S, 2] / [rows, S, 2K] / [rows, S, 2K]
+  BeamPolicy p;
+  BeamWs ws;
 };
 
 struct TrieTopkScratch {                  // the row pass's fixed LDS scratch, at the start of its dynamic region
+  BeamListScratch lists;
   int banl[TB_BAN_MAX];
-  float lkey[4][2 * TB_MAX_K], lval[4][2 * TB_MAX_K];
-  int ltok[4][2 * TB_MAX_K];
-  int mtok[2 * TB_MAX_K];
-  float red_m[4], red_s[4];
-  int red_nan[4];
+  int mtok[2 * BEAM_MAX_K];
   int nban, ngot;
   float unk_val;
   int pad_;
@@ -97,11 +65,12 @@ struct TrieTopkScratch {                  // the row pass's fixed LDS scratch, a
 static_assert(sizeof(TrieTopkScratch) % 16 == 0, "the staged row behind the scratch is read with 16-byte LDS loads");
 
 template <typename T>
-__global__ __launch_bounds__(TB_THREADS) void trie_beam_topk_kernel(TrieTopkArgs a) {
+__global__ __launch_bounds__(BEAM_THREADS) void trie_beam_topk_kernel(TrieTopkArgs a) {
   constexpr int NV = Vec<T>::N;
   const int split = blockIdx.x, row = blockIdx.y;
-  if (a.done && a.done[row / a.K]) return;
-  if (a.step == 0 && row % a.K != 0) return;                  // the sentence pass reads beam 0 only at step 0
+  const BeamPolicy& p = a.p;
+  if (p.done && p.done[row / a.K]) return;
+  if (p.step == 0 && row % a.K != 0) return;                  // the sentence pass reads beam 0 only at step 0
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K2 = 2 * a.K, nv = a.D / NV;
   // all LDS scratch lives in the dynamic region, so its base -- and with it the 16-byte reads of the staged row -- stays 16-byte
@@ -111,32 +80,21 @@ __global__ __launch_bounds__(TB_THREADS) void trie_beam_topk_kernel(TrieTopkArgs
   uint4* hrow = tb_smem + sizeof(TrieTopkScratch) / 16;       // [D / NV] the hidden row, raw
   float* key = (float*)(hrow + nv);                           // [epw] logits, then ordering keys (NaN: no candidate)
   int* tokl = (int*)(key + a.epw);                            // [epw] their tokens
-  int (&banl)[TB_BAN_MAX] = sh.banl;
-  int& nban = sh.nban;
-  int& ngot = sh.ngot;
-  float& unk_val = sh.unk_val;
-  float (&red_m)[4] = sh.red_m;
-  float (&red_s)[4] = sh.red_s;
-  int (&red_nan)[4] = sh.red_nan;
-  float (&lkey)[4][2 * TB_MAX_K] = sh.lkey;
-  float (&lval)[4][2 * TB_MAX_K] = sh.lval;
-  int (&ltok)[4][2 * TB_MAX_K] = sh.ltok;
-  int (&mtok)[2 * TB_MAX_K] = sh.mtok;
 
   const int64_t part = (int64_t)row * a.S + split;
-  float* st = a.stats + part * 2;
-  float* ov = a.cval + part * K2;
-  int* ot = a.ctok + part * K2;
+  float* st = a.ws.stats + part * 2;
+  float* ov = a.ws.cval + part * K2;
+  int* ot = a.ws.ctok + part * K2;
   // ---- the layout's parts this plan never uses: empty
   if (split == 0) {
-    for (int e = tid; e < (a.S - a.Su) * K2; e += TB_THREADS) {
+    for (int e = tid; e < (a.S - a.Su) * K2; e += BEAM_THREADS) {
       const int64_t o = ((int64_t)row * a.S + a.Su) * K2 + e;
-      a.cval[o] = -INFINITY;
-      a.ctok[o] = -1;
+      a.ws.cval[o] = -INFINITY;
+      a.ws.ctok[o] = -1;
     }
-    for (int s = a.Su + tid; s < a.S; s += TB_THREADS) {
-      a.stats[((int64_t)row * a.S + s) * 2] = -INFINITY;
-      a.stats[((int64_t)row * a.S + s) * 2 + 1] = 0.f;
+    for (int s = a.Su + tid; s < a.S; s += BEAM_THREADS) {
+      a.ws.stats[((int64_t)row * a.S + s) * 2] = -INFINITY;
+      a.ws.stats[((int64_t)row * a.S + s) * 2 + 1] = 0.f;
     }
   }
   // ---- the row's node and this workgroup's slice of its edges (all uniform)
@@ -152,30 +110,21 @@ __global__ __launch_bounds__(TB_THREADS) void trie_beam_topk_kernel(TrieTopkArgs
   const int cnt = live ? max(0, min(a.epw, e1 - b0)) : 0;
   if (cnt == 0) {                                             // a dead row (NaN normaliser: the whole row is -inf) or an empty slice
     if (tid == 0) {
-      st[0] = (!live && split == 0) ? __int_as_float(0x7fc00000) : -INFINITY;
+      st[0] = (!live && split == 0) ? NAN : -INFINITY;
       st[1] = 0.f;
     }
-    for (int r = tid; r < K2; r += TB_THREADS) { ov[r] = -INFINITY; ot[r] = -1; }
+    for (int r = tid; r < K2; r += BEAM_THREADS) { ov[r] = -INFINITY; ot[r] = -1; }
     return;
   }
   const uint4* hsrc = (const uint4*)((const T*)a.h + (int64_t)row * a.ld_h);
-  for (int v = tid; v < nv; v += TB_THREADS) hrow[v] = hsrc[v];
-  if (tid == 0) { nban = 0; unk_val = 0.f; }
+  for (int v = tid; v < nv; v += BEAM_THREADS) hrow[v] = hsrc[v];
+  if (tid == 0) { sh.nban = 0; sh.unk_val = 0.f; }
   __syncthreads();
-  // ---- n-gram bans of this row (history tokens[row, 0..step]): every earlier occurrence of the last n-1 tokens bans its successor
-  const int ng = a.ngram;
-  if (ng > 0 && a.step + 2 - ng >= 0) {
-    const int64_t* hist = a.tokens + (int64_t)row * a.tok_ld;
-    const int last = a.step - ng + 2;
-    for (int i = tid; i + ng - 1 <= a.step; i += TB_THREADS) {
-      bool match = true;
-      for (int q = 0; q < ng - 1; ++q) match = match && (hist[i + q] == hist[last + q]);
-      if (match) {
-        const int q = atomicAdd(&nban, 1);
-        if (q < TB_BAN_MAX) banl[q] = (int)hist[i + ng - 1];
-      }
-    }
-  }
+  // ---- n-gram bans of this row, as a list
+  beam_ngram_scan(p, row, tid, [&](int64_t tok) {
+    const int q = atomicAdd(&sh.nban, 1);
+    if (q < TB_BAN_MAX) sh.banl[q] = (int)tok;
+  });
   // ---- one dot product per edge: 16 lanes per edge, four edges per wave at a time
   const int grp = lane >> 4, gl = lane & 15;
   for (int base = wave * 4; base < cnt; base += 16) {         // (wave-uniform bound: all 64 lanes reach the DPP reduction)
@@ -195,11 +144,11 @@ __global__ __launch_bounds__(TB_THREADS) void trie_beam_topk_kernel(TrieTopkArgs
     }
     acc = row16_sum(acc);
     if (gl == 0 && i < cnt) {
-      float z = __int_as_float(0x7fc00000);
+      float z = NAN;
       if (ok) {
         z = acc;
         if (a.bias) z += ld1<T>((const T*)a.bias + tok);
-        if (a.temperature != 1.f) z = z / a.temperature;
+        if (p.temperature != 1.f) z = z / p.temperature;
       }
       key[i] = z;
       tokl[i] = tok;
@@ -209,50 +158,33 @@ __global__ __launch_bounds__(TB_THREADS) void trie_beam_topk_kernel(TrieTopkArgs
   // ---- this slice's part of the normaliser
   float m = -INFINITY;
   int has_nan = 0;
-  for (int i = tid; i < cnt; i += TB_THREADS) {
+  for (int i = tid; i < cnt; i += BEAM_THREADS) {
     const float v = key[i];
     if (v != v) has_nan = 1;
     else m = fmaxf(m, v);
   }
-  m = wave_max(m);
-  float s = 0.f;
-  if (m != -INFINITY)
-    for (int i = tid; i < cnt; i += TB_THREADS) {
+  beam_normaliser_part(sh.lists, tid, m, has_nan, [&](float wm) {
+    float s = 0.f;
+    for (int i = tid; i < cnt; i += BEAM_THREADS) {
       const float v = key[i];
-      if (v == v) s += expf(v - m);
+      if (v == v) s += expf(v - wm);
     }
-  s = wave_sum(s);
-  has_nan = __any(has_nan) ? 1 : 0;
-  if (lane == 0) { red_m[wave] = m; red_s[wave] = s; red_nan[wave] = has_nan; }
-  __syncthreads();
-  if (tid == 0) {
-    const float M = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
-    float S = 0.f;
-    for (int w = 0; w < 4; ++w)
-      if (red_m[w] != -INFINITY) S += red_s[w] * expf(red_m[w] - M);
-    const bool bad = red_nan[0] | red_nan[1] | red_nan[2] | red_nan[3];
-    st[0] = bad ? __int_as_float(0x7fc00000) : M;
-    st[1] = S;
-  }
+    return s;
+  }, st);                                                     // (its barrier also orders the ban list)
   // ---- post-normaliser masks -> ordering keys; -inf is no candidate (entry i is read and written by thread i % 256 only)
-  const int nb = min(nban, TB_BAN_MAX);
-  for (int i = tid; i < cnt; i += TB_THREADS) {
-    float v = key[i];
+  const int nb = min(sh.nban, TB_BAN_MAX);
+  for (int i = tid; i < cnt; i += BEAM_THREADS) {
     const int c = tokl[i];
-    if (c == a.eos && a.step < a.min_len) v = -INFINITY;
-    if (v != v) v = -INFINITY;
-    if (c == a.pad) v = -INFINITY;
-    if (a.step >= a.max_len && c != a.eos) v = -INFINITY;
-    for (int q = 0; q < nb; ++q)
-      if (banl[q] == c) v = -INFINITY;
-    if (c == a.unk) { unk_val = v; v = v - a.unk_pen; }
-    key[i] = v == -INFINITY ? __int_as_float(0x7fc00000) : v;
+    bool banned = false;
+    for (int q = 0; q < nb; ++q) banned = banned || sh.banl[q] == c;
+    const float v = beam_mask_key(p, key[i], c, banned, sh.unk_val);
+    key[i] = v == -INFINITY ? NAN : v;
   }
   // ---- per-wave top 2K, sorted by (key desc, token asc)
   for (int it = 0; it < K2; ++it) {
-    float lb = __int_as_float(0x7fc00000);
+    float lb = NAN;
     int lc = 0x7fffffff, li = -1;
-    for (int i = tid; i < cnt; i += TB_THREADS) {
+    for (int i = tid; i < cnt; i += BEAM_THREADS) {
       const float v = key[i];
       if (v == v) {
         const int c = tokl[i];
@@ -260,54 +192,33 @@ __global__ __launch_bounds__(TB_THREADS) void trie_beam_topk_kernel(TrieTopkArgs
       }
     }
     float mx; int mc;
-    if (!tb_wave_argmax(lb, lc, mx, mc)) {
-      if (lane == 0) for (int r = it; r < K2; ++r) { lkey[wave][r] = __int_as_float(0x7fc00000); ltok[wave][r] = -1; }
+    if (!wave_argmax(lb, lc, mx, mc)) {
+      beam_close_list(sh.lists, wave, lane, it, K2);
       break;
     }
     if (li >= 0 && lc == mc) {
-      lkey[wave][it] = lb;
-      lval[wave][it] = mc == a.unk ? unk_val : lb;
-      ltok[wave][it] = mc;
-      key[li] = __int_as_float(0x7fc00000);
+      sh.lists.lkey[wave][it] = lb;
+      sh.lists.lval[wave][it] = mc == p.unk ? sh.unk_val : lb;
+      sh.lists.ltok[wave][it] = mc;
+      key[li] = NAN;
     }
   }
   __syncthreads();
-  // ---- wave 0 merges the four sorted lists (<= 128 entries: two per lane)
   if (wave == 0) {
-    float k0 = __int_as_float(0x7fc00000), k1 = k0;
-    int t0 = 0x7fffffff, t1 = 0x7fffffff;
-    const int x0 = lane, x1 = lane + 64;
-    if (x0 < 4 * K2 && ltok[x0 / K2][x0 % K2] >= 0) { k0 = lkey[x0 / K2][x0 % K2]; t0 = ltok[x0 / K2][x0 % K2]; }
-    if (x1 < 4 * K2 && ltok[x1 / K2][x1 % K2] >= 0) { k1 = lkey[x1 / K2][x1 % K2]; t1 = ltok[x1 / K2][x1 % K2]; }
-    int got = 0;
-    for (int it = 0; it < K2; ++it) {
-      const bool use0 = k0 == k0 && (!(k1 == k1) || k0 > k1 || (k0 == k1 && t0 < t1));
-      const float lb = use0 ? k0 : k1;
-      const int lt = use0 ? t0 : t1;
-      float mx; int mt;
-      if (!tb_wave_argmax(lb, lt, mx, mt)) break;
-      if (lb == lb && lt == mt) {
-        const int x = use0 ? x0 : x1;
-        ov[it] = lval[x / K2][x % K2];
-        ot[it] = mt;
-        mtok[it] = mt;
-        if (use0) k0 = __int_as_float(0x7fc00000); else k1 = __int_as_float(0x7fc00000);
-      }
-      ++got;
-    }
-    if (lane == 0) ngot = got;
+    const int got = beam_merge_lists(sh.lists, lane, K2, ov, ot, sh.mtok);
+    if (lane == 0) sh.ngot = got;
   }
   __syncthreads();
   // ---- fewer than 2K finite candidates: split 0 refills with -inf at the lowest token ids it has not listed, the others stay empty
   if (tid == 0) {
-    const int got = ngot;
+    const int got = sh.ngot;
     int t = 0;
     for (int r = got; r < K2; ++r) {
       int tok = -1;
       if (split == 0) {
         for (; t < a.V; ++t) {
           bool used = false;
-          for (int q = 0; q < got; ++q) used = used || mtok[q] == t;
+          for (int q = 0; q < got; ++q) used = used || sh.mtok[q] == t;
           if (!used) break;
         }
         if (t < a.V) tok = t++;
@@ -326,12 +237,12 @@ struct TrieAdvanceArgs {
   const int* ignore; const int64_t* reorder; int* done; int* nfin;
 };
 
-__global__ __launch_bounds__(TB_THREADS) void trie_beam_advance_kernel(TrieAdvanceArgs a) {
+__global__ __launch_bounds__(BEAM_THREADS) void trie_beam_advance_kernel(TrieAdvanceArgs a) {
   const int sent = blockIdx.x;
   if (a.done[sent]) return;                                   // finished (possibly by this step's sentence pass): its nodes are not read again
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = a.K, r0 = sent * K;
-  __shared__ int old[TB_MAX_K];
+  __shared__ int old[BEAM_MAX_K];
   __shared__ int alive;
   if (tid < K) old[tid] = a.node[r0 + tid];
   if (tid == 0) alive = 0;
@@ -366,8 +277,6 @@ __global__ __launch_bounds__(TB_THREADS) void trie_beam_advance_kernel(TrieAdvan
   }
 }
 
-static inline bool tb_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace ofa
 
 using namespace ofa;
@@ -386,35 +295,24 @@ extern "C" int ofa_trie_beam_topk(const void* h, int64_t ld_h, int dtype, const 
   OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "ofa_trie_beam_topk: bad dtype %d", dtype);
   OFA_REQUIRE(rows > 0 && V > 1 && D > 0 && step >= 0 && N > 0 && E > 0, OFA_ERR_INVALID,
               "ofa_trie_beam_topk: rows=%d V=%d D=%d step=%d N=%d E=%d", rows, V, D, step, N, E);
-  OFA_REQUIRE(K >= 1 && K <= TB_MAX_K, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: beam size %d outside [1, %d]", K, TB_MAX_K);
-  OFA_REQUIRE(rows % K == 0, OFA_ERR_INVALID, "ofa_trie_beam_topk: rows %d not a multiple of the beam size %d", rows, K);
-  OFA_REQUIRE((int64_t)K * V < (1 << 24), OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: beam * vocabulary must stay below 2^24");
+  if (const int rc = beam_check_row_pass("ofa_trie_beam_topk", rows, V, K, temperature, step, ngram, tokens, tok_ld)) return rc;
   OFA_REQUIRE(max_degree >= 1 && max_degree <= V && max_degree <= E, OFA_ERR_INVALID,
               "ofa_trie_beam_topk: max_degree %d outside [1, min(V, E)]", max_degree);
-  OFA_REQUIRE(temperature > 0.f, OFA_ERR_INVALID, "ofa_trie_beam_topk: temperature must be > 0");
-  OFA_REQUIRE(ngram <= 0 || (tokens && tok_ld > step), OFA_ERR_INVALID, "ofa_trie_beam_topk: n-gram bans need the token history");
   OFA_REQUIRE(ngram <= 0 || step < TB_BAN_MAX, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: n-gram bans beyond step %d", TB_BAN_MAX);
-  const int vn = dt_vecn(dtype);
-  OFA_REQUIRE(D % vn == 0 && ld_h % vn == 0 && ld_w % vn == 0 && ld_h >= D && ld_w >= D && tb_aligned16(h) && tb_aligned16(W),
-              OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: rows must be 16-byte aligned (D=%d ld_h=%lld ld_w=%lld)", D, (long long)ld_h,
-              (long long)ld_w);
-  TrieTopkArgs a{h, ld_h, W, ld_w, bias, D, V, rows, K, tb_layout_splits(V), 0, tb_edges_per_wg(max_degree, V), node, node_edge_off,
-                 edge_token, N, E, temperature, step, min_len, max_len, pad, unk, eos, unk_penalty, ngram, tokens, tok_ld, done,
-                 nullptr, nullptr, nullptr};
-  a.Su = cdiv(max_degree, a.epw);
+  if (const int rc = check_proj_operands("ofa_trie_beam_topk", dtype, D, h, ld_h, W, ld_w)) return rc;
+  const int S = beam_splits(V), epw = tb_edges_per_wg(max_degree, V);
+  TrieTopkArgs a{h, ld_h, W, ld_w, bias, D, V, rows, K, S, cdiv(max_degree, epw), epw, node, node_edge_off, edge_token, N, E,
+                 BeamPolicy{temperature, step, min_len, max_len, pad, unk, eos, unk_penalty, ngram, tokens, tok_ld, done},
+                 beam_ws_carve(ws, rows, S, K)};
   const size_t smem = sizeof(TrieTopkScratch) + (size_t)D * (dtype == OFA_F32 ? 4 : 2) + (size_t)a.epw * 8;
   OFA_REQUIRE(smem <= TB_LDS_MAX, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: D=%d with %d edges per workgroup needs %zu bytes of LDS",
               D, a.epw, smem);
   OFA_REQUIRE(rows <= 65535, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: %d rows", rows);
-  const int64_t S = a.S;
-  a.stats = (float*)ws;
-  a.cval = a.stats + (int64_t)rows * S * 2;
-  a.ctok = (int*)(a.cval + (int64_t)rows * S * 2 * K);
   dim3 grid(a.Su, rows);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32) hipLaunchKernelGGL(trie_beam_topk_kernel<float>, grid, dim3(TB_THREADS), smem, st, a);
-  else if (dtype == OFA_BF16) hipLaunchKernelGGL(trie_beam_topk_kernel<bf16_t>, grid, dim3(TB_THREADS), smem, st, a);
-  else hipLaunchKernelGGL(trie_beam_topk_kernel<f16_t>, grid, dim3(TB_THREADS), smem, st, a);
+  if (dtype == OFA_F32) hipLaunchKernelGGL(trie_beam_topk_kernel<float>, grid, dim3(BEAM_THREADS), smem, st, a);
+  else if (dtype == OFA_BF16) hipLaunchKernelGGL(trie_beam_topk_kernel<bf16_t>, grid, dim3(BEAM_THREADS), smem, st, a);
+  else hipLaunchKernelGGL(trie_beam_topk_kernel<f16_t>, grid, dim3(BEAM_THREADS), smem, st, a);
   return check_launch("ofa_trie_beam_topk");
 }
 
@@ -426,12 +324,12 @@ extern "C" int ofa_trie_beam_advance(int* node, const int* node_edge_off, const 
               OFA_ERR_INVALID, "ofa_trie_beam_advance: null pointer");
   OFA_REQUIRE(bsz > 0 && step >= 0 && N > 0 && E > 0 && N < (1 << 24), OFA_ERR_INVALID, "ofa_trie_beam_advance: bsz=%d step=%d N=%d E=%d",
               bsz, step, N, E);
-  OFA_REQUIRE(K >= 1 && K <= TB_MAX_K, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_advance: beam size %d outside [1, %d]", K, TB_MAX_K);
+  OFA_REQUIRE(K >= 1 && K <= BEAM_MAX_K, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_advance: beam size %d outside [1, %d]", K, BEAM_MAX_K);
   OFA_REQUIRE(tok_cap >= step + 1 && tok_ld >= tok_cap && score_ld > step, OFA_ERR_INVALID,
               "ofa_trie_beam_advance: history buffers too short for step %d (tok_cap=%d tok_ld=%lld score_ld=%lld)", step, tok_cap,
               (long long)tok_ld, (long long)score_ld);
   TrieAdvanceArgs a{node, node_edge_off, edge_token, edge_child, N, E, bsz, K, step, tokens, tok_ld, tok_cap, scores, score_ld,
                     ignore, reorder, done, nfin};
-  hipLaunchKernelGGL(trie_beam_advance_kernel, dim3(bsz), dim3(TB_THREADS), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(trie_beam_advance_kernel, dim3(bsz), dim3(BEAM_THREADS), 0, (hipStream_t)stream, a);
   return check_launch("ofa_trie_beam_advance");
 }

@@ -101,23 +101,13 @@ class StepDecoder:
         elif graphed:
             g = torch.cuda.CUDAGraph()
             torch.cuda.synchronize()
-            # kernels.workspace() caches scratch per stream, and every capture runs on torch's one default capture stream: a
-            # buffer allocated inside this capture lives in THIS decoder's private pool.  Left in the shared cache, a later
-            # capture (a TrainStep) would address it without owning it and fault once it is dropped and the pool released.  The
-            # decoder's captures therefore see only their own scratch, kept alive here for as long as its graphs.
-            saved = dict(K._ws_cache)
-            K._ws_cache.clear()
-            K._ws_cache.update(self._ws)
-            try:
-                with torch.no_grad(), torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
-                    logits = self._run(t)
-                    if post is not None:
-                        post(logits, t)
-            finally:
-                self._ws = dict(K._ws_cache)
-                self._ws_keep.extend(v for v in self._ws.values() if all(v is not w for w in self._ws_keep))
-                K._ws_cache.clear()
-                K._ws_cache.update(saved)
+            # the decoder's captures see only their own scratch (kernels.capture_workspaces), kept alive for as long as its graphs
+            with K.capture_workspaces(self._ws) as added, torch.no_grad(), \
+                    torch.cuda.graph(g, pool=self._pool, capture_error_mode="thread_local"):
+                logits = self._run(t)
+                if post is not None:
+                    post(logits, t)
+            self._ws_keep.extend(added.values())
             if self._pool is None:
                 self._pool = g.pool()
             self._graphs[t] = (g, logits)
@@ -280,25 +270,47 @@ class SequenceGenerator:
         st["reorder"].copy_(torch.arange(rows, dtype=torch.long, device=device))
         return st
 
-    def _step_kernels(self, logits, t, dec, st, max_len, ngram_step0=True):
-        """Everything a step does after the decoder, on the device (recorded into the step graph)."""
-        V = logits.shape[1]
-        ngram = self.no_repeat_ngram_size if (t > 0 or ngram_step0) else 0
+    # ------------------------------------------------------------------ what TrieBeamGenerator overrides
+    def _setup(self, model, max_len, device):
+        """Before the loop: (steps after the first, i.e. the longest hypothesis without its EOS; the vocabulary width of the
+        state; whatever `_row_pass` and `_advance` need)."""
+        return max_len, self.vocab_size, None
+
+    def _decoder(self, model, capacity):
+        if self._dec is None or self._dec.model is not model:
+            self._dec = StepDecoder(model, capacity, use_graph=self.use_graph)
+        return self._dec
+
+    def _check_output(self, logits):
+        if logits.shape[1] > self.vocab_size:
+            raise ValueError(f"decoder output width {logits.shape[1]} > dictionary size {self.vocab_size}")
+
+    def _row_pass(self, logits, t, dec, st, max_len, ngram, ctx):
+        """The step's row pass into st["ws"]; returns the vocabulary width the sentence pass works with."""
         K.beam_topk(logits, self.beam_size, t, st["ws"], tokens=dec.tokens, done=st["done"], temperature=self.temperature,
                     constraint_range=None if self.constraint_start is None else (self.constraint_start, self.constraint_end),
                     min_len=self.min_len, max_len=max_len, pad=self.pad, unk=self.unk, eos=self.eos,
                     unk_penalty=self.unk_penalty, ngram=ngram)
+        return logits.shape[1]
+
+    def _advance(self, t, st, ctx):
+        """Device work between the sentence pass and the cache reorder."""
+
+    def _step_kernels(self, out, t, dec, st, max_len, ngram_step0=True, ctx=None):
+        """Everything a step does after the decoder, on the device (recorded into the step graph)."""
+        ngram = self.no_repeat_ngram_size if (t > 0 or ngram_step0) else 0
+        V = self._row_pass(out, t, dec, st, max_len, ngram, ctx)
         st["tokens"] = dec.tokens
         K.beam_select(st["ws"], st, self.beam_size, V, t, max_len, eos=self.eos, unk=self.unk, unk_penalty=self.unk_penalty,
                       normalize=self.normalize_scores, len_penalty=self.len_penalty)
+        self._advance(t, st, ctx)
         dec.reorder(st["reorder"], caches_only=True)
 
     # ------------------------------------------------------------------ generate
     @torch.no_grad()
     def generate(self, model, sample, **kwargs):
         ngram_step0 = self.check_sample(sample, **kwargs)
-        slots = sample["net_input"]["slots"]
-        source_slots = [s for s in slots if s.is_src]
+        source_slots = [s for s in sample["net_input"]["slots"] if s.is_src]
         first = source_slots[0].value
         src = first["fbank"] if isinstance(first, dict) else first
         bsz, device = src.shape[0], src.device
@@ -306,19 +318,14 @@ class SequenceGenerator:
         rows = bsz * beam
         max_len = self.effective_max_len(sample)
         assert self.min_len <= max_len, "min_len cannot be larger than max_len, please adjust these!"
-        if self._dec is None or self._dec.model is not model:
-            self._dec = StepDecoder(model, max_len + 1, use_graph=self.use_graph)
-        dec = self._dec
+        steps, V, ctx = self._setup(model, max_len, device)
+        dec = self._decoder(model, steps + 1)
         dec.begin(source_slots, torch.arange(bsz, device=device).repeat_interleave(beam))
         dec.tokens.fill_(self.pad)
         dec.tokens[:, 0] = self.bos
-        st = self._buffers(rows, bsz, self.vocab_size, max_len, device)
-        post = lambda logits, t: self._step_kernels(logits, t, dec, st, max_len, ngram_step0)   # noqa: E731
-
-        def check(logits):
-            if logits.shape[1] > self.vocab_size:
-                raise ValueError(f"decoder output width {logits.shape[1]} > dictionary size {self.vocab_size}")
-        self._loop(dec, st, bsz, max_len + 1, post, check)
+        st = self._buffers(rows, bsz, V, steps, device)
+        post = lambda out, t: self._step_kernels(out, t, dec, st, max_len, ngram_step0, ctx)   # noqa: E731
+        self._loop(dec, st, bsz, steps + 1, post, self._check_output)
         return self._collect(st, bsz)
 
     def _loop(self, dec, st, bsz, nsteps, post, check=None):
@@ -390,50 +397,36 @@ class TrieBeamGenerator(SequenceGenerator):
         st["node"].zero_()                                # every row starts at the root
         return st
 
-    def _trie_step(self, feats, t, dec, st, dev, weight, bias, max_len, ngram_step0=True):
-        """Everything a step does after the decoder, on the device (recorded into the step graph)."""
-        ngram = self.no_repeat_ngram_size if (t > 0 or ngram_step0) else 0
-        if feats.dtype != weight.dtype:
-            feats = feats.to(weight.dtype)
-        K.trie_beam_topk(feats, weight, bias, dev, st["node"], self.beam_size, t, st["ws"], tokens=dec.tokens, done=st["done"],
-                         temperature=self.temperature, min_len=self.min_len, max_len=max_len, pad=self.pad, unk=self.unk,
-                         eos=self.eos, unk_penalty=self.unk_penalty, ngram=ngram)
-        st["tokens"] = dec.tokens
-        K.beam_select(st["ws"], st, self.beam_size, weight.shape[0], t, max_len, eos=self.eos, unk=self.unk,
-                      unk_penalty=self.unk_penalty, normalize=self.normalize_scores, len_penalty=self.len_penalty)
-        K.trie_beam_advance(dev, st["node"], st, self.beam_size, t)
-        dec.reorder(st["reorder"], caches_only=True)
-
-    @torch.no_grad()
-    def generate(self, model, sample, **kwargs):
+    def _setup(self, model, max_len, device):
         from .traverse import TraverseTask
-        ngram_step0 = self.check_sample(sample, **kwargs)
-        source_slots = [s for s in sample["net_input"]["slots"] if s.is_src]
-        first = source_slots[0].value
-        src = first["fbank"] if isinstance(first, dict) else first
-        bsz, device = src.shape[0], src.device
-        beam = self.beam_size
-        rows = bsz * beam
-        max_len = self.effective_max_len(sample)
-        assert self.min_len <= max_len, "min_len cannot be larger than max_len, please adjust these!"
-        steps = min(max_len, self.plan.Tmax)              # no hypothesis is longer than the deepest answer (+ EOS)
         weight, bias = TraverseTask.output_projection(model)
         V = weight.shape[0]
         if V > self.vocab_size:
             raise ValueError(f"decoder output width {V} > dictionary size {self.vocab_size}")
         if int(self.plan.edge_token.max()) >= V:
             raise ValueError(f"the closed set holds token id {int(self.plan.edge_token.max())}, the output projection has {V} rows")
-        if self._dec is None or self._dec.model is not model or self._dec.max_len != steps + 1:
-            self._dec = StepDecoder(model, steps + 1, use_graph=self.use_graph, features_only=True)
-        dec = self._dec
-        dec.begin(source_slots, torch.arange(bsz, device=device).repeat_interleave(beam))
-        dec.tokens.fill_(self.pad)
-        dec.tokens[:, 0] = self.bos
-        st = self._buffers(rows, bsz, V, steps, device)
-        dev = self._plan_on(device)
-        post = lambda feats, t: self._trie_step(feats, t, dec, st, dev, weight, bias, max_len, ngram_step0)   # noqa: E731
-        self._loop(dec, st, bsz, steps + 1, post)
-        return self._collect(st, bsz)
+        # no hypothesis is longer than the deepest answer (+ EOS)
+        return min(max_len, self.plan.Tmax), V, (self._plan_on(device), weight, bias)
+
+    def _decoder(self, model, capacity):
+        if self._dec is None or self._dec.model is not model or self._dec.max_len != capacity:
+            self._dec = StepDecoder(model, capacity, use_graph=self.use_graph, features_only=True)
+        return self._dec
+
+    def _check_output(self, feats):
+        pass                                              # features [rows, D]: the projection's width was checked in _setup
+
+    def _row_pass(self, feats, t, dec, st, max_len, ngram, ctx):
+        dev, weight, bias = ctx
+        if feats.dtype != weight.dtype:
+            feats = feats.to(weight.dtype)
+        K.trie_beam_topk(feats, weight, bias, dev, st["node"], self.beam_size, t, st["ws"], tokens=dec.tokens, done=st["done"],
+                         temperature=self.temperature, min_len=self.min_len, max_len=max_len, pad=self.pad, unk=self.unk,
+                         eos=self.eos, unk_penalty=self.unk_penalty, ngram=ngram)
+        return weight.shape[0]
+
+    def _advance(self, t, st, ctx):
+        K.trie_beam_advance(ctx[0], st["node"], st, self.beam_size, t)
 
     def _collect(self, st, bsz):
         if self.return_n_best == 1:                       # (the reference indexes an empty list here)

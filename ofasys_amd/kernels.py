@@ -3,6 +3,7 @@
 Each wrapper allocates outputs with torch (plumbing: device memory + streams), checks layout, and enqueues the HIP
 kernel on torch's current stream.  Everything here requires GPU tensors; nothing falls back to torch math.
 """
+import contextlib
 import ctypes
 
 import torch
@@ -22,6 +23,24 @@ def workspace(nbytes, device, tag="ws"):
         buf = torch.empty(max(n, 1 << 20), dtype=torch.float32, device=device)
         _ws_cache[key] = buf
     return buf
+
+
+@contextlib.contextmanager
+def capture_workspaces(cache):
+    """For the duration of a graph capture, workspace() sees only `cache`: the scratch of the owner's earlier captures.  Every
+    capture runs on torch's one default capture stream, and a buffer allocated inside a capture lives in that capture's private
+    pool: left in the shared cache, a later capture of another owner would address it without owning it and fault once it is
+    dropped and the pool released.  On exit `cache` also holds what the capture allocated, the shared cache is back, and the
+    yielded dict holds the new buffers alone -- the owner keeps them alive for as long as its graphs."""
+    global _ws_cache
+    saved, _ws_cache = _ws_cache, dict(cache)
+    added = {}
+    try:
+        yield added
+    finally:
+        added.update({k: v for k, v in _ws_cache.items() if cache.get(k) is not v})
+        cache.update(added)
+        _ws_cache = saved
 
 
 class _FoldJob(ctypes.Structure):
