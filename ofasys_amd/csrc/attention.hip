@@ -78,7 +78,11 @@ struct AttnL {
 __device__ __forceinline__ void seg_zero_fill(const int* seg, int B, int b, int h, bool k_side, int rows, bf16_t* o1, int64_t ld1,
                                               bf16_t* o2, int64_t ld2, int tid, float* stat_h = nullptr) {
   const int4 s = reinterpret_cast<const int4*>(seg)[b];
-  const int lo = k_side ? s.z + s.w : s.x + s.y;
+  // A sample whose OTHER side is empty (no keys: a decoder sample whose source is all padding; or no queries) is entered by no
+  // workgroup (seg_enter), so its own rows count as filler: out / dq / lse / delta without keys, dk / dv without queries are zero --
+  // the fully-masked-row convention of the dense kernels.
+  const bool other_empty = k_side ? s.y <= 0 : s.w <= 0;
+  const int lo = other_empty ? (k_side ? s.z : s.x) : (k_side ? s.z + s.w : s.x + s.y);
   int hi = rows;
   if (b + 1 < B) {
     const int4 n = reinterpret_cast<const int4*>(seg)[b + 1];
@@ -90,7 +94,7 @@ __device__ __forceinline__ void seg_zero_fill(const int* seg, int B, int b, int 
     if (o1) *reinterpret_cast<uint4*>(o1 + (int64_t)r * ld1 + h * HD + c) = z;
     if (o2) *reinterpret_cast<uint4*>(o2 + (int64_t)r * ld2 + h * HD + c) = z;
   }
-  if (stat_h) {                                                     // a per-row fp32 statistic of head h (delta): same filler rows
+  if (stat_h) {                                                     // a per-row fp32 statistic of head h (lse / delta): same filler rows
     for (int r = lo + tid; r < hi; r += 256) stat_h[r] = 0.f;
     if (b == 0)
       for (int r = tid; r < (k_side ? s.z : s.x); r += 256) stat_h[r] = 0.f;
@@ -556,7 +560,7 @@ __device__ __forceinline__ void attn_fwd_body(AttnL a) {
   const int h = bh % a.heads;
   const int qb0 = blockIdx.x * 128;
   if (a.seg && blockIdx.x == gridDim.x - 1) {            // ragged mode: the extra grid column zero-fills the filler rows
-    seg_zero_fill(a.seg, a.B, b, h, false, a.rows_q, a.out, a.ldo, nullptr, 0, tid);
+    seg_zero_fill(a.seg, a.B, b, h, false, a.rows_q, a.out, a.ldo, nullptr, 0, tid, a.lse ? a.lse + (int64_t)h * a.Tpad : nullptr);
     return;
   }
 #ifdef OFA_ATTN_TIMELINE
@@ -1090,6 +1094,18 @@ __device__ __forceinline__ void attn_bwd_dkv_body(AttnL a) {
   }
   const bool key_dead = ki >= a.S || (a.kpm && a.kpm[(int64_t)b * a.S + krow] != 0);
   const float live = key_dead ? 0.f : 1.f;
+  if constexpr (BIAS != 1) {
+    // A dead key takes part with a zero K row: its score is 0 (+ bias), so the `exp2(score - lse) * live` of the blocks without a
+    // diagonal is 0 * finite.  With its own row a padded key may outscore lse by more than exp2 holds, and inf * 0 is NaN.  (Once,
+    // in front of the loop: the loop itself is at its register limit.  The dense-bias form selects per element anyway.)
+    const uint32_t keep = key_dead ? 0u : ~0u;
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      uint4 w = __builtin_bit_cast(uint4, kf[kk]);
+      w.x &= keep; w.y &= keep; w.z &= keep; w.w &= keep;
+      kf[kk] = __builtin_bit_cast(bf16x8, w);
+    }
+  }
   const float c = head_scale(a, h);
   const bf16_t* qbase = a.q + (int64_t)b * a.T * a.ldq;
   const bf16_t* dobase = a.dout + (int64_t)b * a.T * a.ldo;
