@@ -311,6 +311,26 @@ int ofa_segment_rowsum(const void* dout, const int32_t* order, const int32_t* se
 int ofa_embedding_bwd_slices(int64_t V, int D);
 int ofa_embedding_bwd(const void* dout, const int64_t* ids, void* dweight, int64_t n, int D, int64_t V,
                       int64_t padding_idx, uint8_t* present_ws, float* slice_ws, int dtype, void* stream);
+/* The same gradient id-major, in one launch without scratch: for id lists of at most OFA_EMBEDDING_IDS_MAX entries (staged in LDS) and
+ * rows of whole 16-byte vectors -- ofa_embedding_bwd_ids_ok() says whether (n, D, V, dtype) qualifies.  The first position that holds an
+ * id adds every row of that id in increasing position order and updates dweight[id] once.  slices: 1, or the
+ * ofa_embedding_bwd_slices(V, D) the caller would have given ofa_embedding_bwd a slice_ws for -- the sums are then grouped as its slices
+ * are, so the result equals ofa_embedding_bwd's bit for bit either way.  Rows of ids that do not occur are not touched; the padding id and
+ * ids outside [0, V) are skipped. */
+#define OFA_EMBEDDING_IDS_MAX 15360
+int ofa_embedding_bwd_ids_ok(int64_t n, int D, int64_t V, int dtype);
+int ofa_embedding_bwd_ids(const void* dout, const int64_t* ids, void* dweight, int64_t n, int D, int64_t V, int64_t padding_idx,
+                          int slices, int dtype, void* stream);
+/* The gradient of a lookup by the contiguous ids r0 .. r0 + T - 1 (position tables read with arange(T), the same rows for every sample),
+ * from the gradient of the [batch, T, D] tensor the rows were broadcast into: dweight[r0 + t] += round(sum_b dout[b][t]) -- the batch
+ * sum in fp32 in batch order, rounded to the storage type as ofa_batch_sum rounds it, then added as ofa_embedding_bwd adds a row:
+ * ofa_batch_sum + ofa_embedding_bwd in one pass over dout, bit for bit.  batch == 1: dout is the [T, D] gradient of the rows themselves.
+ * The caller promises the ids; nothing is read to check them. */
+int ofa_embedding_range_bwd(const void* dout, void* dweight, int batch, int64_t T, int D, int64_t V, int64_t r0, int dtype, void* stream);
+/* Debug library only (OFA_STEP_EDGES_OLD = bit mask over the items below): should this caller take the path it took before the
+ * one-launch forms above existed?  Always 0 in the product library. */
+enum { OFA_EDGE_POS_RANGE = 0, OFA_EDGE_TOKEN_BWD = 1, OFA_EDGE_COLSUM_FOLD = 2, OFA_EDGE_IM2COL = 3 };
+int ofa_step_edges_old(int item);
 
 /* ---- elementwise pieces of the layer (transformer_layer.py:167-208): */
 int ofa_gelu_fwd(const void* x, void* y, int64_t n, int dtype, void* stream);                  /* module/gelu.py:18-19 */
@@ -520,10 +540,14 @@ typedef struct ofa_fold_job {
   int64_t cols;
   int64_t stride;      /* elements between consecutive partial rows (>= cols) */
   int32_t nslots;
-  int32_t accumulate;  /* != 0: added to the current contents of out */
+  int32_t accumulate;  /* bit 0: added to the current contents of out; OFA_FOLD_LANES16: see below */
   float alpha;
   int32_t out_dtype;   /* OFA_F32 / OFA_BF16 */
 } ofa_fold_job;
+/* `accumulate | OFA_FOLD_LANES16`: a job of more than 16 slots is summed in sixteen slot lanes (lane l: slots l, l + 16, ...; lanes
+ * added in lane order) -- the order of ofa_colsum's own final pass, so that a deferred column sum has the bits of an immediate one.
+ * Without it such a job is summed in eight lanes (the order of the LayerNorm reduce kernels).  At most 16 slots: slot order either way. */
+#define OFA_FOLD_LANES16 4
 int ofa_fold_batched(const ofa_fold_job* jobs, int njobs, void* stream);
 /* Batched device-to-device copy: dst_i[0 .. bytes_i) = src_i[0 .. bytes_i) for any number of (dense) buffers in as few launches as
  * possible (96 jobs per launch) -- the static inputs of a replayed step graph (engine/trainer.py's _prepare_sample moves a batch to

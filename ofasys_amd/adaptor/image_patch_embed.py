@@ -58,4 +58,4 @@ class ImagePatchEmbedAdaptor(BaseAdaptor):
         mask = ops.cached_index(self, ("nomask", batch_size, n), lambda: torch.zeros((batch_size, n), dtype=torch.bool, device=image.device))
         pos = ops.cached_index(self, ("arange", n), lambda: torch.arange(n, dtype=torch.long, device=image.device).unsqueeze(0))
         # one lookup of the n positions, expanded (stride 0) to the batch: ops.shared_rows
-        return AdaptorOutput(x, mask, self.embed_image_positions(pos).expand(batch_size, -1, -1), None)
+        return AdaptorOutput(x, mask, self.embed_image_positions(pos, range_start=0).expand(batch_size, -1, -1), None)   # (pos IS arange(n))

@@ -92,7 +92,7 @@ class TextAdaptor(BaseAdaptor):
         # the [B, T, D] the contract names through a stride-0 expand (ops.shared_rows: the post-hook, the entangled add and the
         # position bias read the one copy)
         positions = ops.cached_index(self, ("arange", seq_len), lambda: torch.arange(seq_len, device=src_tokens.device).unsqueeze(0))
-        pos_embed = self.embed_positions(positions).expand(bsz, -1, -1)
+        pos_embed = self.embed_positions(positions, range_start=0).expand(bsz, -1, -1)      # (`positions` IS arange(T): the promise)
         return AdaptorOutput(token_embedding, padding_masks, pos_embed, [])
 
     def forward_output(self, x: Tensor, extra: Dict[str, Any], slot: Slot, **kwargs):

@@ -9,6 +9,12 @@
 
 namespace ofa {
 
+// v rounded to the storage type T and read back (the value a store of v followed by a load hands on)
+template <typename T> __device__ __forceinline__ float round_to(float v);
+template <> __device__ __forceinline__ float round_to<float>(float v) { return v; }
+template <> __device__ __forceinline__ float round_to<bf16_t>(float v) { return bf2f(f2bf(v)); }
+template <> __device__ __forceinline__ float round_to<f16_t>(float v) { return (float)(f16_t)v; }
+
 template <typename T, bool BWD>
 __global__ __launch_bounds__(256) void gelu_kernel(const T* __restrict__ dy, const T* __restrict__ x, T* __restrict__ y,
                                                    int64_t nvec, int64_t n) {
@@ -320,6 +326,151 @@ __global__ __launch_bounds__(256) void embedding_fold_kernel(const float* __rest
   }
 }
 
+// The same scatter-add ID-MAJOR, for id lists that fit the LDS (the token table: V = 51265 rows, a few thousand ids -- the V-sized grid
+// above spends its time on waves that read a presence byte and leave, behind a memset, a mark pass and their launches).  Every block
+// stages the ids once as int32 (-1: out of range or the padding id); one wave per POSITION: the first position that holds an id owns
+// it, every other wave leaves after the look-back.  The owner walks the list from its own position on, 64 ids per ballot, and queues
+// the matching positions (in order) in LDS; the queue is drained G rows at a time -- G row loads in flight, then the additions in
+// increasing position order (an id every sample holds, like <bos>, is otherwise one exposed memory latency per sample) -- with SLICED in
+// the slices embedding_bwd_kernel would cut (`per` ids each, partial sums folded in slice order).  Then the one read-modify-write of
+// dw[v]: bit for bit what the table-row-major kernels give.
+constexpr int EMB_IDS_WAVES = 8;
+template <typename T, int NV, bool SLICED>
+__global__ __launch_bounds__(EMB_IDS_WAVES * 64) void embedding_bwd_ids_kernel(const T* __restrict__ dout, const int64_t* __restrict__ ids,
+                                                                               T* __restrict__ dw, int n, int D, int64_t V,
+                                                                               int64_t padding_idx, int per) {
+  constexpr int N = Vec<T>::N;
+  constexpr int G = NV <= 1 ? 8 : 4;                             // rows in flight per drain step (registers: two blocks per CU)
+  typedef typename Vec<T>::type raw_t;
+  extern __shared__ int sid[];                                   // (n rounded up to 64) ids, then 64 queue entries per wave
+  const int npad = (n + 63) & ~63;
+  for (int i = threadIdx.x; i < npad; i += EMB_IDS_WAVES * 64) {
+    const int64_t id = i < n ? ids[i] : -1;
+    sid[i] = (id >= 0 && id < V && id != padding_idx) ? (int)id : -1;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  int* queue = sid + npad + (threadIdx.x >> 6) * 64;
+  for (int pos = blockIdx.x * EMB_IDS_WAVES + (threadIdx.x >> 6); pos < n; pos += gridDim.x * EMB_IDS_WAVES) {      // (wave-uniform)
+    const int v = sid[pos];
+    if (v < 0) continue;
+    const int base0 = pos & ~63;
+    bool earlier = false;                                        // does an earlier position hold v?  (no exit inside: the reads pipeline)
+    for (int base = 0; base <= base0; base += 64) earlier |= (base + lane < pos) && sid[base + lane] == v;
+    if (__ballot(earlier)) continue;
+    float acc[NV][N], tot[SLICED ? NV : 1][N];                   // the current slice's sum / the folded slices
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+#pragma unroll
+      for (int j = 0; j < N; ++j) acc[i][j] = 0.f;
+#pragma unroll
+    for (int i = 0; i < (SLICED ? NV : 1); ++i)
+#pragma unroll
+      for (int j = 0; j < N; ++j) tot[i][j] = 0.f;
+    int cnt = 0;                                                 // queued positions (wave-uniform)
+    auto drain = [&]() {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the queue entries other lanes of this wave wrote
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      for (int k = 0; k < cnt; k += G) {
+        raw_t raw[G][NV];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          const T* row = dout + (int64_t)queue[k + g < cnt ? k + g : cnt - 1] * D;
+#pragma unroll
+          for (int i = 0; i < NV; ++i) {
+            const int c = (i * 64 + lane) * N;
+            if (c < D) raw[g][i] = *reinterpret_cast<const raw_t*>(row + c);
+          }
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          if (k + g < cnt) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+              if ((i * 64 + lane) * N < D) {
+                float x[N];
+                unpack16<T>(__builtin_bit_cast(uint4, raw[g][i]), x);
+#pragma unroll
+                for (int j = 0; j < N; ++j) acc[i][j] += x[j];
+              }
+            }
+          }
+        }
+      }
+      __builtin_amdgcn_wave_barrier();                           // (the reads above before the next entries are written)
+      cnt = 0;
+    };
+    auto push = [&](unsigned long long m, int base) {            // (positions before `pos` in the first chunk cannot match)
+      if (!m) return;
+      const int c = __popcll(m);
+      if (cnt + c > 64) drain();
+      if ((m >> lane) & 1) queue[cnt + __popcll(m & ((1ull << lane) - 1))] = base + lane;
+      cnt += c;
+    };
+    int base = base0;
+    if (!SLICED) {
+      for (; base + 256 <= npad; base += 256) {                  // four LDS reads in flight per trip
+        const int a0 = sid[base + lane], a1 = sid[base + 64 + lane], a2 = sid[base + 128 + lane], a3 = sid[base + 192 + lane];
+        const unsigned long long m0 = __ballot(a0 == v), m1 = __ballot(a1 == v), m2 = __ballot(a2 == v), m3 = __ballot(a3 == v);
+        if (m0 | m1 | m2 | m3) {
+          push(m0, base);
+          push(m1, base + 64);
+          push(m2, base + 128);
+          push(m3, base + 192);
+        }
+      }
+    }
+    for (; base < npad; base += 64) {
+      if (SLICED && base > base0 && base % per == 0) {           // a slice ends: fold its partial sum, start the next from zero
+        drain();
+#pragma unroll
+        for (int i = 0; i < NV; ++i)
+#pragma unroll
+          for (int j = 0; j < N; ++j) { tot[SLICED ? i : 0][j] += acc[i][j]; acc[i][j] = 0.f; }
+      }
+      push(__ballot(sid[base + lane] == v), base);
+    }
+    drain();
+    T* wr = dw + (int64_t)v * D;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = (i * 64 + lane) * N;
+      if (c < D) {
+        float o[N];
+        load_vec<T>(wr + c, o);
+#pragma unroll
+        for (int j = 0; j < N; ++j) o[j] += SLICED ? tot[SLICED ? i : 0][j] + acc[i][j] : acc[i][j];
+        store_vec<T>(wr + c, o);
+      }
+    }
+  }
+}
+
+// Lookup by a contiguous id range r0 .. r0 + T - 1 (position tables read with arange(T)): the gradient needs no scatter.
+// dw[r0 + t] += round_T(sum_b dout[b][t]) -- the batch sum accumulated in fp32 in batch order and rounded to the storage type (what
+// batch_sum_kernel hands on), then the one fp32 add per table element the row-major kernels do (0 + x first, as their accumulators do).
+template <typename T>
+__global__ __launch_bounds__(256) void embedding_range_bwd_kernel(const T* __restrict__ dout, T* __restrict__ dw, int batch, int64_t n) {
+  constexpr int N = Vec<T>::N;
+  const int64_t total = n / N;
+  for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < total; v += (int64_t)gridDim.x * 256) {
+    float acc[N], t[N], o[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) acc[j] = 0.f;
+#pragma unroll 8
+    for (int b = 0; b < batch; ++b) {
+      load_vec<T>(dout + (int64_t)b * n + v * N, t);
+#pragma unroll
+      for (int j = 0; j < N; ++j) acc[j] += t[j];
+    }
+    load_vec<T>(dw + v * N, o);
+#pragma unroll
+    for (int j = 0; j < N; ++j) o[j] += 0.f + round_to<T>(acc[j]);
+    store_vec<T>(dw + v * N, o);
+  }
+}
+
 // col[(b*(lead + nph*npw) + lead + ph*npw + pw)][c*p*p + i*p + j] = img[b][c][ph*p+i][pw*p+j]; columns K..Kpad-1 are zero, and so are the
 // `lead` rows in front of every sample's patches (the class-token position of adaptor/image_patch_embed.py:71-73: the projection GEMM then
 // runs over the [B, 1 + N, D] rows the adaptor returns -- no concatenation -- and the weight-gradient GEMM over the same rows sees zeros there)
@@ -340,6 +491,38 @@ __global__ __launch_bounds__(256) void im2col_patch_kernel(const T* __restrict__
       v = ld1<T>(img + ((b * C + c) * H + ph * p + i) * W + pw * p + j);
     }
     st1<T>(col + e, v);
+  }
+}
+// The same matrix for 16-bit types and even p, moved in runs: a patch row is p contiguous pixels of the image -- 2p bytes that start and
+// end on a dword boundary in both the image (W is a multiple of p) and the column row (c*p*p + i*p is even) -- so a dword never straddles
+// two runs.  One thread writes 16 bytes of a column row (Kpad % 8 == 0) from four dword loads, walking (c, i, j) by increments: five
+// 32-bit divisions per 8 elements instead of nine 64-bit ones per element.
+template <typename T>
+__global__ __launch_bounds__(256) void im2col_patch_runs_kernel(const T* __restrict__ img, T* __restrict__ col, int B, int C, int H,
+                                                                int W, int p, int Kpad, int lead) {
+  static_assert(sizeof(T) == 2, "dword runs of 16-bit elements");
+  const int nph = H / p, npw = W / p, K = C * p * p, vpr = Kpad / 8;
+  const int per = lead + nph * npw;
+  const unsigned total = (unsigned)B * per * vpr;              // (the host checks that it fits)
+  const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(img);
+  for (unsigned v = blockIdx.x * 256 + threadIdx.x; v < total; v += gridDim.x * 256) {
+    const unsigned r = v / vpr;
+    const int k0 = (int)(v - r * vpr) * 8;
+    const int b = (int)(r / per), rs = (int)(r - (unsigned)b * per) - lead;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (rs >= 0 && k0 < K) {
+      const int ph = rs / npw, pw = rs - ph * npw;
+      int c = k0 / (p * p);
+      int i = (k0 - c * p * p) / p;
+      int j = k0 - c * p * p - i * p;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (k0 + 2 * q < K) w[q] = src[((((int64_t)b * C + c) * H + ph * p + i) * W + pw * p + j) >> 1];
+        j += 2;
+        if (j >= p) { j = 0; if (++i >= p) { i = 0; ++c; } }
+      }
+    }
+    *reinterpret_cast<uint4*>(col + (int64_t)v * 8) = make_uint4(w[0], w[1], w[2], w[3]);
   }
 }
 
@@ -708,6 +891,81 @@ extern "C" int ofa_embedding_bwd(const void* dout, const int64_t* ids, void* dwe
   return check_launch("embedding_fold");
 }
 
+// debug builds: OFA_STEP_EDGES_OLD = a bit mask of OFA_EDGE_* items whose callers take the path they took before (A/B runs, the tests
+// that compare the two); the product library has one path
+extern "C" int ofa_step_edges_old(int item) {
+#ifdef OFA_DEBUG_SWITCHES
+  if (const char* e = getenv("OFA_STEP_EDGES_OLD")) return (atoi(e) >> item) & 1;
+#endif
+  return 0;
+}
+
+extern "C" int ofa_embedding_bwd_ids_ok(int64_t n, int D, int64_t V, int dtype) {
+  const int vecn = dtype == OFA_F32 ? 4 : 8;
+  return OFA_DT_OK(dtype) && n >= 0 && n <= OFA_EMBEDDING_IDS_MAX && V > 0 && V < ((int64_t)1 << 31) && D > 0 && D % vecn == 0 &&
+         D <= 64 * vecn * 4;
+}
+
+extern "C" int ofa_embedding_bwd_ids(const void* dout, const int64_t* ids, void* dweight, int64_t n, int D, int64_t V,
+                                     int64_t padding_idx, int slices, int dtype, void* stream) {
+  OFA_DT_CHECK("embedding_bwd_ids");
+  OFA_REQUIRE(n >= 0 && D > 0 && V > 0 && slices >= 1 && dout && ids && dweight, OFA_ERR_INVALID, "embedding_bwd_ids: bad argument");
+  OFA_REQUIRE(ofa_embedding_bwd_ids_ok(n, D, V, dtype), OFA_ERR_UNSUPPORTED,
+              "embedding_bwd_ids: n=%lld ids (at most %d), D=%d (whole 16-byte vectors, at most 256 of them): use ofa_embedding_bwd",
+              (long long)n, OFA_EMBEDDING_IDS_MAX, D);
+  OFA_REQUIRE((((uintptr_t)dout | (uintptr_t)dweight) & 15) == 0, OFA_ERR_UNSUPPORTED, "embedding_bwd_ids: buffers not 16-byte aligned");
+  if (n == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const int vecn = dtype == OFA_F32 ? 4 : 8;
+  const int nv = cdiv(D, 64 * vecn);
+  const int per = (int)(((n + slices - 1) / slices + 63) / 64 * 64);         // embedding_bwd_kernel's slice length
+  const int blocks = cdiv(n, EMB_IDS_WAVES) < 1024 ? cdiv(n, EMB_IDS_WAVES) : 1024;      // a position per wave and sweep
+  const size_t lds = (size_t)((n + 63) / 64 * 64 + EMB_IDS_WAVES * 64) * sizeof(int);
+#define EMB_LAUNCH(T, NV, SL)                                                                                       \
+  hipLaunchKernelGGL((embedding_bwd_ids_kernel<T, NV, SL>), dim3(blocks), dim3(EMB_IDS_WAVES * 64), lds, st, (const T*)dout, ids, \
+                     (T*)dweight, (int)n, D, V, padding_idx, per)
+#define EMB_CASE(T, SL)                     \
+  do {                                      \
+    if (nv <= 1) EMB_LAUNCH(T, 1, SL);      \
+    else if (nv <= 2) EMB_LAUNCH(T, 2, SL); \
+    else EMB_LAUNCH(T, 4, SL);              \
+  } while (0)
+#define EMB_DT(SL)                            \
+  do {                                        \
+    if (dtype == OFA_F32) EMB_CASE(float, SL); \
+    else if (dtype == OFA_BF16) EMB_CASE(bf16_t, SL); \
+    else EMB_CASE(f16_t, SL);                 \
+  } while (0)
+  if (slices > 1) EMB_DT(true);
+  else EMB_DT(false);
+#undef EMB_DT
+#undef EMB_CASE
+#undef EMB_LAUNCH
+  return check_launch("embedding_bwd_ids");
+}
+
+extern "C" int ofa_embedding_range_bwd(const void* dout, void* dweight, int batch, int64_t T, int D, int64_t V, int64_t r0, int dtype,
+                                       void* stream) {
+  OFA_DT_CHECK("embedding_range_bwd");
+  OFA_REQUIRE(dout && dweight && batch >= 1 && T >= 0 && D > 0 && V > 0 && r0 >= 0 && r0 + T <= V, OFA_ERR_INVALID,
+              "embedding_range_bwd: bad argument (rows %lld .. %lld of %lld)", (long long)r0, (long long)(r0 + T), (long long)V);
+  OFA_REQUIRE(D % (dtype == OFA_F32 ? 4 : 8) == 0 && (((uintptr_t)dout | (uintptr_t)dweight) & 15) == 0, OFA_ERR_UNSUPPORTED,
+              "embedding_range_bwd: D=%d / buffers not whole 16-byte vectors: use ofa_embedding_bwd", D);
+  if (T == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n = T * D;
+  if (dtype == OFA_F32)
+    hipLaunchKernelGGL((embedding_range_bwd_kernel<float>), dim3(grid_for(n / 4)), dim3(256), 0, st, (const float*)dout,
+                       (float*)dweight + r0 * D, batch, n);
+  else if (dtype == OFA_BF16)
+    hipLaunchKernelGGL((embedding_range_bwd_kernel<bf16_t>), dim3(grid_for(n / 8)), dim3(256), 0, st, (const bf16_t*)dout,
+                       (bf16_t*)dweight + r0 * D, batch, n);
+  else
+    hipLaunchKernelGGL((embedding_range_bwd_kernel<f16_t>), dim3(grid_for(n / 8)), dim3(256), 0, st, (const f16_t*)dout,
+                       (f16_t*)dweight + r0 * D, batch, n);
+  return check_launch("embedding_range_bwd");
+}
+
 extern "C" int ofa_im2col_patch(const void* img, void* col, int B, int C, int H, int W, int p, int Kpad, int lead, int dtype,
                                 void* stream) {
   OFA_DT_CHECK("im2col_patch");
@@ -715,6 +973,18 @@ extern "C" int ofa_im2col_patch(const void* img, void* col, int B, int C, int H,
               "im2col_patch: bad argument (H=%d W=%d p=%d Kpad=%d)", H, W, p, Kpad);
   hipStream_t st = (hipStream_t)stream;
   const int64_t total = (int64_t)B * (lead + (int64_t)(H / p) * (W / p)) * Kpad;
+  if (total == 0) return 0;
+  // 16-bit images with even p: whole runs as dwords (im2col_patch_runs_kernel); odd p, fp32, unaligned buffers: element by element
+  if (dtype != OFA_F32 && p % 2 == 0 && Kpad % 8 == 0 && ((uintptr_t)img & 3) == 0 && ((uintptr_t)col & 15) == 0 &&
+      total / 8 < ((int64_t)1 << 31) && !ofa_step_edges_old(OFA_EDGE_IM2COL)) {
+    if (dtype == OFA_BF16)
+      hipLaunchKernelGGL((im2col_patch_runs_kernel<bf16_t>), dim3(grid_for(total / 8)), dim3(256), 0, st, (const bf16_t*)img,
+                         (bf16_t*)col, B, C, H, W, p, Kpad, lead);
+    else
+      hipLaunchKernelGGL((im2col_patch_runs_kernel<f16_t>), dim3(grid_for(total / 8)), dim3(256), 0, st, (const f16_t*)img,
+                         (f16_t*)col, B, C, H, W, p, Kpad, lead);
+    return check_launch("im2col_patch_runs");
+  }
   if (dtype == OFA_F32)
     hipLaunchKernelGGL((im2col_patch_kernel<float>), dim3(grid_for(total)), dim3(256), 0, st, (const float*)img, (float*)col,
                        B, C, H, W, p, Kpad, lead);

@@ -21,7 +21,7 @@ struct FoldJobs {
   float alpha[FOLD_MAX_JOBS];
   int nslots[FOLD_MAX_JOBS];
   unsigned block0[FOLD_MAX_JOBS + 1];   // first block of each job
-  unsigned char flags[FOLD_MAX_JOBS];   // bit 0: accumulate, bit 1: out is fp32 (else bf16)
+  unsigned char flags[FOLD_MAX_JOBS];   // bit 0: accumulate, bit 1: out is fp32, bit 2: WIDE, bit 3: out is fp16 (else bf16), bit 4: 16 slot lanes
   int njobs;
 };
 
@@ -81,8 +81,11 @@ __device__ __forceinline__ void fold_store(const FoldJobs& J, int j, int64_t c, 
 // Two shapes of job: TALL (many partial rows, few columns: LayerNorm 256 x 768, column sums 128 x 768) -- a block is
 // 32 column-quads x 8 slot-lanes over 128 columns; WIDE (split-K slabs: 3..16 rows of 10^5..10^6 columns) -- a block is
 // 256 column-quads over 1024 columns, each thread walking the slots itself.  flags bit 2 selects WIDE.
+// A TALL job with flags bit 4 (OFA_FOLD_LANES16) is summed as colsum_final_kernel sums its row groups -- slot lane l of SIXTEEN takes
+// slots l, l + 16, ..., the lanes are added in lane order -- so that a column sum finished here has the bits of one finished by
+// ofa_colsum itself: each of the 8 slot-lanes of the block carries two of the sixteen sums (l and l + 8).
 __global__ __launch_bounds__(256) void fold_batched_kernel(FoldJobs J) {
-  __shared__ float4 red[8][32];
+  __shared__ float4 red[16][32];
   int j = 0;
   while (j + 1 < J.njobs && blockIdx.x >= J.block0[j + 1]) ++j;       // uniform scan over <= 56 entries
   const int64_t chunk = blockIdx.x - J.block0[j];
@@ -129,8 +132,39 @@ __global__ __launch_bounds__(256) void fold_batched_kernel(FoldJobs J) {
   }
   const int q = threadIdx.x & 31, sl = threadIdx.x >> 5;
   const int64_t c = chunk * 128 + q * 4;
-  float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (c < cols) {
+  float4 a = make_float4(0.f, 0.f, 0.f, 0.f), a2 = a;
+  const bool l16 = J.flags[j] & 16;
+  if (c < cols && l16) {
+    if (vec) {
+      const float* r = p + c;
+      int s = sl;
+      for (; s + 24 < ns; s += 32) {                      // lane sl: slots s, s+16; lane sl + 8: slots s+8, s+24
+        const float4 v0 = *reinterpret_cast<const float4*>(r + (int64_t)s * stride);
+        const float4 v1 = *reinterpret_cast<const float4*>(r + (int64_t)(s + 8) * stride);
+        const float4 v2 = *reinterpret_cast<const float4*>(r + (int64_t)(s + 16) * stride);
+        const float4 v3 = *reinterpret_cast<const float4*>(r + (int64_t)(s + 24) * stride);
+        a.x = (a.x + v0.x) + v2.x; a.y = (a.y + v0.y) + v2.y; a.z = (a.z + v0.z) + v2.z; a.w = (a.w + v0.w) + v2.w;
+        a2.x = (a2.x + v1.x) + v3.x; a2.y = (a2.y + v1.y) + v3.y; a2.z = (a2.z + v1.z) + v3.z; a2.w = (a2.w + v1.w) + v3.w;
+      }
+      for (; s < ns; s += 16) {
+        const float4 v = *reinterpret_cast<const float4*>(r + (int64_t)s * stride);
+        a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+        if (s + 8 < ns) {
+          const float4 u = *reinterpret_cast<const float4*>(r + (int64_t)(s + 8) * stride);
+          a2.x += u.x; a2.y += u.y; a2.z += u.z; a2.w += u.w;
+        }
+      }
+    } else {
+      for (int s = sl; s < ns; s += 8) {
+        const float* r = p + (int64_t)s * stride + c;
+        float4& t = (s & 8) ? a2 : a;
+        t.x += r[0];
+        if (c + 1 < cols) t.y += r[1];
+        if (c + 2 < cols) t.z += r[2];
+        if (c + 3 < cols) t.w += r[3];
+      }
+    }
+  } else if (c < cols) {
     if (vec) {
       const float* r = p + c;
       int s = sl;
@@ -159,12 +193,19 @@ __global__ __launch_bounds__(256) void fold_batched_kernel(FoldJobs J) {
     }
   }
   red[sl][q] = a;
+  if (l16) red[sl + 8][q] = a2;
   __syncthreads();
   if (sl == 0 && c < cols) {
     float t[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int r = 0; r < 8; ++r) {            // fixed order: lane r holds slots r, r+8, ...
       t[0] += red[r][q].x; t[1] += red[r][q].y; t[2] += red[r][q].z; t[3] += red[r][q].w;
+    }
+    if (l16) {
+#pragma unroll
+      for (int r = 8; r < 16; ++r) {         // (... r, r+16, ...: the other eight lanes)
+        t[0] += red[r][q].x; t[1] += red[r][q].y; t[2] += red[r][q].z; t[3] += red[r][q].w;
+      }
     }
     fold_store(J, j, c, cols, t);
   }
@@ -247,7 +288,8 @@ extern "C" int ofa_fold_batched(const ofa_fold_job* jobs, int njobs, void* strea
       J.part[i] = b.part; J.out[i] = b.out; J.cols[i] = b.cols; J.stride[i] = b.stride; J.alpha[i] = b.alpha;
       J.nslots[i] = b.nslots;
       const bool wide = b.nslots <= 16;
-      J.flags[i] = (unsigned char)((b.accumulate ? 1 : 0) | (b.out_dtype == OFA_F32 ? 2 : 0) | (wide ? 4 : 0) | (b.out_dtype == OFA_F16 ? 8 : 0));
+      J.flags[i] = (unsigned char)(((b.accumulate & ~OFA_FOLD_LANES16) ? 1 : 0) | (b.out_dtype == OFA_F32 ? 2 : 0) | (wide ? 4 : 0) |
+                                   (b.out_dtype == OFA_F16 ? 8 : 0) | ((b.accumulate & OFA_FOLD_LANES16) ? 16 : 0));
       J.block0[i] = blocks;
       blocks += (unsigned)(wide ? (b.cols + 1023) / 1024 : (b.cols + 127) / 128);
     }

@@ -71,6 +71,7 @@ def copy_batched(pairs):
 
 
 DEFER_FOLD = 2            # OFA_DEFER_FOLD
+FOLD_LANES16 = 4          # OFA_FOLD_LANES16
 GEMM_DEFER_REDUCE = 128   # OFA_GEMM_DEFER_REDUCE
 
 
@@ -86,15 +87,16 @@ class FoldQueue:
     def __init__(self):
         self.jobs, self.keep, self.bytes, self.outs, self.want_flush = [], [], 0, set(), False
 
-    def add(self, part, part_off, out, cols, stride, nslots, alpha=1.0, accumulate=True, flush_ok=True):
+    def add(self, part, part_off, out, cols, stride, nslots, alpha=1.0, accumulate=True, flush_ok=True, lanes16=False):
+        """lanes16: sum the slots in the order of ofa_colsum's own final pass (OFA_FOLD_LANES16)."""
         assert part.dtype == torch.float32 and out.is_contiguous()
         if out.data_ptr() in self.outs:
             # a second contribution to the same gradient (a module applied to several slots): jobs of one launch run
             # concurrently, so two read-modify-writes of one output must not share a launch
             self.flush()
         self.outs.add(out.data_ptr())
-        self.jobs.append(_FoldJob(dptr(part) + part_off * 4, dptr(out), cols, stride, nslots, int(accumulate),
-                                  float(alpha), dtype_code(out)))
+        self.jobs.append(_FoldJob(dptr(part) + part_off * 4, dptr(out), cols, stride, nslots,
+                                  int(bool(accumulate)) | (FOLD_LANES16 if lanes16 else 0), float(alpha), dtype_code(out)))
         self.keep.append((part, out))
         self.bytes += nslots * stride * 4
         self.want_flush = self.bytes > self.MAX_PENDING_BYTES
@@ -117,10 +119,10 @@ class ImmediateFold:
     """The FoldQueue's `add` for a caller whose partial rows are already written and that has no queue to defer to (gradients consumed
     from inside backward: data-parallel bucket all-reduces): one fold launch per job, same arithmetic and summation order."""
 
-    def add(self, part, part_off, out, cols, stride, nslots, alpha=1.0, accumulate=True, flush_ok=True):
+    def add(self, part, part_off, out, cols, stride, nslots, alpha=1.0, accumulate=True, flush_ok=True, lanes16=False):
         assert part.dtype == torch.float32 and out.is_contiguous()
-        job = (_FoldJob * 1)(_FoldJob(dptr(part) + part_off * 4, dptr(out), cols, stride, nslots, int(accumulate), float(alpha),
-                                      dtype_code(out)))
+        job = (_FoldJob * 1)(_FoldJob(dptr(part) + part_off * 4, dptr(out), cols, stride, nslots,
+                                      int(bool(accumulate)) | (FOLD_LANES16 if lanes16 else 0), float(alpha), dtype_code(out)))
         lib().call("ofa_fold_batched", ctypes.addressof(job), 1, stream())
 
     def flush_if_large(self):
@@ -843,17 +845,51 @@ def scatter_rows_part(dpacked, inverse, B, nk, Ttot, start):
     return out
 
 
-def embedding_bwd(dout, ids, V, padding_idx=-1, dweight=None):
+# items of the debug library's OFA_STEP_EDGES_OLD mask (include/ofasys_amd.h: OFA_EDGE_*)
+EDGE_POS_RANGE, EDGE_TOKEN_BWD, EDGE_COLSUM_FOLD, EDGE_IM2COL = 0, 1, 2, 3
+
+
+def edge_old(item):
+    """Debug library with OFA_STEP_EDGES_OLD set: take the path this caller took before its one-launch form (A/B runs); else False."""
+    return bool(lib().cdll.ofa_step_edges_old(int(item)))
+
+
+def embedding_bwd(dout, ids, V, padding_idx=-1, dweight=None, id_major=None):
+    """dweight[v] += sum of the rows of dout whose id is v.  id_major: True / False picks the one-launch id-major kernel / the table-row-
+    major ones (same bits either way); None: id-major for wide-vocabulary tables (one slice: few hits per row) whose id list fits it."""
     dout = dout.contiguous()
     ids = ids.contiguous()
     D = dout.shape[-1]
     if dweight is None:
         dweight = torch.zeros(V, D, dtype=dout.dtype, device=dout.device)
-    present = workspace(V, dout.device, "embed_present") if V > 4096 else None
     S = lib().cdll.ofa_embedding_bwd_slices(V, D)
+    pad = -1 if padding_idx is None else padding_idx
+    if id_major is None:
+        id_major = S == 1 and not edge_old(EDGE_TOKEN_BWD)
+    if (id_major and lib().cdll.ofa_embedding_bwd_ids_ok(ids.numel(), D, V, dtype_code(dout))
+            and (dout.data_ptr() | dweight.data_ptr()) % 16 == 0):
+        lib().call("ofa_embedding_bwd_ids", ptr(dout), ptr(ids), ptr(dweight), ids.numel(), D, V, pad, S, dtype_code(dout), stream())
+        return dweight
+    present = workspace(V, dout.device, "embed_present") if V > 4096 else None
     slices = workspace(S * V * D * 4, dout.device, "embed_slices") if S > 1 else None
     lib().call("ofa_embedding_bwd", ptr(dout), ptr(ids), ptr(dweight), ids.numel(), D, V,
-               -1 if padding_idx is None else padding_idx, ptr(present), ptr(slices), dtype_code(dout), stream())
+               pad, ptr(present), ptr(slices), dtype_code(dout), stream())
+    return dweight
+
+
+def embedding_range_ok(x):
+    """Can ofa_embedding_range_bwd take gradient rows like x's (whole 16-byte vectors)?"""
+    return x.shape[-1] % (4 if x.dtype == torch.float32 else 8) == 0 and not edge_old(EDGE_POS_RANGE)
+
+
+def embedding_range_bwd(dout, dweight, r0, T):
+    """dweight[r0 + t] += round(sum_b dout[b, t]): the gradient of the table rows r0 .. r0 + T - 1 a lookup by arange handed to every
+    sample, from dout [batch, T, D] (or [T, D]) -- batch sum and scatter-add of the generic route in one pass, the same bits."""
+    dout = dout.contiguous()
+    V, D = dweight.shape
+    batch = dout.numel() // (T * D)
+    assert dweight.is_contiguous() and dweight.dtype == dout.dtype and batch * T * D == dout.numel()
+    lib().call("ofa_embedding_range_bwd", ptr(dout), ptr(dweight), batch, T, D, V, int(r0), dtype_code(dout), stream())
     return dweight
 
 
@@ -985,9 +1021,11 @@ def adam_step(master, exp_avg, exp_avg_sq, grad, model_param, coef, lr, beta1, b
                dtype_code(grad), stream())
 
 
-def colsum(x, alpha=1.0, out=None, accumulate=False, out_dtype=torch.float32, fold=None):
+def colsum(x, alpha=1.0, out=None, accumulate=False, out_dtype=torch.float32, fold=None, same_bits=False):
     """Column sums of a 2-D tensor (last dim contiguous): fresh tensor of `out_dtype`, or (accumulated) into `out`.
-    fold (with out): only the row-group partials are computed now, the FoldQueue finishes the sum at its flush."""
+    fold (with out): only the row-group partials are computed now, the FoldQueue finishes the sum at its flush.  same_bits: the queue
+    adds the partials in the order of the immediate final pass (for the callers that used to finish the sum themselves); without it
+    a sum over more than 1024 rows is grouped as the queue's LayerNorm jobs are."""
     if x.stride(-1) != 1:
         x = x.contiguous()
     rows, cols = x.shape
@@ -997,7 +1035,7 @@ def colsum(x, alpha=1.0, out=None, accumulate=False, out_dtype=torch.float32, fo
     if fold is not None and out.is_contiguous():
         ns = lib().cdll.ofa_colsum_slots(rows)
         ws = torch.empty(ns * cols, dtype=torch.float32, device=x.device)
-        fold.add(ws, 0, out, cols, cols, ns, alpha, accumulate)
+        fold.add(ws, 0, out, cols, cols, ns, alpha, accumulate, lanes16=same_bits)
         lib().call("ofa_colsum", ptr(x), ptr(out), ptr(ws), rows, cols, x.stride(0), float(alpha), DEFER_FOLD,
                    dtype_code(x), dtype_code(out), stream())
         fold.flush_if_large()

@@ -44,8 +44,9 @@ def Linear(in_features, out_features, bias=True):
 
 
 class OfaEmbedding(nn.Embedding):
-    def forward(self, ids):
-        return ops.embedding(ids, self.weight, self.padding_idx)
+    def forward(self, ids, range_start=None):
+        """range_start: the caller's promise that ids is arange(range_start, range_start + n) (ops.embedding)."""
+        return ops.embedding(ids, self.weight, self.padding_idx, range_start=range_start)
 
 
 def Embedding(num_embeddings, embedding_dim, padding_idx=None, zero_init=False):

@@ -146,6 +146,12 @@ def _fold():
     return q
 
 
+def _edge_fold():
+    """_fold() for the column sums of the adaptors' backward (type vectors, patch-embedding bias and class token), which used to finish
+    their sums themselves: queued with the immediate final pass's summation order (K.colsum(same_bits=True)), the same gradient bits."""
+    return None if K.edge_old(K.EDGE_COLSUM_FOLD) else _fold()
+
+
 # Grouped weight gradients: the nn.Linear weight gradients of a Transformer layer (dW += dY^T X into the arena) are
 # collected while the layer's backward runs and launched together at a layer boundary (wgrad_boundary) -- one launch of
 # 256 x 256 tiles (kernels.gemm_group_tn).  The queue holds dY and X until then.
@@ -562,12 +568,15 @@ class AddFn(torch.autograd.Function):
     positions shared by the batch) -- it is then read with a period and its gradient is the sum over the batch."""
 
     @staticmethod
-    def forward(ctx, a, b, vec, rowmask, vec_param=None):
+    def forward(ctx, a, b, vec, rowmask, vec_param=None, b_range=None):
         ctx.save_for_backward(rowmask)
         ctx.has = (b is not None, vec is not None)
         ctx.vdtype = vec.dtype if vec is not None else None
         ctx.b_shape = tuple(b.shape) if (b is not None and b.numel() != a.numel()) else None
         ctx.vec_param = vec_param                      # the parameter `vec` is a view of: its gradient goes straight to the arena
+        # (table, r0): the batch-shared b is rows r0 .. of `table`, looked up by arange (ops.embedding(range_start=)) and handed in
+        # detached -- its gradient, summed over the batch, is added to the table's arena gradient by ONE kernel here
+        ctx.b_range = b_range
         return K.add_rowvec_mask(a, b, vec, rowmask)
 
     @staticmethod
@@ -578,12 +587,16 @@ class AddFn(torch.autograd.Function):
         if ctx.has[1]:
             gv = _sink(ctx.vec_param)
             if gv is not None and gv.is_contiguous():
-                K.colsum(g, out=gv.view(-1), accumulate=True)
+                K.colsum(g, out=gv.view(-1), accumulate=True, fold=_edge_fold(), same_bits=True)
                 _sink_done(ctx.vec_param)
             else:
                 dvec = K.colsum(g, out_dtype=ctx.vdtype)
         db = None
-        if ctx.has[0]:
+        if ctx.b_range is not None:
+            table, r0 = ctx.b_range
+            K.embedding_range_bwd(g, _sink(table), r0, ctx.b_shape[0])
+            _sink_done(table)
+        elif ctx.has[0]:
             if ctx.b_shape is None:
                 db = g
             else:
@@ -591,7 +604,7 @@ class AddFn(torch.autograd.Function):
                 for d in ctx.b_shape:
                     nb *= d
                 db = K.batch_sum(g, g.numel() // nb).view(ctx.b_shape)
-        return g, db, dvec, None, None
+        return g, db, dvec, None, None, None
 
 
 def dropout_add(x, residual, p, training):
@@ -631,6 +644,18 @@ def first_sample(x):
     return base if base is not None else x[:1]
 
 
+def _range_sink(b):
+    """(table, r0) when the [1, T, D] tensor b is ops.embedding(range_start=r0)'s output -- rows r0 .. r0 + T - 1 of `table`, by the caller's
+    promise -- and the table has a contiguous arena gradient the range kernel can add to; else None."""
+    rng = getattr(b, "_ofa_range", None)
+    if rng is None or not b.requires_grad or not b.is_contiguous():
+        return None
+    gw = _sink(rng[0])
+    if gw is None or not gw.is_contiguous() or gw.dtype != b.dtype or not K.embedding_range_ok(b):
+        return None
+    return rng
+
+
 def add_rowvec_mask(a, b=None, vec=None, rowmask=None, vec_param=None):
     """a [B, T, D] + b + vec: b is [B, T, D] or -- batch-shared -- [1, T, D] / a stride-0 expand of it (read once per sample, never
     materialised B times; its gradient comes back summed over the batch).  vec_param: the parameter `vec` is a flat view of (its
@@ -645,7 +670,10 @@ def add_rowvec_mask(a, b=None, vec=None, rowmask=None, vec_param=None):
             b = base
         if b.shape[0] == 1 and a.dim() == 3 and a.shape[0] > 1 and a.is_contiguous() and tuple(a.shape[1:]) == tuple(b.shape[1:]):
             m = rowmask.reshape(-1) if rowmask is not None else None
-            return AddFn.apply(a.view(-1, a.shape[-1]), b.reshape(-1, b.shape[-1]), vec, m, vec_param).view(a.shape)
+            b_range = _range_sink(b) if (a.requires_grad and torch.is_grad_enabled()) else None
+            if b_range is not None:
+                b = b.detach()                         # the gradient takes the direct route
+            return AddFn.apply(a.view(-1, a.shape[-1]), b.reshape(-1, b.shape[-1]), vec, m, vec_param, b_range).view(a.shape)
         b = like_layout(b, a)
     a2d, restore = rows_view(a)
     b2d = rows_view(b)[0] if b is not None else None
@@ -779,12 +807,14 @@ _TOKEN_KEYED_CACHES.append(SegmentPlan._cache)
 
 class EmbeddingFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, ids, weight, padding_idx, plan_key=None, pad_mask_of=None):
+    def forward(ctx, ids, weight, padding_idx, plan_key=None, pad_mask_of=None, range_start=None):
         ctx.save_for_backward(ids)
         ctx.V, ctx.padding_idx = weight.shape[0], padding_idx
         ctx.weight_ref = weight
         ctx.plan_key = plan_key
+        ctx.range_start = range_start
         ctx.with_mask = pad_mask_of is not None
+        ctx.set_materialize_grads(False)               # (the mask output has no gradient: no zero fill of one per backward)
         if pad_mask_of is None:
             return K.embedding_fwd(weight, ids)
         out, mask = K.embedding_fwd(weight, ids, pad_mask_of)          # the ids' padding mask from the same pass
@@ -793,7 +823,9 @@ class EmbeddingFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, *_unused):
-        return EmbeddingFn._backward(ctx, dout) + (None,)
+        if dout is None:
+            return (None,) * 6
+        return EmbeddingFn._backward(ctx, dout) + (None, None)
 
     @staticmethod
     def _backward(ctx, dout):
@@ -801,6 +833,15 @@ class EmbeddingFn(torch.autograd.Function):
         pad = -1 if ctx.padding_idx is None else ctx.padding_idx
         gw = _sink(ctx.weight_ref)
         D = dout.shape[-1]
+        if (ctx.range_start is not None and ctx.padding_idx is None and K.embedding_range_ok(dout)
+                and (gw is None or (gw.is_contiguous() and gw.dtype == dout.dtype))):
+            # ids are range_start .. range_start + n - 1 by the caller's promise: row t of dout is the gradient of table row range_start + t
+            out = gw if gw is not None else torch.zeros(ctx.V, D, dtype=dout.dtype, device=dout.device)
+            K.embedding_range_bwd(dout.reshape(-1, D), out, ctx.range_start, ids.numel())
+            if gw is not None:
+                _sink_done(ctx.weight_ref)
+                return None, None, None, None
+            return None, out, None, None
         plan = None
         if ctx.plan_key is not None and D <= 64 and ctx.padding_idx is None:
             plan = SegmentPlan.get((ctx.plan_key, tuple(ids.shape), str(ids.device)), ids)
@@ -822,10 +863,18 @@ class EmbeddingFn(torch.autograd.Function):
         return None, dw, None, None
 
 
-def embedding(ids, weight, padding_idx=None, plan_key=None):
+def embedding(ids, weight, padding_idx=None, plan_key=None, range_start=None):
     """F.embedding.  plan_key (hashable, optional): promises that every call with this key and shape looks up the SAME ids (a rel-pos
-    bucket table slice) -- the gradient then uses a cached sort of the ids (SegmentPlan) instead of scanning them per table row."""
-    return EmbeddingFn.apply(ids, weight, padding_idx, plan_key)
+    bucket table slice) -- the gradient then uses a cached sort of the ids (SegmentPlan) instead of scanning them per table row.
+    range_start (int, optional): promises that ids IS arange(range_start, range_start + ids.numel()) (positions; nothing checks it) --
+    the gradient of table row range_start + t is then row t of the output's, added without a scatter, and a consumer that broadcasts the
+    rows over a batch (add_rowvec_mask) sums its gradient over the batch in the same kernel."""
+    if range_start is None:
+        return EmbeddingFn.apply(ids, weight, padding_idx, plan_key)
+    out = EmbeddingFn.apply(ids, weight, padding_idx, plan_key, None, int(range_start))
+    if ids.dim() == 2 and ids.shape[0] == 1 and padding_idx is None:
+        out._ofa_range = (weight, int(range_start))
+    return out
 
 
 def embedding_with_pad_mask(ids, weight, padding_idx, pad):
@@ -1676,16 +1725,17 @@ class PatchEmbedFn(torch.autograd.Function):
         if cls is not None:
             gc = _sink(cls)
             if gc is not None:
-                K.colsum(first, out=gc.view(-1), accumulate=True)
+                K.colsum(first, out=gc.view(-1), accumulate=True, fold=_edge_fold(), same_bits=True)
                 _sink_done(cls)
             else:
                 dcls = K.colsum(first, out_dtype=dout.dtype).view(cls.shape)
         if bias is not None:
             gb = _sink(bias)
             if gb is not None:
-                K.colsum(d2, out=gb, accumulate=True)
+                K.colsum(d2, out=gb, accumulate=True, fold=_edge_fold(), same_bits=True)
                 if lead:
-                    K.colsum(first, alpha=-1.0, out=gb, accumulate=True)               # the class-token rows never saw the bias
+                    # the class-token rows never saw the bias (a second contribution to gb: the queue keeps it out of the first one's launch)
+                    K.colsum(first, alpha=-1.0, out=gb, accumulate=True, fold=_edge_fold(), same_bits=True)
                 _sink_done(bias)
             else:
                 db = K.colsum(d2, out_dtype=dout.dtype)
