@@ -621,6 +621,32 @@ int ofa_beam_select(const void* ws, int bsz, int K, int V, int step, int max_len
                     int64_t score_ld, int* ignore, int* done, int* nfin, int64_t* reorder, int64_t* fin_tok, float* fin_pos,
                     int64_t fin_ld, float* fin_score, int* fin_len, int* fin_cnt, void* stream);
 
+/* ---- beam search under a forced target prefix (sample["prefix_tokens"], generator/sequence_generator.py:297-343, 497-523).
+ * prefix int64 [bsz, prefix_ld]: the prefix tokens, <pad> where a sentence's prefix has ended; plen int [bsz]: its non-pad
+ * entries per sentence.  A step with step < the prefix width and step < max_len is a PREFIX STEP: three launches, recorded in
+ * the step graph like the two above.  Rows whose prefix token prefix[sentence, step] is not <pad> are forced, the others free.
+ * ofa_beam_prefix_topk: ofa_beam_topk's row pass with the n-gram bans restricted to rows with plen < step + ngram - 1.  With
+ * prefix != NULL (a prefix step) the min_len mask is applied to no row, every row stores the scaled logit of its prefix token
+ * (constraint_range and temperature applied) in glogit fp32 [rows], and a forced row writes its normaliser parts only.  With
+ * prefix == NULL it is a free step of a sample that carries a prefix (glogit unused).
+ * ofa_beam_prefix_fill: one workgroup per forced row.  f = min over the rows of the unfinished sentences of
+ * (glogit - normaliser) - 1, NaN if any is NaN; the row's candidates under the tie rule (value descending, token ascending) --
+ * its prefix token with its own lprob, then the lowest unmasked tokens at f, unk at f - unk_penalty; NaN / -inf f: -inf -- are
+ * written to ws as lprobs.  Needs 2K + step + 4 <= min(V, 1024).
+ * ofa_beam_prefix_select: ofa_beam_select, taking the candidate values of forced rows as lprobs already. */
+int ofa_beam_prefix_topk(const void* logits, int64_t ld, int rows, int V, int K, float temperature, int cstart, int cend, int step,
+                         int min_len, int max_len, int pad, int unk, int eos, float unk_penalty, int ngram, const int64_t* tokens,
+                         int64_t tok_ld, const int* done, const int64_t* prefix, int64_t prefix_ld, const int* plen, float* glogit,
+                         void* ws, int dtype, void* stream);
+int ofa_beam_prefix_fill(void* ws, int rows, int V, int K, int step, int pad, int unk, float unk_penalty, int ngram,
+                         const int64_t* tokens, int64_t tok_ld, const int* done, const int64_t* prefix, int64_t prefix_ld,
+                         const int* plen, const float* glogit, void* stream);
+int ofa_beam_prefix_select(const void* ws, int bsz, int K, int V, int step, int max_len, int eos, int unk, float unk_penalty,
+                           int normalize, float len_penalty, int64_t* tokens, int64_t tok_ld, int tok_cap, float* scores,
+                           int64_t score_ld, int* ignore, int* done, int* nfin, int64_t* reorder, int64_t* fin_tok, float* fin_pos,
+                           int64_t fin_ld, float* fin_score, int* fin_len, int* fin_cnt, const int64_t* prefix, int64_t prefix_ld,
+                           int pad, void* stream);
+
 /* ---- closed-set scoring (csrc/closed_set_score.hip): TraverseTask.inference (task/traverse_task.py:63-110) without the
  * full-vocabulary projection.  The answer trie arrives as flat int arrays (ofasys_amd/traverse.py TraversePlan): N nodes, E edges
  * grouped by node (node_edge_off [N + 1], edge_token [E], edge_node [E]), per node the (answer, position) whose decoder row

@@ -70,10 +70,12 @@ static_assert(sizeof(BeamListScratch) % 16 == 0, "embedded in front of 16-byte a
 
 // n-gram bans of a row (utils/ngram_repeat_block.py over the history tokens[row, 0..step]): every earlier occurrence of the row's
 // last n-1 tokens bans the token that followed it; ban(token) is called by the thread that found the occurrence.
+// plen >= 0: the sample carries prefix_tokens and the row's prefix has plen tokens -- the reference then skips the rows with
+// plen >= step + n - 1 (sequence_generator.py:327-334).
 template <typename Sink>
-__device__ __forceinline__ void beam_ngram_scan(const BeamPolicy& p, int row, int tid, Sink ban) {
+__device__ __forceinline__ void beam_ngram_scan(const BeamPolicy& p, int row, int tid, Sink ban, int plen = -1) {
   const int n = p.ngram;
-  if (n > 0 && p.step + 2 - n >= 0) {
+  if (n > 0 && p.step + 2 - n >= 0 && plen < p.step + n - 1) {
     const int64_t* h = p.tokens + (int64_t)row * p.tok_ld;
     const int last = p.step - n + 2;                        // the row's last n-1 tokens start here
     for (int i = tid; i + n - 1 <= p.step; i += BEAM_THREADS) {
@@ -82,6 +84,22 @@ __device__ __forceinline__ void beam_ngram_scan(const BeamPolicy& p, int row, in
       if (match) ban(h[i + n - 1]);
     }
   }
+}
+
+// A row's fp32 normaliser from its S parts (max, sum); bad: a part held a NaN or the result is not finite -- the whole row is -inf.
+__device__ __forceinline__ float beam_row_lse(const float* st, int S, bool& bad) {
+  float M = -INFINITY;
+  bool isnan_ = false;
+  for (int s = 0; s < S; ++s) {
+    const float ms = st[2 * s];
+    if (ms != ms) isnan_ = true; else M = fmaxf(M, ms);
+  }
+  float sum = 0.f;
+  for (int s = 0; s < S; ++s)
+    if (st[2 * s] != -INFINITY) sum += st[2 * s + 1] * expf(st[2 * s] - M);
+  const float l = M + logf(sum);
+  bad = isnan_ || !(fabsf(l) <= 3.4e38f);
+  return l;
 }
 
 // The workgroup's part of the fp32 normaliser: m = the lane's max over its non-NaN values, has_nan = it saw a NaN,

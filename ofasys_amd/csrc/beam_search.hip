@@ -19,6 +19,12 @@
 //    (the active_mask topk), carries cands_to_ignore, and gathers the token / score histories in place.  A finished sentence
 //    (K hypotheses or step == max_len) sets its done flag, bumps the all-finished counter and is a no-op afterwards; its rows
 //    keep the identity reorder.
+// 3. Steps under a forced target prefix (sample["prefix_tokens"], sequence_generator.py:297-343, 497-523), three launches:
+//    ofa_beam_prefix_topk -- the row pass above without the min_len mask; it also stores every row's scaled logit at its prefix
+//    token, and a forced row (prefix token != pad) stops after its normaliser part: no selection loop.  ofa_beam_prefix_fill --
+//    one workgroup per forced row: the batch-wide fill f = min(prefix lprobs) - 1 and the row's candidates under the tie rule, as
+//    lprobs.  ofa_beam_prefix_select -- the sentence pass, taking a forced row's values as normalised.  On the free steps of such
+//    a sample ofa_beam_prefix_topk (prefix = null) is the row pass of 1. with the n-gram bans following the prefix lengths.
 #include "beam_common.h"
 
 namespace ofa {
@@ -29,13 +35,30 @@ struct BeamTopkArgs {
   int cstart, cend;
   BeamPolicy p;
   BeamWs ws;
+  // ofa_beam_prefix_topk only (PREFIX): the forced tokens of this step (null: a free step), the prefix lengths, g's logit
+  const int64_t* prefix; int64_t prefix_ld;
+  const int* plen;
+  float* glogit;
 };
 
-template <typename T>
-__global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(BeamTopkArgs a) {
+// The row pass of both entry points.  PREFIX (ofa_beam_prefix_topk): every row stores the scaled logit of its prefix token; a
+// forced row (prefix token != pad) stops after its normaliser part -- its candidates come from beam_prefix_fill_kernel -- and the
+// n-gram bans follow the prefix length.
+template <typename T, bool PREFIX>
+__device__ __forceinline__ void beam_row_pass(const BeamTopkArgs& a) {
   const int split = blockIdx.x, row = blockIdx.y;
   const BeamPolicy& p = a.p;
   if (p.done && p.done[row / a.K]) return;
+  int64_t ftok = -1;                                         // the row's prefix token at this step (PREFIX, prefix step)
+  bool forced = false;
+  int plen = -1;
+  if constexpr (PREFIX) {
+    if (a.prefix) {
+      ftok = a.prefix[(int64_t)(row / a.K) * a.prefix_ld + p.step];
+      forced = ftok != p.pad;
+    }
+    plen = a.plen[row / a.K];
+  }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int base = split * BEAM_CHUNK, K2 = 2 * a.K;
   const int64_t part = (int64_t)row * a.S + split;
@@ -53,10 +76,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(BeamTopkArgs a)
   for (int i = tid; i < BEAM_CHUNK / 32; i += BEAM_THREADS) ban[i] = 0u;
   __syncthreads();
   // ---- n-gram bans of this row, as a bitmap over the chunk
-  beam_ngram_scan(p, row, tid, [&](int64_t tok) {
-    const int64_t col = tok - base;
-    if (col >= 0 && col < BEAM_CHUNK) atomicOr(&ban[col >> 5], 1u << (col & 31));
-  });
+  if (!forced)
+    beam_ngram_scan(p, row, tid, [&](int64_t tok) {
+      const int64_t col = tok - base;
+      if (col >= 0 && col < BEAM_CHUNK) atomicOr(&ban[col >> 5], 1u << (col & 31));
+    }, plen);
   // ---- pre-normaliser masks + the chunk's normaliser part
   float m = -INFINITY;
   int has_nan = 0;
@@ -70,6 +94,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(BeamTopkArgs a)
     if (c < a.V) {
       if (v != v) has_nan = 1;
       else m = fmaxf(m, v);
+      if constexpr (PREFIX) if (c == ftok) a.glogit[row] = v;
     }
   }
   beam_normaliser_part(sh, tid, m, has_nan, [&](float wm) {
@@ -81,6 +106,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(BeamTopkArgs a)
     }
     return s;
   }, a.ws.stats + part * 2);                                // (its barrier also orders the ban bitmap)
+  if (forced) return;                                        // (the whole workgroup: one row)
   // ---- post-normaliser masks -> ordering keys (NaN key = no candidate; -inf stays a candidate)
   float unk_val = 0.f;
 #pragma unroll
@@ -121,6 +147,122 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(BeamTopkArgs a)
   }
 }
 
+template <typename T>
+__global__ __launch_bounds__(BEAM_THREADS) void beam_topk_kernel(BeamTopkArgs a) { beam_row_pass<T, false>(a); }
+
+template <typename T>
+__global__ __launch_bounds__(BEAM_THREADS) void beam_prefix_row_kernel(BeamTopkArgs a) { beam_row_pass<T, true>(a); }
+
+// ---- the candidates of the forced rows of a prefix step (ofa_beam_prefix_fill), one workgroup per forced row.
+// f = min over the rows of every unfinished sentence of g[r] - 1 (g[r] = lprob of the row's prefix token, <pad> for a free row;
+// torch.min: a NaN wins) is recomputed by every workgroup from the rows' normaliser parts and ofa_beam_prefix_topk's logits:
+// rows x S x 2 floats from L2 and one thread per row, against a launch of its own in between.  The row's distribution is then
+// f everywhere but at its prefix token; after the reference's later masks (NaN -> -inf, PAD, unk penalty, n-gram bans) and the
+// tie rule its best 2K are the prefix token, the 2K lowest unmasked tokens at f and unk at f - unk_penalty, ranked.  They are
+// written as split 0's list, ALREADY NORMALISED (the sentence pass takes a forced row's normaliser as 0), so every filled
+// token of a row carries the identical float.  The host guarantees 2K unmasked tokens below BEAM_FILL_POOL.
+constexpr int BEAM_FILL_POOL = 1024;
+
+struct BeamFillArgs {
+  BeamWs ws;
+  int rows, V, K, S;
+  const int64_t* prefix; int64_t prefix_ld;
+  const int* plen;
+  const float* glogit;
+  BeamPolicy p;
+};
+
+__global__ __launch_bounds__(BEAM_THREADS) void beam_prefix_fill_kernel(BeamFillArgs a) {
+  const int row = blockIdx.x, sent = row / a.K;
+  const BeamPolicy& p = a.p;
+  if (p.done && p.done[sent]) return;
+  const int64_t ftok = a.prefix[(int64_t)sent * a.prefix_ld + p.step];
+  if (ftok == p.pad) return;                                 // a free row: ofa_beam_prefix_topk listed its candidates
+  if (p.step == 0 && row % a.K) return;                      // step 0 reads the first beam only
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int K2 = 2 * a.K;
+  __shared__ float red_m[4];
+  __shared__ int red_nan[4], wcnt[4];
+  __shared__ float g_own;
+  __shared__ uint32_t ban[BEAM_FILL_POOL / 32];
+  __shared__ int ftok_banned;
+  __shared__ int plain[2 * BEAM_MAX_K];
+  __shared__ float ekey[2 * BEAM_MAX_K + 2], eval_[2 * BEAM_MAX_K + 2];
+  __shared__ int etok[2 * BEAM_MAX_K + 2];
+
+  // ---- f: the batch-wide minimum
+  float mn = INFINITY;
+  int has_nan = 0;
+  for (int r = tid; r < a.rows; r += BEAM_THREADS) {
+    if (p.done && p.done[r / a.K]) continue;
+    bool bad;
+    const float l = beam_row_lse(a.ws.stats + (int64_t)r * a.S * 2, a.S, bad);
+    const float g = bad ? NAN : a.glogit[r] - l;
+    if (g != g) has_nan = 1; else mn = fminf(mn, g);
+    if (r == row) g_own = g;
+  }
+  for (int i = tid; i < BEAM_FILL_POOL / 32; i += BEAM_THREADS) ban[i] = 0u;
+  if (tid == 0) ftok_banned = 0;
+  mn = -wave_max(-mn);
+  has_nan = __any(has_nan) ? 1 : 0;
+  if (lane == 0) { red_m[wave] = mn; red_nan[wave] = has_nan; }
+  __syncthreads();
+  const bool f_nan = red_nan[0] | red_nan[1] | red_nan[2] | red_nan[3];
+  const float fval = f_nan ? -INFINITY : fminf(fminf(red_m[0], red_m[1]), fminf(red_m[2], red_m[3])) - 1.f;   // NaN -> -inf
+  const bool fin = fval != -INFINITY;
+  // ---- n-gram bans of this row: a bitmap over the pool, and whether the prefix token is banned
+  beam_ngram_scan(p, row, tid, [&](int64_t tok) {
+    if (tok == ftok) ftok_banned = 1;
+    if (tok >= 0 && tok < BEAM_FILL_POOL) atomicOr(&ban[tok >> 5], 1u << (tok & 31));
+  }, a.plen[sent]);
+  __syncthreads();
+  // ---- the 2K lowest tokens that stay at f: not the prefix token and, unless f is -inf anyway, not masked and not unk
+  const bool unk_apart = fin && p.unk_pen != 0.f && p.unk != ftok && p.unk >= 0 && p.unk < a.V;
+  int have = 0;
+  for (int base = 0; base < BEAM_FILL_POOL && base < a.V && have < K2; base += BEAM_THREADS) {
+    const int c = base + tid;
+    const bool banned = (ban[c >> 5] >> (c & 31)) & 1u;
+    const bool is_plain = c < a.V && c != ftok && (!fin || (c != p.pad && !(unk_apart && c == p.unk) && !banned));
+    const unsigned long long mask = __ballot(is_plain);
+    if (lane == 0) wcnt[wave] = __popcll(mask);
+    __syncthreads();
+    int at = have + __popcll(mask & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) at += wcnt[w];
+    if (is_plain && at < K2) plain[at] = c;
+    have += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+    __syncthreads();
+  }
+  if (have > K2) have = K2;
+  // ---- rank the <= 2K + 2 entries by (key desc, token asc): the plain run, the prefix token, unk
+  const int n = have + 1 + (unk_apart ? 1 : 0);
+  if (tid < n) {
+    float v = fval;
+    int tok = 0;
+    if (tid < have) tok = plain[tid];
+    else if (tid == have) {
+      tok = (int)ftok;
+      v = g_own;
+      if (v != v || ftok_banned) v = -INFINITY;
+    } else {
+      tok = p.unk;
+      if ((ban[tok >> 5] >> (tok & 31)) & 1u) v = -INFINITY;
+    }
+    eval_[tid] = v;                                          // (before the unk penalty, as the layout has it)
+    ekey[tid] = tok == p.unk ? v - p.unk_pen : v;
+    etok[tid] = tok;
+  }
+  __syncthreads();
+  float* ov = a.ws.cval + (int64_t)row * a.S * K2;
+  int* ot = a.ws.ctok + (int64_t)row * a.S * K2;
+  if (tid < n) {
+    int rank = 0;
+    for (int e = 0; e < n; ++e) rank += (ekey[e] > ekey[tid] || (ekey[e] == ekey[tid] && etok[e] < etok[tid])) ? 1 : 0;
+    if (rank < K2) { ov[rank] = eval_[tid]; ot[rank] = etok[tid]; }
+  }
+  const int listed = n < K2 ? n : K2;
+  for (int e = listed + tid; e < a.S * K2; e += BEAM_THREADS) ot[e] = -1;     // the other splits hold nothing
+}
+
 struct BeamSelectArgs {
   BeamWs ws;
   int bsz, K, V, S, step, max_len, eos, unk; float unk_pen;
@@ -129,6 +271,7 @@ struct BeamSelectArgs {
   float* scores; int64_t score_ld;
   int* ignore; int* done; int* nfin; int64_t* reorder;
   int64_t* fin_tok; float* fin_pos; int64_t fin_ld; float* fin_score; int* fin_len; int* fin_cnt;
+  const int64_t* prefix; int64_t prefix_ld; int pad;        // ofa_beam_prefix_select: the forced tokens of this step (else null)
 };
 
 __global__ __launch_bounds__(BEAM_THREADS) void beam_select_kernel(BeamSelectArgs a) {
@@ -154,19 +297,11 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_select_kernel(BeamSelectArg
 
   // ---- each beam row's normaliser from its splits' parts
   if (tid < nr) {
-    const float* st = a.ws.stats + (int64_t)(r0 + tid) * a.S * 2;
-    float M = -INFINITY;
-    bool isnan_ = false;
-    for (int s = 0; s < a.S; ++s) {
-      const float ms = st[2 * s];
-      if (ms != ms) isnan_ = true; else M = fmaxf(M, ms);
-    }
-    float S = 0.f;
-    for (int s = 0; s < a.S; ++s)
-      if (st[2 * s] != -INFINITY) S += st[2 * s + 1] * expf(st[2 * s] - M);
-    const float l = M + logf(S);
+    bool b;
+    float l = beam_row_lse(a.ws.stats + (int64_t)(r0 + tid) * a.S * 2, a.S, b);
+    if (a.prefix && a.prefix[(int64_t)sent * a.prefix_ld + step] != a.pad) { l = 0.f; b = false; }   // a forced row's list is normalised
     lse[tid] = l;
-    bad[tid] = isnan_ || !(fabsf(l) <= 3.4e38f);             // NaN or infinite: the whole row is -inf (log_softmax -> NaN -> -inf)
+    bad[tid] = b;                                            // NaN or infinite: the whole row is -inf (log_softmax -> NaN -> -inf)
     cum[tid] = step > 0 ? a.scores[(int64_t)(r0 + tid) * a.score_ld + step - 1] : 0.f;
   }
   __syncthreads();
@@ -344,7 +479,7 @@ extern "C" int ofa_beam_topk(const void* logits, int64_t ld, int rows, int V, in
   const int S = beam_splits(V);
   BeamTopkArgs a{logits, ld, rows, V, K, S, cstart, cend,
                  BeamPolicy{temperature, step, min_len, max_len, pad, unk, eos, unk_penalty, ngram, tokens, tok_ld, done},
-                 beam_ws_carve(ws, rows, S, K)};
+                 beam_ws_carve(ws, rows, S, K), nullptr, 0, nullptr, nullptr};
   dim3 grid(S, rows);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == OFA_F32) hipLaunchKernelGGL(beam_topk_kernel<float>, grid, dim3(BEAM_THREADS), 0, st, a);
@@ -353,26 +488,94 @@ extern "C" int ofa_beam_topk(const void* logits, int64_t ld, int rows, int V, in
   return check_launch("ofa_beam_topk");
 }
 
+// the sentence pass of ofa_beam_select and ofa_beam_prefix_select (prefix: the forced tokens of a prefix step, else null)
+static int beam_select_launch(const char* who, const void* ws, int bsz, int K, int V, int step, int max_len, int eos, int unk,
+                              float unk_penalty, int normalize, float len_penalty, int64_t* tokens, int64_t tok_ld, int tok_cap,
+                              float* scores, int64_t score_ld, int* ignore, int* done, int* nfin, int64_t* reorder, int64_t* fin_tok,
+                              float* fin_pos, int64_t fin_ld, float* fin_score, int* fin_len, int* fin_cnt, const int64_t* prefix,
+                              int64_t prefix_ld, int pad, void* stream) {
+  OFA_REQUIRE(ws && tokens && scores && ignore && done && nfin && reorder && fin_tok && fin_pos && fin_score && fin_len && fin_cnt,
+              OFA_ERR_INVALID, "%s: null pointer", who);
+  OFA_REQUIRE(bsz > 0 && V > 1 && step >= 0 && step <= max_len, OFA_ERR_INVALID, "%s: bsz=%d V=%d step=%d max_len=%d", who,
+              bsz, V, step, max_len);
+  OFA_REQUIRE(K >= 1 && K <= BEAM_MAX_K, OFA_ERR_UNSUPPORTED, "%s: beam size %d outside [1, %d]", who, K, BEAM_MAX_K);
+  OFA_REQUIRE((int64_t)K * V < (1 << 24), OFA_ERR_UNSUPPORTED, "%s: beam * vocabulary must stay below 2^24", who);
+  OFA_REQUIRE(tok_cap >= step + 1 && tok_ld >= tok_cap && score_ld > step && fin_ld > step, OFA_ERR_INVALID,
+              "%s: history buffers too short for step %d (tok_cap=%d tok_ld=%lld score_ld=%lld fin_ld=%lld)", who, step,
+              tok_cap, (long long)tok_ld, (long long)score_ld, (long long)fin_ld);
+  const int S = beam_splits(V);
+  const size_t smem = select_smem(K, S, step);
+  OFA_REQUIRE(smem <= 65536, OFA_ERR_UNSUPPORTED, "%s: beam %d x %d vocabulary splits x step %d needs %zu bytes of LDS", who,
+              K, S, step, smem);
+  BeamSelectArgs a{beam_ws_carve(ws, (int64_t)bsz * K, S, K), bsz, K, V, S, step, max_len, eos, unk, unk_penalty, normalize, len_penalty,
+                   tokens, tok_ld, tok_cap, scores, score_ld, ignore, done, nfin, reorder, fin_tok, fin_pos, fin_ld, fin_score,
+                   fin_len, fin_cnt, prefix, prefix_ld, pad};
+  hipLaunchKernelGGL(beam_select_kernel, dim3(bsz), dim3(BEAM_THREADS), smem, (hipStream_t)stream, a);
+  return check_launch(who);
+}
+
 extern "C" int ofa_beam_select(const void* ws, int bsz, int K, int V, int step, int max_len, int eos, int unk, float unk_penalty,
                                int normalize, float len_penalty, int64_t* tokens, int64_t tok_ld, int tok_cap, float* scores,
                                int64_t score_ld, int* ignore, int* done, int* nfin, int64_t* reorder, int64_t* fin_tok,
                                float* fin_pos, int64_t fin_ld, float* fin_score, int* fin_len, int* fin_cnt, void* stream) {
-  OFA_REQUIRE(ws && tokens && scores && ignore && done && nfin && reorder && fin_tok && fin_pos && fin_score && fin_len && fin_cnt,
-              OFA_ERR_INVALID, "ofa_beam_select: null pointer");
-  OFA_REQUIRE(bsz > 0 && V > 1 && step >= 0 && step <= max_len, OFA_ERR_INVALID, "ofa_beam_select: bsz=%d V=%d step=%d max_len=%d",
-              bsz, V, step, max_len);
-  OFA_REQUIRE(K >= 1 && K <= BEAM_MAX_K, OFA_ERR_UNSUPPORTED, "ofa_beam_select: beam size %d outside [1, %d]", K, BEAM_MAX_K);
-  OFA_REQUIRE((int64_t)K * V < (1 << 24), OFA_ERR_UNSUPPORTED, "ofa_beam_select: beam * vocabulary must stay below 2^24");
-  OFA_REQUIRE(tok_cap >= step + 1 && tok_ld >= tok_cap && score_ld > step && fin_ld > step, OFA_ERR_INVALID,
-              "ofa_beam_select: history buffers too short for step %d (tok_cap=%d tok_ld=%lld score_ld=%lld fin_ld=%lld)", step,
-              tok_cap, (long long)tok_ld, (long long)score_ld, (long long)fin_ld);
+  return beam_select_launch("ofa_beam_select", ws, bsz, K, V, step, max_len, eos, unk, unk_penalty, normalize, len_penalty, tokens,
+                            tok_ld, tok_cap, scores, score_ld, ignore, done, nfin, reorder, fin_tok, fin_pos, fin_ld, fin_score,
+                            fin_len, fin_cnt, nullptr, 0, 0, stream);
+}
+
+// ---------------------------------------------------------------- steps under a forced target prefix
+extern "C" int ofa_beam_prefix_topk(const void* logits, int64_t ld, int rows, int V, int K, float temperature, int cstart, int cend,
+                                    int step, int min_len, int max_len, int pad, int unk, int eos, float unk_penalty, int ngram,
+                                    const int64_t* tokens, int64_t tok_ld, const int* done, const int64_t* prefix,
+                                    int64_t prefix_ld, const int* plen, float* glogit, void* ws, int dtype, void* stream) {
+  OFA_REQUIRE(logits && ws && plen, OFA_ERR_INVALID, "ofa_beam_prefix_topk: null pointer");
+  OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "ofa_beam_prefix_topk: bad dtype %d", dtype);
+  OFA_REQUIRE(rows > 0 && V > 1 && ld >= V && step >= 0, OFA_ERR_INVALID, "ofa_beam_prefix_topk: rows=%d V=%d ld=%lld step=%d", rows,
+              V, (long long)ld, step);
+  OFA_REQUIRE(!prefix || (glogit && prefix_ld > step && step < max_len), OFA_ERR_INVALID,
+              "ofa_beam_prefix_topk: a prefix step needs glogit, prefix_ld=%lld > step=%d and step < max_len=%d", (long long)prefix_ld,
+              step, max_len);
+  if (const int rc = beam_check_row_pass("ofa_beam_prefix_topk", rows, V, K, temperature, step, ngram, tokens, tok_ld)) return rc;
   const int S = beam_splits(V);
-  const size_t smem = select_smem(K, S, step);
-  OFA_REQUIRE(smem <= 65536, OFA_ERR_UNSUPPORTED, "ofa_beam_select: beam %d x %d vocabulary splits x step %d needs %zu bytes of LDS",
-              K, S, step, smem);
-  BeamSelectArgs a{beam_ws_carve(ws, (int64_t)bsz * K, S, K), bsz, K, V, S, step, max_len, eos, unk, unk_penalty, normalize, len_penalty,
-                   tokens, tok_ld, tok_cap, scores, score_ld, ignore, done, nfin, reorder, fin_tok, fin_pos, fin_ld, fin_score,
-                   fin_len, fin_cnt};
-  hipLaunchKernelGGL(beam_select_kernel, dim3(bsz), dim3(BEAM_THREADS), smem, (hipStream_t)stream, a);
-  return check_launch("ofa_beam_select");
+  // a prefix step applies the min_len mask to no row (the `elif` of sequence_generator.py:297-301)
+  BeamTopkArgs a{logits, ld, rows, V, K, S, cstart, cend,
+                 BeamPolicy{temperature, step, prefix ? 0 : min_len, max_len, pad, unk, eos, unk_penalty, ngram, tokens, tok_ld, done},
+                 beam_ws_carve(ws, rows, S, K), prefix, prefix_ld, plen, glogit};
+  dim3 grid(S, rows);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == OFA_F32) hipLaunchKernelGGL(beam_prefix_row_kernel<float>, grid, dim3(BEAM_THREADS), 0, st, a);
+  else if (dtype == OFA_BF16) hipLaunchKernelGGL(beam_prefix_row_kernel<bf16_t>, grid, dim3(BEAM_THREADS), 0, st, a);
+  else hipLaunchKernelGGL(beam_prefix_row_kernel<f16_t>, grid, dim3(BEAM_THREADS), 0, st, a);
+  return check_launch("ofa_beam_prefix_topk");
+}
+
+extern "C" int ofa_beam_prefix_fill(void* ws, int rows, int V, int K, int step, int pad, int unk, float unk_penalty, int ngram,
+                                    const int64_t* tokens, int64_t tok_ld, const int* done, const int64_t* prefix,
+                                    int64_t prefix_ld, const int* plen, const float* glogit, void* stream) {
+  OFA_REQUIRE(ws && prefix && plen && glogit, OFA_ERR_INVALID, "ofa_beam_prefix_fill: null pointer");
+  OFA_REQUIRE(rows > 0 && V > 1 && step >= 0 && prefix_ld > step, OFA_ERR_INVALID, "ofa_beam_prefix_fill: rows=%d V=%d step=%d prefix_ld=%lld",
+              rows, V, step, (long long)prefix_ld);
+  if (const int rc = beam_check_row_pass("ofa_beam_prefix_fill", rows, V, K, 1.f, step, ngram, tokens, tok_ld)) return rc;
+  // at most step + 4 of the lowest tokens are not at f (the prefix token, pad, unk, step + 1 banned ones): 2K more are there
+  const int pool = V < BEAM_FILL_POOL ? V : BEAM_FILL_POOL;
+  OFA_REQUIRE(2 * K + step + 4 <= pool && unk < pool, OFA_ERR_UNSUPPORTED,
+              "ofa_beam_prefix_fill: beam %d at step %d needs %d tokens among the first %d of the vocabulary", K, step,
+              2 * K + step + 4, pool);
+  const int S = beam_splits(V);
+  BeamFillArgs a{beam_ws_carve(ws, rows, S, K), rows, V, K, S, prefix, prefix_ld, plen, glogit,
+                 BeamPolicy{1.f, step, 0, 0, pad, unk, -1, unk_penalty, ngram, tokens, tok_ld, done}};
+  hipLaunchKernelGGL(beam_prefix_fill_kernel, dim3(rows), dim3(BEAM_THREADS), 0, (hipStream_t)stream, a);
+  return check_launch("ofa_beam_prefix_fill");
+}
+
+extern "C" int ofa_beam_prefix_select(const void* ws, int bsz, int K, int V, int step, int max_len, int eos, int unk,
+                                      float unk_penalty, int normalize, float len_penalty, int64_t* tokens, int64_t tok_ld,
+                                      int tok_cap, float* scores, int64_t score_ld, int* ignore, int* done, int* nfin,
+                                      int64_t* reorder, int64_t* fin_tok, float* fin_pos, int64_t fin_ld, float* fin_score,
+                                      int* fin_len, int* fin_cnt, const int64_t* prefix, int64_t prefix_ld, int pad, void* stream) {
+  OFA_REQUIRE(prefix && prefix_ld > step, OFA_ERR_INVALID, "ofa_beam_prefix_select: prefix=%p prefix_ld=%lld step=%d", (const void*)prefix,
+              (long long)prefix_ld, step);
+  return beam_select_launch("ofa_beam_prefix_select", ws, bsz, K, V, step, max_len, eos, unk, unk_penalty, normalize, len_penalty,
+                            tokens, tok_ld, tok_cap, scores, score_ld, ignore, done, nfin, reorder, fin_tok, fin_pos, fin_ld,
+                            fin_score, fin_len, fin_cnt, prefix, prefix_ld, pad, stream);
 }

@@ -6,7 +6,8 @@ One decoding step of OFA-base is ~130 small kernels; launched eagerly from Pytho
 are decoded (host-bound).  `StepDecoder` keeps every buffer a step touches at a fixed address -- target tokens, encoder
 output, the KV caches at their final capacity -- and records ONE hipGraph PER STEP LENGTH (the prefix length and the cache
 length are kernel arguments, so each length is its own graph; a sequence of T steps replays T graphs).  Graphs are keyed by
-(rows, source length, step) and reused by every later batch of the same shape.  `greedy` below is the minimal loop used
+(rows, source length, step) -- plus the `variant` a caller passes to `step` when it records different work at one step -- and reused
+by every later batch of the same shape.  `greedy` below is the minimal loop used
 by tests and benchmarks.  With `features_only` a step returns the last position's features [rows, D] instead of logits (the
 output projection is not run): what `TrieBeamGenerator` consumes.
 
@@ -17,6 +18,8 @@ into the step's graph, so a step has no host synchronisation.  Differences from 
 (beam search)"):
 the row count stays fixed (finished sentences are masked, not removed; rows are independent, so results are the same),
 the returned tensors are on the CPU, and `attention` is empty (the decoder returns no alignment).
+A sample whose `prefix_tokens` has columns (a target that opens with fixed text) is decoded one token per step like any other:
+while a sentence's prefix lasts, its rows are forced onto the prefix token by three launches (`_prefix_step_kernels`).
 
 `TrieBeamGenerator` is the same search restricted, at every step, to the next layer of a closed set's answer trie (the reference's
 `constraint_trie`, generator/sequence_generator.py:729-741): the row pass computes one dot product per child edge of the row's trie
@@ -39,7 +42,7 @@ class StepDecoder:
         self.warmup_sequences = warmup_sequences
         self.features_only = bool(features_only)          # a step returns [rows, D] features; the output projection is skipped
         self._shape = None
-        self._graphs: Dict[int, tuple] = {}
+        self._graphs: Dict[Any, tuple] = {}              # step, or (step, variant)
         self._pool = None
         self._seq = 0
         self._ws: Dict[tuple, torch.Tensor] = {}          # scratch buffers allocated inside this decoder's captures (see step)
@@ -84,18 +87,20 @@ class StepDecoder:
         self.t = 0
         return self
 
-    def step(self, next_tokens: Optional[torch.Tensor], post=None) -> torch.Tensor:
+    def step(self, next_tokens: Optional[torch.Tensor], post=None, variant=None) -> torch.Tensor:
         """Append one token per row and return the logits of that position: [rows, V] ([rows, D] features with `features_only`).
         next_tokens None: column t of `tokens` was already written on the device (beam search).  post(logits, t): device work
-        recorded into the same step graph after the decoder (the beam-search kernels and the cache reorder)."""
+        recorded into the same step graph after the decoder (the beam-search kernels and the cache reorder).  variant (hashable):
+        names what `post` records when that differs between sequences at one step -- a graph is replayed only for its own variant."""
         t = self.t
+        key = t if variant is None else (t, variant)
         if t >= self.max_len:
             raise ValueError(f"StepDecoder: max_len={self.max_len} exceeded")
         if next_tokens is not None:
             self.tokens[:, t].copy_(next_tokens.reshape(-1))
         graphed = self.use_graph and self._seq >= self.warmup_sequences
-        if graphed and t in self._graphs:
-            g, logits = self._graphs[t]
+        if graphed and key in self._graphs:
+            g, logits = self._graphs[key]
             self._set_lengths(t + 1)
             g.replay()
         elif graphed:
@@ -110,7 +115,7 @@ class StepDecoder:
             self._ws_keep.extend(added.values())
             if self._pool is None:
                 self._pool = g.pool()
-            self._graphs[t] = (g, logits)
+            self._graphs[key] = (g, logits)
             g.replay()                                    # capture only records: run the step once
         else:
             with torch.no_grad():
@@ -186,7 +191,7 @@ class SequenceGeneratorOutput:
 class SequenceGenerator:
     """Beam search with the reference's constructor and defaults (generator/sequence_generator.py:66-159).  Unsupported
     options of the reference raise NotImplementedError: other search strategies, an LM, a constraint trie, match_source_len,
-    prefix tokens and lexical constraints."""
+    lexical constraints and a prefix that holds <eos>."""
 
     MAX_BEAM = 16
 
@@ -235,16 +240,36 @@ class SequenceGenerator:
     def check_sample(self, sample, **kwargs) -> bool:
         """Refuse what is not implemented; returns whether the step-0 n-gram bans apply.  A collated batch always carries
         `prefix_tokens`; for a plain target it is [bsz, 0], which the reference treats as no prefix (`step < prefix_tokens.size(1)`
-        never holds).  A prefix with columns -- even all <pad> -- changes the reference's step (:283-288: no min_len mask while
-        step < its width) and is refused.  One trace of an empty prefix remains: the n-gram blocker skips rows whose prefix is not
-        shorter than step + n - 1 (:319-327), so with n = 1 nothing is banned at step 0."""
+        never holds).  One trace of an empty prefix remains: the n-gram blocker skips rows whose prefix is not shorter than
+        step + n - 1 (:319-327), so with n = 1 nothing is banned at step 0.  A prefix with columns is accepted in the form the
+        collator builds (`_prefix_of`); checked once per generate."""
         if kwargs.get("constraints") is not None:
             raise NotImplementedError("SequenceGenerator: lexical constraints are not implemented")
         prefix = sample.get("prefix_tokens")
-        if prefix is not None and prefix.dim() == 2 and prefix.size(1) > 0:
-            raise NotImplementedError("SequenceGenerator: prefix_tokens are not implemented (got a prefix of "
-                                      f"{prefix.size(1)} columns)")
+        self._prefix_of(sample)
         return not (prefix is not None and self.no_repeat_ngram_size == 1)
+
+    def _prefix_of(self, sample):
+        """(prefix [bsz, W] int64, plen [bsz]) of a sample whose prefix has columns, else None.  The collator strips BOS and EOS
+        and pads on the right up to the longest prefix of the batch; what it cannot produce is refused: <eos> inside (the
+        reference then copies the first beam over all beams, :509-522), <bos>, ids outside the dictionary, <pad> in front of a
+        token, and a width that no row fills."""
+        prefix = sample.get("prefix_tokens")
+        if prefix is None or prefix.dim() != 2 or prefix.size(1) == 0:
+            return None
+        prefix = prefix.long()
+        keep = prefix.ne(self.pad)
+        plen = keep.sum(1)
+        W = prefix.size(1)
+        ragged = (keep != (torch.arange(W, device=prefix.device).unsqueeze(0) < plen.unsqueeze(1))).any()
+        facts = torch.stack([prefix.eq(self.eos).any(), prefix.eq(self.bos).any(), (prefix.lt(0) | prefix.ge(self.vocab_size)).any(),
+                             ragged, plen.max().lt(W)]).tolist()                # one host read
+        for bad, what in zip(facts, ("<eos>", "<bos>", "a token id outside the dictionary", "<pad> in front of a token",
+                                     "only <pad> in its last column")):
+            if bad:
+                raise NotImplementedError(f"SequenceGenerator: prefix_tokens with {what} are not implemented (the collator's "
+                                          "prefixes are right-padded and hold neither <bos> nor <eos>)")
+        return prefix, plen
 
     # ------------------------------------------------------------------ device state
     def _buffers(self, rows, bsz, V, max_len, device):
@@ -263,6 +288,10 @@ class SequenceGenerator:
                 "fin_score": torch.zeros(bsz, K_, dtype=torch.float32, device=device),
                 "fin_len": torch.zeros(bsz, K_, **i32), "fin_cnt": torch.zeros(bsz, **i32),
                 "host": torch.zeros(2, dtype=torch.int32, pin_memory=True),
+                # a forced target prefix, at fixed addresses for the step graphs: tokens (pad beyond a sentence's prefix), lengths,
+                # and the prefix steps' scaled logit of every row's prefix token
+                "prefix": torch.full((bsz, max_len + 1), self.pad, dtype=torch.long, device=device),
+                "plen": torch.zeros(bsz, **i32), "glogit": torch.zeros(rows, dtype=torch.float32, device=device),
             }
         st = self._state
         for name in ("scores", "ignore", "done", "nfin", "fin_cnt"):
@@ -296,6 +325,27 @@ class SequenceGenerator:
     def _advance(self, t, st, ctx):
         """Device work between the sentence pass and the cache reorder."""
 
+    def _prefix_step_kernels(self, out, t, dec, st, max_len, forced):
+        """A step of a sample whose prefix has columns.  forced: a prefix step (t < width and t < max_len) -- the row pass without
+        the min_len mask and without candidates for forced rows, the fill, and the sentence pass told which rows are normalised.
+        Otherwise a free step: the plain two launches, with the n-gram bans following the prefix lengths."""
+        beam, V = self.beam_size, out.shape[1]
+        policy = dict(tokens=dec.tokens, done=st["done"], pad=self.pad, unk=self.unk, unk_penalty=self.unk_penalty,
+                      ngram=self.no_repeat_ngram_size)
+        K.beam_prefix_topk(out, beam, t, st["ws"], st["plen"], prefix=st["prefix"] if forced else None, glogit=st["glogit"],
+                           temperature=self.temperature, min_len=self.min_len, max_len=max_len, eos=self.eos,
+                           constraint_range=None if self.constraint_start is None else (self.constraint_start, self.constraint_end),
+                           **policy)
+        st["tokens"] = dec.tokens
+        sel = dict(eos=self.eos, unk=self.unk, unk_penalty=self.unk_penalty, normalize=self.normalize_scores,
+                   len_penalty=self.len_penalty)
+        if forced:
+            K.beam_prefix_fill(st["ws"], out.shape[0], V, beam, t, st["prefix"], st["plen"], st["glogit"], **policy)
+            K.beam_prefix_select(st["ws"], st, beam, V, t, max_len, st["prefix"], pad=self.pad, **sel)
+        else:
+            K.beam_select(st["ws"], st, beam, V, t, max_len, **sel)
+        dec.reorder(st["reorder"], caches_only=True)
+
     def _step_kernels(self, out, t, dec, st, max_len, ngram_step0=True, ctx=None):
         """Everything a step does after the decoder, on the device (recorded into the step graph)."""
         ngram = self.no_repeat_ngram_size if (t > 0 or ngram_step0) else 0
@@ -310,6 +360,7 @@ class SequenceGenerator:
     @torch.no_grad()
     def generate(self, model, sample, **kwargs):
         ngram_step0 = self.check_sample(sample, **kwargs)
+        prefix = self._prefix_of(sample)
         source_slots = [s for s in sample["net_input"]["slots"] if s.is_src]
         first = source_slots[0].value
         src = first["fbank"] if isinstance(first, dict) else first
@@ -325,14 +376,24 @@ class SequenceGenerator:
         dec.tokens[:, 0] = self.bos
         st = self._buffers(rows, bsz, V, steps, device)
         post = lambda out, t: self._step_kernels(out, t, dec, st, max_len, ngram_step0, ctx)   # noqa: E731
-        self._loop(dec, st, bsz, steps + 1, post, self._check_output)
+        variant = None
+        if prefix is not None:
+            tok, plen = prefix
+            width = min(tok.size(1), max_len)                 # prefix steps: t < tok.size(1) and t < max_len
+            st["prefix"].fill_(self.pad)
+            st["prefix"][:, :width] = tok[:, :width]
+            st["plen"].copy_(plen)
+            post = lambda out, t: self._prefix_step_kernels(out, t, dec, st, max_len, t < width)   # noqa: E731
+            variant = lambda t: "prefix" if t < width else "free after a prefix"               # noqa: E731
+        self._loop(dec, st, bsz, steps + 1, post, self._check_output, variant)
         return self._collect(st, bsz)
 
-    def _loop(self, dec, st, bsz, nsteps, post, check=None):
-        """At most `nsteps` decoding steps, stopping once every sentence is finished."""
+    def _loop(self, dec, st, bsz, nsteps, post, check=None, variant=None):
+        """At most `nsteps` decoding steps, stopping once every sentence is finished.  variant(step): what distinguishes this
+        sequence's `post` at that step from another sequence's (the key of the step's graph)."""
         host, events = st["host"], [None, None]
         for step in range(nsteps):
-            out = dec.step(None, post=post)
+            out = dec.step(None, post=post, variant=None if variant is None else variant(step))
             if check is not None:
                 check(out)
             # the all-finished counter reaches the host one step late, through pinned memory: no synchronisation inside a step
@@ -383,6 +444,13 @@ class TrieBeamGenerator(SequenceGenerator):
             raise ValueError("TrieBeamGenerator: the plan was built with other BOS / EOS / PAD ids than the dictionary's")
         self.plan = plan
         self._dev: Dict[torch.device, Dict[str, object]] = {}
+
+    def _prefix_of(self, sample):
+        prefix = sample.get("prefix_tokens")
+        if prefix is not None and prefix.dim() == 2 and prefix.size(1) > 0:
+            raise NotImplementedError("TrieBeamGenerator: prefix_tokens are not implemented (got a prefix of "
+                                      f"{prefix.size(1)} columns)")
+        return None
 
     def _plan_on(self, device):
         if device not in self._dev:

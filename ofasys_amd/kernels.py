@@ -1363,6 +1363,56 @@ def beam_select(ws, st, K, V, step, max_len, eos=2, unk=3, unk_penalty=0.0, norm
                stream())
 
 
+def beam_prefix_topk(logits2d, K, step, ws, plen, prefix=None, glogit=None, tokens=None, done=None, temperature=1.0,
+                     constraint_range=None, min_len=1, max_len=256, pad=1, unk=3, eos=2, unk_penalty=0.0, ngram=0):
+    """beam_topk for a sample that carries prefix_tokens.  plen: int32 [bsz] prefix lengths (the n-gram bans skip rows with
+    plen >= step + ngram - 1).  prefix int64 [bsz, > step] (a prefix step; None: a free step): no min_len mask, every row's scaled
+    logit at prefix[sentence, step] goes to glogit fp32 [rows], and forced rows (prefix token != pad) get their candidates from
+    beam_prefix_fill."""
+    rows, V = logits2d.shape
+    if logits2d.stride(1) != 1:
+        raise OfaError("beam_prefix_topk: the logits' last dimension must be contiguous")
+    if plen.dtype != torch.int32 or plen.numel() * int(K) != rows or not plen.is_contiguous():
+        raise OfaError("beam_prefix_topk: plen must be a contiguous int32 [rows / K]")
+    _check_prefix("beam_prefix_topk", prefix, glogit, rows, K)
+    cs, ce = (-1, -1) if constraint_range is None else (int(constraint_range[0]), int(constraint_range[1]))
+    tok_ld = tokens.stride(0) if tokens is not None else 0
+    lib().call("ofa_beam_prefix_topk", ptr(logits2d), logits2d.stride(0), rows, V, int(K), float(temperature), cs, ce, int(step),
+               int(min_len), int(max_len), int(pad), int(unk), int(eos), float(unk_penalty), int(ngram), ptr(tokens), tok_ld,
+               ptr(done), ptr(prefix), prefix.stride(0) if prefix is not None else 0, ptr(plen), ptr(glogit), ptr(ws),
+               dtype_code(logits2d), stream())
+
+
+def _check_prefix(who, prefix, glogit, rows, K):
+    if prefix is None:
+        return
+    if prefix.dtype != torch.int64 or prefix.dim() != 2 or prefix.shape[0] * int(K) != rows or prefix.stride(1) != 1:
+        raise OfaError(f"{who}: prefix must be int64 [rows / K, width] with a contiguous last dimension")
+    if glogit is not None and (glogit.dtype != torch.float32 or glogit.numel() != rows or not glogit.is_contiguous()):
+        raise OfaError(f"{who}: glogit must be a contiguous float32 [rows]")
+
+
+def beam_prefix_fill(ws, rows, V, K, step, prefix, plen, glogit, tokens=None, done=None, pad=1, unk=3, unk_penalty=0.0, ngram=0):
+    """Between beam_prefix_topk and beam_prefix_select of a prefix step: the batch-wide fill value and the candidates of every
+    forced row, written to `ws` as lprobs."""
+    _check_prefix("beam_prefix_fill", prefix, glogit, rows, K)
+    tok_ld = tokens.stride(0) if tokens is not None else 0
+    lib().call("ofa_beam_prefix_fill", ptr(ws), int(rows), int(V), int(K), int(step), int(pad), int(unk), float(unk_penalty),
+               int(ngram), ptr(tokens), tok_ld, ptr(done), ptr(prefix), prefix.stride(0), ptr(plen), ptr(glogit), stream())
+
+
+def beam_prefix_select(ws, st, K, V, step, max_len, prefix, pad=1, eos=2, unk=3, unk_penalty=0.0, normalize=False, len_penalty=1.0):
+    """beam_select of a prefix step: the candidate values of forced rows (prefix[sentence, step] != pad) are lprobs already."""
+    tokens, scores = st["tokens"], st["scores"]
+    bsz = st["done"].numel()
+    _check_prefix("beam_prefix_select", prefix, None, bsz * int(K), K)
+    lib().call("ofa_beam_prefix_select", ptr(ws), bsz, int(K), int(V), int(step), int(max_len), int(eos), int(unk),
+               float(unk_penalty), int(bool(normalize)), float(len_penalty), ptr(tokens), tokens.stride(0), tokens.shape[1],
+               ptr(scores), scores.stride(0), ptr(st["ignore"]), ptr(st["done"]), ptr(st["nfin"]), ptr(st["reorder"]),
+               ptr(st["fin_tok"]), ptr(st["fin_pos"]), st["fin_tok"].stride(1), ptr(st["fin_score"]), ptr(st["fin_len"]),
+               ptr(st["fin_cnt"]), ptr(prefix), prefix.stride(0), int(pad), stream())
+
+
 # ------------------------------------------------------------------ closed-set scoring (csrc/closed_set_score.hip)
 def closed_set_ws_bytes(bsz, E, N):
     return int(lib().cdll.ofa_closed_set_ws_bytes(int(bsz), int(E), int(N)))

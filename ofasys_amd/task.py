@@ -270,13 +270,19 @@ class Task:
 
     def inference(self, model, sample, **kwargs):
         """Beam search on `sample` (a collated batch); for TEXT targets every hypothesis gets `.text` through the task's text
-        tokenizer (preprocessor/default/text.py:340-371).  The model is left in eval mode."""
+        tokenizer (preprocessor/default/text.py:340-371).  As there, a sample with `prefix_tokens` has the sentence's prefix (its
+        entries that are neither <pad> nor <eos>) cut from the front of `.tokens` before decoding; scores and positional scores
+        keep the prefix positions.  The model is left in eval mode."""
         model.eval()
         outputs = self.generator.generate(model, sample, **kwargs)
         if self.target_modality == ModalityType.TEXT:
             pre = self.general_preprocess.name2pre["text"]
-            for single in outputs:
+            prefix = sample.get("prefix_tokens")
+            for idx, single in enumerate(outputs):
                 for hyp in (single if isinstance(single, list) else [single]):
+                    if prefix is not None:
+                        row = prefix[idx]
+                        hyp.tokens = hyp.tokens[int((row.ne(self.global_dict.pad()) & row.ne(self.global_dict.eos())).sum()):]
                     hyp.text = pre.decode(hyp.tokens)
         return outputs
 

@@ -1,7 +1,9 @@
 """Beam-search generation at the cfg-2 model size (OFA-base, bf16; 32 sentences x beam 5 = 160 rows, no_repeat_ngram_size 3,
 max_len 32): ms per generation step and sentences/s through the captured per-step graphs, next to StepDecoder.greedy on the
 same 160 rows; then the two beam kernels alone (us, and GB/s against the bytes of the logits they read) and the
-self-attention cache reorder alone.  Usage: python tools/beam_bench.py"""
+self-attention cache reorder alone.  With --prefix-width W the same generation runs under a forced target prefix of W tokens per
+sentence, and the policy launches of a prefix step (row pass, fill, sentence pass) are timed next to a free step's in the same run.
+Usage: python tools/beam_bench.py [--prefix-width W]"""
 import os
 import sys
 import time
@@ -32,11 +34,16 @@ def timed(fn, n=20):
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--prefix-width", type=int, default=0, help="force a target prefix of this many tokens on every sentence")
+    width = ap.parse_args().prefix_width
     args = argparse.Namespace(arch="base", workload="cfg2", batch=BSZ)
     model, d = bench.build(args, dev)
     model.eval()
     batch, _, _ = bench.make_batch(d, BSZ, 191, 8, 0, dev, "cfg2")
     sample = {"net_input": {"slots": batch["slots"]}}
+    if width > 0:
+        sample["prefix_tokens"] = torch.randint(4, len(d), (BSZ, width), generator=torch.Generator().manual_seed(0)).to(dev)
     # 1. generation: min_len = max_len keeps every sentence open for all max_len + 1 steps (a fixed amount of work to time)
     gen = SequenceGenerator(d, beam_size=BEAM, max_len=MAX_LEN, min_len=MAX_LEN, no_repeat_ngram_size=NGRAM, normalize_scores=False)
     runs = []
@@ -77,6 +84,21 @@ def main():
     print(f"ofa_beam_select bsz={BSZ} beam={BEAM}: {t_sel:7.1f} us")
     t_re = timed(lambda: gen._dec.reorder(st["reorder"], caches_only=True)) * 1e3
     print(f"self-attention cache reorder (all layers, full capacity): {t_re:7.1f} us")
+    if width > 0:
+        # 3. a prefix step's policy launches at the same shape and step: every row forced (the collator's case while the prefix lasts)
+        st["prefix"][:, :width] = sample["prefix_tokens"]
+        st["prefix"][:, step] = torch.randint(4, V, (BSZ,), generator=torch.Generator().manual_seed(1)).to(dev)
+        st["plen"].fill_(step + 1)
+        pol = dict(tokens=st["tokens"], done=st["done"], pad=d.pad(), unk=d.unk(), ngram=NGRAM)
+        t_row = timed(lambda: K.beam_prefix_topk(logits, BEAM, step, ws, st["plen"], prefix=st["prefix"], glogit=st["glogit"],
+                                                 min_len=1, max_len=MAX_LEN, eos=d.eos(), **pol)) * 1e3
+        t_fill = timed(lambda: K.beam_prefix_fill(ws, rows, V, BEAM, step, st["prefix"], st["plen"], st["glogit"], **pol)) * 1e3
+        t_psel = timed(lambda: K.beam_prefix_select(ws, st, BEAM, V, step, MAX_LEN, st["prefix"], pad=d.pad(), eos=d.eos(),
+                                                    unk=d.unk())) * 1e3
+        print(f"ofa_beam_prefix_topk (all rows forced) rows={rows} V={V} bf16: {t_row:7.1f} us  {nbytes / t_row / 1e3:7.1f} GB/s")
+        print(f"ofa_beam_prefix_fill   rows={rows}: {t_fill:7.1f} us")
+        print(f"ofa_beam_prefix_select bsz={BSZ} beam={BEAM}: {t_psel:7.1f} us")
+        print(f"policy launches of a step: prefix {t_row + t_fill + t_psel:7.1f} us, free {t_topk + t_sel:7.1f} us")
 
 
 if __name__ == "__main__":
