@@ -90,12 +90,11 @@ extern "C" int ofa_attn_bwd_prep(const void* dout, const void* out, float* delta
   OFA_REQUIRE(dtype == OFA_BF16 || dtype == OFA_F16, OFA_ERR_UNSUPPORTED, "attn_bwd_prep: bf16 / fp16 only");
   OFA_REQUIRE(dout && out && delta && (ldo % 8) == 0 && Tpad >= T, OFA_ERR_INVALID, "attn_bwd_prep: bad argument");
   const int64_t threads = (int64_t)B * T * heads * 8;
-  if (dtype == OFA_BF16)
-    hipLaunchKernelGGL(attn_delta_kernel<bf16_t>, dim3(cdiv(threads, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dout,
-                       (const bf16_t*)out, delta, B, heads, T, Tpad, ldo);
-  else
-    hipLaunchKernelGGL(attn_delta_kernel<f16_t>, dim3(cdiv(threads, 256)), dim3(256), 0, (hipStream_t)stream, (const f16_t*)dout,
-                       (const f16_t*)out, delta, B, heads, T, Tpad, ldo);
+  dispatch_dtype16(dtype, [&](auto tag) {
+    using TT = typename decltype(tag)::type;             // (T is the query length here)
+    hipLaunchKernelGGL(attn_delta_kernel<TT>, dim3(cdiv(threads, 256)), dim3(256), 0, (hipStream_t)stream, (const TT*)dout,
+                       (const TT*)out, delta, B, heads, T, Tpad, ldo);
+  });
   return check_launch("attn_bwd_prep");
 }
 
@@ -118,12 +117,10 @@ extern "C" int ofa_mean_heads(const void* p, void* out, int B, int heads, int64_
   OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "mean_heads: bad dtype %d", dtype);
   int64_t gx = (n + 255) / 256;
   dim3 grid((unsigned)(gx > 1024 ? 1024 : gx), B), block(256);
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((mean_heads_kernel<float>), grid, block, 0, (hipStream_t)stream, (const float*)p, (float*)out, heads, n);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((mean_heads_kernel<bf16_t>), grid, block, 0, (hipStream_t)stream, (const bf16_t*)p, (bf16_t*)out, heads, n);
-  else
-    hipLaunchKernelGGL((mean_heads_kernel<f16_t>), grid, block, 0, (hipStream_t)stream, (const f16_t*)p, (f16_t*)out, heads, n);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((mean_heads_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T*)p, (T*)out, heads, n);
+  });
   return check_launch("mean_heads");
 }
 
@@ -145,14 +142,10 @@ extern "C" int ofa_c_attn_grad(const float* delta, const void* c_attn, void* dc,
   OFA_REQUIRE(delta && c_attn && dc && B > 0 && heads > 0 && T > 0 && ld >= T, OFA_ERR_INVALID, "c_attn_grad: bad argument");
   OFA_REQUIRE(OFA_DT_OK(c_attn_dtype), OFA_ERR_INVALID, "c_attn_grad: bad dtype %d", c_attn_dtype);
   hipStream_t st = (hipStream_t)stream;
-  if (c_attn_dtype == OFA_F32)
-    hipLaunchKernelGGL((c_attn_grad_kernel<float>), dim3(heads), dim3(1024), 0, st, delta, (const float*)c_attn, (float*)dc, B, heads,
-                       T, ld, accumulate);
-  else if (c_attn_dtype == OFA_BF16)
-    hipLaunchKernelGGL((c_attn_grad_kernel<bf16_t>), dim3(heads), dim3(1024), 0, st, delta, (const bf16_t*)c_attn, (bf16_t*)dc, B,
-                       heads, T, ld, accumulate);
-  else
-    hipLaunchKernelGGL((c_attn_grad_kernel<f16_t>), dim3(heads), dim3(1024), 0, st, delta, (const f16_t*)c_attn, (f16_t*)dc, B,
-                       heads, T, ld, accumulate);
+  dispatch_dtype(c_attn_dtype, [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    hipLaunchKernelGGL((c_attn_grad_kernel<TT>), dim3(heads), dim3(1024), 0, st, delta, (const TT*)c_attn, (TT*)dc, B, heads, T, ld,
+                       accumulate);
+  });
   return check_launch("c_attn_grad");
 }

@@ -125,7 +125,7 @@ extern "C" int ofa_attn_decode(const void* q, const void* k, const void* v, cons
   OFA_REQUIRE(B > 0 && heads > 0 && S > 0, OFA_ERR_INVALID, "attn_decode: bad shape B=%d heads=%d S=%d", B, heads, S);
   OFA_REQUIRE(S <= 32768, OFA_ERR_UNSUPPORTED, "attn_decode: S=%d exceeds the LDS score buffer (32768)", S);
   OFA_REQUIRE(q && k && v && out, OFA_ERR_INVALID, "attn_decode: null pointer");
-  const int n = dtype == OFA_F32 ? 4 : 8;
+  const int n = dt_vecn(dtype);
   OFA_REQUIRE(ldk % n == 0 && k_batch_stride % n == 0 && ldk >= (int64_t)heads * 64, OFA_ERR_INVALID,
               "attn_decode: cache strides must keep 16-byte alignment (ld=%lld, batch stride=%lld)", (long long)ldk,
               (long long)k_batch_stride);
@@ -137,19 +137,10 @@ extern "C" int ofa_attn_decode(const void* q, const void* k, const void* v, cons
   const int kpi = 256 / (64 / n);
   const size_t lds = ((size_t)((S + 3) & ~3) + (size_t)kpi * 64) * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32) {
-    auto kern = attn_decode_kernel<float>;
+  dispatch_dtype(dtype, [&](auto tag) {
+    auto kern = attn_decode_kernel<typename decltype(tag)::type>;
     if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kern, dim3(B * heads), dim3(256), lds, st, a);
-  } else if (dtype == OFA_BF16) {
-    auto kern = attn_decode_kernel<bf16_t>;
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(B * heads), dim3(256), lds, st, a);
-  }
-  else {
-    auto kern = attn_decode_kernel<f16_t>;
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(B * heads), dim3(256), lds, st, a);
-  }
+  });
   return check_launch("attn_decode");
 }

@@ -482,9 +482,9 @@ extern "C" int ofa_beam_topk(const void* logits, int64_t ld, int rows, int V, in
                  beam_ws_carve(ws, rows, S, K), nullptr, 0, nullptr, nullptr};
   dim3 grid(S, rows);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32) hipLaunchKernelGGL(beam_topk_kernel<float>, grid, dim3(BEAM_THREADS), 0, st, a);
-  else if (dtype == OFA_BF16) hipLaunchKernelGGL(beam_topk_kernel<bf16_t>, grid, dim3(BEAM_THREADS), 0, st, a);
-  else hipLaunchKernelGGL(beam_topk_kernel<f16_t>, grid, dim3(BEAM_THREADS), 0, st, a);
+  dispatch_dtype(dtype, [&](auto tag) {
+    hipLaunchKernelGGL(beam_topk_kernel<typename decltype(tag)::type>, grid, dim3(BEAM_THREADS), 0, st, a);
+  });
   return check_launch("ofa_beam_topk");
 }
 
@@ -543,9 +543,9 @@ extern "C" int ofa_beam_prefix_topk(const void* logits, int64_t ld, int rows, in
                  beam_ws_carve(ws, rows, S, K), prefix, prefix_ld, plen, glogit};
   dim3 grid(S, rows);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32) hipLaunchKernelGGL(beam_prefix_row_kernel<float>, grid, dim3(BEAM_THREADS), 0, st, a);
-  else if (dtype == OFA_BF16) hipLaunchKernelGGL(beam_prefix_row_kernel<bf16_t>, grid, dim3(BEAM_THREADS), 0, st, a);
-  else hipLaunchKernelGGL(beam_prefix_row_kernel<f16_t>, grid, dim3(BEAM_THREADS), 0, st, a);
+  dispatch_dtype(dtype, [&](auto tag) {
+    hipLaunchKernelGGL(beam_prefix_row_kernel<typename decltype(tag)::type>, grid, dim3(BEAM_THREADS), 0, st, a);
+  });
   return check_launch("ofa_beam_prefix_topk");
 }
 

@@ -252,26 +252,22 @@ using namespace ofa;
 
 extern "C" int ofa_bias_outer_grad(const void* dbias, void* d_frames, void* d_patches, int A, int T, int start, int F, int P, int dtype,
                                    void* stream) {
-  OFA_REQUIRE(dtype == OFA_BF16 || dtype == OFA_F16 || dtype == OFA_F32, OFA_ERR_INVALID, "bias_outer_grad: bad dtype %d", dtype);
+  OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "bias_outer_grad: bad dtype %d", dtype);
   OFA_REQUIRE(dbias && d_frames && d_patches && A > 0 && F > 0 && P > 0 && start >= 0 && start + F * P <= T, OFA_ERR_INVALID,
               "bias_outer_grad: bad argument (T=%d start=%d F=%d P=%d)", T, start, F, P);
   hipStream_t st = (hipStream_t)stream;
   const dim3 gf(F * F, A), gp((P + 3) / 4, A), blk(256);
   const bool v4 = (start & 3) == 0 && (T & 3) == 0 && (P & 3) == 0 && !((uintptr_t)dbias & 15);
-#define OFA_OUTER(TT)                                                                                                              \
-  do {                                                                                                                             \
-    if (v4) {                                                                                                                      \
-      hipLaunchKernelGGL((bias_outer_grad_frames_kernel<TT, 4>), gf, blk, 0, st, (const TT*)dbias, (TT*)d_frames, A, T, start, F, P);   \
-      hipLaunchKernelGGL((bias_outer_grad_patches_kernel<TT, 4>), gp, blk, 0, st, (const TT*)dbias, (TT*)d_patches, A, T, start, F, P); \
-    } else {                                                                                                                       \
-      hipLaunchKernelGGL((bias_outer_grad_frames_kernel<TT, 1>), gf, blk, 0, st, (const TT*)dbias, (TT*)d_frames, A, T, start, F, P);   \
-      hipLaunchKernelGGL((bias_outer_grad_patches_kernel<TT, 1>), gp, blk, 0, st, (const TT*)dbias, (TT*)d_patches, A, T, start, F, P); \
-    }                                                                                                                              \
-  } while (0)
-  if (dtype == OFA_F32) OFA_OUTER(float);
-  else if (dtype == OFA_BF16) OFA_OUTER(bf16_t);
-  else OFA_OUTER(f16_t);
-#undef OFA_OUTER
+  dispatch_dtype(dtype, [&](auto tag) {
+    using TT = typename decltype(tag)::type;             // (T is the bias side length here)
+    if (v4) {
+      hipLaunchKernelGGL((bias_outer_grad_frames_kernel<TT, 4>), gf, blk, 0, st, (const TT*)dbias, (TT*)d_frames, A, T, start, F, P);
+      hipLaunchKernelGGL((bias_outer_grad_patches_kernel<TT, 4>), gp, blk, 0, st, (const TT*)dbias, (TT*)d_patches, A, T, start, F, P);
+    } else {
+      hipLaunchKernelGGL((bias_outer_grad_frames_kernel<TT, 1>), gf, blk, 0, st, (const TT*)dbias, (TT*)d_frames, A, T, start, F, P);
+      hipLaunchKernelGGL((bias_outer_grad_patches_kernel<TT, 1>), gp, blk, 0, st, (const TT*)dbias, (TT*)d_patches, A, T, start, F, P);
+    }
+  });
   return check_launch("bias_outer_grad");
 }
 
@@ -307,14 +303,12 @@ extern "C" int ofa_bias_build(const void* abs_bias, const ofa_bias_slots* slots,
   for (int h0 = 0; h0 < heads; h0 += 24) {                       // (a workgroup holds the block of up to 24 heads in LDS)
     const int A = heads - h0 < 24 ? heads - h0 : 24;
     const size_t lds = (size_t)A * 32 * BIAS_TP * 2;
-    if (dtype == OFA_BF16)
-      hipLaunchKernelGGL((bias_build_kernel<bf16_t>), grid, block, lds, (hipStream_t)stream,
-                         abs_bias ? (const bf16_t*)abs_bias + h0 * per_head : nullptr, d, out ? (bf16_t*)out + h0 * per_head : nullptr,
-                         (bf16_t*)swz_row + h0 * swz_head, (bf16_t*)swz_col + h0 * swz_head, A, Tb, Sb, heads, h0);
-    else
-      hipLaunchKernelGGL((bias_build_kernel<f16_t>), grid, block, lds, (hipStream_t)stream,
-                         abs_bias ? (const f16_t*)abs_bias + h0 * per_head : nullptr, d, out ? (f16_t*)out + h0 * per_head : nullptr,
-                         (f16_t*)swz_row + h0 * swz_head, (f16_t*)swz_col + h0 * swz_head, A, Tb, Sb, heads, h0);
+    dispatch_dtype16(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL((bias_build_kernel<T>), grid, block, lds, (hipStream_t)stream,
+                         abs_bias ? (const T*)abs_bias + h0 * per_head : nullptr, d, out ? (T*)out + h0 * per_head : nullptr,
+                         (T*)swz_row + h0 * swz_head, (T*)swz_col + h0 * swz_head, A, Tb, Sb, heads, h0);
+    });
   }
   return check_launch("bias_build");
 }
@@ -330,15 +324,11 @@ extern "C" int ofa_bias_block_add(void* bias, const void* values, int B, int A, 
   OFA_REQUIRE(bias && values && B > 0 && A > 0 && n > 0 && start >= 0 && start + n <= T, OFA_ERR_INVALID,
               "bias_block_add: bad argument (T=%d start=%d n=%d)", T, start, n);
   const int64_t total = (int64_t)B * A * n * n;
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((bias_block_add_kernel<float>), dim3(bias_grid(total)), dim3(256), 0, (hipStream_t)stream,
-                       (float*)bias, (const float*)values, B, A, T, start, n);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((bias_block_add_kernel<bf16_t>), dim3(bias_grid(total)), dim3(256), 0, (hipStream_t)stream,
-                       (bf16_t*)bias, (const bf16_t*)values, B, A, T, start, n);
-  else
-    hipLaunchKernelGGL((bias_block_add_kernel<f16_t>), dim3(bias_grid(total)), dim3(256), 0, (hipStream_t)stream,
-                       (f16_t*)bias, (const f16_t*)values, B, A, T, start, n);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    hipLaunchKernelGGL((bias_block_add_kernel<TT>), dim3(bias_grid(total)), dim3(256), 0, (hipStream_t)stream, (TT*)bias,
+                       (const TT*)values, B, A, T, start, n);
+  });
   return check_launch("bias_block_add");
 }
 
@@ -349,15 +339,11 @@ static int bias_block_batch_launch(void* bias, void* values, int B, int A, int T
   OFA_REQUIRE(bias && values && B > 0 && A > 0 && n > 0 && start >= 0 && start + n <= T, OFA_ERR_INVALID,
               "%s: bad argument (T=%d start=%d n=%d)", what, T, start, n);
   const int64_t total = (int64_t)B * A * n * n;
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((bias_block_batch_kernel<float, ADD>), dim3(bias_grid(total)), dim3(256), 0, (hipStream_t)stream,
-                       (float*)bias, (float*)values, B, A, T, start, n);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((bias_block_batch_kernel<bf16_t, ADD>), dim3(bias_grid(total)), dim3(256), 0, (hipStream_t)stream,
-                       (bf16_t*)bias, (bf16_t*)values, B, A, T, start, n);
-  else
-    hipLaunchKernelGGL((bias_block_batch_kernel<f16_t, ADD>), dim3(bias_grid(total)), dim3(256), 0, (hipStream_t)stream,
-                       (f16_t*)bias, (f16_t*)values, B, A, T, start, n);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    hipLaunchKernelGGL((bias_block_batch_kernel<TT, ADD>), dim3(bias_grid(total)), dim3(256), 0, (hipStream_t)stream, (TT*)bias,
+                       (TT*)values, B, A, T, start, n);
+  });
   return check_launch(what);
 }
 
@@ -377,14 +363,10 @@ extern "C" int ofa_bias_block_grad(const void* dbias, void* dvalues, int B, int 
   OFA_REQUIRE(dbias && dvalues && B > 0 && A > 0 && n > 0 && start >= 0 && start + n <= T, OFA_ERR_INVALID,
               "bias_block_grad: bad argument (T=%d start=%d n=%d)", T, start, n);
   const dim3 grid((n + 63) / 64, n);
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((bias_block_grad_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const float*)dbias, (float*)dvalues, B, A, T, start, n);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((bias_block_grad_kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)dbias, (bf16_t*)dvalues, B, A, T, start, n);
-  else
-    hipLaunchKernelGGL((bias_block_grad_kernel<f16_t>), grid, dim3(256), 0, (hipStream_t)stream,
-                       (const f16_t*)dbias, (f16_t*)dvalues, B, A, T, start, n);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using TT = typename decltype(tag)::type;
+    hipLaunchKernelGGL((bias_block_grad_kernel<TT>), grid, dim3(256), 0, (hipStream_t)stream, (const TT*)dbias, (TT*)dvalues, B, A,
+                       T, start, n);
+  });
   return check_launch("bias_block_grad");
 }

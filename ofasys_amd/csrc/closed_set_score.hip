@@ -135,16 +135,16 @@ extern "C" int ofa_closed_set_edge_logits(const void* h, int64_t ld_h, int dtype
   OFA_REQUIRE(D > 0 && V > 0 && bsz > 0 && chunk > 0 && T > 0 && c0 >= 0 && N > 0 && E > 0 && n_items >= 0, OFA_ERR_INVALID,
               "ofa_closed_set_edge_logits: D=%d V=%d bsz=%d chunk=%d T=%d c0=%d E=%d items=%d", D, V, bsz, chunk, T, c0, E, n_items);
   if (const int rc = check_proj_operands("ofa_closed_set_edge_logits", dtype, D, h, ld_h, W, ld_w)) return rc;
-  const size_t smem = (size_t)CS_BT * D * (dtype == OFA_F32 ? 4 : 2);
+  const size_t smem = (size_t)CS_BT * D * dt_size(dtype);
   OFA_REQUIRE(smem <= CS_LDS_MAX, OFA_ERR_UNSUPPORTED, "ofa_closed_set_edge_logits: D=%d needs %zu bytes of LDS", D, smem);
   if (n_items == 0) return OFA_OK;
   ClosedSetEdgeArgs a{h, ld_h, W, ld_w, bias, D, V, bsz, chunk, T, c0, E, N, items, edge_token, rep_ans, rep_pos, (float*)ws};
   dim3 grid(n_items, cdiv(bsz, CS_BT));
   OFA_REQUIRE(grid.y <= 65535, OFA_ERR_UNSUPPORTED, "ofa_closed_set_edge_logits: bsz %d too large", bsz);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32) hipLaunchKernelGGL(closed_set_edge_kernel<float>, grid, dim3(WAVE), smem, st, a);
-  else if (dtype == OFA_BF16) hipLaunchKernelGGL(closed_set_edge_kernel<bf16_t>, grid, dim3(WAVE), smem, st, a);
-  else hipLaunchKernelGGL(closed_set_edge_kernel<f16_t>, grid, dim3(WAVE), smem, st, a);
+  dispatch_dtype(dtype, [&](auto tag) {
+    hipLaunchKernelGGL(closed_set_edge_kernel<typename decltype(tag)::type>, grid, dim3(WAVE), smem, st, a);
+  });
   return check_launch("ofa_closed_set_edge_logits");
 }
 

@@ -121,6 +121,19 @@ template <> __device__ __forceinline__ void st1<bf16_t>(bf16_t* p, float v) { *p
 // ---------------------------------------------------------------- element-type dispatch of the C-ABI entry points
 #define OFA_DT_OK(dt) ((dt) == OFA_F32 || (dt) == OFA_BF16 || (dt) == OFA_F16)
 __host__ __device__ inline int dt_vecn(int dt) { return dt == OFA_F32 ? 4 : 8; }   // elements per 16-byte vector
+__host__ __device__ inline int dt_size(int dt) { return dt == OFA_F32 ? 4 : 2; }   // bytes per element
+// dispatch_dtype(dt, f) calls f(DtTag<T>{}) with the storage type T that dt names (dt has passed OFA_DT_OK) and returns what f returns;
+// dispatch_dtype16 is its sibling for entry points that have refused fp32.  The body names the type once:
+//   dispatch_dtype(dtype, [&](auto tag) { using T = typename decltype(tag)::type; hipLaunchKernelGGL((k<T>), ..., (const T*)x, n / Vec<T>::N); });
+template <typename T> struct DtTag { typedef T type; };
+template <typename F> inline auto dispatch_dtype16(int dt, F&& f) {
+  if (dt == OFA_BF16) return f(DtTag<bf16_t>{});
+  return f(DtTag<f16_t>{});
+}
+template <typename F> inline auto dispatch_dtype(int dt, F&& f) {
+  if (dt == OFA_F32) return f(DtTag<float>{});
+  return dispatch_dtype16(dt, f);
+}
 
 // ---------------------------------------------------------------- wave64 reductions
 // DPP data sharing instead of __shfl_xor: a shuffle compiles to ds_bpermute_b32 -- an LDS-pipe instruction with ~100+

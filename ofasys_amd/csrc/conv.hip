@@ -514,28 +514,23 @@ extern "C" int ofa_im2col(const void* x, void* col, int B, int H, int W, int C, 
   OFA_REQUIRE(Ho > 0 && Wo > 0, OFA_ERR_INVALID, "im2col: empty output (H=%d W=%d k=%dx%d s=%d p=%d)", H, W, KH, KW, stride, pad);
   hipStream_t st = (hipStream_t)stream;
   const int64_t total = (int64_t)B * Ho * Wo * Kpad;
-  const int es = dtype == OFA_F32 ? 4 : 2;
+  const int es = dt_size(dtype);
   if (x_nchw && (Kpad * es) % 16 == 0 && (size_t)64 * Kpad * es <= 48 * 1024 && (int64_t)B * Ho * Wo <= ((int64_t)1 << 36)) {
     const int64_t rows = (int64_t)B * Ho * Wo;
     const dim3 g((unsigned)((rows + 63) / 64)), blk(256);
     const size_t lds = (size_t)64 * Kpad * es;
-    if (dtype == OFA_F32) hipLaunchKernelGGL((im2col_nchw_lds_kernel<float>), g, blk, lds, st, (const float*)x, (float*)col, B, H, W, C, KH, KW, stride, pad, Ho, Wo, Kpad, rows);
-    else if (dtype == OFA_BF16) hipLaunchKernelGGL((im2col_nchw_lds_kernel<bf16_t>), g, blk, lds, st, (const bf16_t*)x, (bf16_t*)col, B, H, W, C, KH, KW, stride, pad, Ho, Wo, Kpad, rows);
-    else hipLaunchKernelGGL((im2col_nchw_lds_kernel<f16_t>), g, blk, lds, st, (const f16_t*)x, (f16_t*)col, B, H, W, C, KH, KW, stride, pad, Ho, Wo, Kpad, rows);
+    dispatch_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL((im2col_nchw_lds_kernel<T>), g, blk, lds, st, (const T*)x, (T*)col, B, H, W, C, KH, KW, stride, pad, Ho, Wo, Kpad, rows);
+    });
     return check_launch("im2col_nchw");
   }
   dim3 grid(grid_1d(total / 4)), block(256);
-  if (dtype == OFA_F32) {
-    if (x_nchw) hipLaunchKernelGGL((im2col_kernel<float, true>), grid, block, 0, st, (const float*)x, (float*)col, B, H, W, C, KH, KW, stride, pad, Ho, Wo, Kpad);
-    else hipLaunchKernelGGL((im2col_kernel<float, false>), grid, block, 0, st, (const float*)x, (float*)col, B, H, W, C, KH, KW, stride, pad, Ho, Wo, Kpad);
-  } else if (dtype == OFA_BF16) {
-    if (x_nchw) hipLaunchKernelGGL((im2col_kernel<bf16_t, true>), grid, block, 0, st, (const bf16_t*)x, (bf16_t*)col, B, H, W, C, KH, KW, stride, pad, Ho, Wo, Kpad);
-    else hipLaunchKernelGGL((im2col_kernel<bf16_t, false>), grid, block, 0, st, (const bf16_t*)x, (bf16_t*)col, B, H, W, C, KH, KW, stride, pad, Ho, Wo, Kpad);
-  }
-  else {
-    if (x_nchw) hipLaunchKernelGGL((im2col_kernel<f16_t, true>), grid, block, 0, st, (const f16_t*)x, (f16_t*)col, B, H, W, C, KH, KW, stride, pad, Ho, Wo, Kpad);
-    else hipLaunchKernelGGL((im2col_kernel<f16_t, false>), grid, block, 0, st, (const f16_t*)x, (f16_t*)col, B, H, W, C, KH, KW, stride, pad, Ho, Wo, Kpad);
-  }
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (x_nchw) hipLaunchKernelGGL((im2col_kernel<T, true>), grid, block, 0, st, (const T*)x, (T*)col, B, H, W, C, KH, KW, stride, pad, Ho, Wo, Kpad);
+    else hipLaunchKernelGGL((im2col_kernel<T, false>), grid, block, 0, st, (const T*)x, (T*)col, B, H, W, C, KH, KW, stride, pad, Ho, Wo, Kpad);
+  });
   return check_launch("im2col");
 }
 
@@ -543,17 +538,15 @@ extern "C" int ofa_col2im(const void* dcol, void* dx, int B, int H, int W, int C
                           int dtype, void* stream) {
   OFA_DT("col2im");
   OFA_REQUIRE(dcol && dx && B > 0 && H > 0 && W > 0 && C > 0 && Kpad >= KH * KW * C, OFA_ERR_INVALID, "col2im: bad argument");
-  const int n = dtype == OFA_F32 ? 4 : 8;
+  const int n = dt_vecn(dtype);
   OFA_REQUIRE(C % n == 0 && Kpad % n == 0, OFA_ERR_UNSUPPORTED, "col2im: C=%d / Kpad=%d must be multiples of %d", C, Kpad, n);
   const int Ho = ofa_conv_out_size(H, KH, stride, pad), Wo = ofa_conv_out_size(W, KW, stride, pad);
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(grid_1d((int64_t)B * H * W * (C / n))), block(256);
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((col2im_kernel<float>), grid, block, 0, st, (const float*)dcol, (float*)dx, B, H, W, C, KH, KW, stride, pad, Ho, Wo, Kpad);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((col2im_kernel<bf16_t>), grid, block, 0, st, (const bf16_t*)dcol, (bf16_t*)dx, B, H, W, C, KH, KW, stride, pad, Ho, Wo, Kpad);
-  else
-    hipLaunchKernelGGL((col2im_kernel<f16_t>), grid, block, 0, st, (const f16_t*)dcol, (f16_t*)dx, B, H, W, C, KH, KW, stride, pad, Ho, Wo, Kpad);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((col2im_kernel<T>), grid, block, 0, st, (const T*)dcol, (T*)dx, B, H, W, C, KH, KW, stride, pad, Ho, Wo, Kpad);
+  });
   return check_launch("col2im");
 }
 
@@ -572,29 +565,25 @@ extern "C" int ofa_batchnorm_ws_floats(int C) { return 4 * 256 * C + 2 * C; }   
 
 // column statistics of x into ws (fp64 partials [groups][2][C]); returns the group count
 static int bn_fwd_colstat(const void* x, float* ws, int64_t rows, int C, int dtype, hipStream_t st) {
-  const int n = dtype == OFA_F32 ? 4 : 8;
+  const int n = dt_vecn(dtype);
   const int groups = bn_groups(rows);
   const int cwl = bn_cw_log2(C / n);
   dim3 grid(cdiv(C / n, 1 << cwl), groups), block(256);
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((bn_colstat_kernel<float, 0>), grid, block, 0, st, (const float*)x, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (double*)ws, rows, C, 0, cwl);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((bn_colstat_kernel<bf16_t, 0>), grid, block, 0, st, (const bf16_t*)x, (const bf16_t*)nullptr, (const bf16_t*)nullptr, (const float*)nullptr, (const float*)nullptr, (double*)ws, rows, C, 0, cwl);
-  else
-    hipLaunchKernelGGL((bn_colstat_kernel<f16_t, 0>), grid, block, 0, st, (const f16_t*)x, (const f16_t*)nullptr, (const f16_t*)nullptr, (const float*)nullptr, (const float*)nullptr, (double*)ws, rows, C, 0, cwl);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((bn_colstat_kernel<T, 0>), grid, block, 0, st, (const T*)x, (const T*)nullptr, (const T*)nullptr, (const float*)nullptr, (const float*)nullptr, (double*)ws, rows, C, 0, cwl);
+  });
   return groups;
 }
 
 static int bn_apply_launch(const void* x, const void* gamma, const void* beta, const void* residual, void* y, const float* mean,
                            const float* rstd, int64_t rows, int C, int relu, int dtype, hipStream_t st) {
-  const int n = dtype == OFA_F32 ? 4 : 8;
+  const int n = dt_vecn(dtype);
   dim3 grid(grid_1d(rows * (C / n))), block(256);
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((bn_apply_kernel<float>), grid, block, 0, st, (const float*)x, (const float*)gamma, (const float*)beta, (const float*)mean, (const float*)rstd, (const float*)residual, (float*)y, rows, C, relu);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((bn_apply_kernel<bf16_t>), grid, block, 0, st, (const bf16_t*)x, (const bf16_t*)gamma, (const bf16_t*)beta, (const float*)mean, (const float*)rstd, (const bf16_t*)residual, (bf16_t*)y, rows, C, relu);
-  else
-    hipLaunchKernelGGL((bn_apply_kernel<f16_t>), grid, block, 0, st, (const f16_t*)x, (const f16_t*)gamma, (const f16_t*)beta, (const float*)mean, (const float*)rstd, (const f16_t*)residual, (f16_t*)y, rows, C, relu);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((bn_apply_kernel<T>), grid, block, 0, st, (const T*)x, (const T*)gamma, (const T*)beta, (const float*)mean, (const float*)rstd, (const T*)residual, (T*)y, rows, C, relu);
+  });
   return check_launch("batchnorm_apply");
 }
 
@@ -604,7 +593,7 @@ extern "C" int ofa_batchnorm_fwd(const void* x, const void* gamma, const void* b
                                  float eps, float momentum, int use_running, int relu, int dtype, void* stream) {
   OFA_DT("batchnorm_fwd");
   OFA_REQUIRE(x && gamma && beta && y && mean && rstd && ws && rows > 0 && C > 0, OFA_ERR_INVALID, "batchnorm_fwd: bad argument");
-  const int n = dtype == OFA_F32 ? 4 : 8;
+  const int n = dt_vecn(dtype);
   OFA_REQUIRE(C % n == 0, OFA_ERR_UNSUPPORTED, "batchnorm: C=%d must be a multiple of %d", C, n);
   OFA_REQUIRE(!use_running || (running_mean && running_var), OFA_ERR_INVALID, "batchnorm_fwd: eval mode needs running statistics");
   hipStream_t st = (hipStream_t)stream;
@@ -626,7 +615,7 @@ extern "C" int ofa_batchnorm_fwd(const void* x, const void* gamma, const void* b
 extern "C" int ofa_batchnorm_fwd_stats(const void* x, double* sums, float* ws, int64_t rows, int C, int dtype, void* stream) {
   OFA_DT("batchnorm_fwd_stats");
   OFA_REQUIRE(x && sums && ws && rows > 0 && C > 0, OFA_ERR_INVALID, "batchnorm_fwd_stats: bad argument");
-  OFA_REQUIRE(C % (dtype == OFA_F32 ? 4 : 8) == 0, OFA_ERR_UNSUPPORTED, "batchnorm: C=%d is not vectorizable", C);
+  OFA_REQUIRE(C % dt_vecn(dtype) == 0, OFA_ERR_UNSUPPORTED, "batchnorm: C=%d is not vectorizable", C);
   hipStream_t st = (hipStream_t)stream;
   const int groups = bn_fwd_colstat(x, ws, rows, C, dtype, st);
   hipLaunchKernelGGL(bn_fold_sums_kernel, dim3(cdiv(C, 16)), dim3(256), 0, st, (const double*)ws, groups, C, sums, rows);
@@ -640,7 +629,7 @@ extern "C" int ofa_batchnorm_fwd_apply(const void* x, const void* gamma, const v
   OFA_DT("batchnorm_fwd_apply");
   OFA_REQUIRE(x && gamma && beta && y && mean && rstd && sums && groups >= 0 && rows > 0 && C > 0, OFA_ERR_INVALID,
               "batchnorm_fwd_apply: bad argument");
-  OFA_REQUIRE(C % (dtype == OFA_F32 ? 4 : 8) == 0, OFA_ERR_UNSUPPORTED, "batchnorm: C=%d is not vectorizable", C);
+  OFA_REQUIRE(C % dt_vecn(dtype) == 0, OFA_ERR_UNSUPPORTED, "batchnorm: C=%d is not vectorizable", C);
   hipStream_t st = (hipStream_t)stream;
   if (groups == 0)   // SyncBatchNorm: the reduced sums are ONE group of partials over sums[2*C] rows (the count lives on the device)
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 16)), dim3(256), 0, st, sums, 1, C, rows, eps, momentum, mean, rstd, running_mean, running_var, sums + 2 * (int64_t)C);
@@ -655,38 +644,28 @@ extern "C" int ofa_batchnorm_fwd_apply(const void* x, const void* gamma, const v
 static int bn_bwd_stats_launch(const void* dy, const void* y, const void* x, const void* gamma, const float* mean, const float* rstd,
                                float* sums, void* dgamma, void* dbeta, float* ws, int64_t rows, int C, int relu, int accumulate,
                                const void* beta, int dtype, hipStream_t st) {
-  const int n = dtype == OFA_F32 ? 4 : 8;
+  const int n = dt_vecn(dtype);
   const int groups = bn_groups(rows);
   const int cwl = bn_cw_log2(C / n);
   dim3 grid(cdiv(C / n, 1 << cwl), groups), block(256);
-  if (dtype == OFA_F32) {
-    if (beta) hipLaunchKernelGGL((bn_colstat_kernel<float, 2>), grid, block, 0, st, (const float*)x, (const float*)dy, (const float*)y, mean, rstd, (double*)ws, rows, C, relu, cwl, (const float*)gamma, (const float*)beta);
-    else hipLaunchKernelGGL((bn_colstat_kernel<float, 1>), grid, block, 0, st, (const float*)x, (const float*)dy, (const float*)y, mean, rstd, (double*)ws, rows, C, relu, cwl);
-    hipLaunchKernelGGL((bn_bwd_finalize_kernel<float>), dim3(cdiv(C, 16)), dim3(256), 0, st, (const double*)ws, groups, C, sums, (float*)dgamma, (float*)dbeta, accumulate);
-  } else if (dtype == OFA_BF16) {
-    if (beta) hipLaunchKernelGGL((bn_colstat_kernel<bf16_t, 2>), grid, block, 0, st, (const bf16_t*)x, (const bf16_t*)dy, (const bf16_t*)y, mean, rstd, (double*)ws, rows, C, relu, cwl, (const bf16_t*)gamma, (const bf16_t*)beta);
-    else hipLaunchKernelGGL((bn_colstat_kernel<bf16_t, 1>), grid, block, 0, st, (const bf16_t*)x, (const bf16_t*)dy, (const bf16_t*)y, mean, rstd, (double*)ws, rows, C, relu, cwl);
-    hipLaunchKernelGGL((bn_bwd_finalize_kernel<bf16_t>), dim3(cdiv(C, 16)), dim3(256), 0, st, (const double*)ws, groups, C, sums, (bf16_t*)dgamma, (bf16_t*)dbeta, accumulate);
-  }
-  else {
-    if (beta) hipLaunchKernelGGL((bn_colstat_kernel<f16_t, 2>), grid, block, 0, st, (const f16_t*)x, (const f16_t*)dy, (const f16_t*)y, mean, rstd, (double*)ws, rows, C, relu, cwl, (const f16_t*)gamma, (const f16_t*)beta);
-    else hipLaunchKernelGGL((bn_colstat_kernel<f16_t, 1>), grid, block, 0, st, (const f16_t*)x, (const f16_t*)dy, (const f16_t*)y, mean, rstd, (double*)ws, rows, C, relu, cwl);
-    hipLaunchKernelGGL((bn_bwd_finalize_kernel<f16_t>), dim3(cdiv(C, 16)), dim3(256), 0, st, (const double*)ws, groups, C, sums, (f16_t*)dgamma, (f16_t*)dbeta, accumulate);
-  }
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (beta) hipLaunchKernelGGL((bn_colstat_kernel<T, 2>), grid, block, 0, st, (const T*)x, (const T*)dy, (const T*)y, mean, rstd, (double*)ws, rows, C, relu, cwl, (const T*)gamma, (const T*)beta);
+    else hipLaunchKernelGGL((bn_colstat_kernel<T, 1>), grid, block, 0, st, (const T*)x, (const T*)dy, (const T*)y, mean, rstd, (double*)ws, rows, C, relu, cwl);
+    hipLaunchKernelGGL((bn_bwd_finalize_kernel<T>), dim3(cdiv(C, 16)), dim3(256), 0, st, (const double*)ws, groups, C, sums, (T*)dgamma, (T*)dbeta, accumulate);
+  });
   return check_launch("batchnorm_bwd_stats");
 }
 
 static int bn_bwd_dx_launch(const void* dy, const void* y, const void* x, const void* gamma, const float* mean, const float* rstd,
                             const float* sums, void* dx, void* dres, int64_t rows, const double* stat_rows, int C, int batch_stats,
                             int relu, const void* beta, int dtype, hipStream_t st) {
-  const int n = dtype == OFA_F32 ? 4 : 8;
+  const int n = dt_vecn(dtype);
   dim3 g2(grid_1d(rows * (C / n))), block(256);
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((bn_bwd_dx_kernel<float>), g2, block, 0, st, (const float*)dy, (const float*)y, (const float*)x, (const float*)gamma, mean, rstd, (const float*)sums, (float*)dx, (float*)dres, rows, C, relu, batch_stats, (const float*)beta, stat_rows);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((bn_bwd_dx_kernel<bf16_t>), g2, block, 0, st, (const bf16_t*)dy, (const bf16_t*)y, (const bf16_t*)x, (const bf16_t*)gamma, mean, rstd, (const float*)sums, (bf16_t*)dx, (bf16_t*)dres, rows, C, relu, batch_stats, (const bf16_t*)beta, stat_rows);
-  else
-    hipLaunchKernelGGL((bn_bwd_dx_kernel<f16_t>), g2, block, 0, st, (const f16_t*)dy, (const f16_t*)y, (const f16_t*)x, (const f16_t*)gamma, mean, rstd, (const float*)sums, (f16_t*)dx, (f16_t*)dres, rows, C, relu, batch_stats, (const f16_t*)beta, stat_rows);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((bn_bwd_dx_kernel<T>), g2, block, 0, st, (const T*)dy, (const T*)y, (const T*)x, (const T*)gamma, mean, rstd, (const float*)sums, (T*)dx, (T*)dres, rows, C, relu, batch_stats, (const T*)beta, stat_rows);
+  });
   return check_launch("batchnorm_bwd_dx");
 }
 
@@ -698,7 +677,7 @@ extern "C" int ofa_batchnorm_bwd(const void* dy, const void* y, const void* x, c
   OFA_REQUIRE(dy && x && gamma && mean && rstd && dx && ws && rows > 0 && C > 0 && (!relu || y || beta), OFA_ERR_INVALID, "batchnorm_bwd: bad argument");
   OFA_REQUIRE(!beta || (relu && !dres), OFA_ERR_INVALID, "batchnorm_bwd: the gate can be recomputed from x (beta != NULL) only for a ReLU layer without a residual input");
   if (beta) relu = 2;
-  const int n = dtype == OFA_F32 ? 4 : 8;
+  const int n = dt_vecn(dtype);
   OFA_REQUIRE(C % n == 0, OFA_ERR_UNSUPPORTED, "batchnorm: C=%d must be a multiple of %d", C, n);
   hipStream_t st = (hipStream_t)stream;
   float* sums = ws + (int64_t)4 * 256 * C;
@@ -717,7 +696,7 @@ extern "C" int ofa_batchnorm_bwd_stats(const void* dy, const void* y, const void
   OFA_DT("batchnorm_bwd_stats");
   OFA_REQUIRE(dy && x && gamma && mean && rstd && sums && ws && rows > 0 && C > 0 && (!relu || y || beta), OFA_ERR_INVALID, "batchnorm_bwd_stats: bad argument");
   if (beta) relu = 2;
-  OFA_REQUIRE(C % (dtype == OFA_F32 ? 4 : 8) == 0, OFA_ERR_UNSUPPORTED, "batchnorm: C=%d is not vectorizable", C);
+  OFA_REQUIRE(C % dt_vecn(dtype) == 0, OFA_ERR_UNSUPPORTED, "batchnorm: C=%d is not vectorizable", C);
   return bn_bwd_stats_launch(dy, y, x, gamma, mean, rstd, sums, dgamma, dbeta, ws, rows, C, relu, accumulate, beta, dtype, (hipStream_t)stream);
 }
 
@@ -728,7 +707,7 @@ extern "C" int ofa_batchnorm_bwd_dx(const void* dy, const void* y, const void* x
   OFA_REQUIRE(dy && x && gamma && mean && rstd && sums && dx && rows > 0 && total_rows && C > 0 && (!relu || y || beta), OFA_ERR_INVALID, "batchnorm_bwd_dx: bad argument");
   OFA_REQUIRE(!beta || (relu && !dres), OFA_ERR_INVALID, "batchnorm_bwd_dx: the gate can be recomputed from x (beta != NULL) only for a ReLU layer without a residual input");
   if (beta) relu = 2;
-  OFA_REQUIRE(C % (dtype == OFA_F32 ? 4 : 8) == 0, OFA_ERR_UNSUPPORTED, "batchnorm: C=%d is not vectorizable", C);
+  OFA_REQUIRE(C % dt_vecn(dtype) == 0, OFA_ERR_UNSUPPORTED, "batchnorm: C=%d is not vectorizable", C);
   return bn_bwd_dx_launch(dy, y, x, gamma, mean, rstd, sums, dx, dres, rows, total_rows, C, 1, relu, beta, dtype, (hipStream_t)stream);
 }
 
@@ -738,12 +717,13 @@ extern "C" int ofa_maxpool_fwd(const void* x, void* y, uint8_t* arg, int B, int 
   OFA_REQUIRE(x && y && arg && B > 0 && H > 0 && W > 0 && C > 0 && K > 0 && K * K <= 255 && stride > 0 && pad >= 0, OFA_ERR_INVALID, "maxpool_fwd: bad argument");
   const int Ho = ofa_conv_out_size(H, K, stride, pad), Wo = ofa_conv_out_size(W, K, stride, pad);
   hipStream_t st = (hipStream_t)stream;
-  const int nvec = dtype == OFA_F32 ? 4 : 8;
+  const int nvec = dt_vecn(dtype);
   OFA_REQUIRE(C % nvec == 0, OFA_ERR_UNSUPPORTED, "maxpool_fwd: C=%d must be a multiple of %d", C, nvec);
   dim3 grid(grid_1d((int64_t)B * Ho * Wo * (C / nvec))), block(256);
-  if (dtype == OFA_F32) hipLaunchKernelGGL((maxpool_fwd_kernel<float>), grid, block, 0, st, (const float*)x, (float*)y, arg, B, H, W, C, K, stride, pad, Ho, Wo);
-  else if (dtype == OFA_BF16) hipLaunchKernelGGL((maxpool_fwd_kernel<bf16_t>), grid, block, 0, st, (const bf16_t*)x, (bf16_t*)y, arg, B, H, W, C, K, stride, pad, Ho, Wo);
-  else hipLaunchKernelGGL((maxpool_fwd_kernel<f16_t>), grid, block, 0, st, (const f16_t*)x, (f16_t*)y, arg, B, H, W, C, K, stride, pad, Ho, Wo);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((maxpool_fwd_kernel<T>), grid, block, 0, st, (const T*)x, (T*)y, arg, B, H, W, C, K, stride, pad, Ho, Wo);
+  });
   return check_launch("maxpool_fwd");
 }
 
@@ -753,12 +733,13 @@ extern "C" int ofa_maxpool_bwd(const void* dy, const uint8_t* arg, void* dx, int
   OFA_REQUIRE(dy && dx && arg && B > 0 && H > 0 && W > 0 && C > 0 && K > 0, OFA_ERR_INVALID, "maxpool_bwd: bad argument");
   const int Ho = ofa_conv_out_size(H, K, stride, pad), Wo = ofa_conv_out_size(W, K, stride, pad);
   hipStream_t st = (hipStream_t)stream;
-  const int nvec = dtype == OFA_F32 ? 4 : 8;
+  const int nvec = dt_vecn(dtype);
   OFA_REQUIRE(C % nvec == 0, OFA_ERR_UNSUPPORTED, "maxpool_bwd: C=%d must be a multiple of %d", C, nvec);
   dim3 grid(grid_1d((int64_t)B * H * W * (C / nvec))), block(256);
-  if (dtype == OFA_F32) hipLaunchKernelGGL((maxpool_bwd_kernel<float>), grid, block, 0, st, (const float*)dy, arg, (float*)dx, B, H, W, C, K, stride, pad, Ho, Wo);
-  else if (dtype == OFA_BF16) hipLaunchKernelGGL((maxpool_bwd_kernel<bf16_t>), grid, block, 0, st, (const bf16_t*)dy, arg, (bf16_t*)dx, B, H, W, C, K, stride, pad, Ho, Wo);
-  else hipLaunchKernelGGL((maxpool_bwd_kernel<f16_t>), grid, block, 0, st, (const f16_t*)dy, arg, (f16_t*)dx, B, H, W, C, K, stride, pad, Ho, Wo);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((maxpool_bwd_kernel<T>), grid, block, 0, st, (const T*)dy, arg, (T*)dx, B, H, W, C, K, stride, pad, Ho, Wo);
+  });
   return check_launch("maxpool_bwd");
 }
 
@@ -768,8 +749,9 @@ extern "C" int ofa_relu(const void* x, const void* gate, void* y, int64_t n, int
   OFA_REQUIRE(n >= 0 && (n == 0 || (x && y)), OFA_ERR_INVALID, "relu: bad argument");
   if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32) hipLaunchKernelGGL((relu_kernel<float>), dim3(grid_1d(n)), dim3(256), 0, st, (const float*)x, (const float*)gate, (float*)y, n);
-  else if (dtype == OFA_BF16) hipLaunchKernelGGL((relu_kernel<bf16_t>), dim3(grid_1d(n)), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)gate, (bf16_t*)y, n);
-  else hipLaunchKernelGGL((relu_kernel<f16_t>), dim3(grid_1d(n)), dim3(256), 0, st, (const f16_t*)x, (const f16_t*)gate, (f16_t*)y, n);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((relu_kernel<T>), dim3(grid_1d(n)), dim3(256), 0, st, (const T*)x, (const T*)gate, (T*)y, n);
+  });
   return check_launch("relu");
 }

@@ -595,15 +595,11 @@ extern "C" int ofa_gelu_fwd(const void* x, void* y, int64_t n, int dtype, void* 
   OFA_REQUIRE(n >= 0 && (n == 0 || (x && y)), OFA_ERR_INVALID, "gelu_fwd: bad argument");
   if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((gelu_kernel<float, false>), dim3(grid_for(n / 4)), dim3(256), 0, st, (const float*)nullptr,
-                       (const float*)x, (float*)y, n / 4, n);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((gelu_kernel<bf16_t, false>), dim3(grid_for(n / 8)), dim3(256), 0, st, (const bf16_t*)nullptr,
-                       (const bf16_t*)x, (bf16_t*)y, n / 8, n);
-  else
-    hipLaunchKernelGGL((gelu_kernel<f16_t, false>), dim3(grid_for(n / 8)), dim3(256), 0, st, (const f16_t*)nullptr,
-                       (const f16_t*)x, (f16_t*)y, n / 8, n);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((gelu_kernel<T, false>), dim3(grid_for(n / Vec<T>::N)), dim3(256), 0, st, (const T*)nullptr, (const T*)x,
+                       (T*)y, n / Vec<T>::N, n);
+  });
   return check_launch("gelu_fwd");
 }
 
@@ -612,15 +608,11 @@ extern "C" int ofa_gelu_bwd(const void* dy, const void* x, void* dx, int64_t n, 
   OFA_REQUIRE(n >= 0 && (n == 0 || (dy && x && dx)), OFA_ERR_INVALID, "gelu_bwd: bad argument");
   if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((gelu_kernel<float, true>), dim3(grid_for(n / 4)), dim3(256), 0, st, (const float*)dy,
-                       (const float*)x, (float*)dx, n / 4, n);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((gelu_kernel<bf16_t, true>), dim3(grid_for(n / 8)), dim3(256), 0, st, (const bf16_t*)dy,
-                       (const bf16_t*)x, (bf16_t*)dx, n / 8, n);
-  else
-    hipLaunchKernelGGL((gelu_kernel<f16_t, true>), dim3(grid_for(n / 8)), dim3(256), 0, st, (const f16_t*)dy,
-                       (const f16_t*)x, (f16_t*)dx, n / 8, n);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((gelu_kernel<T, true>), dim3(grid_for(n / Vec<T>::N)), dim3(256), 0, st, (const T*)dy, (const T*)x,
+                       (T*)dx, n / Vec<T>::N, n);
+  });
   return check_launch("gelu_bwd");
 }
 
@@ -631,17 +623,11 @@ extern "C" int ofa_dropout_add_fwd(const void* x, const void* residual, void* y,
   if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(grid_for((n + 7) / 8)), block(256);
-  if (dtype == OFA_F32) {
-    if (residual) hipLaunchKernelGGL((dropout_kernel<float, true>), grid, block, 0, st, (const float*)x, (const float*)residual, (float*)y, n, p, seed, offset, offset_base);
-    else hipLaunchKernelGGL((dropout_kernel<float, false>), grid, block, 0, st, (const float*)x, (const float*)nullptr, (float*)y, n, p, seed, offset, offset_base);
-  } else if (dtype == OFA_BF16) {
-    if (residual) hipLaunchKernelGGL((dropout_kernel<bf16_t, true>), grid, block, 0, st, (const bf16_t*)x, (const bf16_t*)residual, (bf16_t*)y, n, p, seed, offset, offset_base);
-    else hipLaunchKernelGGL((dropout_kernel<bf16_t, false>), grid, block, 0, st, (const bf16_t*)x, (const bf16_t*)nullptr, (bf16_t*)y, n, p, seed, offset, offset_base);
-  }
-  else {
-    if (residual) hipLaunchKernelGGL((dropout_kernel<f16_t, true>), grid, block, 0, st, (const f16_t*)x, (const f16_t*)residual, (f16_t*)y, n, p, seed, offset, offset_base);
-    else hipLaunchKernelGGL((dropout_kernel<f16_t, false>), grid, block, 0, st, (const f16_t*)x, (const f16_t*)nullptr, (f16_t*)y, n, p, seed, offset, offset_base);
-  }
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (residual) hipLaunchKernelGGL((dropout_kernel<T, true>), grid, block, 0, st, (const T*)x, (const T*)residual, (T*)y, n, p, seed, offset, offset_base);
+    else hipLaunchKernelGGL((dropout_kernel<T, false>), grid, block, 0, st, (const T*)x, (const T*)nullptr, (T*)y, n, p, seed, offset, offset_base);
+  });
   return check_launch("dropout_add_fwd");
 }
 
@@ -654,49 +640,37 @@ extern "C" int ofa_add_rowvec_mask(const void* a, const void* b, const void* vec
                                    int64_t rows, int cols, int64_t b_period, int dtype, void* stream) {
   OFA_DT_CHECK("add_rowvec_mask");
   OFA_REQUIRE(rows >= 0 && cols > 0 && a && y && b_period >= 0, OFA_ERR_INVALID, "add_rowvec_mask: bad argument");
-  OFA_REQUIRE(cols % (dtype == OFA_F32 ? 4 : 8) == 0, OFA_ERR_UNSUPPORTED, "add_rowvec_mask: cols=%d not vectorizable", cols);
+  OFA_REQUIRE(cols % dt_vecn(dtype) == 0, OFA_ERR_UNSUPPORTED, "add_rowvec_mask: cols=%d not vectorizable", cols);
   if (rows == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((add_rowvec_mask_kernel<float>), dim3(grid_for(rows * cols / 4)), dim3(256), 0, st, (const float*)a,
-                       (const float*)b, (const float*)vec, rowmask, (float*)y, rows, cols, b_period);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((add_rowvec_mask_kernel<bf16_t>), dim3(grid_for(rows * cols / 8)), dim3(256), 0, st,
-                       (const bf16_t*)a, (const bf16_t*)b, (const bf16_t*)vec, rowmask, (bf16_t*)y, rows, cols, b_period);
-  else
-    hipLaunchKernelGGL((add_rowvec_mask_kernel<f16_t>), dim3(grid_for(rows * cols / 8)), dim3(256), 0, st,
-                       (const f16_t*)a, (const f16_t*)b, (const f16_t*)vec, rowmask, (f16_t*)y, rows, cols, b_period);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((add_rowvec_mask_kernel<T>), dim3(grid_for(rows * cols / Vec<T>::N)), dim3(256), 0, st, (const T*)a,
+                       (const T*)b, (const T*)vec, rowmask, (T*)y, rows, cols, b_period);
+  });
   return check_launch("add_rowvec_mask");
 }
 
 extern "C" int ofa_embedding_fwd(const void* weight, const int64_t* ids, void* out, int64_t n, int D, int64_t V, uint8_t* is_pad,
                                  int64_t pad_id, int dtype, void* stream) {
   OFA_DT_CHECK("embedding_fwd");
-  OFA_REQUIRE(!is_pad || D % (dtype == OFA_F32 ? 4 : 8) == 0, OFA_ERR_UNSUPPORTED, "embedding_fwd: the pad mask rides with the vector kernel (D = %d)", D);
+  OFA_REQUIRE(!is_pad || D % dt_vecn(dtype) == 0, OFA_ERR_UNSUPPORTED, "embedding_fwd: the pad mask rides with the vector kernel (D = %d)", D);
   OFA_REQUIRE(n >= 0 && D > 0 && V > 0 && weight && ids && out, OFA_ERR_INVALID, "embedding_fwd: bad argument");
   if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (D % (dtype == OFA_F32 ? 4 : 8) != 0) {
-    if (dtype == OFA_F32)
-      hipLaunchKernelGGL((embedding_fwd_scalar_kernel<float>), dim3(grid_for(n * D)), dim3(256), 0, st, (const float*)weight,
-                         ids, (float*)out, n, D, V);
-    else if (dtype == OFA_BF16)
-      hipLaunchKernelGGL((embedding_fwd_scalar_kernel<bf16_t>), dim3(grid_for(n * D)), dim3(256), 0, st,
-                         (const bf16_t*)weight, ids, (bf16_t*)out, n, D, V);
-    else
-      hipLaunchKernelGGL((embedding_fwd_scalar_kernel<f16_t>), dim3(grid_for(n * D)), dim3(256), 0, st,
-                         (const f16_t*)weight, ids, (f16_t*)out, n, D, V);
+  if (D % dt_vecn(dtype) != 0) {
+    dispatch_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL((embedding_fwd_scalar_kernel<T>), dim3(grid_for(n * D)), dim3(256), 0, st, (const T*)weight, ids, (T*)out,
+                         n, D, V);
+    });
     return check_launch("embedding_fwd_scalar");
   }
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((embedding_fwd_kernel<float>), dim3(grid_for(n * D / 4)), dim3(256), 0, st, (const float*)weight, ids,
-                       (float*)out, n, D, V, is_pad, pad_id);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((embedding_fwd_kernel<bf16_t>), dim3(grid_for(n * D / 8)), dim3(256), 0, st, (const bf16_t*)weight,
-                       ids, (bf16_t*)out, n, D, V, is_pad, pad_id);
-  else
-    hipLaunchKernelGGL((embedding_fwd_kernel<f16_t>), dim3(grid_for(n * D / 8)), dim3(256), 0, st, (const f16_t*)weight,
-                       ids, (f16_t*)out, n, D, V, is_pad, pad_id);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((embedding_fwd_kernel<T>), dim3(grid_for(n * D / Vec<T>::N)), dim3(256), 0, st, (const T*)weight, ids,
+                       (T*)out, n, D, V, is_pad, pad_id);
+  });
   return check_launch("embedding_fwd");
 }
 
@@ -704,18 +678,14 @@ extern "C" int ofa_gather_rows(const void* src, const int64_t* index, void* out,
                                void* stream) {
   OFA_DT_CHECK("gather_rows");
   OFA_REQUIRE(n >= 0 && D > 0 && src_rows > 0 && src && index && out, OFA_ERR_INVALID, "gather_rows: bad argument");
-  OFA_REQUIRE(D % (dtype == OFA_F32 ? 4 : 8) == 0, OFA_ERR_INVALID, "gather_rows: D=%d must be a multiple of the 16-byte vector width", D);
+  OFA_REQUIRE(D % dt_vecn(dtype) == 0, OFA_ERR_INVALID, "gather_rows: D=%d must be a multiple of the 16-byte vector width", D);
   if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((gather_rows_kernel<float>), dim3(grid_for(n * D / 4)), dim3(256), 0, st, (const float*)src, index,
-                       (float*)out, n, D, src_rows);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((gather_rows_kernel<bf16_t>), dim3(grid_for(n * D / 8)), dim3(256), 0, st, (const bf16_t*)src, index,
-                       (bf16_t*)out, n, D, src_rows);
-  else
-    hipLaunchKernelGGL((gather_rows_kernel<f16_t>), dim3(grid_for(n * D / 8)), dim3(256), 0, st, (const f16_t*)src, index,
-                       (f16_t*)out, n, D, src_rows);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((gather_rows_kernel<T>), dim3(grid_for(n * D / Vec<T>::N)), dim3(256), 0, st, (const T*)src, index, (T*)out,
+                       n, D, src_rows);
+  });
   return check_launch("gather_rows");
 }
 
@@ -723,7 +693,7 @@ extern "C" int ofa_gather_rows_parts(const void* const* srcs, const int* lens, i
                                      int64_t batch, int dtype, void* stream) {
   OFA_DT_CHECK("gather_rows_parts");
   OFA_REQUIRE(srcs && lens && index && out && nparts >= 1 && nparts <= 8 && n >= 0 && D > 0 && batch > 0, OFA_ERR_INVALID, "gather_rows_parts: bad argument");
-  OFA_REQUIRE(D % (dtype == OFA_F32 ? 4 : 8) == 0, OFA_ERR_UNSUPPORTED, "gather_rows_parts: D=%d not vectorizable", D);
+  OFA_REQUIRE(D % dt_vecn(dtype) == 0, OFA_ERR_UNSUPPORTED, "gather_rows_parts: D=%d not vectorizable", D);
   if (n == 0) return 0;
   GatherParts gp;
   gp.n = nparts;
@@ -739,12 +709,10 @@ extern "C" int ofa_gather_rows_parts(const void* const* srcs, const int* lens, i
   }
   const int Ttot = gp.start[nparts];
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((gather_rows_parts_kernel<float>), dim3(grid_for(n * D / 4)), dim3(256), 0, st, gp, index, (float*)out, n, D, Ttot, batch);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((gather_rows_parts_kernel<bf16_t>), dim3(grid_for(n * D / 8)), dim3(256), 0, st, gp, index, (bf16_t*)out, n, D, Ttot, batch);
-  else
-    hipLaunchKernelGGL((gather_rows_parts_kernel<f16_t>), dim3(grid_for(n * D / 8)), dim3(256), 0, st, gp, index, (f16_t*)out, n, D, Ttot, batch);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((gather_rows_parts_kernel<T>), dim3(grid_for(n * D / Vec<T>::N)), dim3(256), 0, st, gp, index, (T*)out, n, D, Ttot, batch);
+  });
   return check_launch("gather_rows_parts");
 }
 
@@ -753,15 +721,13 @@ extern "C" int ofa_scatter_rows_part(const void* src, const int64_t* inverse, vo
   OFA_DT_CHECK("scatter_rows_part");
   OFA_REQUIRE(src && inverse && out && batch > 0 && nk > 0 && start >= 0 && start + nk <= Ttot && D > 0 && src_rows > 0, OFA_ERR_INVALID,
               "scatter_rows_part: bad argument");
-  OFA_REQUIRE(D % (dtype == OFA_F32 ? 4 : 8) == 0, OFA_ERR_UNSUPPORTED, "scatter_rows_part: D=%d not vectorizable", D);
+  OFA_REQUIRE(D % dt_vecn(dtype) == 0, OFA_ERR_UNSUPPORTED, "scatter_rows_part: D=%d not vectorizable", D);
   hipStream_t st = (hipStream_t)stream;
-  const int64_t work = batch * nk * D / (dtype == OFA_F32 ? 4 : 8);
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((scatter_rows_part_kernel<float>), dim3(grid_for(work)), dim3(256), 0, st, (const float*)src, inverse, (float*)out, batch, nk, Ttot, start, D, src_rows);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((scatter_rows_part_kernel<bf16_t>), dim3(grid_for(work)), dim3(256), 0, st, (const bf16_t*)src, inverse, (bf16_t*)out, batch, nk, Ttot, start, D, src_rows);
-  else
-    hipLaunchKernelGGL((scatter_rows_part_kernel<f16_t>), dim3(grid_for(work)), dim3(256), 0, st, (const f16_t*)src, inverse, (f16_t*)out, batch, nk, Ttot, start, D, src_rows);
+  const int64_t work = batch * nk * D / dt_vecn(dtype);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((scatter_rows_part_kernel<T>), dim3(grid_for(work)), dim3(256), 0, st, (const T*)src, inverse, (T*)out, batch, nk, Ttot, start, D, src_rows);
+  });
   return check_launch("scatter_rows_part");
 }
 
@@ -831,9 +797,9 @@ extern "C" int ofa_segment_rowsum(const void* dout, const int32_t* order, const 
               "segment_rowsum: bad argument (D = %d, at most 64 columns)", D);
   if (nseg == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32) launch_segment_rowsum<float>(dout, order, seg_off, seg_row, dweight, nseg, D, accumulate, st);
-  else if (dtype == OFA_BF16) launch_segment_rowsum<bf16_t>(dout, order, seg_off, seg_row, dweight, nseg, D, accumulate, st);
-  else launch_segment_rowsum<f16_t>(dout, order, seg_off, seg_row, dweight, nseg, D, accumulate, st);
+  dispatch_dtype(dtype, [&](auto tag) {
+    launch_segment_rowsum<typename decltype(tag)::type>(dout, order, seg_off, seg_row, dweight, nseg, D, accumulate, st);
+  });
   return check_launch("segment_rowsum");
 }
 
@@ -841,7 +807,7 @@ extern "C" int ofa_embedding_bwd(const void* dout, const int64_t* ids, void* dwe
                                  int64_t padding_idx, uint8_t* present_ws, float* slice_ws, int dtype, void* stream) {
   OFA_DT_CHECK("embedding_bwd");
   OFA_REQUIRE(n >= 0 && D > 0 && V > 0 && dout && ids && dweight, OFA_ERR_INVALID, "embedding_bwd: bad argument");
-  const int vecn = dtype == OFA_F32 ? 4 : 8;
+  const int vecn = dt_vecn(dtype);
   OFA_REQUIRE(D <= 2048, OFA_ERR_UNSUPPORTED, "embedding_bwd: D=%d exceeds 2048", D);
   const bool vec_ok = D % vecn == 0 && D <= 64 * vecn * 4 && (((uintptr_t)dout | (uintptr_t)dweight) & 15) == 0;
   if (n == 0) return 0;
@@ -856,38 +822,27 @@ extern "C" int ofa_embedding_bwd(const void* dout, const int64_t* ids, void* dwe
 #define EMB_LAUNCH(T, NV)                                                                                               \
   hipLaunchKernelGGL((embedding_bwd_kernel<T, NV>), grid, block, 0, st, (const T*)dout, ids, (T*)dweight, slice_ws, n, D, V, \
                      padding_idx, (const uint8_t*)present_ws, S)
-#define EMB_CASE(T)                  \
-  do {                               \
-    if (nv <= 1) EMB_LAUNCH(T, 1);   \
-    else if (nv <= 2) EMB_LAUNCH(T, 2); \
-    else EMB_LAUNCH(T, 4);           \
-  } while (0)
-  if (!vec_ok) {
-    if (dtype == OFA_F32)
-      hipLaunchKernelGGL((embedding_bwd_scalar_kernel<float>), grid, block, 0, st, (const float*)dout, ids, (float*)dweight,
-                         slice_ws, n, D, V, padding_idx, (const uint8_t*)present_ws, S);
-    else if (dtype == OFA_BF16)
-      hipLaunchKernelGGL((embedding_bwd_scalar_kernel<bf16_t>), grid, block, 0, st, (const bf16_t*)dout, ids,
-                         (bf16_t*)dweight, slice_ws, n, D, V, padding_idx, (const uint8_t*)present_ws, S);
-    else
-      hipLaunchKernelGGL((embedding_bwd_scalar_kernel<f16_t>), grid, block, 0, st, (const f16_t*)dout, ids,
-                         (f16_t*)dweight, slice_ws, n, D, V, padding_idx, (const uint8_t*)present_ws, S);
-  } else if (dtype == OFA_F32) EMB_CASE(float);
-  else if (dtype == OFA_BF16) EMB_CASE(bf16_t);
-         else EMB_CASE(f16_t);
-#undef EMB_CASE
+  if (!vec_ok)
+    dispatch_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL((embedding_bwd_scalar_kernel<T>), grid, block, 0, st, (const T*)dout, ids, (T*)dweight, slice_ws, n, D, V,
+                         padding_idx, (const uint8_t*)present_ws, S);
+    });
+  else
+    dispatch_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      if (nv <= 1) EMB_LAUNCH(T, 1);
+      else if (nv <= 2) EMB_LAUNCH(T, 2);
+      else EMB_LAUNCH(T, 4);
+    });
 #undef EMB_LAUNCH
   int rc = check_launch("embedding_bwd");
   if (rc || S == 1) return rc;
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((embedding_fold_kernel<float>), dim3((unsigned)V), dim3(256), 0, st, slice_ws, (float*)dweight, D, V,
-                       padding_idx, (const uint8_t*)present_ws, S);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((embedding_fold_kernel<bf16_t>), dim3((unsigned)V), dim3(256), 0, st, slice_ws, (bf16_t*)dweight, D, V,
-                       padding_idx, (const uint8_t*)present_ws, S);
-  else
-    hipLaunchKernelGGL((embedding_fold_kernel<f16_t>), dim3((unsigned)V), dim3(256), 0, st, slice_ws, (f16_t*)dweight, D, V,
-                       padding_idx, (const uint8_t*)present_ws, S);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((embedding_fold_kernel<T>), dim3((unsigned)V), dim3(256), 0, st, slice_ws, (T*)dweight, D, V, padding_idx,
+                       (const uint8_t*)present_ws, S);
+  });
   return check_launch("embedding_fold");
 }
 
@@ -901,7 +856,7 @@ extern "C" int ofa_step_edges_old(int item) {
 }
 
 extern "C" int ofa_embedding_bwd_ids_ok(int64_t n, int D, int64_t V, int dtype) {
-  const int vecn = dtype == OFA_F32 ? 4 : 8;
+  const int vecn = dt_vecn(dtype);
   return OFA_DT_OK(dtype) && n >= 0 && n <= OFA_EMBEDDING_IDS_MAX && V > 0 && V < ((int64_t)1 << 31) && D > 0 && D % vecn == 0 &&
          D <= 64 * vecn * 4;
 }
@@ -916,7 +871,7 @@ extern "C" int ofa_embedding_bwd_ids(const void* dout, const int64_t* ids, void*
   OFA_REQUIRE((((uintptr_t)dout | (uintptr_t)dweight) & 15) == 0, OFA_ERR_UNSUPPORTED, "embedding_bwd_ids: buffers not 16-byte aligned");
   if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  const int vecn = dtype == OFA_F32 ? 4 : 8;
+  const int vecn = dt_vecn(dtype);
   const int nv = cdiv(D, 64 * vecn);
   const int per = (int)(((n + slices - 1) / slices + 63) / 64 * 64);         // embedding_bwd_kernel's slice length
   const int blocks = cdiv(n, EMB_IDS_WAVES) < 1024 ? cdiv(n, EMB_IDS_WAVES) : 1024;      // a position per wave and sweep
@@ -924,22 +879,20 @@ extern "C" int ofa_embedding_bwd_ids(const void* dout, const int64_t* ids, void*
 #define EMB_LAUNCH(T, NV, SL)                                                                                       \
   hipLaunchKernelGGL((embedding_bwd_ids_kernel<T, NV, SL>), dim3(blocks), dim3(EMB_IDS_WAVES * 64), lds, st, (const T*)dout, ids, \
                      (T*)dweight, (int)n, D, V, padding_idx, per)
-#define EMB_CASE(T, SL)                     \
-  do {                                      \
-    if (nv <= 1) EMB_LAUNCH(T, 1, SL);      \
-    else if (nv <= 2) EMB_LAUNCH(T, 2, SL); \
-    else EMB_LAUNCH(T, 4, SL);              \
-  } while (0)
-#define EMB_DT(SL)                            \
-  do {                                        \
-    if (dtype == OFA_F32) EMB_CASE(float, SL); \
-    else if (dtype == OFA_BF16) EMB_CASE(bf16_t, SL); \
-    else EMB_CASE(f16_t, SL);                 \
-  } while (0)
-  if (slices > 1) EMB_DT(true);
-  else EMB_DT(false);
-#undef EMB_DT
-#undef EMB_CASE
+  if (slices > 1)
+    dispatch_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      if (nv <= 1) EMB_LAUNCH(T, 1, true);
+      else if (nv <= 2) EMB_LAUNCH(T, 2, true);
+      else EMB_LAUNCH(T, 4, true);
+    });
+  else
+    dispatch_dtype(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      if (nv <= 1) EMB_LAUNCH(T, 1, false);
+      else if (nv <= 2) EMB_LAUNCH(T, 2, false);
+      else EMB_LAUNCH(T, 4, false);
+    });
 #undef EMB_LAUNCH
   return check_launch("embedding_bwd_ids");
 }
@@ -949,20 +902,16 @@ extern "C" int ofa_embedding_range_bwd(const void* dout, void* dweight, int batc
   OFA_DT_CHECK("embedding_range_bwd");
   OFA_REQUIRE(dout && dweight && batch >= 1 && T >= 0 && D > 0 && V > 0 && r0 >= 0 && r0 + T <= V, OFA_ERR_INVALID,
               "embedding_range_bwd: bad argument (rows %lld .. %lld of %lld)", (long long)r0, (long long)(r0 + T), (long long)V);
-  OFA_REQUIRE(D % (dtype == OFA_F32 ? 4 : 8) == 0 && (((uintptr_t)dout | (uintptr_t)dweight) & 15) == 0, OFA_ERR_UNSUPPORTED,
+  OFA_REQUIRE(D % dt_vecn(dtype) == 0 && (((uintptr_t)dout | (uintptr_t)dweight) & 15) == 0, OFA_ERR_UNSUPPORTED,
               "embedding_range_bwd: D=%d / buffers not whole 16-byte vectors: use ofa_embedding_bwd", D);
   if (T == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = T * D;
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((embedding_range_bwd_kernel<float>), dim3(grid_for(n / 4)), dim3(256), 0, st, (const float*)dout,
-                       (float*)dweight + r0 * D, batch, n);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((embedding_range_bwd_kernel<bf16_t>), dim3(grid_for(n / 8)), dim3(256), 0, st, (const bf16_t*)dout,
-                       (bf16_t*)dweight + r0 * D, batch, n);
-  else
-    hipLaunchKernelGGL((embedding_range_bwd_kernel<f16_t>), dim3(grid_for(n / 8)), dim3(256), 0, st, (const f16_t*)dout,
-                       (f16_t*)dweight + r0 * D, batch, n);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using TT = typename decltype(tag)::type;             // (T is the row count here)
+    hipLaunchKernelGGL((embedding_range_bwd_kernel<TT>), dim3(grid_for(n / Vec<TT>::N)), dim3(256), 0, st, (const TT*)dout,
+                       (TT*)dweight + r0 * D, batch, n);
+  });
   return check_launch("embedding_range_bwd");
 }
 
@@ -977,23 +926,18 @@ extern "C" int ofa_im2col_patch(const void* img, void* col, int B, int C, int H,
   // 16-bit images with even p: whole runs as dwords (im2col_patch_runs_kernel); odd p, fp32, unaligned buffers: element by element
   if (dtype != OFA_F32 && p % 2 == 0 && Kpad % 8 == 0 && ((uintptr_t)img & 3) == 0 && ((uintptr_t)col & 15) == 0 &&
       total / 8 < ((int64_t)1 << 31) && !ofa_step_edges_old(OFA_EDGE_IM2COL)) {
-    if (dtype == OFA_BF16)
-      hipLaunchKernelGGL((im2col_patch_runs_kernel<bf16_t>), dim3(grid_for(total / 8)), dim3(256), 0, st, (const bf16_t*)img,
-                         (bf16_t*)col, B, C, H, W, p, Kpad, lead);
-    else
-      hipLaunchKernelGGL((im2col_patch_runs_kernel<f16_t>), dim3(grid_for(total / 8)), dim3(256), 0, st, (const f16_t*)img,
-                         (f16_t*)col, B, C, H, W, p, Kpad, lead);
+    dispatch_dtype16(dtype, [&](auto tag) {
+      using T = typename decltype(tag)::type;
+      hipLaunchKernelGGL((im2col_patch_runs_kernel<T>), dim3(grid_for(total / 8)), dim3(256), 0, st, (const T*)img, (T*)col, B, C,
+                         H, W, p, Kpad, lead);
+    });
     return check_launch("im2col_patch_runs");
   }
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((im2col_patch_kernel<float>), dim3(grid_for(total)), dim3(256), 0, st, (const float*)img, (float*)col,
-                       B, C, H, W, p, Kpad, lead);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((im2col_patch_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, st, (const bf16_t*)img,
-                       (bf16_t*)col, B, C, H, W, p, Kpad, lead);
-  else
-    hipLaunchKernelGGL((im2col_patch_kernel<f16_t>), dim3(grid_for(total)), dim3(256), 0, st, (const f16_t*)img,
-                       (f16_t*)col, B, C, H, W, p, Kpad, lead);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((im2col_patch_kernel<T>), dim3(grid_for(total)), dim3(256), 0, st, (const T*)img, (T*)col, B, C, H, W, p,
+                       Kpad, lead);
+  });
   return check_launch("im2col_patch");
 }
 
@@ -1010,28 +954,22 @@ extern "C" int ofa_colsum(const void* x, void* out, float* ws, int64_t rows, int
   OFA_REQUIRE(OFA_DT_OK(out_dtype), OFA_ERR_INVALID, "colsum: bad out dtype %d", out_dtype);
   OFA_REQUIRE(rows >= 0 && cols > 0 && ld >= cols && x && (out || accumulate == OFA_DEFER_FOLD) && ws, OFA_ERR_INVALID,
               "colsum: bad argument");
-  const int n = dtype == OFA_F32 ? 4 : 8;
+  const int n = dt_vecn(dtype);
   OFA_REQUIRE(cols % n == 0 && ld % n == 0, OFA_ERR_UNSUPPORTED, "colsum: cols=%d / ld not vectorizable", cols);
   hipStream_t st = (hipStream_t)stream;
   const int groups = ofa_colsum_slots(rows);
   dim3 grid(cdiv(cols / n, 32), groups), block(256);
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((colsum_partial_kernel<float>), grid, block, 0, st, (const float*)x, ws, rows, cols, ld);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((colsum_partial_kernel<bf16_t>), grid, block, 0, st, (const bf16_t*)x, ws, rows, cols, ld);
-  else
-    hipLaunchKernelGGL((colsum_partial_kernel<f16_t>), grid, block, 0, st, (const f16_t*)x, ws, rows, cols, ld);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((colsum_partial_kernel<T>), grid, block, 0, st, (const T*)x, ws, rows, cols, ld);
+  });
   int rc = check_launch("colsum_partial");
   if (rc || accumulate == OFA_DEFER_FOLD) return rc;          // deferred: the caller folds ws (ofa_fold_batched)
-  if (out_dtype == OFA_F32)
-    hipLaunchKernelGGL((colsum_final_kernel<float>), dim3(cdiv(cols, 64)), dim3(1024), 0, st, (const float*)ws, (float*)out,
-                       cols, groups, alpha, accumulate);
-  else if (out_dtype == OFA_BF16)
-    hipLaunchKernelGGL((colsum_final_kernel<bf16_t>), dim3(cdiv(cols, 64)), dim3(1024), 0, st, (const float*)ws,
-                       (bf16_t*)out, cols, groups, alpha, accumulate);
-  else
-    hipLaunchKernelGGL((colsum_final_kernel<f16_t>), dim3(cdiv(cols, 64)), dim3(1024), 0, st, (const float*)ws,
-                       (f16_t*)out, cols, groups, alpha, accumulate);
+  dispatch_dtype(out_dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((colsum_final_kernel<T>), dim3(cdiv(cols, 64)), dim3(1024), 0, st, (const float*)ws, (T*)out, cols, groups,
+                       alpha, accumulate);
+  });
   return check_launch("colsum_final");
 }
 
@@ -1134,10 +1072,11 @@ extern "C" int ofa_add_n(const void* const* inputs, int n, void* out, int64_t nu
   OFA_REQUIRE(!((uintptr_t)out & 15), OFA_ERR_INVALID, "add_n: out is not 16-byte aligned");
   a.n = n;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t work = numel / (dtype == OFA_F32 ? 4 : 8) + 1;
-  if (dtype == OFA_F32) hipLaunchKernelGGL((add_n_kernel<float>), dim3(grid_for(work)), dim3(256), 0, st, a, (float*)out, numel);
-  else if (dtype == OFA_BF16) hipLaunchKernelGGL((add_n_kernel<bf16_t>), dim3(grid_for(work)), dim3(256), 0, st, a, (bf16_t*)out, numel);
-  else hipLaunchKernelGGL((add_n_kernel<f16_t>), dim3(grid_for(work)), dim3(256), 0, st, a, (f16_t*)out, numel);
+  const int64_t work = numel / dt_vecn(dtype) + 1;
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((add_n_kernel<T>), dim3(grid_for(work)), dim3(256), 0, st, a, (T*)out, numel);
+  });
   return check_launch("add_n");
 }
 
@@ -1163,27 +1102,26 @@ __global__ __launch_bounds__(256) void batch_sum_kernel(const T* __restrict__ x,
 extern "C" int ofa_batch_sum(const void* x, void* out, int batch, int64_t n, int accumulate, int dtype, void* stream) {
   OFA_DT_CHECK("batch_sum");
   OFA_REQUIRE(x && out && batch >= 1 && n >= 0, OFA_ERR_INVALID, "batch_sum: bad argument");
-  OFA_REQUIRE(n % (dtype == OFA_F32 ? 4 : 8) == 0, OFA_ERR_UNSUPPORTED, "batch_sum: n=%lld not vectorizable", (long long)n);
+  OFA_REQUIRE(n % dt_vecn(dtype) == 0, OFA_ERR_UNSUPPORTED, "batch_sum: n=%lld not vectorizable", (long long)n);
   if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32) hipLaunchKernelGGL((batch_sum_kernel<float>), dim3(grid_for(n / 4)), dim3(256), 0, st, (const float*)x, (float*)out, batch, n, accumulate);
-  else if (dtype == OFA_BF16) hipLaunchKernelGGL((batch_sum_kernel<bf16_t>), dim3(grid_for(n / 8)), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)out, batch, n, accumulate);
-  else hipLaunchKernelGGL((batch_sum_kernel<f16_t>), dim3(grid_for(n / 8)), dim3(256), 0, st, (const f16_t*)x, (f16_t*)out, batch, n, accumulate);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((batch_sum_kernel<T>), dim3(grid_for(n / Vec<T>::N)), dim3(256), 0, st, (const T*)x, (T*)out, batch, n, accumulate);
+  });
   return check_launch("batch_sum");
 }
 
 extern "C" int ofa_mul(const void* a, const void* b, void* y, int64_t rows, int cols, int b_rowvec, int dtype, void* stream) {
   OFA_DT_CHECK("mul");
   OFA_REQUIRE(rows >= 0 && cols > 0 && a && b && y, OFA_ERR_INVALID, "mul: bad argument");
-  OFA_REQUIRE(cols % (dtype == OFA_F32 ? 4 : 8) == 0, OFA_ERR_UNSUPPORTED, "mul: cols=%d not vectorizable", cols);
+  OFA_REQUIRE(cols % dt_vecn(dtype) == 0, OFA_ERR_UNSUPPORTED, "mul: cols=%d not vectorizable", cols);
   if (rows == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((mul_kernel<float>), dim3(grid_for(rows * cols / 4)), dim3(256), 0, st, (const float*)a, (const float*)b, (float*)y, rows, cols, b_rowvec);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((mul_kernel<bf16_t>), dim3(grid_for(rows * cols / 8)), dim3(256), 0, st, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)y, rows, cols, b_rowvec);
-  else
-    hipLaunchKernelGGL((mul_kernel<f16_t>), dim3(grid_for(rows * cols / 8)), dim3(256), 0, st, (const f16_t*)a, (const f16_t*)b, (f16_t*)y, rows, cols, b_rowvec);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((mul_kernel<T>), dim3(grid_for(rows * cols / Vec<T>::N)), dim3(256), 0, st, (const T*)a, (const T*)b, (T*)y, rows, cols, b_rowvec);
+  });
   return check_launch("mul");
 }
 
@@ -1191,15 +1129,13 @@ extern "C" int ofa_scale_row_groups(const void* x, const float* scale, void* y, 
                                     void* stream) {
   OFA_DT_CHECK("scale_row_groups");
   OFA_REQUIRE(rows >= 0 && cols > 0 && group > 0 && x && scale && y, OFA_ERR_INVALID, "scale_row_groups: bad argument");
-  OFA_REQUIRE(cols % (dtype == OFA_F32 ? 4 : 8) == 0, OFA_ERR_UNSUPPORTED, "scale_row_groups: cols=%d not vectorizable", cols);
+  OFA_REQUIRE(cols % dt_vecn(dtype) == 0, OFA_ERR_UNSUPPORTED, "scale_row_groups: cols=%d not vectorizable", cols);
   if (rows == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((scale_row_groups_kernel<float>), dim3(grid_for(rows * cols / 4)), dim3(256), 0, st, (const float*)x, scale, (float*)y, rows, cols, group);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((scale_row_groups_kernel<bf16_t>), dim3(grid_for(rows * cols / 8)), dim3(256), 0, st, (const bf16_t*)x, scale, (bf16_t*)y, rows, cols, group);
-  else
-    hipLaunchKernelGGL((scale_row_groups_kernel<f16_t>), dim3(grid_for(rows * cols / 8)), dim3(256), 0, st, (const f16_t*)x, scale, (f16_t*)y, rows, cols, group);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((scale_row_groups_kernel<T>), dim3(grid_for(rows * cols / Vec<T>::N)), dim3(256), 0, st, (const T*)x, scale, (T*)y, rows, cols, group);
+  });
   return check_launch("scale_row_groups");
 }
 

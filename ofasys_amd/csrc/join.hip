@@ -749,7 +749,7 @@ static int join_wpr(int cols, int n) {
 }
 static int join_check(int64_t rows, int cols, int dtype, const char* what) {
   OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "%s: bad dtype %d", what, dtype);
-  const int n = dtype == OFA_F32 ? 4 : 8;
+  const int n = dt_vecn(dtype);
   OFA_REQUIRE(rows >= 0 && cols > 0 && cols % n == 0 && cols <= 64 * n * 8, OFA_ERR_UNSUPPORTED,
               "%s: cols=%d must be a multiple of %d and <= %d", what, cols, n, 64 * n * 8);
   const int wpr = join_wpr(cols, n);
@@ -797,37 +797,28 @@ extern "C" int ofa_join_fwd(const void* x, const void* residual, const void* gam
   dim3 grid(cdiv(rows, 4)), block(256);
   if (const int k = join_row_k(cols, dtype, false)) {
     uint8_t* kb = ofa_join_keep_bytes(rows, cols, dtype) ? keep_bits : nullptr;
-#define JOIN_FWD_ROW(NF, TAIL)                                                                                                      \
-  do {                                                                                                                              \
-    if (dtype == OFA_BF16)                                                                                                          \
-      hipLaunchKernelGGL((join_fwd_row_kernel<bf16_t, RowMap<NF, TAIL>>), grid, block, 0, st, (const bf16_t*)x, (const bf16_t*)residual, \
-                         (const bf16_t*)gamma_a, (const bf16_t*)beta_a, (const bf16_t*)gamma_b, (const bf16_t*)beta_b, (bf16_t*)y,   \
-                         (bf16_t*)z, stats, kb, rows, eps, rg);                                                                     \
-    else                                                                                                                            \
-      hipLaunchKernelGGL((join_fwd_row_kernel<f16_t, RowMap<NF, TAIL>>), grid, block, 0, st, (const f16_t*)x, (const f16_t*)residual,  \
-                         (const f16_t*)gamma_a, (const f16_t*)beta_a, (const f16_t*)gamma_b, (const f16_t*)beta_b, (f16_t*)y,        \
-                         (f16_t*)z, stats, kb, rows, eps, rg);                                                                      \
-  } while (0)
+#define JOIN_FWD_ROW(NF, TAIL)                                                                                                 \
+  dispatch_dtype16(dtype, [&](auto tag) {                                                                                      \
+    using T = typename decltype(tag)::type;                                                                                    \
+    hipLaunchKernelGGL((join_fwd_row_kernel<T, RowMap<NF, TAIL>>), grid, block, 0, st, (const T*)x, (const T*)residual,        \
+                       (const T*)gamma_a, (const T*)beta_a, (const T*)gamma_b, (const T*)beta_b, (T*)y, (T*)z, stats, kb, rows, \
+                       eps, rg);                                                                                               \
+  })
     JOIN_ROW_DISPATCH(k, JOIN_FWD_ROW);
 #undef JOIN_FWD_ROW
     return check_launch("join_fwd");
   }
-  const int n = dtype == OFA_F32 ? 4 : 8;
-  const int nv = cdiv(cols, 64 * n);
+  const int nv = cdiv(cols, 64 * dt_vecn(dtype));
 #define JOIN_FWD(T, NV)                                                                                                  \
   hipLaunchKernelGGL((join_fwd_kernel<T, NV>), grid, block, 0, st, (const T*)x, (const T*)residual, (const T*)gamma_a,   \
                      (const T*)beta_a, (const T*)gamma_b, (const T*)beta_b, (T*)y, (T*)z, stats, rows, cols, eps, rg)
-#define JOIN_FWD_T(T)                 \
-  do {                                \
-    if (nv <= 1) JOIN_FWD(T, 1);      \
-    else if (nv <= 2) JOIN_FWD(T, 2); \
-    else if (nv <= 4) JOIN_FWD(T, 4); \
-    else JOIN_FWD(T, 8);              \
-  } while (0)
-  if (dtype == OFA_F32) JOIN_FWD_T(float);
-  else if (dtype == OFA_BF16) JOIN_FWD_T(bf16_t);
-  else JOIN_FWD_T(f16_t);
-#undef JOIN_FWD_T
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (nv <= 1) JOIN_FWD(T, 1);
+    else if (nv <= 2) JOIN_FWD(T, 2);
+    else if (nv <= 4) JOIN_FWD(T, 4);
+    else JOIN_FWD(T, 8);
+  });
 #undef JOIN_FWD
   return check_launch("join_fwd");
 }
@@ -837,7 +828,7 @@ extern "C" int ofa_join_bwd_slots(int64_t rows, int cols, int dtype) {
   if (join_row_k(cols, dtype, true)) {
     rpb = 8;
   } else {
-    const int wpr = join_wpr(cols, dtype == OFA_F32 ? 4 : 8);
+    const int wpr = join_wpr(cols, dt_vecn(dtype));
     rpb = join_wpb(wpr) / wpr;
   }
   int64_t nblk = (rows + rpb - 1) / rpb;
@@ -868,31 +859,25 @@ extern "C" int ofa_join_bwd(const void* dy, const void* dz, const void* x, const
   const JoinRng rg{p, seed, offset, offset_base};
   if (const int k = (p > 0.f && !keep_bits) ? 0 : join_row_k(cols, dtype, true)) {
     const int nblk = ofa_join_bwd_slots(rows, cols, dtype);
-    if (dtype == OFA_BF16)
-      join_bwd_row_cols<bf16_t>(k, gamma_a, gamma_b, p > 0.f, join_bwd_variant(), nblk, st, dy, gamma_b ? dz : nullptr, x, y, gamma_a,
-                                gamma_b, stats, keep_bits, dres, dx, ws, rows, rg, want_dx_colsum);
-    else
-      join_bwd_row_cols<f16_t>(k, gamma_a, gamma_b, p > 0.f, join_bwd_variant(), nblk, st, dy, gamma_b ? dz : nullptr, x, y, gamma_a,
-                               gamma_b, stats, keep_bits, dres, dx, ws, rows, rg, want_dx_colsum);
+    dispatch_dtype16(dtype, [&](auto tag) {
+      join_bwd_row_cols<typename decltype(tag)::type>(k, gamma_a, gamma_b, p > 0.f, join_bwd_variant(), nblk, st, dy, gamma_b ? dz : nullptr,
+                                                      x, y, gamma_a, gamma_b, stats, keep_bits, dres, dx, ws, rows, rg, want_dx_colsum);
+    });
     return check_launch("join_bwd");
   }
-  const int wpr = join_wpr(cols, dtype == OFA_F32 ? 4 : 8);
+  const int wpr = join_wpr(cols, dt_vecn(dtype));
   dim3 grid(ofa_join_bwd_slots(rows, cols, dtype)), block(64 * join_wpb(wpr));
 #define JOIN_BWD(T, WPR)                                                                                              \
   hipLaunchKernelGGL((join_bwd_kernel<T, WPR>), grid, block, 0, st, (const T*)dy, (const T*)(gamma_b ? dz : nullptr),  \
                      (const T*)x, (const T*)y, (const T*)gamma_a, (const T*)gamma_b, stats, (T*)dres, (T*)dx, ws, rows, cols, rg, \
                      want_dx_colsum)
-#define JOIN_BWD_T(T)                  \
-  do {                                 \
-    if (wpr == 1) JOIN_BWD(T, 1);      \
-    else if (wpr == 2) JOIN_BWD(T, 2); \
-    else if (wpr == 4) JOIN_BWD(T, 4); \
-    else JOIN_BWD(T, 8);               \
-  } while (0)
-  if (dtype == OFA_F32) JOIN_BWD_T(float);
-  else if (dtype == OFA_BF16) JOIN_BWD_T(bf16_t);
-  else JOIN_BWD_T(f16_t);
-#undef JOIN_BWD_T
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (wpr == 1) JOIN_BWD(T, 1);
+    else if (wpr == 2) JOIN_BWD(T, 2);
+    else if (wpr == 4) JOIN_BWD(T, 4);
+    else JOIN_BWD(T, 8);
+  });
 #undef JOIN_BWD
   return check_launch("join_bwd");
 }

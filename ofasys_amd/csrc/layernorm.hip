@@ -400,7 +400,7 @@ static int ln_bwd_dispatch(const void* dy, const void* x, const void* g, const f
 static int ln_check(int64_t rows, int cols, int dtype, bool bwd) {
   OFA_REQUIRE(rows >= 0 && cols > 0, OFA_ERR_INVALID, "layernorm: bad shape rows=%lld cols=%d", (long long)rows, cols);
   OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "layernorm: bad dtype %d", dtype);
-  const int n = dtype == OFA_F32 ? 4 : 8;
+  const int n = dt_vecn(dtype);
   OFA_REQUIRE(cols % n == 0, OFA_ERR_UNSUPPORTED, "layernorm: cols=%d must be a multiple of %d", cols, n);
   if (bwd) {                                      // the same row split the dispatcher makes; <= 8 vectors per lane
     int wpr = 1;
@@ -419,7 +419,7 @@ using namespace ofa;
 extern "C" int ofa_layernorm_bwd_ws_rows(void) { return 3 * LN_BWD_BLOCKS; }
 
 extern "C" int ofa_layernorm_bwd_slots(int64_t rows, int cols, int dtype, int gelu) {
-  const int wpr = ln_bwd_wpr(cols, dtype == OFA_F32 ? 4 : 8, gelu != 0);
+  const int wpr = ln_bwd_wpr(cols, dt_vecn(dtype), gelu != 0);
   const int rpb = (wpr == 6 ? 12 : LN_WPB) / wpr;
   int64_t nblk = (rows + rpb - 1) / rpb;
   return (int)(nblk < 1 ? 1 : (nblk > LN_BWD_BLOCKS ? LN_BWD_BLOCKS : nblk));
@@ -431,9 +431,9 @@ extern "C" int ofa_layernorm_fwd(const void* x, const void* gamma, const void* b
   OFA_REQUIRE(x && gamma && beta && y, OFA_ERR_INVALID, "layernorm_fwd: null pointer");
   if (rows == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  return dtype == OFA_F32    ? ln_fwd_dispatch<float, false>(x, gamma, beta, y, mean, rstd, rows, cols, eps, st)
-         : dtype == OFA_BF16 ? ln_fwd_dispatch<bf16_t, false>(x, gamma, beta, y, mean, rstd, rows, cols, eps, st)
-                             : ln_fwd_dispatch<f16_t, false>(x, gamma, beta, y, mean, rstd, rows, cols, eps, st);
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return ln_fwd_dispatch<typename decltype(tag)::type, false>(x, gamma, beta, y, mean, rstd, rows, cols, eps, st);
+  });
 }
 
 extern "C" int ofa_gelu_layernorm_fwd(const void* h, const void* gamma, const void* beta, void* y, float* mean,
@@ -442,9 +442,9 @@ extern "C" int ofa_gelu_layernorm_fwd(const void* h, const void* gamma, const vo
   OFA_REQUIRE(h && gamma && beta && y, OFA_ERR_INVALID, "gelu_layernorm_fwd: null pointer");
   if (rows == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  return dtype == OFA_F32    ? ln_fwd_dispatch<float, true>(h, gamma, beta, y, mean, rstd, rows, cols, eps, st)
-         : dtype == OFA_BF16 ? ln_fwd_dispatch<bf16_t, true>(h, gamma, beta, y, mean, rstd, rows, cols, eps, st)
-                             : ln_fwd_dispatch<f16_t, true>(h, gamma, beta, y, mean, rstd, rows, cols, eps, st);
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return ln_fwd_dispatch<typename decltype(tag)::type, true>(h, gamma, beta, y, mean, rstd, rows, cols, eps, st);
+  });
 }
 
 extern "C" int ofa_layernorm_bwd(const void* dy, const void* x, const void* gamma, const float* mean, const float* rstd,
@@ -454,11 +454,9 @@ extern "C" int ofa_layernorm_bwd(const void* dy, const void* x, const void* gamm
   OFA_REQUIRE(dy && x && gamma && mean && rstd && dx && dgamma && dbeta && ws, OFA_ERR_INVALID,
               "layernorm_bwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  return dtype == OFA_F32
-             ? ln_bwd_dispatch<float, false>(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, nullptr, ws, rows, cols, accumulate, st)
-         : dtype == OFA_BF16
-             ? ln_bwd_dispatch<bf16_t, false>(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, nullptr, ws, rows, cols, accumulate, st)
-             : ln_bwd_dispatch<f16_t, false>(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, nullptr, ws, rows, cols, accumulate, st);
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return ln_bwd_dispatch<typename decltype(tag)::type, false>(dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, nullptr, ws, rows, cols, accumulate, st);
+  });
 }
 
 extern "C" int ofa_gelu_layernorm_bwd(const void* dy, const void* h, const void* gamma, const float* mean,
@@ -468,9 +466,7 @@ extern "C" int ofa_gelu_layernorm_bwd(const void* dy, const void* h, const void*
   OFA_REQUIRE(dy && h && gamma && mean && rstd && dh && dgamma && dbeta && ws, OFA_ERR_INVALID,
               "gelu_layernorm_bwd: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  return dtype == OFA_F32
-             ? ln_bwd_dispatch<float, true>(dy, h, gamma, mean, rstd, nullptr, dh, dgamma, dbeta, dbias, ws, rows, cols, accumulate, st)
-         : dtype == OFA_BF16
-             ? ln_bwd_dispatch<bf16_t, true>(dy, h, gamma, mean, rstd, nullptr, dh, dgamma, dbeta, dbias, ws, rows, cols, accumulate, st)
-             : ln_bwd_dispatch<f16_t, true>(dy, h, gamma, mean, rstd, nullptr, dh, dgamma, dbeta, dbias, ws, rows, cols, accumulate, st);
+  return dispatch_dtype(dtype, [&](auto tag) {
+    return ln_bwd_dispatch<typename decltype(tag)::type, true>(dy, h, gamma, mean, rstd, nullptr, dh, dgamma, dbeta, dbias, ws, rows, cols, accumulate, st);
+  });
 }

@@ -555,15 +555,13 @@ extern "C" int ofa_cross_entropy_fwd(const void* logits, const int64_t* target, 
                                      int64_t V, int64_t ld, int64_t ignore_index, int dtype, void* stream) {
   OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "cross_entropy_fwd: bad dtype %d", dtype);
   OFA_REQUIRE(rows >= 0 && V > 0 && ld >= V && logits && target && lse && row_loss, OFA_ERR_INVALID, "cross_entropy_fwd: bad argument");
-  OFA_REQUIRE(ld % (dtype == OFA_F32 ? 4 : 8) == 0, OFA_ERR_INVALID, "cross_entropy_fwd: ld=%lld must be a multiple of the 16-byte vector width", (long long)ld);
+  OFA_REQUIRE(ld % dt_vecn(dtype) == 0, OFA_ERR_INVALID, "cross_entropy_fwd: ld=%lld must be a multiple of the 16-byte vector width", (long long)ld);
   if (rows == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((ce_fwd_kernel<float>), dim3((unsigned)rows), dim3(256), 0, st, (const float*)logits, target, lse, row_loss, V, ld, ignore_index);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((ce_fwd_kernel<bf16_t>), dim3((unsigned)rows), dim3(256), 0, st, (const bf16_t*)logits, target, lse, row_loss, V, ld, ignore_index);
-  else
-    hipLaunchKernelGGL((ce_fwd_kernel<f16_t>), dim3((unsigned)rows), dim3(256), 0, st, (const f16_t*)logits, target, lse, row_loss, V, ld, ignore_index);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((ce_fwd_kernel<T>), dim3((unsigned)rows), dim3(256), 0, st, (const T*)logits, target, lse, row_loss, V, ld, ignore_index);
+  });
   return check_launch("cross_entropy_fwd");
 }
 
@@ -595,8 +593,10 @@ extern "C" int ofa_cross_entropy_fwd_grad(const void* logits, const int64_t* tar
   OFA_REQUIRE(rows >= 0 && logits && target && lse && row_loss && dlogits, OFA_ERR_INVALID, "cross_entropy_fwd_grad: bad argument");
   if (rows == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  const bool ok = dtype == OFA_BF16 ? ce_fwd_grad_launch<bf16_t>((const bf16_t*)logits, target, grad_scale, lse, row_loss, (bf16_t*)dlogits, rows, V, ld, ignore_index, st)
-                                    : ce_fwd_grad_launch<f16_t>((const f16_t*)logits, target, grad_scale, lse, row_loss, (f16_t*)dlogits, rows, V, ld, ignore_index, st);
+  const bool ok = dispatch_dtype16(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return ce_fwd_grad_launch<T>((const T*)logits, target, grad_scale, lse, row_loss, (T*)dlogits, rows, V, ld, ignore_index, st);
+  });
   OFA_REQUIRE(ok, OFA_ERR_UNSUPPORTED, "cross_entropy_fwd_grad: row too long");
   return check_launch("cross_entropy_fwd_grad");
 }
@@ -606,15 +606,13 @@ extern "C" int ofa_cross_entropy_bwd(const void* logits, const int64_t* target, 
                                      void* stream) {
   OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "cross_entropy_bwd: bad dtype %d", dtype);
   OFA_REQUIRE(rows >= 0 && V > 0 && ld >= V && logits && target && lse && dlogits, OFA_ERR_INVALID, "cross_entropy_bwd: bad argument");
-  OFA_REQUIRE(ld % (dtype == OFA_F32 ? 4 : 8) == 0, OFA_ERR_INVALID, "cross_entropy_bwd: ld must be a multiple of the 16-byte vector width");
+  OFA_REQUIRE(ld % dt_vecn(dtype) == 0, OFA_ERR_INVALID, "cross_entropy_bwd: ld must be a multiple of the 16-byte vector width");
   if (rows == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((ce_bwd_kernel<float>), dim3((unsigned)rows), dim3(256), 0, st, (const float*)logits, target, lse, grad_scale, (float*)dlogits, V, ld, ignore_index);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((ce_bwd_kernel<bf16_t>), dim3((unsigned)rows), dim3(256), 0, st, (const bf16_t*)logits, target, lse, grad_scale, (bf16_t*)dlogits, V, ld, ignore_index);
-  else
-    hipLaunchKernelGGL((ce_bwd_kernel<f16_t>), dim3((unsigned)rows), dim3(256), 0, st, (const f16_t*)logits, target, lse, grad_scale, (f16_t*)dlogits, V, ld, ignore_index);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((ce_bwd_kernel<T>), dim3((unsigned)rows), dim3(256), 0, st, (const T*)logits, target, lse, grad_scale, (T*)dlogits, V, ld, ignore_index);
+  });
   return check_launch("cross_entropy_bwd");
 }
 
@@ -629,12 +627,10 @@ extern "C" int ofa_ls_cross_entropy_fwd(const void* logits, const int64_t* targe
   if (rows == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const LsCfg cfg{eps, cstart, cend, cmask};
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((lsce_fwd_kernel<float>), dim3((unsigned)rows), dim3(256), 0, st, (const float*)logits, target, lse, row_loss, row_nll, row_cnt, V, ld, ignore_index, cfg);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((lsce_fwd_kernel<bf16_t>), dim3((unsigned)rows), dim3(256), 0, st, (const bf16_t*)logits, target, lse, row_loss, row_nll, row_cnt, V, ld, ignore_index, cfg);
-  else
-    hipLaunchKernelGGL((lsce_fwd_kernel<f16_t>), dim3((unsigned)rows), dim3(256), 0, st, (const f16_t*)logits, target, lse, row_loss, row_nll, row_cnt, V, ld, ignore_index, cfg);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((lsce_fwd_kernel<T>), dim3((unsigned)rows), dim3(256), 0, st, (const T*)logits, target, lse, row_loss, row_nll, row_cnt, V, ld, ignore_index, cfg);
+  });
   return check_launch("ls_cross_entropy_fwd");
 }
 
@@ -648,12 +644,10 @@ extern "C" int ofa_ls_cross_entropy_bwd(const void* logits, const int64_t* targe
   if (rows == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const LsCfg cfg{eps, cstart, cend, cmask};
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((lsce_bwd_kernel<float>), dim3((unsigned)rows), dim3(256), 0, st, (const float*)logits, target, lse, row_cnt, row_w, grad_scale, (float*)dlogits, V, ld, ignore_index, cfg);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((lsce_bwd_kernel<bf16_t>), dim3((unsigned)rows), dim3(256), 0, st, (const bf16_t*)logits, target, lse, row_cnt, row_w, grad_scale, (bf16_t*)dlogits, V, ld, ignore_index, cfg);
-  else
-    hipLaunchKernelGGL((lsce_bwd_kernel<f16_t>), dim3((unsigned)rows), dim3(256), 0, st, (const f16_t*)logits, target, lse, row_cnt, row_w, grad_scale, (f16_t*)dlogits, V, ld, ignore_index, cfg);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((lsce_bwd_kernel<T>), dim3((unsigned)rows), dim3(256), 0, st, (const T*)logits, target, lse, row_cnt, row_w, grad_scale, (T*)dlogits, V, ld, ignore_index, cfg);
+  });
   return check_launch("ls_cross_entropy_bwd");
 }
 
@@ -663,9 +657,10 @@ extern "C" int ofa_probs_fwd(const void* logits, float* out, int64_t rows, int64
   OFA_REQUIRE(rows >= 0 && V > 0 && ld >= V && logits && out, OFA_ERR_INVALID, "probs_fwd: bad argument");
   if (rows == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32) hipLaunchKernelGGL((probs_fwd_kernel<float>), dim3((unsigned)rows), dim3(256), 0, st, (const float*)logits, out, V, ld, log_probs);
-  else if (dtype == OFA_BF16) hipLaunchKernelGGL((probs_fwd_kernel<bf16_t>), dim3((unsigned)rows), dim3(256), 0, st, (const bf16_t*)logits, out, V, ld, log_probs);
-  else hipLaunchKernelGGL((probs_fwd_kernel<f16_t>), dim3((unsigned)rows), dim3(256), 0, st, (const f16_t*)logits, out, V, ld, log_probs);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((probs_fwd_kernel<T>), dim3((unsigned)rows), dim3(256), 0, st, (const T*)logits, out, V, ld, log_probs);
+  });
   return check_launch("probs_fwd");
 }
 
@@ -675,9 +670,10 @@ extern "C" int ofa_probs_bwd(const float* dy, const float* y, void* dlogits, int
   OFA_REQUIRE(rows >= 0 && V > 0 && ld >= V && dy && y && dlogits, OFA_ERR_INVALID, "probs_bwd: bad argument");
   if (rows == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32) hipLaunchKernelGGL((probs_bwd_kernel<float>), dim3((unsigned)rows), dim3(256), 0, st, dy, y, (float*)dlogits, V, ld, log_probs);
-  else if (dtype == OFA_BF16) hipLaunchKernelGGL((probs_bwd_kernel<bf16_t>), dim3((unsigned)rows), dim3(256), 0, st, dy, y, (bf16_t*)dlogits, V, ld, log_probs);
-  else hipLaunchKernelGGL((probs_bwd_kernel<f16_t>), dim3((unsigned)rows), dim3(256), 0, st, dy, y, (f16_t*)dlogits, V, ld, log_probs);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((probs_bwd_kernel<T>), dim3((unsigned)rows), dim3(256), 0, st, dy, y, (T*)dlogits, V, ld, log_probs);
+  });
   return check_launch("probs_bwd");
 }
 
@@ -688,12 +684,13 @@ extern "C" int ofa_sumsq(const void* x, float* out, float* ws, int64_t n, int dt
   OFA_REQUIRE(n >= 0 && out && ws && (n == 0 || x), OFA_ERR_INVALID, "sumsq: bad argument");
   if (n == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
-  const int vecw = dtype == OFA_F32 ? 4 : 8;
+  const int vecw = dt_vecn(dtype);
   int64_t nbl = (n / vecw + 255) / 256;
   const int nb = (int)(nbl < 1 ? 1 : (nbl > 1024 ? 1024 : nbl));
-  if (dtype == OFA_F32) hipLaunchKernelGGL((sumsq_kernel<float>), dim3(nb), dim3(256), 0, st, (const float*)x, ws, n);
-  else if (dtype == OFA_BF16) hipLaunchKernelGGL((sumsq_kernel<bf16_t>), dim3(nb), dim3(256), 0, st, (const bf16_t*)x, ws, n);
-  else hipLaunchKernelGGL((sumsq_kernel<f16_t>), dim3(nb), dim3(256), 0, st, (const f16_t*)x, ws, n);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((sumsq_kernel<T>), dim3(nb), dim3(256), 0, st, (const T*)x, ws, n);
+  });
   int rc = check_launch("sumsq");
   if (rc) return rc;
   hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, out, nb);
@@ -716,12 +713,10 @@ extern "C" int ofa_adam_step(float* master, float* exp_avg, float* exp_avg_sq, c
               OFA_ERR_INVALID, "adam_step: arenas must be 16-byte (fp32 state) / 8-byte (grad, model copy) aligned");
   int64_t nbl = (n + 255) / 256;
   const int nb = (int)(nbl > 65536 ? 65536 : nbl);      // (small blocks of work: the tail of a 4096-block grid cost 15 %)
-  if (dtype == OFA_F32)
-    hipLaunchKernelGGL((adam_kernel<float>), dim3(nb), dim3(256), 0, st, master, exp_avg, exp_avg_sq, (const float*)grad, (float*)model_param, coef, n, lr, beta1, beta2, eps, weight_decay, step_size, dev_sched);
-  else if (dtype == OFA_BF16)
-    hipLaunchKernelGGL((adam_kernel<bf16_t>), dim3(nb), dim3(256), 0, st, master, exp_avg, exp_avg_sq, (const bf16_t*)grad, (bf16_t*)model_param, coef, n, lr, beta1, beta2, eps, weight_decay, step_size, dev_sched);
-  else
-    hipLaunchKernelGGL((adam_kernel<f16_t>), dim3(nb), dim3(256), 0, st, master, exp_avg, exp_avg_sq, (const f16_t*)grad, (f16_t*)model_param, coef, n, lr, beta1, beta2, eps, weight_decay, step_size, dev_sched);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((adam_kernel<T>), dim3(nb), dim3(256), 0, st, master, exp_avg, exp_avg_sq, (const T*)grad, (T*)model_param, coef, n, lr, beta1, beta2, eps, weight_decay, step_size, dev_sched);
+  });
   return check_launch("adam_step");
 }
 

@@ -114,18 +114,12 @@ static int softmax_launch(const void* x, const void* bias, const uint8_t* mask, 
   if (rows == 0) return 0;
   dim3 grid(cdiv(rows, 4)), block(256);
   const int ni = (sk + 63) / 64;
-#define SM_CASE(NI)                                                                                                  \
-  do {                                                                                                               \
-    if (dtype == OFA_F32)                                                                                            \
-      hipLaunchKernelGGL((softmax_fwd_kernel<float, MODE, NI>), grid, block, 0, st, (const float*)x,                 \
-                         (const float*)bias, mask, (float*)y, scale, rows, sq, sk, np, mask_b, causal);              \
-    else if (dtype == OFA_BF16)                                                                                      \
-      hipLaunchKernelGGL((softmax_fwd_kernel<bf16_t, MODE, NI>), grid, block, 0, st, (const bf16_t*)x,               \
-                         (const bf16_t*)bias, mask, (bf16_t*)y, scale, rows, sq, sk, np, mask_b, causal);            \
-    else                                                                                                             \
-      hipLaunchKernelGGL((softmax_fwd_kernel<f16_t, MODE, NI>), grid, block, 0, st, (const f16_t*)x,                 \
-                         (const f16_t*)bias, mask, (f16_t*)y, scale, rows, sq, sk, np, mask_b, causal);              \
-  } while (0)
+#define SM_CASE(NI)                                                                                                     \
+  dispatch_dtype(dtype, [&](auto tag) {                                                                                 \
+    using T = typename decltype(tag)::type;                                                                             \
+    hipLaunchKernelGGL((softmax_fwd_kernel<T, MODE, NI>), grid, block, 0, st, (const T*)x, (const T*)bias, mask, (T*)y, \
+                       scale, rows, sq, sk, np, mask_b, causal);                                                        \
+  })
   if (ni <= 1) SM_CASE(1);
   else if (ni <= 2) SM_CASE(2);
   else if (ni <= 4) SM_CASE(4);
@@ -148,24 +142,18 @@ extern "C" int ofa_scaled_softmax_fwd(const void* x, void* y, float scale, int b
 
 static int softmax_bwd_launch(const void* dy, const void* y, void* dx, float scale, int64_t rows, int sk, int causal,
                               int dtype, hipStream_t st) {
-  OFA_REQUIRE(dtype == OFA_F32 || dtype == OFA_BF16 || dtype == OFA_F16, OFA_ERR_INVALID, "softmax_bwd: bad dtype %d", dtype);
+  OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "softmax_bwd: bad dtype %d", dtype);
   OFA_REQUIRE(sk > 0 && sk <= 64 * SM_MAX_PER_LANE, OFA_ERR_UNSUPPORTED, "softmax_bwd: sk=%d must be in [1,4096]", sk);
   OFA_REQUIRE(rows >= 0 && dy && y && dx, OFA_ERR_INVALID, "softmax_bwd: null pointer / negative size");
   if (rows == 0) return 0;
   dim3 grid(cdiv(rows, 4)), block(256);
   const int ni = (sk + 63) / 64;
-#define SM_CASE(NI)                                                                                              \
-  do {                                                                                                           \
-    if (dtype == OFA_F32)                                                                                        \
-      hipLaunchKernelGGL((softmax_bwd_kernel<float, NI>), grid, block, 0, st, (const float*)dy, (const float*)y, \
-                         (float*)dx, scale, rows, sk, causal);                                                   \
-    else if (dtype == OFA_BF16)                                                                                  \
-      hipLaunchKernelGGL((softmax_bwd_kernel<bf16_t, NI>), grid, block, 0, st, (const bf16_t*)dy,                \
-                         (const bf16_t*)y, (bf16_t*)dx, scale, rows, sk, causal);                                \
-    else                                                                                                         \
-      hipLaunchKernelGGL((softmax_bwd_kernel<f16_t, NI>), grid, block, 0, st, (const f16_t*)dy,                  \
-                         (const f16_t*)y, (f16_t*)dx, scale, rows, sk, causal);                                  \
-  } while (0)
+#define SM_CASE(NI)                                                                                                        \
+  dispatch_dtype(dtype, [&](auto tag) {                                                                                    \
+    using T = typename decltype(tag)::type;                                                                                \
+    hipLaunchKernelGGL((softmax_bwd_kernel<T, NI>), grid, block, 0, st, (const T*)dy, (const T*)y, (T*)dx, scale, rows, sk, \
+                       causal);                                                                                            \
+  })
   if (ni <= 1) SM_CASE(1);
   else if (ni <= 2) SM_CASE(2);
   else if (ni <= 4) SM_CASE(4);

@@ -304,15 +304,15 @@ extern "C" int ofa_trie_beam_topk(const void* h, int64_t ld_h, int dtype, const 
   TrieTopkArgs a{h, ld_h, W, ld_w, bias, D, V, rows, K, S, cdiv(max_degree, epw), epw, node, node_edge_off, edge_token, N, E,
                  BeamPolicy{temperature, step, min_len, max_len, pad, unk, eos, unk_penalty, ngram, tokens, tok_ld, done},
                  beam_ws_carve(ws, rows, S, K)};
-  const size_t smem = sizeof(TrieTopkScratch) + (size_t)D * (dtype == OFA_F32 ? 4 : 2) + (size_t)a.epw * 8;
+  const size_t smem = sizeof(TrieTopkScratch) + (size_t)D * dt_size(dtype) + (size_t)a.epw * 8;
   OFA_REQUIRE(smem <= TB_LDS_MAX, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: D=%d with %d edges per workgroup needs %zu bytes of LDS",
               D, a.epw, smem);
   OFA_REQUIRE(rows <= 65535, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: %d rows", rows);
   dim3 grid(a.Su, rows);
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == OFA_F32) hipLaunchKernelGGL(trie_beam_topk_kernel<float>, grid, dim3(BEAM_THREADS), smem, st, a);
-  else if (dtype == OFA_BF16) hipLaunchKernelGGL(trie_beam_topk_kernel<bf16_t>, grid, dim3(BEAM_THREADS), smem, st, a);
-  else hipLaunchKernelGGL(trie_beam_topk_kernel<f16_t>, grid, dim3(BEAM_THREADS), smem, st, a);
+  dispatch_dtype(dtype, [&](auto tag) {
+    hipLaunchKernelGGL(trie_beam_topk_kernel<typename decltype(tag)::type>, grid, dim3(BEAM_THREADS), smem, st, a);
+  });
   return check_launch("ofa_trie_beam_topk");
 }
 
