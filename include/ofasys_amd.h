@@ -173,94 +173,87 @@ int ofa_get_batch_per_block(int sq, int sk, int b, int np); /* scaled_masked_sof
 int ofa_attn_softmax_fwd(const void* x, const void* bias, const uint8_t* kpm, void* p, float scale, int BA, int heads,
                          int T, int S, int causal, int dtype, void* stream);
 
-/* ---- fused attention (bf16, head_dim 64): multihead_attention.py:218-346 without materialising [BA,T,S].
- * q: [B, T, heads*64] rows (ld = ldq elements); k, v: [B, S, heads*64] rows (both with ld = ldk);
- * bias: optional dense [B*heads, T, S] additive bias (same dtype); kpm: optional uint8 [B,S]; c_attn: optional
- * [heads] per-head output scale (:342-345), fp32 or bf16 as c_attn_dtype says (the parameter itself, no cast kernel). out: [B, T, heads*64] (ld = ldo); lse: fp32 [B*heads, Tpad].  scale
- * multiplies q.k (the reference pre-scales q, :218) and must be positive (the kernel takes row maxima on the raw scores; a
- * non-positive scale is refused).  Tpad: a multiple of 32 covering T.
- * Attention dropout is not supported here (the reference default is attention_dropout = 0.0).
- * Ragged ("packed rows") mode, seg != NULL: the reference pads every sample to the longest and masks the padding
- * (multihead_attention.py:319-326); here the batch may arrive packed instead.  seg: device int32 [B][4] = {q_off, q_len, k_off,
- * k_len} (16-byte aligned; q_off a multiple of 4).  q / out are [rows_q, ld] with sample b's queries in rows q_off .. q_off+q_len-1,
- * k / v are [rows_k, ld] likewise; lse is fp32 [heads, Tpad] indexed by the packed query row (Tpad >= rows_q); T, S are upper
- * bounds of q_len, k_len (they size the launch grid); rows_q / rows_k: total packed rows; bias and kpm must be NULL.  The rows of
- * `out` outside every segment (alignment / bucket filler) are written as zeros. */
-int ofa_attn_fwd(const void* q, const void* k, const void* v, const void* bias, const uint8_t* kpm,
-                 const void* c_attn, int c_attn_dtype, void* out, float* lse, int B, int heads, int T, int S, int Tpad,
-                 int64_t ldq, int64_t ldk, int64_t ldo, float scale, int causal, const int32_t* seg, int rows_q, int rows_k,
-                 int dtype, void* stream);
-/* Backward.  lse: fp32 [B*heads, Tpad] as written by ofa_attn_fwd (base-2 log-sum-exp of the scaled, biased, masked
- * scores); delta: fp32 [B*heads, Tpad] = rowsum(dO*O); dout: [B,T,heads*64] rows (ld = ldo).
- * out != NULL (the forward output O, rows like dout): the dQ kernel computes delta from dO and O on its way in and WRITES it
- * (rows t < T; in ragged mode also zeros in the filler rows) -- for the dK/dV kernel and ofa_c_attn_grad; no separate pass.
- * out == NULL: delta is an input, filled by ofa_attn_bwd_prep beforehand.
- * Writes dq [B,T,D] (ld = ldq), dk, dv [B,S,D] (ld = ldk); dbias (optional, [B*heads,T,S]) receives dS.
- * No transposed operand copies are needed: the kernels transpose tiles on the LDS read (ds_read_b64_tr_b16).
- * seg != NULL: ragged mode as in ofa_attn_fwd (delta from ofa_attn_bwd_prep(B = 1, T = rows_q): [heads, Tpad] by packed row;
- * dq / dk / dv rows outside every segment are written as zeros). */
-int ofa_attn_bwd_prep(const void* dout, const void* out, float* delta, int B, int heads, int T, int Tpad, int64_t ldo,
-                      int dtype, void* stream);
-int ofa_attn_bwd(const void* q, const void* k, const void* v, const void* dout, const void* bias, const uint8_t* kpm,
-                 const void* c_attn, int c_attn_dtype, const float* lse, float* delta, const void* out, void* dq, void* dk,
-                 void* dv, void* dbias, int B, int heads, int T, int S, int Tpad, int64_t ldq, int64_t ldk, int64_t ldo,
-                 float scale, int causal, const int32_t* seg, int rows_q, int rows_k, int dtype, void* stream);
-
-/* ofa_attn_bwd that also leaves the COLUMN SUMS of its outputs as fp32 partial rows for ofa_fold_batched -- the bias gradients of the
- * q / k / v projections (multihead_attention.py:199-217: q_proj / k_proj / v_proj carry biases) and the gradient of c_attn (:342-345) --
- * instead of a column-sum pass over dq / dk / dv and ofa_c_attn_grad afterwards.  One partial row per (sample, 128-row tile, wave):
- * cs_q: [ofa_attn_cs_slots(B, T)][cs_ldq], columns [64 h, 64 h + 64) of a row written by one wave of the dQ workgroup of head h;
- * cs_k, cs_v: [ofa_attn_cs_slots(B, S)][cs_ldk] likewise by the dK/dV kernel; cs_c: [ofa_attn_cs_slots(B, T)][heads], sum over the
- * wave's 32 rows of delta / c_attn[h].  Any of them may be NULL.  Every partial row is written on every call (empty tiles of a ragged batch:
- * zeros), the sums are over the fp32 values BEFORE their rounding to `dtype`, in a fixed order.  Ragged mode: B = the segment count, T / S = max_q / max_k. */
-int ofa_attn_cs_slots(int B, int rows);
-int ofa_attn_bwd_cs(const void* q, const void* k, const void* v, const void* dout, const void* bias, const uint8_t* kpm,
-                    const void* c_attn, int c_attn_dtype, const float* lse, float* delta, const void* out, void* dq, void* dk,
-                    void* dv, void* dbias, int B, int heads, int T, int S, int Tpad, int64_t ldq, int64_t ldk, int64_t ldo,
-                    float scale, int causal, const int32_t* seg, int rows_q, int rows_k, int dtype, float* cs_q, int64_t cs_ldq,
-                    float* cs_k, float* cs_v, int64_t cs_ldk, float* cs_c, void* stream);
-
-/* ---- Attention with a batch-SHARED position bias.
- * The reference adds a dense bias [B*A, T, S] to the scores of every attention of its default configuration (use_self_attn_bias,
- * model/ofa.py:110-113; multihead_attention.py:308-311): abs-pos (pos_q_linear(pos) * pos_scaling) pos_k_linear(pos)^T per head
- * (adaptor/general.py:223-243; cross attention: model/transformer.py:280-299) + table_l[bucket[i][j]] on every slot's diagonal block
- * (general.py:265-280; text.py:101-104, image_resnet.py:116-128, video_image_sequence.py:187-204).  Position embeddings do not depend
- * on the batch row (text: arange; image / video: the patch grid), so that tensor is B copies of ONE [A, T, S] matrix per layer -- which
- * is what these entry points take, indexed by (head, query position, key position) for every sample; in ragged mode by the position
- * INSIDE the sample (so a batch whose valid positions are a prefix of each padded row packs without touching the bias).  Tb >= T,
- * Sb >= S.  Everything else as ofa_attn_fwd (seg != NULL: kpm must be NULL).
+/* ---- fused attention (bf16, head_dim 64): multihead_attention.py:218-346 without materialising [BA,T,S].  One descriptor for the
+ * forward and the backward; a field a call does not use is zero / NULL, and the MODE follows from which pointers are set.
+ * Attention dropout is not supported here (the reference default is attention_dropout = 0.0).  No transposed operand copies are
+ * needed: the kernels transpose tiles on the LDS read (ds_read_b64_tr_b16).
  *
+ * Operands.  q: [B, T, heads*64] rows (ld = ldq elements); k, v: [B, S, heads*64] rows (both ld = ldk); out: [B, T, heads*64]
+ * (ld = ldo); lse: fp32 [B*heads, Tpad], the base-2 log-sum-exp of the scaled, biased, masked scores (the forward writes it; it may
+ * be NULL there with neither seg nor a shared bias); Tpad: a multiple of 32 covering T.  scale multiplies q.k (the reference
+ * pre-scales q, :218) and must be positive (the kernel takes row maxima on the raw scores; the forward refuses a non-positive scale).
+ * kpm: optional uint8 [B,S]; c_attn: optional [heads] per-head output scale (:342-345), fp32 or bf16 as c_attn_dtype says (the
+ * parameter itself, no cast kernel); causal: non-zero masks above the diagonal; dtype: OFA_BF16 or OFA_F16.
+ * Backward: dout: [B,T,heads*64] rows (ld = ldo); delta: fp32 [B*heads, Tpad] = rowsum(dO*O).  out != NULL (the forward output O,
+ * rows like dout): the dQ kernel computes delta from dO and O on its way in and WRITES it (rows t < T; in ragged mode also zeros in
+ * the filler rows) -- for the dK/dV kernel and ofa_c_attn_grad; no separate pass.  out == NULL (not with a shared bias): delta is an
+ * input, filled by ofa_attn_bwd_prep beforehand.  Writes dq [B,T,D] (ld = ldq), dk, dv [B,S,D] (ld = ldk).
+ *
+ * Dense bias (bias != NULL, bias_swz_row == NULL): [B*heads, T, S] additive, same dtype; dbias (optional, [B*heads,T,S]) receives dS.
+ *
+ * Batch-SHARED position bias (bias_swz_row != NULL).  The reference adds a dense bias [B*A, T, S] to the scores of every attention
+ * of its default configuration (use_self_attn_bias, model/ofa.py:110-113; multihead_attention.py:308-311): abs-pos
+ * (pos_q_linear(pos) * pos_scaling) pos_k_linear(pos)^T per head (adaptor/general.py:223-243; cross attention:
+ * model/transformer.py:280-299) + table_l[bucket[i][j]] on every slot's diagonal block (general.py:265-280; text.py:101-104,
+ * image_resnet.py:116-128, video_image_sequence.py:187-204).  Position embeddings do not depend on the batch row (text: arange;
+ * image / video: the patch grid), so that tensor is B copies of ONE [A, Tb, Sb] matrix per layer -- which is what this mode takes,
+ * indexed by (head, query position, key position) for every sample; in ragged mode by the position INSIDE the sample (so a batch
+ * whose valid positions are a prefix of each padded row packs without touching the bias).  Tb >= T, Sb >= S.
  * The kernels do not read the row-major [heads, Tb, Sb] tensor but its two TILE-SWIZZLED images written by ofa_bias_build (which
  * also does the per-layer assembly of general.py:265-280): per head and 32 x 32 block, the 16 values MFMA lane l = (hi << 5 | i)
  * holds -- element r: row image  bias[32 qt + i][32 kt + (r & 3) + 8 (r >> 2) + 4 hi]  at ((h * nqt + qt) * nkt + kt) * 1024 + 16 l + r,
  * column image  bias[32 qt + (r & 3) + 8 (r >> 2) + 4 hi][32 kt + i]  at ((h * nkt + kt) * nqt + qt) * 1024 + 16 l + r,
  * nqt = ceil(Tb / 32), nkt = ceil(Sb / 32), positions outside [Tb, Sb] zero.  A wave then fetches a block's bias as 2 KiB of
- * consecutive bytes and feeds it to the score MFMAs as their initial accumulator. */
-int ofa_attn_sbias_fwd(const void* q, const void* k, const void* v, const void* bias_swz_row, int Tb, int Sb, const uint8_t* kpm,
-                       const void* c_attn, int c_attn_dtype, void* out, float* lse, int B, int heads, int T, int S, int Tpad,
-                       int64_t ldq, int64_t ldk, int64_t ldo, float scale, int causal, const int32_t* seg, int rows_q, int rows_k,
-                       int dtype, void* stream);
-/* Backward (out != NULL always: delta is computed on the way in and written).  dbias_sum (optional): [heads, Tb, Sb] in dbias_dtype
- * (OFA_F32, or a 16-bit code: rounded once, from the fp32 sum) = sum over the batch of dS -- the gradient of the shared bias.  The reference obtains it by materialising dS as [B*A, T, S] and
- * reducing the expand; here a third kernel walks (a chunk of) the batch per [128 x 64] tile of one head, recomputes S and dP of that
- * tile (lse / delta are known) and accumulates dS in registers: no [B*A,T,S] tensor, no atomics, bitwise reproducible.
- * bias: the row-major [heads, Tb, Sb] tensor in `dtype` (read once per tile by that third kernel; may be NULL when dbias_sum is).
- * ws / ws_bytes: see ofa_attn_sbias_chunks. */
-int ofa_attn_sbias_bwd(const void* q, const void* k, const void* v, const void* dout, const void* bias, const void* bias_swz_row,
-                       const void* bias_swz_col, int Tb, int Sb, const uint8_t* kpm, const void* c_attn, int c_attn_dtype,
-                       const float* lse, float* delta, const void* out, void* dq, void* dk, void* dv, void* dbias_sum, int dbias_dtype,
-                       float* ws, int64_t ws_bytes, int B, int heads, int T, int S, int Tpad, int64_t ldq, int64_t ldk, int64_t ldo, float scale,
-                       int causal, const int32_t* seg, int rows_q, int rows_k, int dtype, void* stream);
-/* ... with the column-sum partial rows of ofa_attn_bwd_cs */
-int ofa_attn_sbias_bwd_cs(const void* q, const void* k, const void* v, const void* dout, const void* bias, const void* bias_swz_row,
-                          const void* bias_swz_col, int Tb, int Sb, const uint8_t* kpm, const void* c_attn, int c_attn_dtype,
-                          const float* lse, float* delta, const void* out, void* dq, void* dk, void* dv, void* dbias_sum, int dbias_dtype,
-                          float* ws, int64_t ws_bytes, int B, int heads, int T, int S, int Tpad, int64_t ldq, int64_t ldk, int64_t ldo, float scale,
-                          int causal, const int32_t* seg, int rows_q, int rows_k, int dtype, float* cs_q, int64_t cs_ldq, float* cs_k,
-                          float* cs_v, int64_t cs_ldk, float* cs_c, void* stream);
-/* Batch chunks the dS-sum kernel of ofa_attn_sbias_bwd cuts B samples into (short sequences: the [128 x 64] tiles of the heads alone
- * would leave the chip idle).  1 and dbias_dtype == OFA_F32 or == dtype: it writes dbias_sum itself, ws may be NULL.  Otherwise ws must hold
- * n * heads * Tb * Sb floats (the chunks' partial sums, folded in chunk order -- and cast -- by ofa_fold_batched inside the call). */
+ * consecutive bytes and feeds it to the score MFMAs as their initial accumulator.  The forward reads bias_swz_row (and needs lse);
+ * the backward reads both images (and needs out).  dbias (optional): [heads, Tb, Sb] in dbias_dtype (OFA_F32, or a 16-bit code:
+ * rounded once, from the fp32 sum) = sum over the batch of dS -- the gradient of the shared bias.  The reference obtains it by
+ * materialising dS as [B*A, T, S] and reducing the expand; here a third kernel walks (a chunk of) the batch per [128 x 64] tile of
+ * one head, recomputes S and dP of that tile (lse / delta are known) and accumulates dS in registers: no [B*A,T,S] tensor, no
+ * atomics, bitwise reproducible.  bias: the row-major [heads, Tb, Sb] tensor in `dtype` (read once per tile by that third kernel;
+ * may be NULL when dbias is).  ws / ws_bytes: see ofa_attn_sbias_chunks.
+ *
+ * Ragged ("packed rows") mode, seg != NULL: the reference pads every sample to the longest and masks the padding
+ * (multihead_attention.py:319-326); here the batch may arrive packed instead.  seg: device int32 [B][4] = {q_off, q_len, k_off,
+ * k_len} (16-byte aligned; q_off a multiple of 4).  q / out / dout / dq are [rows_q, ld] with sample b's queries in rows q_off ..
+ * q_off+q_len-1, k / v / dk / dv are [rows_k, ld] likewise; lse / delta are fp32 [heads, Tpad] indexed by the packed query row
+ * (Tpad >= rows_q; delta from ofa_attn_bwd_prep(B = 1, T = rows_q)); T, S are upper bounds of q_len, k_len (they size the launch
+ * grid); rows_q / rows_k: total packed rows.  kpm must be NULL, and so must a dense bias / dbias (the shared bias is allowed).  The
+ * rows of out / dq / dk / dv outside every segment (alignment / bucket filler) are written as zeros.
+ *
+ * Column sums (backward, any non-NULL cs_*): the backward also leaves the COLUMN SUMS of its outputs as fp32 partial rows for
+ * ofa_fold_batched -- the bias gradients of the q / k / v projections (multihead_attention.py:199-217: q_proj / k_proj / v_proj carry
+ * biases) and the gradient of c_attn (:342-345) -- instead of a column-sum pass over dq / dk / dv and ofa_c_attn_grad afterwards.
+ * One partial row per (sample, 128-row tile, wave): cs_q: [ofa_attn_cs_slots(B, T)][cs_ldq], columns [64 h, 64 h + 64) of a row
+ * written by one wave of the dQ workgroup of head h; cs_k, cs_v: [ofa_attn_cs_slots(B, S)][cs_ldk] likewise by the dK/dV kernel;
+ * cs_c: [ofa_attn_cs_slots(B, T)][heads], sum over the wave's 32 rows of delta / c_attn[h].  Every partial row is written on every
+ * call (empty tiles of a ragged batch: zeros), the sums are over the fp32 values BEFORE their rounding to `dtype`, in a fixed order.
+ * Ragged mode: B = the segment count, T / S = max_q / max_k. */
+typedef struct ofa_attn_call {
+  const void *q, *k, *v, *dout;
+  void* out;                         /* forward: written; backward: read (or NULL) */
+  float *lse, *delta;
+  void *dq, *dk, *dv;
+  const void *bias, *bias_swz_row, *bias_swz_col;
+  void* dbias;
+  float* ws;
+  const uint8_t* kpm;
+  const void* c_attn;
+  const int32_t* seg;
+  float *cs_q, *cs_k, *cs_v, *cs_c;
+  int64_t ldq, ldk, ldo, ws_bytes, cs_ldq, cs_ldk;
+  int32_t B, heads, T, S, Tpad, Tb, Sb;
+  int32_t causal, rows_q, rows_k;
+  int32_t dtype, c_attn_dtype, dbias_dtype;
+  float scale;
+} ofa_attn_call;
+int ofa_attn_fwd(const ofa_attn_call* c, void* stream);
+int ofa_attn_bwd(const ofa_attn_call* c, void* stream);
+int ofa_attn_bwd_prep(const void* dout, const void* out, float* delta, int B, int heads, int T, int Tpad, int64_t ldo,
+                      int dtype, void* stream);
+int ofa_attn_cs_slots(int B, int rows);
+/* Batch chunks the dS-sum kernel of the shared-bias backward cuts B samples into (short sequences: the [128 x 64] tiles of the heads
+ * alone would leave the chip idle).  1 and dbias_dtype == OFA_F32 or == dtype: it writes dbias itself, ws may be NULL.  Otherwise ws must
+ * hold n * heads * Tb * Sb floats (the chunks' partial sums, folded in chunk order -- and cast -- by ofa_fold_batched inside the call). */
 int ofa_attn_sbias_chunks(int B, int heads, int Tb, int Sb);
 /* Gradient of the per-head scale c_attn (multihead_attention.py:58, 342-345: attn[t,b,h,:] *= c_attn[h]; O = c * PV, so
  * d c[h] = sum_{b,t} rowsum(dO*O)[b,h,t] / c[h]) from the delta rows of
@@ -375,8 +368,8 @@ int ofa_head_sum_f32(const float* x, float* out, int B, int heads, int T, int ld
  * the diagonal block [start, start+n)^2 of every (b,a); the gradient reduces that block over the batch. */
 /* Per-layer assembly of the batch-shared position bias, general.py:265-280 on ONE [heads, Tb, Sb] matrix:
  *   out = abs_bias (NULL: zeros);  out[:, s:s+n, s:s+n] += values_k[i][j][h]  for each slot k (values_k: [n, n, heads], `dtype`)
- * written as the row-major tensor (out, optional) and as the two swizzled images the ofa_attn_sbias_* kernels read (swz_row,
- * swz_col: ofa_bias_swz_elems(heads, Tb, Sb) elements each, 16-byte aligned; layout: see ofa_attn_sbias_fwd).  16-bit dtypes only;
+ * written as the row-major tensor (out, optional) and as the two swizzled images the shared-bias attention kernels read (swz_row,
+ * swz_col: ofa_bias_swz_elems(heads, Tb, Sb) elements each, 16-byte aligned; layout: see ofa_attn_call).  16-bit dtypes only;
  * slot blocks need Tb == Sb. */
 typedef struct ofa_bias_slots {
   const void* values[8];

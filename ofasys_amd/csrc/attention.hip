@@ -1424,134 +1424,112 @@ __device__ __forceinline__ void attn_bwd_dsum_body(AttnL a, float* __restrict__ 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void attn_bwd_dsum_kernel(AttnL a, float* G, int64_t g_ld, int64_t g_hs, int64_t g_cs, int Tb, int Sb, int nchunk, int bper, int out16) { attn_bwd_dsum_body<false>(a, G, g_ld, g_hs, g_cs, Tb, Sb, nchunk, bper, out16); }
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void attn_bwd_dsum_f16_kernel(AttnL a, float* G, int64_t g_ld, int64_t g_hs, int64_t g_cs, int Tb, int Sb, int nchunk, int bper, int out16) { attn_bwd_dsum_body<true>(a, G, g_ld, g_hs, g_cs, Tb, Sb, nchunk, bper, out16); }
 
-static int attnl_check(int B, int heads, int T, int S, int Tpad, int64_t ldq, int64_t ldk, int64_t ldo, int dtype) {
-  OFA_REQUIRE(dtype == OFA_BF16 || dtype == OFA_F16, OFA_ERR_UNSUPPORTED, "fused attention is bf16 / fp16 only (dtype %d); use the unfused path", dtype);
-  OFA_REQUIRE(B > 0 && heads > 0 && T > 0 && S > 0, OFA_ERR_INVALID, "attention: bad shape B=%d heads=%d T=%d S=%d", B, heads, T, S);
-  OFA_REQUIRE((ldq % 8) == 0 && (ldk % 8) == 0 && (ldo % 8) == 0, OFA_ERR_INVALID, "attention: leading dims must be multiples of 8");
-  OFA_REQUIRE(Tpad % 32 == 0 && Tpad >= T, OFA_ERR_INVALID, "attention: Tpad must be a multiple of 32 covering T (T=%d Tpad=%d)", T, Tpad);
+// ---- host side: one call descriptor (ofa_attn_call), one set of checks, one AttnL fill, two entry points.  The mode follows from
+// what is present: bias_swz_row -> the batch-SHARED position bias [heads, Tb, Sb] (swizzled-image kernels, BIAS 2 / 3, and with dbias the
+// batch-summed dS kernel); else bias -> the dense [B*heads, T, S] bias (BIAS 1); else none.
+static_assert(sizeof(ofa_attn_call) == 280, "ofa_attn_call: 22 pointers, 6 int64, 13 int32, 1 float, no padding (kernels._AttnCall mirrors it)");
+
+// G = sum_b dS of the shared bias: [128 x 64] tiles of one head; the batch is cut into chunks when the tiles alone would leave the
+// chip idle, the chunks' fp32 partials are folded in chunk order
+struct DsumPlan { int nchunk, bper; bool out16, direct; };
+static DsumPlan dsum_plan(const ofa_attn_call& c) {
+  DsumPlan p;
+  p.nchunk = ofa_attn_sbias_chunks(c.B, c.heads, c.Tb, c.Sb);
+  p.bper = cdiv(c.B, p.nchunk);
+  p.out16 = p.nchunk == 1 && c.dbias_dtype == c.dtype;                     // one chunk, gradient in the operands' 16-bit type: rounded in the kernel
+  p.direct = (p.nchunk == 1 && c.dbias_dtype == OFA_F32) || p.out16;       // the kernel writes dbias itself; otherwise the fold (+ cast) does
+  return p;
+}
+static size_t dsum_lds(const DsumPlan& p) { return 8 * TILE_BYTES + (size_t)p.bper * 16; }
+
+static int attn_check(const ofa_attn_call& c, bool bwd) {
+  const char* who = bwd ? "attn_bwd" : "attn_fwd";
+  const bool shared = c.bias_swz_row != nullptr;
+  OFA_REQUIRE(c.dtype == OFA_BF16 || c.dtype == OFA_F16, OFA_ERR_UNSUPPORTED, "fused attention is bf16 / fp16 only (dtype %d); use the unfused path", c.dtype);
+  OFA_REQUIRE(c.B > 0 && c.heads > 0 && c.T > 0 && c.S > 0, OFA_ERR_INVALID, "attention: bad shape B=%d heads=%d T=%d S=%d", c.B, c.heads, c.T, c.S);
+  OFA_REQUIRE((c.ldq % 8) == 0 && (c.ldk % 8) == 0 && (c.ldo % 8) == 0, OFA_ERR_INVALID, "attention: leading dims must be multiples of 8");
+  OFA_REQUIRE(c.Tpad % 32 == 0 && c.Tpad >= c.T, OFA_ERR_INVALID, "attention: Tpad must be a multiple of 32 covering T (T=%d Tpad=%d)", c.T, c.Tpad);
+  if (shared) {
+    OFA_REQUIRE(c.Tb > 0 && c.Sb > 0, OFA_ERR_INVALID, "%s: the swizzled bias image is of [heads, Tb, Sb] (Tb=%d Sb=%d)", who, c.Tb, c.Sb);
+    OFA_REQUIRE(!((uintptr_t)c.bias_swz_row & 15), OFA_ERR_INVALID, "%s: the swizzled bias image must be 16-byte aligned", who);
+    OFA_REQUIRE(c.Tb >= c.T && c.Sb >= c.S, OFA_ERR_INVALID, "%s: the shared bias covers %d x %d positions, the call needs %d x %d", who, c.Tb, c.Sb, c.T, c.S);
+    OFA_REQUIRE(!bwd || (c.bias_swz_col && !((uintptr_t)c.bias_swz_col & 15) && (c.bias || !c.dbias)), OFA_ERR_INVALID,
+                "attn_bwd: the column image of the shared bias (16-byte aligned) and, for dbias, the row-major tensor are required");
+  }
+  // (the dense forward writes no lse when it is NULL; the dense backward takes out == NULL: delta prepared by ofa_attn_bwd_prep)
+  if (bwd)
+    OFA_REQUIRE(c.q && c.k && c.v && c.dout && c.lse && c.delta && c.dq && c.dk && c.dv && (c.out || !shared), OFA_ERR_INVALID,
+                "attn_bwd: null pointer (q / k / v / dout / lse / delta / dq / dk / dv; with a shared bias also out)");
+  else
+    OFA_REQUIRE(c.q && c.k && c.v && c.out && (c.lse || !shared), OFA_ERR_INVALID, "attn_fwd: null pointer (q / k / v / out; with a shared bias also lse)");
+  OFA_REQUIRE(bwd || c.scale > 0.f, OFA_ERR_INVALID, "attn_fwd: the score scale must be positive (row maxima are taken on the raw scores), got %g", (double)c.scale);
+  OFA_REQUIRE(!c.seg || (!c.kpm && c.lse && !((uintptr_t)c.seg & 15) && (shared || (!c.bias && !(bwd && c.dbias)))), OFA_ERR_INVALID,
+              "%s: the ragged (seg) mode takes no key-padding mask and, unless the bias is shared, no bias / dbias; it needs lse and a 16-byte aligned table", who);
+  OFA_REQUIRE(!c.seg || (c.rows_q > 0 && c.rows_k > 0 && c.Tpad >= c.rows_q), OFA_ERR_INVALID, "%s: ragged mode needs rows_q / rows_k and Tpad >= rows_q", who);
+  OFA_REQUIRE(OFA_DT_OK(c.c_attn_dtype), OFA_ERR_INVALID, "%s: bad c_attn dtype %d", who, c.c_attn_dtype);
+  if (!bwd) return 0;
+  OFA_REQUIRE((!c.cs_q || c.cs_ldq >= (int64_t)c.heads * HD) && ((!c.cs_k && !c.cs_v) || c.cs_ldk >= (int64_t)c.heads * HD), OFA_ERR_INVALID,
+              "attn_bwd: a column-sum partial row holds heads * 64 = %d floats (row strides %lld / %lld)", c.heads * HD, (long long)c.cs_ldq, (long long)c.cs_ldk);
+  OFA_REQUIRE(!c.cs_c || c.c_attn, OFA_ERR_INVALID, "attn_bwd: cs_c (partial sums of the c_attn gradient) without c_attn");
+  if (shared && c.dbias) {
+    const DsumPlan p = dsum_plan(c);
+    const long long need = (long long)p.nchunk * c.heads * c.Tb * c.Sb * 4;
+    OFA_REQUIRE(OFA_DT_OK(c.dbias_dtype), OFA_ERR_INVALID, "attn_bwd: bad dbias dtype %d", c.dbias_dtype);
+    OFA_REQUIRE(p.direct || (c.ws && c.ws_bytes >= need), OFA_ERR_INVALID, "attn_bwd: the batch-sum kernel needs %lld bytes of workspace for %d chunks", need, p.nchunk);
+    OFA_REQUIRE(dsum_lds(p) <= 64 * 1024, OFA_ERR_UNSUPPORTED, "attn_bwd: %d samples per chunk exceed the batch-sum kernel's geometry table", p.bper);
+  }
   return 0;
+}
+
+static AttnL attn_fill(const ofa_attn_call& c, bool bwd) {
+  const bool shared = c.bias_swz_row != nullptr;
+  AttnL a{};
+  a.q = (const bf16_t*)c.q; a.k = (const bf16_t*)c.k; a.v = (const bf16_t*)c.v; a.kpm = c.kpm; a.c_attn = c.c_attn; a.c_dt = c.c_attn_dtype;
+  a.out = (bf16_t*)c.out; a.lse = c.lse;     // backward: out != NULL -> the dQ kernel computes delta itself (and writes it)
+  a.B = c.B; a.heads = c.heads; a.T = c.T; a.S = c.S; a.Tpad = c.Tpad; a.ldq = c.ldq; a.ldk = c.ldk; a.ldo = c.ldo;
+  a.scale = c.scale; a.causal = c.causal; a.seg = c.seg; a.rows_q = c.rows_q; a.rows_k = c.rows_k;
+  if (shared) {
+    a.bias_sr = (const bf16_t*)c.bias_swz_row; a.bias_nqt = cdiv(c.Tb, 32); a.bias_nkt = cdiv(c.Sb, 32);
+  } else {
+    a.bias = (const bf16_t*)c.bias; a.bias_ld = c.S; a.bias_hs = (int64_t)c.T * c.S; a.bias_bs = (int64_t)c.heads * c.T * c.S;
+  }
+  if (!bwd) return a;
+  a.dout = (const bf16_t*)c.dout; a.delta = c.delta; a.dq = (bf16_t*)c.dq; a.dk = (bf16_t*)c.dk; a.dv = (bf16_t*)c.dv;
+  a.cs_q = c.cs_q; a.cs_k = c.cs_k; a.cs_v = c.cs_v; a.cs_c = c.cs_c; a.cs_ldq = c.cs_ldq; a.cs_ldk = c.cs_ldk;
+  if (shared) {    // the row-major tensor is read by the batch-sum kernel only (bias_bs = 0: one matrix for every sample)
+    a.bias = (const bf16_t*)c.bias; a.bias_ld = c.Sb; a.bias_hs = (int64_t)c.Tb * c.Sb; a.bias_sc = (const bf16_t*)c.bias_swz_col;
+  } else {
+    a.dbias = (bf16_t*)c.dbias;             // dS, dense [B*heads, T, S]
+  }
+  return a;
+}
+
+enum AttnKind { ATTN_FWD, ATTN_DQ, ATTN_DKV };
+static int attn_launch(AttnKind kind, const ofa_attn_call& c, const AttnL& a, void* stream, const char* what) {
+  typedef void (*Kernel)(AttnL);
+  static const Kernel kernels[3][2][3] = {   // [kind][fp16][bias: none, dense, shared]
+      {{attn_fwd_lds_kernel, attn_fwd_bias_lds_kernel, attn_fwd_sbias_lds_kernel},
+       {attn_fwd_f16_lds_kernel, attn_fwd_bias_f16_lds_kernel, attn_fwd_sbias_f16_lds_kernel}},
+      {{attn_bwd_dq_lds_kernel, attn_bwd_dq_bias_lds_kernel, attn_bwd_dq_sbias_lds_kernel},
+       {attn_bwd_dq_f16_lds_kernel, attn_bwd_dq_bias_f16_lds_kernel, attn_bwd_dq_sbias_f16_lds_kernel}},
+      {{attn_bwd_dkv_lds_kernel, attn_bwd_dkv_bias_lds_kernel, attn_bwd_dkv_sbias_lds_kernel},
+       {attn_bwd_dkv_f16_lds_kernel, attn_bwd_dkv_bias_f16_lds_kernel, attn_bwd_dkv_sbias_f16_lds_kernel}}};
+  const int bias = c.bias_swz_row ? 2 : c.bias ? 1 : 0;
+  const dim3 grid(cdiv(kind == ATTN_DKV ? c.S : c.T, 128) + (c.seg ? 1 : 0), c.B * c.heads);   // ragged: one more column zero-fills the filler rows
+  const size_t lds = 4 * TILE_BYTES + (kind == ATTN_DKV ? 2 * STAT_BYTES + (bias == 2 ? 2 * BIAS_STAGE_BYTES : 0) : 0);
+  hipLaunchKernelGGL(kernels[kind][c.dtype == OFA_F16][bias], grid, dim3(256), lds, (hipStream_t)stream, a);
+  return check_launch(what);
 }
 
 }  // namespace ofa
 using namespace ofa;
 
-extern "C" int ofa_attn_fwd(const void* q, const void* k, const void* v, const void* bias, const uint8_t* kpm,
-                            const void* c_attn, int c_attn_dtype, void* out, float* lse, int B, int heads, int T, int S,
-                            int Tpad, int64_t ldq, int64_t ldk, int64_t ldo, float scale, int causal, const int32_t* seg,
-                            int rows_q, int rows_k, int dtype, void* stream) {
-  if (int rc = attnl_check(B, heads, T, S, Tpad, ldq, ldk, ldo, dtype)) return rc;
-  OFA_REQUIRE(q && k && v && out, OFA_ERR_INVALID, "attn_fwd: null pointer");
-  OFA_REQUIRE(scale > 0.f, OFA_ERR_INVALID, "attn_fwd: the score scale must be positive (row maxima are taken on the raw scores), got %g", (double)scale);
-  OFA_REQUIRE(!seg || (!bias && !kpm && lse && !((uintptr_t)seg & 15)), OFA_ERR_INVALID,
-              "attn_fwd: the ragged (seg) mode takes no bias / key-padding mask, needs lse and a 16-byte aligned table");
-  OFA_REQUIRE(OFA_DT_OK(c_attn_dtype), OFA_ERR_INVALID, "attn_fwd: bad c_attn dtype %d", c_attn_dtype);
-  AttnL a{};
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.bias = (const bf16_t*)bias; a.kpm = kpm;
-  a.c_attn = c_attn; a.c_dt = c_attn_dtype; a.out = (bf16_t*)out; a.lse = lse; a.B = B; a.heads = heads; a.T = T; a.S = S; a.Tpad = Tpad;
-  a.ldq = ldq; a.ldk = ldk; a.ldo = ldo; a.scale = scale; a.causal = causal; a.seg = seg; a.rows_q = rows_q; a.rows_k = rows_k;
-  a.bias_ld = S; a.bias_hs = (int64_t)T * S; a.bias_bs = (int64_t)heads * T * S;
-  OFA_REQUIRE(!seg || (rows_q > 0 && rows_k > 0 && Tpad >= rows_q), OFA_ERR_INVALID, "attn_fwd: ragged mode needs rows_q / rows_k and Tpad >= rows_q");
-  const dim3 grid(cdiv(T, 128) + (seg ? 1 : 0), B * heads);
-  auto kern = dtype == OFA_F16 ? (bias ? attn_fwd_bias_f16_lds_kernel : attn_fwd_f16_lds_kernel) : (bias ? attn_fwd_bias_lds_kernel : attn_fwd_lds_kernel);
-  hipLaunchKernelGGL(kern, grid, dim3(256), 4 * TILE_BYTES, (hipStream_t)stream, a);
-  return check_launch("attn_fwd");
-}
-
-// the optional column-sum outputs of the backward kernels (AttnL::cs_*)
-struct AttnCs { float* q; int64_t ldq; float* k; float* v; int64_t ldk; float* c; };
-static int attn_cs_set(AttnL& a, const AttnCs& cs, int heads, const void* c_attn) {
-  OFA_REQUIRE((!cs.q || cs.ldq >= (int64_t)heads * HD) && ((!cs.k && !cs.v) || cs.ldk >= (int64_t)heads * HD), OFA_ERR_INVALID,
-              "attn_bwd: a column-sum partial row holds heads * 64 = %d floats (row strides %lld / %lld)", heads * HD, (long long)cs.ldq, (long long)cs.ldk);
-  OFA_REQUIRE(!cs.c || c_attn, OFA_ERR_INVALID, "attn_bwd: cs_c (partial sums of the c_attn gradient) without c_attn");
-  a.cs_q = cs.q; a.cs_k = cs.k; a.cs_v = cs.v; a.cs_c = cs.c; a.cs_ldq = cs.ldq; a.cs_ldk = cs.ldk;
-  return 0;
-}
-
-static int attn_bwd_impl(const void* q, const void* k, const void* v, const void* dout, const void* bias,
-                            const uint8_t* kpm, const void* c_attn, int c_attn_dtype, const float* lse, float* delta,
-                            const void* out, void* dq, void* dk, void* dv, void* dbias, int B, int heads, int T, int S, int Tpad,
-                            int64_t ldq, int64_t ldk, int64_t ldo, float scale, int causal, const int32_t* seg, int rows_q,
-                            int rows_k, int dtype, void* stream, const AttnCs& cs) {
-  if (int rc = attnl_check(B, heads, T, S, Tpad, ldq, ldk, ldo, dtype)) return rc;
-  OFA_REQUIRE(!seg || (!bias && !kpm && !dbias && !((uintptr_t)seg & 15)), OFA_ERR_INVALID,
-              "attn_bwd: the ragged (seg) mode takes no bias / key-padding mask / dbias and a 16-byte aligned table");
-  OFA_REQUIRE(OFA_DT_OK(c_attn_dtype), OFA_ERR_INVALID, "attn_bwd: bad c_attn dtype %d", c_attn_dtype);
-  OFA_REQUIRE(q && k && v && dout && lse && delta && dq && dk && dv, OFA_ERR_INVALID, "attn_bwd: null pointer");
-  AttnL a{};
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.dout = (const bf16_t*)dout;
-  a.bias = (const bf16_t*)bias; a.kpm = kpm; a.c_attn = c_attn; a.c_dt = c_attn_dtype; a.lse = const_cast<float*>(lse); a.delta = delta;
-  a.out = (bf16_t*)const_cast<void*>(out);   // != NULL: the dQ kernel computes delta itself (and writes it)
-  a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv; a.dbias = (bf16_t*)dbias; a.B = B; a.heads = heads; a.T = T;
-  a.S = S; a.Tpad = Tpad; a.ldq = ldq; a.ldk = ldk; a.ldo = ldo; a.scale = scale; a.causal = causal; a.seg = seg;
-  a.rows_q = rows_q; a.rows_k = rows_k;
-  a.bias_ld = S; a.bias_hs = (int64_t)T * S; a.bias_bs = (int64_t)heads * T * S;
-  OFA_REQUIRE(!seg || (rows_q > 0 && rows_k > 0 && Tpad >= rows_q), OFA_ERR_INVALID, "attn_bwd: ragged mode needs rows_q / rows_k and Tpad >= rows_q");
-  if (int rc = attn_cs_set(a, cs, heads, c_attn)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 q_grid(cdiv(T, 128) + (seg ? 1 : 0), B * heads);
-  auto dq_kern = dtype == OFA_F16 ? (bias ? attn_bwd_dq_bias_f16_lds_kernel : attn_bwd_dq_f16_lds_kernel) : (bias ? attn_bwd_dq_bias_lds_kernel : attn_bwd_dq_lds_kernel);
-  hipLaunchKernelGGL(dq_kern, q_grid, dim3(256), 4 * TILE_BYTES, st, a);
-  int rc = check_launch("attn_bwd_dq");
-  if (rc) return rc;
-  const dim3 kv_grid(cdiv(S, 128) + (seg ? 1 : 0), B * heads);
-  auto kv_kern = dtype == OFA_F16 ? (bias ? attn_bwd_dkv_bias_f16_lds_kernel : attn_bwd_dkv_f16_lds_kernel) : (bias ? attn_bwd_dkv_bias_lds_kernel : attn_bwd_dkv_lds_kernel);
-  hipLaunchKernelGGL(kv_kern, kv_grid, dim3(256), 4 * TILE_BYTES + 2 * STAT_BYTES, st, a);
-  return check_launch("attn_bwd_dkv");
-}
-
-extern "C" int ofa_attn_bwd(const void* q, const void* k, const void* v, const void* dout, const void* bias,
-                            const uint8_t* kpm, const void* c_attn, int c_attn_dtype, const float* lse, float* delta,
-                            const void* out, void* dq, void* dk, void* dv, void* dbias, int B, int heads, int T, int S, int Tpad,
-                            int64_t ldq, int64_t ldk, int64_t ldo, float scale, int causal, const int32_t* seg, int rows_q,
-                            int rows_k, int dtype, void* stream) {
-  return attn_bwd_impl(q, k, v, dout, bias, kpm, c_attn, c_attn_dtype, lse, delta, out, dq, dk, dv, dbias, B, heads, T, S, Tpad, ldq, ldk, ldo,
-                       scale, causal, seg, rows_q, rows_k, dtype, stream, AttnCs{});
+extern "C" int ofa_attn_fwd(const ofa_attn_call* c, void* stream) {
+  if (int rc = attn_check(*c, false)) return rc;
+  return attn_launch(ATTN_FWD, *c, attn_fill(*c, false), stream, "attn_fwd");
 }
 
 extern "C" int ofa_attn_cs_slots(int B, int rows) { return B * cdiv(rows, 128) * 4; }   // one partial row per wave of a (sample, tile) workgroup
-
-extern "C" int ofa_attn_bwd_cs(const void* q, const void* k, const void* v, const void* dout, const void* bias,
-                               const uint8_t* kpm, const void* c_attn, int c_attn_dtype, const float* lse, float* delta,
-                               const void* out, void* dq, void* dk, void* dv, void* dbias, int B, int heads, int T, int S, int Tpad,
-                               int64_t ldq, int64_t ldk, int64_t ldo, float scale, int causal, const int32_t* seg, int rows_q,
-                               int rows_k, int dtype, float* cs_q, int64_t cs_ldq, float* cs_k, float* cs_v, int64_t cs_ldk, float* cs_c,
-                               void* stream) {
-  return attn_bwd_impl(q, k, v, dout, bias, kpm, c_attn, c_attn_dtype, lse, delta, out, dq, dk, dv, dbias, B, heads, T, S, Tpad, ldq, ldk, ldo,
-                       scale, causal, seg, rows_q, rows_k, dtype, stream, AttnCs{cs_q, cs_ldq, cs_k, cs_v, cs_ldk, cs_c});
-}
-
-
-// ---- batch-SHARED position bias [heads, Tb, Sb]: the swizzled-image kernels (BIAS 2) + the batch-summed dS kernel
-static int sbias_check(const void* bias_sr, int Tb, int Sb, int T, int S, const int32_t* seg) {
-  OFA_REQUIRE(bias_sr && Tb > 0 && Sb > 0, OFA_ERR_INVALID, "attn_sbias: the swizzled bias image of [heads, Tb, Sb] is required (Tb=%d Sb=%d)", Tb, Sb);
-  OFA_REQUIRE(!((uintptr_t)bias_sr & 15), OFA_ERR_INVALID, "attn_sbias: the swizzled bias image must be 16-byte aligned");
-  OFA_REQUIRE(Tb >= T && Sb >= S, OFA_ERR_INVALID, "attn_sbias: the bias covers %d x %d positions, the call needs %d x %d", Tb, Sb, T, S);
-  (void)seg;
-  return 0;
-}
-
-// bias_swz_row: the row image of the [heads, Tb, Sb] bias written by ofa_bias_build (ofa_bias_swz_elems elements)
-extern "C" int ofa_attn_sbias_fwd(const void* q, const void* k, const void* v, const void* bias_swz_row, int Tb, int Sb, const uint8_t* kpm,
-                                  const void* c_attn, int c_attn_dtype, void* out, float* lse, int B, int heads, int T, int S, int Tpad,
-                                  int64_t ldq, int64_t ldk, int64_t ldo, float scale, int causal, const int32_t* seg, int rows_q,
-                                  int rows_k, int dtype, void* stream) {
-  if (int rc = attnl_check(B, heads, T, S, Tpad, ldq, ldk, ldo, dtype)) return rc;
-  if (int rc = sbias_check(bias_swz_row, Tb, Sb, T, S, seg)) return rc;
-  OFA_REQUIRE(q && k && v && out && lse, OFA_ERR_INVALID, "attn_sbias_fwd: null pointer");
-  OFA_REQUIRE(scale > 0.f, OFA_ERR_INVALID, "attn_sbias_fwd: the score scale must be positive, got %g", (double)scale);
-  OFA_REQUIRE(!seg || (!kpm && !((uintptr_t)seg & 15) && rows_q > 0 && rows_k > 0 && Tpad >= rows_q), OFA_ERR_INVALID,
-              "attn_sbias_fwd: the ragged (seg) mode takes no key-padding mask, a 16-byte aligned table, rows_q / rows_k and Tpad >= rows_q");
-  OFA_REQUIRE(OFA_DT_OK(c_attn_dtype), OFA_ERR_INVALID, "attn_sbias_fwd: bad c_attn dtype %d", c_attn_dtype);
-  AttnL a{};
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.kpm = kpm;
-  a.c_attn = c_attn; a.c_dt = c_attn_dtype; a.out = (bf16_t*)out; a.lse = lse; a.B = B; a.heads = heads; a.T = T; a.S = S; a.Tpad = Tpad;
-  a.ldq = ldq; a.ldk = ldk; a.ldo = ldo; a.scale = scale; a.causal = causal; a.seg = seg; a.rows_q = rows_q; a.rows_k = rows_k;
-  a.bias_sr = (const bf16_t*)bias_swz_row; a.bias_nqt = cdiv(Tb, 32); a.bias_nkt = cdiv(Sb, 32);
-  const dim3 grid(cdiv(T, 128) + (seg ? 1 : 0), B * heads);
-  auto kern = dtype == OFA_F16 ? attn_fwd_sbias_f16_lds_kernel : attn_fwd_sbias_lds_kernel;
-  hipLaunchKernelGGL(kern, grid, dim3(256), 4 * TILE_BYTES, (hipStream_t)stream, a);
-  return check_launch("attn_sbias_fwd");
-}
 
 extern "C" int ofa_attn_sbias_chunks(int B, int heads, int Tb, int Sb) {
   const int64_t tiles = (int64_t)cdiv(Sb, 64) * cdiv(Tb, 128) * heads;
@@ -1564,83 +1542,22 @@ extern "C" int ofa_attn_sbias_chunks(int B, int heads, int Tb, int Sb) {
   return cdiv(B, bper);
 }
 
-// bias: the row-major [heads, Tb, Sb] tensor (read by the batch-sum kernel only: may be NULL when dbias_sum is);
-// bias_swz_row / bias_swz_col: its two swizzled images (ofa_bias_build)
-static int attn_sbias_bwd_impl(const void* q, const void* k, const void* v, const void* dout, const void* bias,
-                                  const void* bias_swz_row, const void* bias_swz_col, int Tb, int Sb, const uint8_t* kpm, const void* c_attn, int c_attn_dtype, const float* lse, float* delta,
-                                  const void* out, void* dq, void* dk, void* dv, void* dbias_sum, int dbias_dtype, float* ws, int64_t ws_bytes, int B,
-                                  int heads, int T, int S, int Tpad, int64_t ldq, int64_t ldk, int64_t ldo, float scale, int causal,
-                                  const int32_t* seg, int rows_q, int rows_k, int dtype, void* stream, const AttnCs& cs) {
-  if (int rc = attnl_check(B, heads, T, S, Tpad, ldq, ldk, ldo, dtype)) return rc;
-  if (int rc = sbias_check(bias_swz_row, Tb, Sb, T, S, seg)) return rc;
-  OFA_REQUIRE(bias_swz_col && !((uintptr_t)bias_swz_col & 15) && (bias || !dbias_sum), OFA_ERR_INVALID,
-              "attn_sbias_bwd: the column image of the bias (16-byte aligned) and, for dbias_sum, the row-major tensor are required");
-  OFA_REQUIRE(!seg || (!kpm && !((uintptr_t)seg & 15) && rows_q > 0 && rows_k > 0 && Tpad >= rows_q), OFA_ERR_INVALID,
-              "attn_sbias_bwd: the ragged (seg) mode takes no key-padding mask, a 16-byte aligned table, rows_q / rows_k and Tpad >= rows_q");
-  OFA_REQUIRE(OFA_DT_OK(c_attn_dtype), OFA_ERR_INVALID, "attn_sbias_bwd: bad c_attn dtype %d", c_attn_dtype);
-  OFA_REQUIRE(q && k && v && dout && lse && delta && out && dq && dk && dv, OFA_ERR_INVALID, "attn_sbias_bwd: null pointer");
-  AttnL a{};
-  a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.dout = (const bf16_t*)dout;
-  a.bias = (const bf16_t*)bias; a.kpm = kpm; a.c_attn = c_attn; a.c_dt = c_attn_dtype; a.lse = const_cast<float*>(lse); a.delta = delta;
-  a.out = (bf16_t*)const_cast<void*>(out);
-  a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv; a.B = B; a.heads = heads; a.T = T;
-  a.S = S; a.Tpad = Tpad; a.ldq = ldq; a.ldk = ldk; a.ldo = ldo; a.scale = scale; a.causal = causal; a.seg = seg;
-  a.rows_q = rows_q; a.rows_k = rows_k;
-  a.bias_ld = Sb; a.bias_hs = (int64_t)Tb * Sb; a.bias_bs = 0;
-  a.bias_sr = (const bf16_t*)bias_swz_row; a.bias_sc = (const bf16_t*)bias_swz_col; a.bias_nqt = cdiv(Tb, 32); a.bias_nkt = cdiv(Sb, 32);
-  if (int rc = attn_cs_set(a, cs, heads, c_attn)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 q_grid(cdiv(T, 128) + (seg ? 1 : 0), B * heads);
-  auto dq_kern = dtype == OFA_F16 ? attn_bwd_dq_sbias_f16_lds_kernel : attn_bwd_dq_sbias_lds_kernel;
-  hipLaunchKernelGGL(dq_kern, q_grid, dim3(256), 4 * TILE_BYTES, st, a);
-  int rc = check_launch("attn_sbias_bwd_dq");
-  if (rc) return rc;
-  const dim3 kv_grid(cdiv(S, 128) + (seg ? 1 : 0), B * heads);
-  auto kv_kern = dtype == OFA_F16 ? attn_bwd_dkv_sbias_f16_lds_kernel : attn_bwd_dkv_sbias_lds_kernel;
-  hipLaunchKernelGGL(kv_kern, kv_grid, dim3(256), 4 * TILE_BYTES + 2 * STAT_BYTES + 2 * BIAS_STAGE_BYTES, st, a);
-  rc = check_launch("attn_sbias_bwd_dkv");
-  if (rc || !dbias_sum) return rc;
-  // G = sum_b dS (after the dQ kernel: it wrote delta): [128 x 64] tiles of one head; the batch is cut into chunks when the tiles
-  // alone would leave the chip idle, the chunks' fp32 partials are folded in chunk order
-  const int nchunk = ofa_attn_sbias_chunks(B, heads, Tb, Sb);
-  OFA_REQUIRE(OFA_DT_OK(dbias_dtype), OFA_ERR_INVALID, "attn_sbias_bwd: bad dbias dtype %d", dbias_dtype);
-  const bool out16 = nchunk == 1 && dbias_dtype == dtype;          // one chunk, gradient in the operands' 16-bit type: rounded in the kernel
-  const bool direct = (nchunk == 1 && dbias_dtype == OFA_F32) || out16;   // the kernel writes dbias_sum itself; otherwise the fold (+ cast) does
-  OFA_REQUIRE(direct || (ws && ws_bytes >= (int64_t)nchunk * heads * Tb * Sb * 4), OFA_ERR_INVALID,
-              "attn_sbias_bwd: the batch-sum kernel needs %lld bytes of workspace for %d chunks", (long long)nchunk * heads * Tb * Sb * 4, nchunk);
-  const int bper = cdiv(B, nchunk);
-  {
-    const dim3 g(cdiv(Sb, 64), cdiv(Tb, 128), heads * nchunk);
-    auto kn = dtype == OFA_F16 ? attn_bwd_dsum_f16_kernel : attn_bwd_dsum_kernel;
-    float* dst = direct ? (float*)dbias_sum : ws;
-    const size_t lds = 8 * TILE_BYTES + (size_t)bper * 16;
-    OFA_REQUIRE(lds <= 64 * 1024, OFA_ERR_UNSUPPORTED, "attn_sbias_bwd: %d samples per chunk exceed the batch-sum kernel's geometry table", bper);
-    hipLaunchKernelGGL(kn, g, dim3(256), lds, st, a, dst, (int64_t)Sb, (int64_t)Tb * Sb, (int64_t)heads * Tb * Sb, Tb, Sb, nchunk, bper, (int)out16);
-    rc = check_launch("attn_sbias_bwd_dsum");
-    if (rc || direct) return rc;
-    ofa_fold_job job{ws, dbias_sum, (int64_t)heads * Tb * Sb, (int64_t)heads * Tb * Sb, nchunk, 0, 1.0f, dbias_dtype};
-    return ofa_fold_batched(&job, 1, stream);
-  }
-}
-
-extern "C" int ofa_attn_sbias_bwd(const void* q, const void* k, const void* v, const void* dout, const void* bias,
-                                  const void* bias_swz_row, const void* bias_swz_col, int Tb, int Sb, const uint8_t* kpm, const void* c_attn, int c_attn_dtype, const float* lse, float* delta,
-                                  const void* out, void* dq, void* dk, void* dv, void* dbias_sum, int dbias_dtype, float* ws, int64_t ws_bytes, int B,
-                                  int heads, int T, int S, int Tpad, int64_t ldq, int64_t ldk, int64_t ldo, float scale, int causal,
-                                  const int32_t* seg, int rows_q, int rows_k, int dtype, void* stream) {
-  return attn_sbias_bwd_impl(q, k, v, dout, bias, bias_swz_row, bias_swz_col, Tb, Sb, kpm, c_attn, c_attn_dtype, lse, delta, out, dq, dk, dv, dbias_sum,
-                             dbias_dtype, ws, ws_bytes, B, heads, T, S, Tpad, ldq, ldk, ldo, scale, causal, seg, rows_q, rows_k, dtype, stream, AttnCs{});
-}
-
-extern "C" int ofa_attn_sbias_bwd_cs(const void* q, const void* k, const void* v, const void* dout, const void* bias,
-                                     const void* bias_swz_row, const void* bias_swz_col, int Tb, int Sb, const uint8_t* kpm, const void* c_attn, int c_attn_dtype, const float* lse, float* delta,
-                                     const void* out, void* dq, void* dk, void* dv, void* dbias_sum, int dbias_dtype, float* ws, int64_t ws_bytes, int B,
-                                     int heads, int T, int S, int Tpad, int64_t ldq, int64_t ldk, int64_t ldo, float scale, int causal,
-                                     const int32_t* seg, int rows_q, int rows_k, int dtype, float* cs_q, int64_t cs_ldq, float* cs_k, float* cs_v,
-                                     int64_t cs_ldk, float* cs_c, void* stream) {
-  return attn_sbias_bwd_impl(q, k, v, dout, bias, bias_swz_row, bias_swz_col, Tb, Sb, kpm, c_attn, c_attn_dtype, lse, delta, out, dq, dk, dv, dbias_sum,
-                             dbias_dtype, ws, ws_bytes, B, heads, T, S, Tpad, ldq, ldk, ldo, scale, causal, seg, rows_q, rows_k, dtype, stream,
-                             AttnCs{cs_q, cs_ldq, cs_k, cs_v, cs_ldk, cs_c});
+extern "C" int ofa_attn_bwd(const ofa_attn_call* c, void* stream) {
+  if (int rc = attn_check(*c, true)) return rc;
+  const AttnL a = attn_fill(*c, true);
+  if (int rc = attn_launch(ATTN_DQ, *c, a, stream, "attn_bwd_dq")) return rc;
+  int rc = attn_launch(ATTN_DKV, *c, a, stream, "attn_bwd_dkv");
+  if (rc || !c->bias_swz_row || !c->dbias) return rc;
+  // the shared bias' gradient, after the dQ kernel: it wrote delta
+  const DsumPlan p = dsum_plan(*c);
+  const int64_t slab = (int64_t)c->heads * c->Tb * c->Sb;
+  const dim3 grid(cdiv(c->Sb, 64), cdiv(c->Tb, 128), c->heads * p.nchunk);
+  hipLaunchKernelGGL(c->dtype == OFA_F16 ? attn_bwd_dsum_f16_kernel : attn_bwd_dsum_kernel, grid, dim3(256), dsum_lds(p), (hipStream_t)stream, a,
+                     p.direct ? (float*)c->dbias : c->ws, (int64_t)c->Sb, (int64_t)c->Tb * c->Sb, slab, c->Tb, c->Sb, p.nchunk, p.bper, (int)p.out16);
+  rc = check_launch("attn_bwd_dsum");
+  if (rc || p.direct) return rc;
+  ofa_fold_job job{c->ws, c->dbias, slab, slab, p.nchunk, 0, 1.0f, c->dbias_dtype};
+  return ofa_fold_batched(&job, 1, stream);
 }
 
 #ifdef OFA_ATTN_TIMELINE

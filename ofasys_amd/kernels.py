@@ -574,70 +574,84 @@ def _shared_swz(bias, bias_shared):
     return bias_build(bias, want_out=False)[1]
 
 
-def attn_fwd(q, k, v, heads, scale, bias=None, kpm=None, c_attn=None, causal=False, seg=None, bias_shared=False):
-    """q [B,T,D], k, v [B,S,D] (row views of a packed buffer are fine) -> out [B,T,D], lse [B*heads, Tpad].
-    seg (packing.Segments): ragged mode -- q [1,rows_q,D], k, v [1,rows_k,D] hold the samples back to back, out rows outside
-    every segment are zero, lse is [heads, pad32(rows_q)] by packed row.
-    bias_shared: bias is [heads, Tb, Sb], the same for every sample, indexed by the position inside the sample (ofa_attn_sbias_*)."""
+class _AttnCall(ctypes.Structure):     # ofa_attn_call
+    _fields_ = ([(n, ctypes.c_void_p) for n in ("q k v dout out lse delta dq dk dv bias bias_swz_row bias_swz_col dbias ws kpm c_attn seg "
+                                                "cs_q cs_k cs_v cs_c").split()]
+                + [(n, ctypes.c_int64) for n in "ldq ldk ldo ws_bytes cs_ldq cs_ldk".split()]
+                + [(n, ctypes.c_int32) for n in "B heads T S Tpad Tb Sb causal rows_q rows_k dtype c_attn_dtype dbias_dtype".split()]
+                + [("scale", ctypes.c_float)])
+
+
+def _attn_call(q, k, v, heads, scale, bias, kpm, c_attn, causal, seg, bias_shared, dense_grads=False):
+    """The part of an ofa_attn_call the forward and the backward share -> (call, q, k, v, bias, swz): the operands as the kernels read
+    them, the shared bias as [heads, Tb, Sb] with its (row image, column image) pair.  call.keep holds every tensor the call points at.
+    dense_grads: the backward allocates dq / dk / dv itself -- dq is written with ld = ldq, dk / dv with ld = ldk, so dense strides
+    give it dense outputs."""
     q, ldq = _rows3(q)
     k, v, ldk = _same_ld(k, v)
     B, T, D = q.shape
     S = k.shape[1]
-    Tpad = pad32(T)
+    if dense_grads and ldq != D:
+        q, ldq = q.contiguous(), D
+    if dense_grads and ldk != D:
+        k, v, ldk = k.contiguous(), v.contiguous(), D
+    c, swz = _AttnCall(), None
+    c.q, c.k, c.v, c.c_attn, c.c_attn_dtype = ptr(q), ptr(k), ptr(v), ptr(c_attn), _c_dtype(c_attn)
+    c.heads, c.Tpad, c.ldq, c.ldk, c.scale, c.causal, c.dtype = heads, pad32(T), ldq, ldk, float(scale), int(causal), dtype_code(q)
+    c.B, c.T, c.S = B, T, S
     if bias_shared:
         bias = _shared_bias(bias, heads, q)
-        Tb, Sb = bias.shape[1], bias.shape[2]
-        bias = _shared_swz(bias, bias_shared)[0]            # the kernel reads the row image
-        if seg is not None:
-            assert B == 1 and kpm is None and seg.rows_q == T and seg.rows_k == S and Tb >= seg.max_q - 31 and Sb >= seg.max_k - 31
-            out = torch.empty(1, T, D, dtype=q.dtype, device=q.device)
-            lse = torch.empty(heads, Tpad, dtype=torch.float32, device=q.device)
-            lib().call("ofa_attn_sbias_fwd", ptr(q), ptr(k), ptr(v), ptr(bias), Tb, Sb, None, ptr(c_attn), _c_dtype(c_attn), ptr(out),
-                       ptr(lse), seg.batch, heads, min(seg.max_q, Tb), min(seg.max_k, Sb), Tpad, ldq, ldk, D, float(scale), int(causal),
-                       ptr(seg.table), T, S, dtype_code(q), stream())
-            return out, lse
-        out = torch.empty(B, T, D, dtype=q.dtype, device=q.device)
-        lse = torch.empty(B * heads, Tpad, dtype=torch.float32, device=q.device)
-        if kpm is not None:
-            kpm = _u8(kpm)
-        lib().call("ofa_attn_sbias_fwd", ptr(q), ptr(k), ptr(v), ptr(bias), Tb, Sb, ptr(kpm), ptr(c_attn), _c_dtype(c_attn), ptr(out),
-                   ptr(lse), B, heads, T, S, Tpad, ldq, ldk, D, float(scale), int(causal), None, 0, 0, dtype_code(q), stream())
-        return out, lse
-    if seg is not None:
-        assert B == 1 and bias is None and kpm is None and seg.rows_q == T and seg.rows_k == S, (B, T, S, seg.rows_q, seg.rows_k)
-        out = torch.empty(1, T, D, dtype=q.dtype, device=q.device)          # filler rows are zeroed by the kernel
-        lse = torch.empty(heads, Tpad, dtype=torch.float32, device=q.device)
-        lib().call("ofa_attn_fwd", ptr(q), ptr(k), ptr(v), None, None, ptr(c_attn), _c_dtype(c_attn), ptr(out), ptr(lse),
-                   seg.batch, heads, seg.max_q, seg.max_k, Tpad, ldq, ldk, D, float(scale), int(causal), ptr(seg.table),
-                   T, S, dtype_code(q), stream())
-        return out, lse
-    out = torch.empty(B, T, D, dtype=q.dtype, device=q.device)
-    lse = torch.empty(B * heads, Tpad, dtype=torch.float32, device=q.device)
-    if bias is not None:
+        c.Tb, c.Sb = Tb, Sb = bias.shape[1], bias.shape[2]
+        swz = _shared_swz(bias, bias_shared)
+        c.bias_swz_row = ptr(swz[0])                        # (the forward reads the row image alone)
+    elif bias is not None:
         bias = bias.contiguous()
-    if kpm is not None:
+        c.bias = ptr(bias)
+    if seg is not None:
+        assert B == 1 and kpm is None and seg.rows_q == T and seg.rows_k == S, (B, T, S, seg.rows_q, seg.rows_k)
+        assert (bias is None) if not bias_shared else (Tb >= seg.max_q - 31 and Sb >= seg.max_k - 31)
+        c.B, c.T, c.S = seg.batch, seg.max_q, seg.max_k
+        if bias_shared:
+            c.T, c.S = min(seg.max_q, Tb), min(seg.max_k, Sb)
+        c.seg, c.rows_q, c.rows_k = ptr(seg.table), T, S
+    elif kpm is not None:
         kpm = _u8(kpm)
-    lib().call("ofa_attn_fwd", ptr(q), ptr(k), ptr(v), ptr(bias), ptr(kpm), ptr(c_attn), _c_dtype(c_attn), ptr(out), ptr(lse),
-               B, heads, T, S, Tpad, ldq, ldk, D, float(scale), int(causal), None, 0, 0, dtype_code(q), stream())
+        c.kpm = ptr(kpm)
+    c.keep = [q, k, v, c_attn, bias, swz, kpm, seg]
+    return c, q, k, v, bias, swz
+
+
+def attn_fwd(q, k, v, heads, scale, bias=None, kpm=None, c_attn=None, causal=False, seg=None, bias_shared=False):
+    """q [B,T,D], k, v [B,S,D] (row views of a packed buffer are fine) -> out [B,T,D], lse [B*heads, Tpad].
+    seg (packing.Segments): ragged mode -- q [1,rows_q,D], k, v [1,rows_k,D] hold the samples back to back, out rows outside
+    every segment are zero (the kernel writes them), lse is [heads, pad32(rows_q)] by packed row.
+    bias_shared: bias is [heads, Tb, Sb], the same for every sample, indexed by the position inside the sample."""
+    c, q = _attn_call(q, k, v, heads, scale, bias, kpm, c_attn, causal, seg, bias_shared)[:2]
+    B, T, D = q.shape
+    out = torch.empty(B, T, D, dtype=q.dtype, device=q.device)
+    lse = torch.empty(B * heads, c.Tpad, dtype=torch.float32, device=q.device)
+    c.out, c.lse, c.ldo = ptr(out), ptr(lse), D
+    lib().call("ofa_attn_fwd", ctypes.addressof(c), stream())
     return out, lse
 
 
 def attn_cs_slots(B, T, seg=None, k_side=False):
-    """Partial rows of the column sums the attention backward kernels leave per call (ofa_attn_bwd_cs): one per (sample, 128-row tile)."""
+    """Partial rows of the column sums the attention backward kernels leave per call (ofa_attn_call.cs_*): one per (sample, 128-row tile)."""
     if seg is not None:
         B, T = seg.batch, (seg.max_k if k_side else seg.max_q)
     return lib().cdll.ofa_attn_cs_slots(int(B), int(T))
 
 
-def _cs_args(cs, heads):
+def _cs_args(c, cs, heads):
     """cs = dict(q=, k=, v=, c=): fp32 2-D views [slots, heads * 64] (row stride free, k and v the same; c: [slots, heads] contiguous)."""
-    q, k, v, c = cs.get("q"), cs.get("k"), cs.get("v"), cs.get("c")
+    q, k, v, cc = cs.get("q"), cs.get("k"), cs.get("v"), cs.get("c")
     for t in (q, k, v):
         assert t is None or (t.dtype == torch.float32 and t.stride(1) == 1 and t.shape[1] == heads * 64)
-    assert c is None or (c.dtype == torch.float32 and c.is_contiguous() and c.shape[1] == heads)
+    assert cc is None or (cc.dtype == torch.float32 and cc.is_contiguous() and cc.shape[1] == heads)
     assert k is None or v is None or k.stride(0) == v.stride(0)
     kv = k if k is not None else v
-    return (ptr(q), q.stride(0) if q is not None else 0, ptr(k), ptr(v), kv.stride(0) if kv is not None else 0, ptr(c))
+    c.cs_q, c.cs_k, c.cs_v, c.cs_c = ptr(q), ptr(k), ptr(v), ptr(cc)
+    c.cs_ldq, c.cs_ldk = q.stride(0) if q is not None else 0, kv.stride(0) if kv is not None else 0
 
 
 def attn_bwd(q, k, v, out, dout, lse, heads, scale, bias=None, kpm=None, c_attn=None, causal=False, need_dbias=False,
@@ -646,8 +660,7 @@ def attn_bwd(q, k, v, out, dout, lse, heads, scale, bias=None, kpm=None, c_attn=
     packed [B,T,3D] buffer next to a packed qkv input) -- the kernels write them in place.
     cs: optional dict of fp32 partial-row buffers (see _cs_args / attn_cs_slots) that receive the column sums of dq / dk / dv and
     the per-head sums of delta / c_attn -- the projections' bias gradients and the c_attn gradient, finished by the FoldQueue."""
-    q, ldq = _rows3(q)
-    k, v, ldk = _same_ld(k, v)
+    c, q, k, v, bias, swz = _attn_call(q, k, v, heads, scale, bias, kpm, c_attn, causal, seg, bias_shared, dense_grads=outs is None)
     dout, ldo = _rows3(dout)
     out, ldo2 = _rows3(out)
     if ldo != ldo2:
@@ -655,62 +668,33 @@ def attn_bwd(q, k, v, out, dout, lse, heads, scale, bias=None, kpm=None, c_attn=
         ldo = dout.stride(1)
     B, T, D = q.shape
     S = k.shape[1]
-    Tpad = pad32(T)
-    delta = torch.empty(B * heads, Tpad, dtype=torch.float32, device=q.device)   # rowsum(dO*O): written by the dQ kernel
-    dbias = torch.empty(B * heads, T, S, dtype=q.dtype, device=q.device) if (need_dbias and not bias_shared) else None
-    if bias is not None and not bias_shared:
-        bias = bias.contiguous()
-    if kpm is not None:
-        kpm = _u8(kpm)
+    delta = torch.empty(B * heads, c.Tpad, dtype=torch.float32, device=q.device)   # rowsum(dO*O): written by the dQ kernel
+    dbias = ws = None
+    if need_dbias and not bias_shared:
+        assert seg is None
+        dbias = torch.empty(B * heads, T, S, dtype=q.dtype, device=q.device)
     if outs is not None:
         dq, dk, dv = outs
-        assert dq.stride(1) == ldq and dk.stride(1) == ldk and dv.stride(1) == ldk
+        assert dq.stride(1) == c.ldq and dk.stride(1) == c.ldk and dv.stride(1) == c.ldk
     else:
-        # dq is written with ld = ldq, dk/dv with ld = ldk: give the kernel dense outputs by passing dense strides
-        if ldq != D:
-            q = q.contiguous()
-            ldq = D
-        if ldk != D:
-            k, v = k.contiguous(), v.contiguous()
-            ldk = D
         dq = torch.empty(B, T, D, dtype=q.dtype, device=q.device)     # (ragged mode: the kernels zero the filler rows)
         dk = torch.empty(B, S, D, dtype=q.dtype, device=q.device)
         dv = torch.empty(B, S, D, dtype=q.dtype, device=q.device)
-    csa = _cs_args(cs, heads) if cs else ()
-    fn = "ofa_attn_bwd_cs" if cs else "ofa_attn_bwd"
+    if cs:
+        _cs_args(c, cs, heads)
     if bias_shared:
-        # dbias (when asked for): fp32 [heads, Tb, Sb] = the sum over the batch of dS, from the batch-walking third kernel
-        bias = _shared_bias(bias, heads, q)
-        Tb, Sb = bias.shape[1], bias.shape[2]
-        swz_row, swz_col = _shared_swz(bias, bias_shared)
-        dbias = torch.empty(heads, Tb, Sb, dtype=dbias_dtype, device=q.device) if need_dbias else None   # (16-bit: cast by the chunk fold)
-        ws, ws_bytes = None, 0
+        c.bias, c.bias_swz_col = ptr(bias), ptr(swz[1])
         if need_dbias:
-            nchunk = lib().cdll.ofa_attn_sbias_chunks(B if seg is None else seg.batch, heads, Tb, Sb)
+            # fp32 (or 16-bit: cast by the chunk fold) [heads, Tb, Sb] = the sum over the batch of dS, from the batch-walking third kernel
+            dbias = torch.empty(heads, c.Tb, c.Sb, dtype=dbias_dtype, device=q.device)
+            c.dbias_dtype = dtype_code(dbias)
+            nchunk = lib().cdll.ofa_attn_sbias_chunks(c.B, heads, c.Tb, c.Sb)
             if nchunk > 1 or dbias_dtype not in (torch.float32, q.dtype):
-                ws = torch.empty(nchunk, heads, Tb, Sb, dtype=torch.float32, device=q.device)
-                ws_bytes = ws.numel() * 4
-        if seg is not None:
-            assert B == 1 and kpm is None and seg.rows_q == T and seg.rows_k == S
-            dims = (seg.batch, heads, min(seg.max_q, Tb), min(seg.max_k, Sb), Tpad, ldq, ldk, ldo, float(scale), int(causal), ptr(seg.table), T, S)
-            kp = None
-        else:
-            dims = (B, heads, T, S, Tpad, ldq, ldk, ldo, float(scale), int(causal), None, 0, 0)
-            kp = ptr(kpm)
-        lib().call("ofa_attn_sbias_bwd_cs" if cs else "ofa_attn_sbias_bwd", ptr(q), ptr(k), ptr(v), ptr(dout), ptr(bias), ptr(swz_row),
-                   ptr(swz_col), Tb, Sb, kp, ptr(c_attn), _c_dtype(c_attn), ptr(lse),
-                   ptr(delta), ptr(out), ptr(dq), ptr(dk), ptr(dv), ptr(dbias), dtype_code(dbias) if dbias is not None else F32, ptr(ws),
-                   ws_bytes, *dims, dtype_code(q), *csa, stream())
-        return dq, dk, dv, dbias, delta
-    if seg is not None:
-        assert B == 1 and bias is None and kpm is None and not need_dbias and seg.rows_q == T and seg.rows_k == S
-        lib().call(fn, ptr(q), ptr(k), ptr(v), ptr(dout), None, None, ptr(c_attn), _c_dtype(c_attn), ptr(lse),
-                   ptr(delta), ptr(out), ptr(dq), ptr(dk), ptr(dv), None, seg.batch, heads, seg.max_q, seg.max_k, Tpad, ldq, ldk, ldo,
-                   float(scale), int(causal), ptr(seg.table), T, S, dtype_code(q), *csa, stream())
-        return dq, dk, dv, None, delta
-    lib().call(fn, ptr(q), ptr(k), ptr(v), ptr(dout), ptr(bias), ptr(kpm), ptr(c_attn), _c_dtype(c_attn), ptr(lse),
-               ptr(delta), ptr(out), ptr(dq), ptr(dk), ptr(dv), ptr(dbias), B, heads, T, S, Tpad, ldq, ldk, ldo, float(scale),
-               int(causal), None, 0, 0, dtype_code(q), *csa, stream())
+                ws = torch.empty(nchunk, heads, c.Tb, c.Sb, dtype=torch.float32, device=q.device)
+                c.ws, c.ws_bytes = ptr(ws), ws.numel() * 4
+    c.dout, c.out, c.lse, c.delta, c.ldo = ptr(dout), ptr(out), ptr(lse), ptr(delta), ldo
+    c.dq, c.dk, c.dv, c.dbias = ptr(dq), ptr(dk), ptr(dv), ptr(dbias)
+    lib().call("ofa_attn_bwd", ctypes.addressof(c), stream())
     return dq, dk, dv, dbias, delta
 
 

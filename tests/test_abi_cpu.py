@@ -90,7 +90,88 @@ def test_status_codes_not_asserts():
     with pytest.raises(L.OfaError, match="dtype"):                                                     # an unknown dtype code
         h.call("ofa_layernorm_fwd", 1, 1, 1, 1, 1, 1, 4, 8, 1e-5, 7, None)
     with pytest.raises(L.OfaError, match="bf16"):
-        h.call("ofa_attn_fwd", 1, 1, 1, None, None, None, L.F32, 1, None, 1, 1, 32, 32, 32, 64, 64, 64, 1.0, 0, None, 0, 0, L.F32, None)
+        from ofasys_amd import kernels as K
+        call = K._AttnCall(q=1, k=1, v=1, out=1, B=1, heads=1, T=32, S=32, Tpad=32, ldq=64, ldk=64, ldo=64, scale=1.0, dtype=L.F32)
+        h.call("ofa_attn_fwd", ctypes.addressof(call), None)
+
+
+def test_attn_call_mirrors_the_c_struct():
+    """kernels._AttnCall is as large as the static_assert in csrc/attention.hip says ofa_attn_call is (no padding on either side)."""
+    import re
+    from ofasys_amd import kernels as K
+    src = open(os.path.join(os.path.dirname(L.LIB_PATH), "csrc", "attention.hip")).read()
+    assert ctypes.sizeof(K._AttnCall) == int(re.search(r"static_assert\(sizeof\(ofa_attn_call\) == (\d+)", src).group(1)) == 280
+
+
+_P = 4096                     # a fake, 16-byte aligned device address: every descriptor below is refused before any launch
+_SEG = dict(seg=_P, rows_q=64, rows_k=64)
+_DSUM = dict(bias=_P, dbias=_P, ws=_P)
+_ATTN_REFUSALS = [
+    # (entry, shared bias, the one change to a valid-looking descriptor, the message of the check that refuses it)
+    ("fwd", 0, dict(dtype=L.F32), r"status 2.*bf16 / fp16 only \(dtype 0\)"),
+    ("bwd", 1, dict(dtype=7), r"status 2.*bf16 / fp16 only \(dtype 7\)"),
+    ("fwd", 0, dict(heads=0), "bad shape B=2 heads=0 T=40 S=50"),
+    ("bwd", 0, dict(S=-3), "bad shape B=2 heads=2 T=40 S=-3"),
+    ("fwd", 0, dict(ldq=132), "leading dims must be multiples of 8"),
+    ("bwd", 1, dict(ldo=129), "leading dims must be multiples of 8"),
+    ("fwd", 0, dict(Tpad=32), r"Tpad must be a multiple of 32 covering T \(T=40 Tpad=32\)"),
+    ("bwd", 0, dict(Tpad=72), r"Tpad must be a multiple of 32 covering T \(T=40 Tpad=72\)"),
+    ("fwd", 0, dict(scale=0.0), "attn_fwd: the score scale must be positive .*got 0"),
+    ("fwd", 1, dict(scale=-0.125), "attn_fwd: the score scale must be positive .*got -0.125"),
+    ("fwd", 0, dict(v=None), "attn_fwd: null pointer"),
+    ("fwd", 1, dict(lse=None), "attn_fwd: null pointer"),                  # (the dense forward takes lse == NULL)
+    ("bwd", 0, dict(delta=None), "attn_bwd: null pointer"),
+    ("bwd", 1, dict(out=None), "attn_bwd: null pointer"),                  # (the dense backward takes out == NULL: ofa_attn_bwd_prep)
+    ("fwd", 0, dict(_SEG, bias=_P), r"attn_fwd: the ragged \(seg\) mode takes no"),
+    ("bwd", 0, dict(_SEG, bias=_P), r"attn_bwd: the ragged \(seg\) mode takes no"),
+    ("bwd", 0, dict(_SEG, dbias=_P), r"attn_bwd: the ragged \(seg\) mode takes no"),
+    ("fwd", 0, dict(_SEG, kpm=_P), r"attn_fwd: the ragged \(seg\) mode takes no"),
+    ("fwd", 1, dict(_SEG, kpm=_P), r"attn_fwd: the ragged \(seg\) mode takes no"),
+    ("bwd", 0, dict(_SEG, kpm=_P), r"attn_bwd: the ragged \(seg\) mode takes no"),
+    ("bwd", 1, dict(_SEG, kpm=_P), r"attn_bwd: the ragged \(seg\) mode takes no"),
+    ("fwd", 0, dict(_SEG, lse=None), r"attn_fwd: the ragged \(seg\) mode .* needs lse"),
+    ("fwd", 0, dict(_SEG, seg=_P + 4), r"attn_fwd: the ragged \(seg\) mode .* 16-byte aligned table"),
+    ("bwd", 1, dict(_SEG, seg=_P + 8), r"attn_bwd: the ragged \(seg\) mode .* 16-byte aligned table"),
+    ("fwd", 0, dict(_SEG, rows_q=0), "attn_fwd: ragged mode needs rows_q / rows_k"),
+    ("bwd", 1, dict(_SEG, rows_k=0), "attn_bwd: ragged mode needs rows_q / rows_k"),
+    ("bwd", 0, dict(_SEG, rows_q=96), "attn_bwd: ragged mode needs rows_q / rows_k and Tpad >= rows_q"),
+    ("fwd", 1, dict(Tb=0), r"attn_fwd: the swizzled bias image is of \[heads, Tb, Sb\] \(Tb=0 Sb=60\)"),
+    ("fwd", 1, dict(bias_swz_row=_P + 8), "attn_fwd: the swizzled bias image must be 16-byte aligned"),
+    ("fwd", 1, dict(Tb=39), "attn_fwd: the shared bias covers 39 x 60 positions, the call needs 40 x 50"),
+    ("bwd", 1, dict(Sb=49), "attn_bwd: the shared bias covers 48 x 49 positions, the call needs 40 x 50"),
+    ("bwd", 1, dict(bias_swz_col=None), "attn_bwd: the column image of the shared bias"),
+    ("bwd", 1, dict(bias_swz_col=_P + 4), "attn_bwd: the column image of the shared bias"),
+    ("bwd", 1, dict(dbias=_P), "attn_bwd: the column image of the shared bias .* for dbias, the row-major tensor"),
+    ("fwd", 0, dict(c_attn_dtype=7), "attn_fwd: bad c_attn dtype 7"),
+    ("bwd", 1, dict(c_attn_dtype=3), "attn_bwd: bad c_attn dtype 3"),
+    ("bwd", 0, dict(cs_q=_P, cs_ldq=120), r"heads \* 64 = 128 floats \(row strides 120 / 0\)"),
+    ("bwd", 1, dict(cs_v=_P, cs_ldq=128, cs_ldk=127), r"heads \* 64 = 128 floats \(row strides 128 / 127\)"),
+    ("bwd", 0, dict(cs_c=_P), "attn_bwd: cs_c .* without c_attn"),
+    ("bwd", 1, dict(_DSUM, dbias_dtype=5), "attn_bwd: bad dbias dtype 5"),
+    # 2 heads x one [128 x 64] tile: the 2 samples become 2 chunks of 2 * 48 * 60 floats each
+    ("bwd", 1, dict(_DSUM, ws_bytes=46079), "attn_bwd: the batch-sum kernel needs 46080 bytes of workspace for 2 chunks"),
+    ("bwd", 1, dict(_DSUM, ws=None, ws_bytes=46080), "attn_bwd: the batch-sum kernel needs 46080 bytes of workspace for 2 chunks"),
+    # 16 heads x 16 tiles fill the chip: one chunk of all 2049 samples, 16 bytes of LDS each on top of the 32 KiB of tiles
+    ("bwd", 1, dict(_DSUM, B=2049, heads=16, ldq=1024, ldk=1024, ldo=1024, Tb=512, Sb=256), "status 2.*attn_bwd: 2049 samples per chunk exceed"),
+]
+
+
+@pytest.mark.parametrize("entry,shared,change,match", _ATTN_REFUSALS)
+def test_attn_call_refusals(entry, shared, change, match):
+    """Every precondition of ofa_attn_fwd / ofa_attn_bwd that is checked before the first launch, one changed field per row; the numbers
+    in the messages come out of the descriptor, so they pin the field offsets of the ctypes mirror."""
+    from ofasys_amd import kernels as K
+    c = K._AttnCall(q=_P, k=_P, v=_P, out=_P, lse=_P, B=2, heads=2, T=40, S=50, Tpad=64, ldq=128, ldk=128, ldo=128, scale=0.125, dtype=L.BF16)
+    if entry == "bwd":
+        c.dout = c.delta = c.dq = c.dk = c.dv = _P
+    if shared:
+        c.bias_swz_row, c.Tb, c.Sb = _P, 48, 60
+        if entry == "bwd":
+            c.bias_swz_col = _P
+    for name, value in change.items():
+        setattr(c, name, value)
+    with pytest.raises(L.OfaError, match=match):
+        L.lib().call("ofa_attn_" + entry, ctypes.addressof(c), None)
 
 
 def test_no_cpu_fallback():

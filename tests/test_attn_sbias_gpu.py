@@ -1,4 +1,4 @@
-"""GPU: attention with a batch-SHARED position bias (ofa_attn_sbias_fwd / _bwd, csrc/attention.hip): the reference's dense [B*A, T, S]
+"""GPU: attention with a batch-SHARED position bias (ofa_attn_fwd / _bwd with ofa_attn_call.bias_swz_row, csrc/attention.hip): the reference's dense [B*A, T, S]
 bias (abs-pos + rel-pos, adaptor/general.py:223-282, model/transformer.py:280-299) is B copies of one [A, T, S] matrix, which the
 kernels take once and index by (head, position, position) for every sample; its gradient -- the sum over the batch of dS -- comes from
 a third backward kernel that walks the batch per tile.  Checked against a plain PyTorch fp32 reference that EXPANDS the bias over the

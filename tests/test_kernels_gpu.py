@@ -1,5 +1,6 @@
 """GPU parity tests of every C-ABI kernel against a plain PyTorch fp32 reference of the same op (and the oracle's
 restatements where the op is OFASys-specific).  Run with: pytest -m gpu"""
+import ctypes
 import math
 
 import pytest
@@ -607,9 +608,11 @@ def test_fused_attention(K, B, heads, T, S, causal, use_bias, use_kpm):
         lib().call("ofa_attn_bwd_prep", ptr(dout), ptr(out), ptr(d2), B, heads, T, Tp, D, 1, stream())
         assert rel(d2.view(B, heads, -1)[:, :, :T], want) < 1e-5
         dq2, dk2, dv2 = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        lib().call("ofa_attn_bwd", ptr(q), ptr(k), ptr(v), ptr(dout), None, ptr(kpm.view(torch.uint8)) if use_kpm else None, ptr(c), 0,
-                   ptr(lse), ptr(d2), None, ptr(dq2), ptr(dk2), ptr(dv2), None, B, heads, T, S, Tp, D, D, D, scale, int(causal), None, 0,
-                   0, 1, stream())
+        kpm8 = kpm.view(torch.uint8) if use_kpm else None
+        call = K._AttnCall(q=ptr(q), k=ptr(k), v=ptr(v), dout=ptr(dout), kpm=ptr(kpm8), c_attn=ptr(c), lse=ptr(lse), delta=ptr(d2), out=None,
+                           dq=ptr(dq2), dk=ptr(dk2), dv=ptr(dv2), B=B, heads=heads, T=T, S=S, Tpad=Tp, ldq=D, ldk=D, ldo=D, scale=scale,
+                           causal=int(causal), dtype=1)
+        lib().call("ofa_attn_bwd", ctypes.addressof(call), stream())
         assert rel(dq2, dq) < 1e-3 and rel(dk2, dk) < 1e-3 and rel(dv2, dv) < 1e-3
 
 
@@ -641,7 +644,7 @@ def _cs_check(cs, dq, dk, dv, delta_rows, c):
                                                              (2, 2, 96, 96, True, False, False), (2, 3, 257, 300, False, False, True),
                                                              (1, 12, 448, 448, False, False, False)])
 def test_attention_backward_column_sums(K, B, heads, T, S, causal, use_kpm, shared):
-    """ofa_attn_bwd_cs / ofa_attn_sbias_bwd_cs: the bias gradients of the q / k / v projections and the c_attn gradient as partial rows
+    """ofa_attn_bwd with cs_* buffers, dense and shared-bias: the bias gradients of the q / k / v projections and the c_attn gradient as partial rows
     out of the backward kernels' epilogues; dq / dk / dv themselves are bit-identical to the plain call."""
     torch.manual_seed(11)
     D = heads * 64
@@ -664,8 +667,10 @@ def test_attention_backward_column_sums(K, B, heads, T, S, causal, use_kpm, shar
     _cs_check(cs, got[0], got[1], got[2], delta_rows, c)
 
 
-def test_attention_backward_column_sums_ragged(K):
-    """... in ragged mode: tiles beyond a sample's length write zero rows, filler rows count as zeros."""
+@pytest.mark.parametrize("shared", [False, True])
+def test_attention_backward_column_sums_ragged(K, shared):
+    """... in ragged mode: tiles beyond a sample's length write zero rows, filler rows count as zeros.  shared: with the batch-shared
+    position bias and its gradient on top -- packed self-attention as the product runs it (shared bias + segments + partial rows)."""
     from ofasys_amd.packing import Segments
     heads, D = 4, 256
     qlens, klens = [150, 24, 300, 1], [40, 260, 129, 7]
@@ -677,11 +682,16 @@ def test_attention_backward_column_sums_ragged(K):
     q, do = (torch.randn(1, Rq, D, generator=g).to(torch.bfloat16).to(DEV) for _ in range(2))
     k, v = (torch.randn(1, Rk, D, generator=g).to(torch.bfloat16).to(DEV) for _ in range(2))
     c = (1 + 0.2 * torch.randn(heads, generator=g)).to(DEV)
-    out, lse = K.attn_fwd(q, k, v, heads, 0.125, seg=seg, c_attn=c)
-    ref = K.attn_bwd(q, k, v, out, do, lse, heads, 0.125, seg=seg, c_attn=c)
+    kw = dict(seg=seg, c_attn=c)
+    if shared:
+        kw.update(bias=(0.5 * torch.randn(heads, 300, 260, generator=g)).to(torch.bfloat16).to(DEV), bias_shared=True)
+    out, lse = K.attn_fwd(q, k, v, heads, 0.125, **kw)
+    if shared:
+        kw["need_dbias"] = True
+    ref = K.attn_bwd(q, k, v, out, do, lse, heads, 0.125, **kw)
     cs = _cs_bufs(K, 1, Rq, Rk, heads, seg=seg)
     assert cs["q"].shape[0] == 4 * 3 * 4 and cs["k"].shape[0] == 4 * 3 * 4           # (sample, tile, wave)
-    got = K.attn_bwd(q, k, v, out, do, lse, heads, 0.125, seg=seg, c_attn=c, cs=cs)
+    got = K.attn_bwd(q, k, v, out, do, lse, heads, 0.125, cs=cs, **kw)
     for a, b in zip(got[:3], ref[:3]):
         assert torch.equal(a, b)
     delta = got[4].view(heads, -1)

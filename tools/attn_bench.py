@@ -20,10 +20,13 @@ for (B, A, T, S, causal) in [(32, 12, 448, 448, False), (32, 12, 64, 64, True), 
     Tp, Sp = K.pad32(T), K.pad32(S)
     delta = torch.zeros(B * A, Tp, device='cuda')
     dq = torch.empty_like(q); dk = torch.empty_like(k); dv = torch.empty_like(v)
+    import ctypes
     from ofasys_amd.lib import lib, ptr, stream
+    kpm8 = kpm.view(torch.uint8)
+    call = K._AttnCall(q=ptr(q), k=ptr(k), v=ptr(v), dout=ptr(dout), kpm=ptr(kpm8), c_attn=ptr(c), lse=ptr(lse), delta=ptr(delta), out=ptr(out),
+                       dq=ptr(dq), dk=ptr(dk), dv=ptr(dv), B=B, heads=A, T=T, S=S, Tpad=Tp, ldq=D, ldk=D, ldo=D, scale=0.125, causal=int(causal), dtype=1)
     def bwd():
-        lib().call("ofa_attn_bwd", ptr(q), ptr(k), ptr(v), ptr(dout), None, ptr(kpm.view(torch.uint8)),
-                   ptr(c), 0, ptr(lse), ptr(delta), ptr(out), ptr(dq), ptr(dk), ptr(dv), None, B, A, T, S, Tp, D, D, D, 0.125, int(causal), None, 0, 0, 1, stream())
+        lib().call("ofa_attn_bwd", ctypes.addressof(call), stream())
     tb = bench(bwd)
     fl = 4.0 * B * A * T * S * 64 * (0.5 if causal else 1)
     print(f"B{B} A{A} T{T} S{S} causal={causal}: fwd {tf:7.1f} us {fl/tf/1e6:6.1f} TF | bwd(dq+dkv) {tb:7.1f} us {2.5*fl/tb/1e6:6.1f} TF")

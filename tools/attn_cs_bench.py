@@ -1,6 +1,6 @@
-"""What the column-sum epilogues of the attention backward kernels cost (ofa_attn_bwd_cs against ofa_attn_bwd, same build, interleaved):
+"""What the column-sum epilogues of the attention backward kernels cost (ofa_attn_bwd with and without the cs_* partial rows, same build, interleaved):
 encoder self-attention, decoder self-attention and cross-attention shapes of cfg-2; arms: all partial rows, q only, c_attn only, k only, k and v."""
-import sys, os, torch
+import ctypes, sys, os, torch
 sys.path.insert(0, '.')
 from ofasys_amd import kernels as K
 from ofasys_amd.lib import lib, ptr, stream
@@ -12,7 +12,6 @@ def bench(fn, n=30):
     for _ in range(n): fn()
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / n * 1e3
-has_cs = hasattr(lib().cdll, "ofa_attn_bwd_cs")
 for (B, A, T, S, causal) in [(32, 12, 448, 448, False), (32, 12, 64, 64, True), (32, 12, 64, 448, False)]:
     D = A * 64
     q = torch.randn(B, T, D, device='cuda').bfloat16(); k = torch.randn(B, S, D, device='cuda').bfloat16(); v = torch.randn(B, S, D, device='cuda').bfloat16()
@@ -24,16 +23,12 @@ for (B, A, T, S, causal) in [(32, 12, 448, 448, False), (32, 12, 64, 64, True), 
     dq = torch.empty_like(q); dk = torch.empty_like(k); dv = torch.empty_like(v)
     nq, nk = 4 * B * ((T + 127) // 128), 4 * B * ((S + 127) // 128)
     wq = torch.empty(nq, D, device='cuda'); wk = torch.empty(nk, D, device='cuda'); wv = torch.empty(nk, D, device='cuda'); wc = torch.empty(nq, A, device='cuda')
-    def plain():
-        lib().call("ofa_attn_bwd", ptr(q), ptr(k), ptr(v), ptr(dout), None, None, ptr(c), 0, ptr(lse), ptr(delta), ptr(out), ptr(dq), ptr(dk), ptr(dv), None, B, A, T, S, Tp, D, D, D, 0.125, int(causal), None, 0, 0, 1, stream())
-    def cs(a, b, cc, d):
-        def f():
-            lib().call("ofa_attn_bwd_cs", ptr(q), ptr(k), ptr(v), ptr(dout), None, None, ptr(c), 0, ptr(lse), ptr(delta), ptr(out), ptr(dq), ptr(dk), ptr(dv), None, B, A, T, S, Tp, D, D, D, 0.125, int(causal), None, 0, 0, 1,
-                       ptr(wq) if a else None, D, ptr(wk) if b else None, ptr(wv) if cc else None, D, ptr(wc) if d else None, stream())
-        return f
-    arms = [("plain", plain)]
-    if has_cs:
-        arms += [("cs all", cs(1, 1, 1, 1)), ("cs q", cs(1, 0, 0, 0)), ("cs c", cs(0, 0, 0, 1)), ("cs k", cs(0, 1, 0, 0)), ("cs kv", cs(0, 1, 1, 0))]
+    def arm(a, b, cc, d):        # the descriptor is built once: the timed region is the bare C call
+        call = K._AttnCall(q=ptr(q), k=ptr(k), v=ptr(v), dout=ptr(dout), c_attn=ptr(c), lse=ptr(lse), delta=ptr(delta), out=ptr(out), dq=ptr(dq), dk=ptr(dk),
+                           dv=ptr(dv), B=B, heads=A, T=T, S=S, Tpad=Tp, ldq=D, ldk=D, ldo=D, scale=0.125, causal=int(causal), dtype=1,
+                           cs_q=ptr(wq) if a else None, cs_ldq=D, cs_k=ptr(wk) if b else None, cs_v=ptr(wv) if cc else None, cs_ldk=D, cs_c=ptr(wc) if d else None)
+        return lambda: lib().call("ofa_attn_bwd", ctypes.addressof(call), stream())
+    arms = [("plain", arm(0, 0, 0, 0)), ("cs all", arm(1, 1, 1, 1)), ("cs q", arm(1, 0, 0, 0)), ("cs c", arm(0, 0, 0, 1)), ("cs k", arm(0, 1, 0, 0)), ("cs kv", arm(0, 1, 1, 0))]
     res = {n: [] for n, _ in arms}
     for r in range(5):
         for n, f in arms:
