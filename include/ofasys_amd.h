@@ -472,6 +472,26 @@ int ofa_step_schedule_scaled(const float* gsq, const double* sample_size, double
 int ofa_adam_step(float* master, float* exp_avg, float* exp_avg_sq, const void* grad, void* model_param,
                   const float* coef, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                   int step, int dtype, void* stream);
+/* EMA shadow of the weights (engine/ema/ema.py:140-194), decided and applied on the device so that a captured step replays the
+ * rule: with t = step[0] (fp64, the number of completed updates) and skip = sched[3] as ofa_step_schedule[_scaled] left them,
+ *   apply <=> skip == 0 and t % update_freq == 0;  d = t < start_update ? 0 : decay;  a = fp32(1 - d), rounded once more to a
+ *   16-bit state's own type.  That second rounding is what torch's CPU add_(alpha =) does and what the recorded reference holds
+ *   (tests/golden/ema.npz); torch's GPU kernel keeps alpha in fp32, so against a reference run on a GPU a bf16 / fp16 state can
+ *   differ in its last bit here (bf16(0.1) = 0.10009765625).  An fp32 state (ema_fp32) is not affected.
+ *   state <- round_S(float(round_S(float(state) * d)) + a * float(p))       (mul_ then add_(alpha =): two roundings to S, no FMA)
+ * state: `state_dtype` elements, fp32 (ema_fp32) or the model's `dtype`; p: the model-dtype parameters as the forward reads them;
+ * shadow (optional, NULL: none): round_dtype(state), the weights of the averaged model.  When the rule does not apply nothing is
+ * written.  max_blocks: 0 = the kernel's own grid cap (a test reaches the second grid-stride trip at a small n with it).
+ * ofa_ema_step: one flat arena of n elements; state 16-byte (fp32) / 8-byte (16-bit) aligned, p and shadow alike for `dtype`. */
+int ofa_ema_step(void* state, const void* p, void* shadow, int64_t n, const double* step, const float* sched, double decay,
+                 int64_t start_update, int64_t update_freq, int dtype, int state_dtype, int max_blocks, void* stream);
+/* ... and the floating-point tensors outside the arena (BatchNorm running statistics) in ONE launch: `segments` is a device table
+ * of n records {const void* src; int64_t off; int64_t len} -- len `dtype` elements at src are averaged into state[off, off + len)
+ * (and shadow[off, off + len)) of a second flat array of state_numel elements; max_len = the longest len.  Records that leave the
+ * array are skipped. */
+int ofa_ema_segments_step(void* state, const void* segments, void* shadow, int64_t n, int64_t state_numel, int64_t max_len,
+                          const double* step, const float* sched, double decay, int64_t start_update, int64_t update_freq,
+                          int dtype, int state_dtype, int max_blocks, void* stream);
 
 /* ---- convolution stack of the image_resnet / video / audio adaptors (module/resnet.py:22-261, module/subsample.py:11-63).
  * Activations are NHWC rows [B*H*W, C]; a convolution is ofa_im2col (taps ordered (kh, kw, c), row length Kpad >=

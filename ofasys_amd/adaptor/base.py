@@ -88,6 +88,8 @@ class BaseAdaptor(torch.nn.Module):
     # matrix per layer and the general adaptor builds it once instead of B times (ops.SharedBias).  A custom adaptor whose
     # positions vary per sample keeps the default False and gets the reference's dense [B, A, T, T] assembly.
     pos_batch_invariant = False
+    # attributes that may alias `embed_tokens_T` (adaptor/text.py: output_projection when the output embedding is shared)
+    _tied_projection_aliases = ("output_projection",)
 
     def __init__(self, embed_tokens: Embedding, dictionary: Dictionary, is_src: bool, general_adaptor,
                  cfg: BaseAdaptorConfig):
@@ -95,10 +97,7 @@ class BaseAdaptor(torch.nn.Module):
         D = cfg.embed_dim
         # the shared token embedding is reached through closures, NOT registered as a child module: the state dict must list it once,
         # under the general adaptor (adaptor/base.py:128-136)
-        self.embed_tokens = lambda ids: embed_tokens(ids)
-        self.embed_tokens_T = lambda rows: ops.linear(rows, embed_tokens.weight)      # tied output projection
-        # (embedding rows, ids == pad) from one launch (adaptor/text.py:108-125 computes the two separately)
-        self.embed_tokens_and_pad_mask = lambda ids, pad: ops.embedding_with_pad_mask(ids, embed_tokens.weight, embed_tokens.padding_idx, pad)
+        self._bind_embed_tokens(embed_tokens)
         self.cfg, self.dictionary, self.is_src = cfg, dictionary, is_src
         self._general_adaptor = [general_adaptor]                                      # (a list: not a child module either)
         self.num_layers = cfg.encoder_layers if is_src else cfg.decoder_layers
@@ -111,6 +110,20 @@ class BaseAdaptor(torch.nn.Module):
         self.layernorm_position = LayerNorm(D) if cfg.layernorm_position else None
         self.type_embedding = Embedding(1, D) if cfg.add_type_embedding else None
         self.register_forward_hook(BaseAdaptor.forward_hook_fn)
+
+    def _bind_embed_tokens(self, embed_tokens):
+        """(Re)build the closures over the shared token embedding.  copy.deepcopy copies functions by reference, so the closures of a
+        copied adaptor still reach the ORIGINAL model's embedding: whoever copies a model (ema.EMA.get_model) calls this on every
+        adaptor of the copy with the copy's own embedding.  The attributes named in `_tied_projection_aliases` follow when they
+        hold the tied projection: an adaptor that stores `self.embed_tokens_T` under another name lists that name there."""
+        old = self.__dict__.get("embed_tokens_T")
+        self.embed_tokens = lambda ids: embed_tokens(ids)
+        self.embed_tokens_T = lambda rows: ops.linear(rows, embed_tokens.weight)      # tied output projection
+        # (embedding rows, ids == pad) from one launch (adaptor/text.py:108-125 computes the two separately)
+        self.embed_tokens_and_pad_mask = lambda ids, pad: ops.embedding_with_pad_mask(ids, embed_tokens.weight, embed_tokens.padding_idx, pad)
+        for name in self._tied_projection_aliases:
+            if old is not None and self.__dict__.get(name) is old:
+                self.__dict__[name] = self.embed_tokens_T
 
     @property
     def general_adaptor(self):

@@ -441,6 +441,154 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ master, f
   }
 }
 
+// ---------------------------------------------------------------- EMA shadow of the weights (engine/ema/ema.py:140-194)
+// Does this update average, and with which decay?  Decided on the device from the schedule state the step just wrote -- step[0] = t,
+// the number of completed updates, and sched[3], the skip flag -- so that a captured step replays the rule, not one outcome of it:
+//   apply <=> the update was not skipped and t % update_freq == 0     (ema.py:188-192: the counter advances on stepped updates only)
+//   d = t < start_update ? 0 : decay ; a = 1 - d                      (ema.py:187; `a` rounded from the host's double: ema_rule)
+// Uniform over the launch: every thread reads the same two words.
+struct EmaRule {
+  float d_on, a_on;          // fp32(decay), 1 - decay as torch's add_(alpha =) takes it (ema_rule)
+  double start_update;
+  int64_t update_freq;
+};
+__device__ __forceinline__ bool ema_decide(const double* __restrict__ step, const float* __restrict__ sched, const EmaRule& r,
+                                           float& d, float& a) {
+  if (sched[3] != 0.f) return false;
+  const double t = step[0];
+  if (r.update_freq > 1 && (int64_t)t % r.update_freq != 0) return false;
+  const bool on = !(t < r.start_update);
+  d = on ? r.d_on : 0.f;
+  a = on ? r.a_on : 1.f;
+  return true;
+}
+// One element: the reference's mul_(d) then add_(p, alpha = a) on a state of type S -- each a rounding to S -- written without
+// contraction: the stated formula rounds both products and the sum to fp32 on their own.  (HIP's __fmul_rn / __fadd_rn are plain
+// `*` / `+` compiled under hipcc's default -ffp-contract=fast inside the header: with them the sum came out as v_pk_fma_f32 whatever
+// the caller's pragma said.  Plain operators under `fp contract(off)` compile to v_pk_mul_f32 / v_pk_add_f32.)
+template <typename S> __device__ __forceinline__ float ema_round(float x);
+template <> __device__ __forceinline__ float ema_round<float>(float x) { return x; }
+template <> __device__ __forceinline__ float ema_round<bf16_t>(float x) { return bf2f(f2bf(x)); }
+// (the fp32 value is pinned in a register first: hipcc selects fptrunc(fmul(fpext(half), float)) as ONE v_fma_mixlo_f16, which rounds
+// the exact product to fp16 once -- torch rounds it to fp32 and then to fp16, and with d = 0.9f the product of an 11-bit state lands
+// within half an fp32 ulp below an fp16 tie in 4 % of the elements: 40 of 1045 were one fp16 ulp off the recorded reference)
+template <> __device__ __forceinline__ float ema_round<f16_t>(float x) {
+  asm volatile("" : "+v"(x));
+  return (float)(f16_t)x;
+}
+template <typename S> __device__ __forceinline__ float ema_one(float e, float p, float d, float a) {
+#pragma clang fp contract(off)
+  const float r = ema_round<S>(e * d);
+  const float ap = a * p;
+  return ema_round<S>(r + ap);
+}
+// the two 32-bit words of a 16-bit quad as four floats (the words arrive as scalars: see adam_kernel on bit_cast of a vector ELEMENT)
+template <typename T> __device__ __forceinline__ void unpack_quad16(uint32_t x, uint32_t y, float* o) {
+  if constexpr (!__is_same(T, bf16_t)) {                                  // fp16
+    const f16x2_t a = __builtin_bit_cast(f16x2_t, x), b = __builtin_bit_cast(f16x2_t, y);
+    o[0] = (float)a[0]; o[1] = (float)a[1]; o[2] = (float)b[0]; o[3] = (float)b[1];
+  } else {
+    o[0] = __uint_as_float(x << 16); o[1] = __uint_as_float(x & 0xffff0000u);
+    o[2] = __uint_as_float(y << 16); o[3] = __uint_as_float(y & 0xffff0000u);
+  }
+}
+
+// state (S = float, or the model dtype T) <- EMA of the model-dtype arena p; `shadow` (optional, T): round_T(state) for the forward
+// of the averaged model.  adam_kernel's streaming pattern: two 4-element quads per thread and trip, every load of the trip issued
+// before the first use; the fp32 state is touched once per step (nontemporal both ways), p was just written by Adam and the 16-bit
+// results are read by an inference forward (plain).  Not applying writes nothing.
+template <typename T, typename S>
+__global__ __launch_bounds__(256) void ema_kernel(S* __restrict__ state, const T* __restrict__ p, T* __restrict__ shadow, int64_t n,
+                                                  const double* __restrict__ step, const float* __restrict__ sched, EmaRule rule) {
+  float d, a;
+  if (!ema_decide(step, sched, rule, d, a)) return;
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  typedef unsigned u2v __attribute__((ext_vector_type(2)));
+  constexpr bool S32 = sizeof(S) == 4, T32 = sizeof(T) == 4;
+  const int64_t nq = n >> 2;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t q0 = (int64_t)blockIdx.x * 256 + threadIdx.x; q0 < nq; q0 += 2 * stride) {
+    f4v e4[2], p4[2];
+    u2v e2[2], p2[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int64_t q = q0 + k * stride;
+      if (q < nq) {
+        const int64_t i = q << 2;
+        if constexpr (S32) e4[k] = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(state + i));
+        else e2[k] = *reinterpret_cast<const u2v*>(state + i);
+        if constexpr (T32) p4[k] = *reinterpret_cast<const f4v*>(p + i);
+        else p2[k] = *reinterpret_cast<const u2v*>(p + i);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int64_t q = q0 + k * stride;
+      if (q < nq) {
+        const int64_t i = q << 2;
+        float e[4], x[4];
+        if constexpr (S32) { e[0] = e4[k].x; e[1] = e4[k].y; e[2] = e4[k].z; e[3] = e4[k].w; }
+        else { const uint32_t ex = e2[k][0], ey = e2[k][1]; unpack_quad16<S>(ex, ey, e); }
+        if constexpr (T32) { x[0] = p4[k].x; x[1] = p4[k].y; x[2] = p4[k].z; x[3] = p4[k].w; }
+        else { const uint32_t px = p2[k][0], py = p2[k][1]; unpack_quad16<T>(px, py, x); }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) e[j] = ema_one<S>(e[j], x[j], d, a);
+        if constexpr (S32) {
+          const f4v eo = {e[0], e[1], e[2], e[3]};
+          __builtin_nontemporal_store(eo, reinterpret_cast<f4v*>(state + i));
+        } else {
+          u2v o;
+          o.x = pack2<S>(e[0], e[1]);
+          o.y = pack2<S>(e[2], e[3]);
+          *reinterpret_cast<u2v*>(state + i) = o;
+        }
+        if (shadow) {
+          if constexpr (T32) {
+            const f4v so = {e[0], e[1], e[2], e[3]};
+            *reinterpret_cast<f4v*>(shadow + i) = so;
+          } else {
+            u2v o;
+            o.x = pack2<T>(e[0], e[1]);
+            o.y = pack2<T>(e[2], e[3]);
+            *reinterpret_cast<u2v*>(shadow + i) = o;
+          }
+        }
+      }
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {       // tail
+    const int64_t i = (nq << 2) + threadIdx.x;
+    const float e = ema_one<S>(ld1<S>(state + i), ld1<T>(p + i), d, a);
+    st1<S>(state + i, e);
+    if (shadow) st1<T>(shadow + i, e);
+  }
+}
+
+// The floating-point buffers of the state dict (BatchNorm running statistics: ~400 tensors of a ResNet-101, none of them in the
+// arena) in ONE launch over a device-resident table: segment s averages len elements at src into state[off, off + len).  The grid
+// is (blocks per segment, segments); a segment's blocks stride over it element by element (the buffers are short and have no
+// alignment to speak of).  A segment that would leave the state array is skipped.
+struct EmaSegment {
+  const void* src;
+  int64_t off, len;
+};
+template <typename T, typename S>
+__global__ __launch_bounds__(256) void ema_segments_kernel(S* __restrict__ state, const EmaSegment* __restrict__ segs,
+                                                           T* __restrict__ shadow, int64_t state_numel,
+                                                           const double* __restrict__ step, const float* __restrict__ sched,
+                                                           EmaRule rule) {
+  float d, a;
+  if (!ema_decide(step, sched, rule, d, a)) return;
+  const EmaSegment sg = segs[blockIdx.y];
+  if (sg.off < 0 || sg.len < 0 || sg.off > state_numel - sg.len) return;
+  const T* src = static_cast<const T*>(sg.src);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < sg.len; i += (int64_t)gridDim.x * 256) {
+    const float e = ema_one<S>(ld1<S>(state + sg.off + i), ld1<T>(src + i), d, a);
+    st1<S>(state + sg.off + i, e);
+    if (shadow) st1<T>(shadow + sg.off + i, e);
+  }
+}
+
 // One thread: the scalar arithmetic between the gradient norm and the Adam update, kept on the device so that a captured
 // train step replays it (trainer.py:857-884 clip + 1/sample_size, adam.py:205-207 bias corrections).  ~25 tiny torch
 // kernels otherwise, ~4.5 us each inside a hipGraph.
@@ -718,6 +866,75 @@ extern "C" int ofa_adam_step(float* master, float* exp_avg, float* exp_avg_sq, c
     hipLaunchKernelGGL((adam_kernel<T>), dim3(nb), dim3(256), 0, st, master, exp_avg, exp_avg_sq, (const T*)grad, (T*)model_param, coef, n, lr, beta1, beta2, eps, weight_decay, step_size, dev_sched);
   });
   return check_launch("adam_step");
+}
+
+// the checks the two EMA entry points share; fills the rule the kernels take
+static int ema_rule(const char* who, const void* state, const void* p, const double* step, const float* sched, double decay,
+                    int64_t start_update, int64_t update_freq, int dtype, int state_dtype, int max_blocks, EmaRule* rule) {
+  OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+  OFA_REQUIRE(state_dtype == OFA_F32 || state_dtype == dtype, OFA_ERR_INVALID,
+              "%s: the state is fp32 or of the model dtype (dtype %d, state dtype %d)", who, dtype, state_dtype);
+  OFA_REQUIRE(state && p && step && sched && max_blocks >= 0, OFA_ERR_INVALID, "%s: bad argument", who);
+  OFA_REQUIRE(decay >= 0.0 && decay <= 1.0 && start_update >= 0 && update_freq >= 1, OFA_ERR_INVALID,
+              "%s: decay in [0, 1], start_update >= 0, update_freq >= 1 (got %g, %lld, %lld)", who, decay, (long long)start_update,
+              (long long)update_freq);
+  // torch hands `mul_` its scalar in fp32 for every dtype, but `add_(alpha =)` on a 16-bit tensor converts alpha to the tensor's
+  // dtype first (the CPU kernel the recorded reference ran: bf16(0.1) = 0.10009765625): a 16-bit state takes that alpha.  torch's GPU
+  // kernel keeps alpha in fp32: a 16-bit state can differ in its last bit from a reference run there (include/ofasys_amd.h)
+  float a = (float)(1.0 - decay);
+  if (state_dtype == OFA_F16) a = (float)(_Float16)a;
+  if (state_dtype == OFA_BF16) {
+    uint32_t u;
+    memcpy(&u, &a, 4);
+    u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;      // round to nearest even
+    memcpy(&a, &u, 4);
+  }
+  *rule = EmaRule{(float)decay, a, (double)start_update, update_freq};
+  return 0;
+}
+
+extern "C" int ofa_ema_step(void* state, const void* p, void* shadow, int64_t n, const double* step, const float* sched,
+                            double decay, int64_t start_update, int64_t update_freq, int dtype, int state_dtype, int max_blocks,
+                            void* stream) {
+  EmaRule rule;
+  if (int rc = ema_rule("ema_step", state, p, step, sched, decay, start_update, update_freq, dtype, state_dtype, max_blocks, &rule)) return rc;
+  OFA_REQUIRE(n >= 0, OFA_ERR_INVALID, "ema_step: bad argument");
+  if (n == 0) return 0;
+  // one quad is 16 bytes of fp32, 8 bytes of a 16-bit type
+  const uintptr_t sa = state_dtype == OFA_F32 ? 15 : 7, ta = dtype == OFA_F32 ? 15 : 7;
+  OFA_REQUIRE(!((uintptr_t)state & sa) && !(((uintptr_t)p | (uintptr_t)shadow) & ta), OFA_ERR_INVALID,
+              "ema_step: arenas must be 16-byte (fp32) / 8-byte (16-bit) aligned");
+  const int64_t nbl = ((n >> 2) + 511) / 512;               // two quads per thread
+  const int64_t cap = max_blocks > 0 ? max_blocks : 65536;
+  const int nb = (int)(nbl < 1 ? 1 : (nbl > cap ? cap : nbl));
+  hipStream_t st = (hipStream_t)stream;
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (state_dtype == OFA_F32) hipLaunchKernelGGL((ema_kernel<T, float>), dim3(nb), dim3(256), 0, st, (float*)state, (const T*)p, (T*)shadow, n, step, sched, rule);
+    else hipLaunchKernelGGL((ema_kernel<T, T>), dim3(nb), dim3(256), 0, st, (T*)state, (const T*)p, (T*)shadow, n, step, sched, rule);
+  });
+  return check_launch("ema_step");
+}
+
+extern "C" int ofa_ema_segments_step(void* state, const void* segments, void* shadow, int64_t n, int64_t state_numel, int64_t max_len,
+                                     const double* step, const float* sched, double decay, int64_t start_update, int64_t update_freq,
+                                     int dtype, int state_dtype, int max_blocks, void* stream) {
+  EmaRule rule;
+  if (int rc = ema_rule("ema_segments_step", state, segments, step, sched, decay, start_update, update_freq, dtype, state_dtype, max_blocks, &rule)) return rc;
+  OFA_REQUIRE(n >= 0 && n <= 65535 && state_numel >= 0 && max_len >= 0 && !((uintptr_t)segments & 7), OFA_ERR_INVALID,
+              "ema_segments_step: at most 65535 segments in an 8-byte aligned table (n=%lld)", (long long)n);
+  if (n == 0 || max_len == 0) return 0;
+  const int64_t nbl = (max_len + 255) / 256;
+  const int64_t cap = max_blocks > 0 ? max_blocks : 64;
+  const int nb = (int)(nbl > cap ? cap : nbl);
+  hipStream_t st = (hipStream_t)stream;
+  const EmaSegment* segs = (const EmaSegment*)segments;
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if (state_dtype == OFA_F32) hipLaunchKernelGGL((ema_segments_kernel<T, float>), dim3(nb, (unsigned)n), dim3(256), 0, st, (float*)state, segs, (T*)shadow, state_numel, step, sched, rule);
+    else hipLaunchKernelGGL((ema_segments_kernel<T, T>), dim3(nb, (unsigned)n), dim3(256), 0, st, (T*)state, segs, (T*)shadow, state_numel, step, sched, rule);
+  });
+  return check_launch("ema_segments_step");
 }
 
 // One micro-batch's contribution to the step statistics [sample_size, loss_sum, ntokens] (engine/trainer.py:842-860: the criterion's

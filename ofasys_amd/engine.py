@@ -7,8 +7,11 @@
     every update: one micro-batch list per task -> TrainStep.train_step             (trainer.py:747-884)
     lr: polynomial decay with linear warm-up (default_trainer.yaml:27-28, lr_scheduler/ofa_polynomial_decay)
 
-Out of scope: CLI / hydra config tree, checkpoints, metrics / logging back-ends, validation loops, EMA,
-FSDP / BMUF.  One process per GPU: when WORLD_SIZE > 1 (torch.distributed.run) the process group is initialised on RCCL.
+EMA (engine/ema/ema.py; `cfg.ema`, or store_ema= / ema_decay= / ... as flat options): kept on the device and updated inside the step
+(ofasys_amd/ema.py); `Trainer.ema` is the object -- get_model(), reverse(model), state_dict().
+
+Out of scope: CLI / hydra config tree, checkpoints (hence ema_seed_model), metrics / logging back-ends,
+validation loops, FSDP / BMUF.  One process per GPU: when WORLD_SIZE > 1 (torch.distributed.run) the process group is initialised on RCCL.
 """
 import logging
 import os
@@ -17,6 +20,7 @@ from typing import List, Optional
 
 import torch
 
+from .ema import EMAConfig, as_config
 from .preprocessor import Dictionary, to_device
 from .task import Task
 from .trainer import TrainStep
@@ -89,6 +93,7 @@ class TrainerConfig:
     common: CommonConfig = field(default_factory=CommonConfig)
     optimization: OptimizationConfig = field(default_factory=OptimizationConfig)
     optimizer: OptimizerConfig = field(default_factory=OptimizerConfig)
+    ema: EMAConfig = field(default_factory=EMAConfig)
 
 
 def polynomial_decay_lr(num_updates, base_lr, max_update, warmup_ratio, end_lr=0.0, power=1.0):
@@ -113,18 +118,25 @@ def polynomial_decay_lr(num_updates, base_lr, max_update, warmup_ratio, end_lr=0
 
 class Trainer:
     def __init__(self, cfg: Optional[TrainerConfig] = None, **overrides):
-        """overrides: max_update=, lr=, clip_norm=, seed=, fp32=, use_graph=, log_interval=, weight_decay= (flat shortcuts)."""
+        """overrides: max_update=, lr=, clip_norm=, seed=, fp32=, use_graph=, log_interval=, weight_decay=, store_ema=, ema_decay=,
+        ema_fp32=, ... (flat shortcuts)."""
         self.cfg = cfg or TrainerConfig()
         for k, v in overrides.items():
-            for section in (self.cfg.common, self.cfg.optimization, self.cfg.optimizer):
+            for section in (self.cfg.common, self.cfg.optimization, self.cfg.optimizer, self.cfg.ema):
                 if hasattr(section, k):
                     setattr(section, k, [v] if k == "lr" and not isinstance(v, (list, tuple)) else v)
                     break
             else:
                 raise TypeError(f"unknown trainer option {k}")
+        as_config(self.cfg.ema)                     # refuses what the step engine would refuse (ema_seed_model) before any set-up
         self.global_dict = None
         self.step_engine: Optional[TrainStep] = None
         self.history = []
+
+    @property
+    def ema(self):
+        """The ema.EMA object of the step engine (None before setup() / fit(), and without store_ema)."""
+        return self.step_engine.ema if self.step_engine is not None else None
 
     # ------------------------------------------------------------------ set-up
     def _init_distributed(self):
@@ -174,7 +186,7 @@ class Trainer:
         self.step_engine = TrainStep(model, lr=cfg.optimization.lr[0], betas=tuple(cfg.optimizer.adam_betas), eps=cfg.optimizer.adam_eps,
                                      weight_decay=cfg.optimizer.weight_decay, clip_norm=cfg.optimization.clip_norm,
                                      use_graph=cfg.common.use_graph, label_smoothing=crit.label_smoothing,
-                                     drop_worst_ratio=crit.drop_worst_ratio, loss_scale=self._loss_scale_cfg(world))
+                                     drop_worst_ratio=crit.drop_worst_ratio, loss_scale=self._loss_scale_cfg(world), ema=cfg.ema)
         for task in tasks:
             task.init_data_iterator("train", rank, world)
         self._device, self._rank, self._world = device, rank, world

@@ -1005,6 +1005,40 @@ def adam_step(master, exp_avg, exp_avg_sq, grad, model_param, coef, lr, beta1, b
                dtype_code(grad), stream())
 
 
+class _EmaSegment(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_void_p), ("off", ctypes.c_int64), ("len", ctypes.c_int64)]
+
+
+def ema_step(state, p, shadow, step, sched, decay, start_update=0, update_freq=1, max_blocks=0):
+    """One EMA update of a flat arena, decided on the device (ofa_ema_step): state (fp32, or p's dtype) <- d * state + (1 - d) * p
+    when sched[3] == 0 and step[0] % update_freq == 0, d = 0 before start_update; shadow (None, or p's dtype): round(state)."""
+    assert state.is_contiguous() and p.is_contiguous() and state.numel() == p.numel() and step.dtype == torch.float64
+    assert shadow is None or (shadow.is_contiguous() and shadow.dtype == p.dtype and shadow.numel() == p.numel())
+    lib().call("ofa_ema_step", ptr(state), ptr(p), ptr(shadow), p.numel(), ptr(step), ptr(sched), float(decay), int(start_update),
+               int(update_freq), dtype_code(p), dtype_code(state), int(max_blocks), stream())
+
+
+def ema_segment_table(sources, offsets, device):
+    """The device table of ofa_ema_segments_step: (source tensor, offset into the state array) per floating-point tensor outside
+    the arena.  Returns (table, longest length); the caller keeps the sources alive for as long as it uses the table."""
+    arr = (_EmaSegment * max(len(sources), 1))()
+    for it, s, o in zip(arr, sources, offsets):
+        assert s.is_contiguous()
+        it.src, it.off, it.len = dptr(s), int(o), s.numel()
+    raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.int64).clone()
+    return raw.to(device), max([s.numel() for s in sources], default=0)
+
+
+def ema_segments_step(state, table, nseg, max_len, shadow, model_dtype, step, sched, decay, start_update=0, update_freq=1,
+                      max_blocks=0):
+    """ema_step for every segment of `table` (ema_segment_table) in one launch; the sources (and `shadow`) are of `model_dtype`."""
+    code = dtype_code(torch.empty(0, dtype=model_dtype))
+    assert state.is_contiguous() and step.dtype == torch.float64 and table.dtype == torch.int64 and table.numel() >= 3 * nseg
+    assert shadow is None or (shadow.is_contiguous() and shadow.numel() == state.numel() and shadow.dtype == model_dtype)
+    lib().call("ofa_ema_segments_step", ptr(state), ptr(table), ptr(shadow), int(nseg), state.numel(), int(max_len), ptr(step),
+               ptr(sched), float(decay), int(start_update), int(update_freq), code, dtype_code(state), int(max_blocks), stream())
+
+
 def colsum(x, alpha=1.0, out=None, accumulate=False, out_dtype=torch.float32, fold=None, same_bits=False):
     """Column sums of a 2-D tensor (last dim contiguous): fresh tensor of `out_dtype`, or (accumulated) into `out`.
     fold (with out): only the row-group partials are computed now, the FoldQueue finishes the sum at its flush.  same_bits: the queue

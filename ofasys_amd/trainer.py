@@ -22,6 +22,7 @@ import torch.utils._python_dispatch          # noqa: F401  (TorchDispatchMode: t
 from . import kernels as K
 from . import ops
 from .distributed import GradBucketReducer, all_reduce_scalars
+from .ema import EMA, as_config
 from .lib import capture_audit
 
 
@@ -249,8 +250,11 @@ class TrainStep:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_norm=1.0, process_group=None,
                  bucket_bytes: int = 64 << 20, use_graph: bool = False, graph_warmup: int = 2,
                  label_smoothing: float = 0.0, constraint_range=None, drop_worst_ratio: float = 0.0, dp_graph: str = None,
-                 loss_scale=None, max_graphs: int = 16, shard_optimizer: bool = False):
-        """shard_optimizer (data parallel, opt-in): gradients are reduce-SCATTERED, every rank clips and updates only the 1 / world of
+                 loss_scale=None, max_graphs: int = 16, shard_optimizer: bool = False, ema=None):
+        """ema: an ema.EMAConfig (or a dict of its fields) with store_ema set keeps an exponential moving average of the weights
+        (engine/ema/ema.py), updated on the device as the last launches of every update; `self.ema` is the ema.EMA object.  Fixed at
+        construction: a captured step holds exactly the launches `_update` made when it was recorded.
+        shard_optimizer (data parallel, opt-in): gradients are reduce-SCATTERED, every rank clips and updates only the 1 / world of
         the arena it owns, and the updated 16-bit parameters are all-gathered (distributed.GradBucketReducer, "sharded exchange") --
         the optimizer pass (0.6 ms of an 11 ms cfg-2 step) shrinks by the world size at the all-reduce's wire volume.  The optimizer
         state arrays keep their full length (what a rank does not own is never touched); the global gradient norm is the sum of the
@@ -328,6 +332,8 @@ class TrainStep:
         self._skipped_seen = 0.0
         self._seed = torch.ones((), dtype=torch.float32, device=dev)   # the backward seed of a micro-batch's loss (autograd's default: one fill per call)
         self.last = {}
+        ema_cfg = as_config(ema)
+        self.ema = EMA(model, self.fp, ema_cfg, step_t=self._step_t) if ema_cfg is not None else None
 
     # ------------------------------------------------------------------ learning rate (host -> device scalar)
     @property
@@ -421,6 +427,8 @@ class TrainStep:
                         self._sched, 0.0, self.betas[0], self.betas[1], self.eps, self.weight_decay, 0)
         self.reducer.gather_params(self.fp.flat)         # (sharded optimizer: the other ranks' updated parameters)
         self._gnorm = self._gnorm_t
+        if self.ema is not None:                         # after the gather: every rank averages the full, updated parameters
+            self.ema._enqueue(self._step_t, self._sched)
 
     def check(self):
         """Host-side poll of the device guard (ONE sync): raises FloatingPointError as engine/trainer.py:866-876 does when an
@@ -482,6 +490,8 @@ class TrainStep:
         own += [self.fp.flat, self.fp.grad, self.master, self.exp_avg, self.exp_avg_sq, self._stats, self._gsq, self._gnorm_t,
                 self._step_t, self._lr_t, self._sched, self._seed, getattr(self, "_ls", None)]
         own += list(ops._Rng.base.values())
+        if self.ema is not None:
+            own += self.ema.arenas()
         return own
 
     def audit_report(self, entry):
