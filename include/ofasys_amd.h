@@ -404,7 +404,10 @@ int ofa_bias_block_slice(const void* dbias, void* dvalues, int B, int A, int T, 
 int ofa_im2col_patch(const void* img, void* col, int B, int C, int H, int W, int p, int Kpad, int lead, int dtype, void* stream);
 
 /* ---- criterion (engine/criterion/cross_entropy.py:27-67): fp32 log-softmax + NLL(sum, ignore_index) per row.
- * logits [rows, V] (ld elements); writes lse[rows] and row_loss[rows] (0 for ignored rows). */
+ * logits [rows, V] (ld elements); writes lse[rows] and row_loss[rows] (0 for ignored rows).
+ * Precondition of all three cross-entropy entry points: the logits of columns 0..V-1 are finite (a row holding -inf logits may come out
+ * NaN: constrained vocabularies are masked inside ofa_ls_cross_entropy_*, by range and byte mask, never by -inf); columns V..ld-1 are
+ * never read into a result. */
 int ofa_cross_entropy_fwd(const void* logits, const int64_t* target, float* lse, float* row_loss, int64_t rows,
                           int64_t V, int64_t ld, int64_t ignore_index, int dtype, void* stream);
 /* Both in ONE pass over the logits (one read, one write instead of two reads and a write): lse, row_loss AND
