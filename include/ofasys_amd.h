@@ -106,7 +106,25 @@ int ofa_join_bwd(const void* dy, const void* dz, const void* x, const void* y, c
  * rows without copies: batch index z addresses operand X at (z / batch_inner)*strideX2 + (z % batch_inner)*strideX
  * (batch_inner <= 0 or >= batch: single level).  bf16 runs on MFMA (v_mfma_f32_32x32x16_bf16) when every
  * leading dimension is a multiple of 8 elements; fp32 (and OFA_GEMM_FORCE_SIMPLE) run an exact fp32-FMA kernel.
- * `ws`/`ws_bytes`: optional fp32 scratch that enables split-K for skinny outputs (may be NULL). */
+ * `ws`/`ws_bytes`: optional fp32 scratch that enables split-K for skinny outputs (may be NULL).
+ *
+ * Stores.  The MFMA kernels store whole quads of columns: with N4 = (N + 3) & ~3 they need ldc >= N4 (and ldc % 4 == 0; a call that does
+ * not offer that runs the exact kernel), and what columns [N, N4) of rows 0 .. M-1 hold after the call is unspecified.  Nothing else
+ * outside [M, N] is written: not the columns from N4 on, not a row from M on.  Split-K slabs (ws, or the caller's with
+ * OFA_GEMM_DEFER_REDUCE) are [splits][M][N4] fp32.
+ * Reads.  Of A and B only op(A)[M, K] and op(B)[K, N] influence C; a vector that crosses the logical edge of an operand is clamped or
+ * its lanes are discarded, so rows past the operand's last row and the columns up to its leading dimension may hold anything.  The one
+ * exception is OFA_GEMM_A_KPAD_ZERO: A[m][K .. lda) must then be zeros up to the next multiple of 64 that fits in lda (at least up to
+ * roundup8(K)); B's rows from K on are not read (the kernels re-read row K-1 against those zeros).
+ *
+ * OFA_GEMM_ACCUM onto a 16-bit C has two arithmetics, and the plan of the call (ofa_gemm_plan) decides which one runs.  With
+ * X = alpha * (op(A) op(B) + bias) in fp32 and rn16 = round to nearest even in C's type:
+ *   - a tile kernel that finishes the product in its own epilogue (REG, LDS_DMA, RING, BIG, PP, MIXED with one K-slice) and the direct
+ *     path of ofa_gemm_group_tn round the tile, add the old C and round again:           C = rn16(rn16(X) + C_old);
+ *   - a split-K product, finished by the reduce launch or by ofa_fold_batched (OFA_GEMM_DEFER_REDUCE, the slabs of ofa_gemm_group_tn),
+ *     and the exact kernel (SIMPLE) add the old C in fp32 and round once:                C = rn16(X + C_old).
+ * The first is what a 16-bit `grad += g` of the reference does, the second is tighter; the same call may give different bits under
+ * another plan.  An fp32 C (OFA_GEMM_OUT_F32, fp32 operands) is accumulated in fp32 on every route.  tests/gemm_exact.py pins both. */
 int ofa_gemm(const void* A, const void* B, void* C, const void* bias, int M, int N, int K, int transA, int transB,
              int64_t lda, int64_t ldb, int64_t ldc, int batch, int64_t strideA, int64_t strideB, int64_t strideC,
              int batch_inner, int64_t strideA2, int64_t strideB2, int64_t strideC2,
