@@ -729,6 +729,35 @@ int ofa_trie_beam_advance(int* node, const int* node_edge_off, const int* edge_t
                           int bsz, int K, int step, const int64_t* tokens, int64_t tok_ld, int tok_cap, const float* scores,
                           int64_t score_ld, const int* ignore, const int64_t* reorder, int* done, int* nfin, void* stream);
 
+/* ---- sampling (csrc/sample.hip): Sampling.step (utils/search.py:596-715) under SequenceGenerator's bookkeeping
+ * (generator/sequence_generator.py:283-492), two launches per decoding step, recorded in the step graph like the beam launches.
+ * Rows are bsz sentences x K slots (K <= 16, V <= 65536); a sentence's K slots are K independent samples.  No random numbers
+ * are made: uniforms fp32 [rows] holds this step's one number in [0, 1) per row.  ws: ofa_sample_ws_bytes(rows, V, K) = 8 * rows
+ * bytes (the drawn lprob fp32 [rows], then the drawn token int [rows]), written by ofa_sample_draw and read by ofa_sample_select.
+ * ofa_sample_draw: one workgroup per row.  lprobs as ofa_beam_topk computes them (same arguments: the fp32 log-softmax of
+ * x / temperature under constraint_range, then the post-normaliser masks); weights w = expf(lprob), not renormalised.  Kept set:
+ * topp > 0: the tokens whose weight ranked strictly ahead (lprob descending, token ascending) is < topp (everything when the
+ * row's total is below topp; topp <= 1); else topk > 0: the topk first of that ranking; else every token.  The draw is the kept
+ * token with the smallest id c* such that the kept weight of ids <= c* exceeds u * (the kept weight of the row): an inverse CDF
+ * in vocabulary order.  Weights are summed as integers in units of 2^-40, so the result does not depend on any summation order;
+ * a row whose kept tokens all weigh less than that unit (or a NaN row: all -inf) draws its top-ranked token.  The lprob written
+ * is the one under the full softmax.  At step 0 every row of a sentence reads the sentence's first row, with its own uniform.
+ * Rows of finished sentences (done) are skipped and their ws entries left alone.
+ * ofa_sample_select: one workgroup per sentence over the K draws: slot j continues itself (slot 0 at step 0) with
+ * score = scores[row, step - 1] + lprob; an EOS draw with a finite score in a slot not ignored is finalised; ignored slots stay
+ * ignored; the slots that go on are compacted to the front in column order (reorder is not the identity once a slot has ended);
+ * a sentence is finished with K hypotheses or at step == max_len.  Histories, fin_* buffers, ignore, done, nfin and reorder as in
+ * ofa_beam_select. */
+int64_t ofa_sample_ws_bytes(int rows, int V, int K);
+int ofa_sample_draw(const void* logits, int64_t ld, int rows, int V, int K, float temperature, int cstart, int cend, int step,
+                    int min_len, int max_len, int pad, int unk, int eos, float unk_penalty, int ngram, const int64_t* tokens,
+                    int64_t tok_ld, const int* done, int topk, float topp, const float* uniforms, void* ws, int dtype,
+                    void* stream);
+int ofa_sample_select(const void* ws, int bsz, int K, int step, int max_len, int eos, int normalize, float len_penalty,
+                      int64_t* tokens, int64_t tok_ld, int tok_cap, float* scores, int64_t score_ld, int* ignore, int* done,
+                      int* nfin, int64_t* reorder, int64_t* fin_tok, float* fin_pos, int64_t fin_ld, float* fin_score,
+                      int* fin_len, int* fin_cnt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,10 @@ while a sentence's prefix lasts, its rows are forced onto the prefix token by th
 `constraint_trie`, generator/sequence_generator.py:729-741): the row pass computes one dot product per child edge of the row's trie
 node instead of reading a [rows, V] projection (csrc/trie_beam.hip), the sentence pass is unchanged, and a third small launch
 advances every row's node.
+
+`SequenceGenerator(search_strategy=Sampling(...))` samples instead (utils/search.py:596-715): a sentence's K rows are K independent
+samples, drawn by csrc/sample.hip from uniform numbers held in `st["uniforms"]` -- supplied by the caller (`generate(uniforms=U)`) or
+filled once per generate, outside the step graphs, from a seeded torch.Generator.
 """
 import math
 from dataclasses import dataclass
@@ -188,10 +192,23 @@ class SequenceGeneratorOutput:
     box: Optional[torch.Tensor] = None
 
 
+class Sampling:
+    """The reference's sampling search strategy (utils/search.py:596-603) as a plain options holder: what
+    `SequenceGenerator(search_strategy=...)` reads.  sampling_topp > 0 (nucleus) wins over sampling_topk > 0; neither: the whole
+    vocabulary.  The step itself is csrc/sample.hip."""
+
+    def __init__(self, tgt_dict, sampling_topk=-1, sampling_topp=-1.0):
+        self.pad, self.unk, self.eos, self.vocab_size = tgt_dict.pad(), tgt_dict.unk(), tgt_dict.eos(), len(tgt_dict)
+        self.sampling_topk, self.sampling_topp = int(sampling_topk), float(sampling_topp)
+        if self.sampling_topp > 1.0:
+            raise ValueError(f"Sampling: sampling_topp={sampling_topp} is above 1")
+
+
 class SequenceGenerator:
-    """Beam search with the reference's constructor and defaults (generator/sequence_generator.py:66-159).  Unsupported
-    options of the reference raise NotImplementedError: other search strategies, an LM, a constraint trie, match_source_len,
-    lexical constraints and a prefix that holds <eos>."""
+    """Beam search with the reference's constructor and defaults (generator/sequence_generator.py:66-159), or sampling with
+    `search_strategy=Sampling(...)` (`seed`: of the uniform numbers `generate` draws when it is given none; None: taken from
+    torch's global generator).  Unsupported options of the reference raise NotImplementedError: other search strategies, an LM,
+    a constraint trie, match_source_len, lexical constraints, a prefix that holds <eos>, and any prefix under sampling."""
 
     MAX_BEAM = 16
 
@@ -199,10 +216,13 @@ class SequenceGenerator:
                  max_len: int = 256, min_len: int = 1, normalize_scores: bool = True, len_penalty: float = 1.0,
                  unk_penalty: float = 0.0, temperature: float = 1.0, match_source_len: bool = False,
                  no_repeat_ngram_size: int = 0, search_strategy=None, lm_model=None, lm_weight: float = 1.0,
-                 constraint_trie=None, constraint_range: Optional[str] = None, use_graph: bool = True, **unused_kwargs):
-        if search_strategy is not None:
-            raise NotImplementedError("SequenceGenerator: only plain beam search is implemented (search_strategy must be None; "
-                                      "sampling, diverse beam and constrained search are not)")
+                 constraint_trie=None, constraint_range: Optional[str] = None, use_graph: bool = True, seed: Optional[int] = None,
+                 **unused_kwargs):
+        if search_strategy is not None and not isinstance(search_strategy, Sampling):
+            raise NotImplementedError("SequenceGenerator: only plain beam search and sampling are implemented (search_strategy must "
+                                      "be None or a Sampling; diverse beam and constrained search are not)")
+        self.sampling: Optional[Sampling] = search_strategy
+        self.seed, self._rng = seed, None
         if lm_model is not None:
             raise NotImplementedError("SequenceGenerator: LM fusion (lm_model) is not implemented")
         if constraint_trie is not None:
@@ -257,6 +277,9 @@ class SequenceGenerator:
         prefix = sample.get("prefix_tokens")
         if prefix is None or prefix.dim() != 2 or prefix.size(1) == 0:
             return None
+        if self.sampling is not None:
+            raise NotImplementedError("SequenceGenerator: prefix_tokens under sampling are not implemented (got a prefix of "
+                                      f"{prefix.size(1)} columns)")
         prefix = prefix.long()
         keep = prefix.ne(self.pad)
         plen = keep.sum(1)
@@ -293,6 +316,10 @@ class SequenceGenerator:
                 "prefix": torch.full((bsz, max_len + 1), self.pad, dtype=torch.long, device=device),
                 "plen": torch.zeros(bsz, **i32), "glogit": torch.zeros(rows, dtype=torch.float32, device=device),
             }
+            if self.sampling is not None:
+                # the draws of a step and the uniform numbers of every step (step t reads row t), at fixed addresses
+                self._state["sample_ws"] = torch.zeros((K.sample_ws_bytes(rows, V, K_) + 3) // 4, dtype=torch.float32, device=device)
+                self._state["uniforms"] = torch.zeros(max_len + 1, rows, dtype=torch.float32, device=device)
         st = self._state
         for name in ("scores", "ignore", "done", "nfin", "fin_cnt"):
             st[name].zero_()
@@ -349,6 +376,8 @@ class SequenceGenerator:
     def _step_kernels(self, out, t, dec, st, max_len, ngram_step0=True, ctx=None):
         """Everything a step does after the decoder, on the device (recorded into the step graph)."""
         ngram = self.no_repeat_ngram_size if (t > 0 or ngram_step0) else 0
+        if self.sampling is not None:
+            return self._sample_step_kernels(out, t, dec, st, max_len, ngram)
         V = self._row_pass(out, t, dec, st, max_len, ngram, ctx)
         st["tokens"] = dec.tokens
         K.beam_select(st["ws"], st, self.beam_size, V, t, max_len, eos=self.eos, unk=self.unk, unk_penalty=self.unk_penalty,
@@ -356,9 +385,38 @@ class SequenceGenerator:
         self._advance(t, st, ctx)
         dec.reorder(st["reorder"], caches_only=True)
 
+    def _sample_step_kernels(self, out, t, dec, st, max_len, ngram):
+        """A sampling step: every row's draw from row t of the uniforms, then the K-wide sentence pass."""
+        K.sample_draw(out, self.beam_size, t, st["sample_ws"], st["uniforms"][t], topk=self.sampling.sampling_topk,
+                      topp=self.sampling.sampling_topp, tokens=dec.tokens, done=st["done"], temperature=self.temperature,
+                      constraint_range=None if self.constraint_start is None else (self.constraint_start, self.constraint_end),
+                      min_len=self.min_len, max_len=max_len, pad=self.pad, unk=self.unk, eos=self.eos,
+                      unk_penalty=self.unk_penalty, ngram=ngram)
+        st["tokens"] = dec.tokens
+        K.sample_select(st["sample_ws"], st, self.beam_size, t, max_len, eos=self.eos, normalize=self.normalize_scores,
+                        len_penalty=self.len_penalty)
+        dec.reorder(st["reorder"], caches_only=True)
+
+    def _fill_uniforms(self, st, uniforms):
+        """One number in [0, 1) per (step, row): the caller's table, or one launch of a generator seeded once -- from `seed`, or
+        from torch's global generator -- so successive generate() calls draw on."""
+        buf = st["uniforms"]
+        if uniforms is not None:
+            if tuple(uniforms.shape) != tuple(buf.shape):
+                raise ValueError(f"generate: uniforms must be [steps + 1, rows] = {tuple(buf.shape)}, got {tuple(uniforms.shape)}")
+            buf.copy_(uniforms.to(torch.float32))
+            return
+        if self._rng is None or self._rng.device != buf.device:
+            self._rng = torch.Generator(device=buf.device)
+            self._rng.manual_seed(int(torch.randint(0, 2 ** 62, (1,)).item()) if self.seed is None else int(self.seed))
+        buf.uniform_(generator=self._rng)
+
     # ------------------------------------------------------------------ generate
     @torch.no_grad()
-    def generate(self, model, sample, **kwargs):
+    def generate(self, model, sample, uniforms=None, **kwargs):
+        """uniforms (sampling only): fp32 [steps + 1, rows], row t the numbers of step t -- the draws are a function of them."""
+        if uniforms is not None and self.sampling is None:
+            raise ValueError("generate: uniforms are read by sampling only (search_strategy=Sampling(...))")
         ngram_step0 = self.check_sample(sample, **kwargs)
         prefix = self._prefix_of(sample)
         source_slots = [s for s in sample["net_input"]["slots"] if s.is_src]
@@ -375,6 +433,8 @@ class SequenceGenerator:
         dec.tokens.fill_(self.pad)
         dec.tokens[:, 0] = self.bos
         st = self._buffers(rows, bsz, V, steps, device)
+        if self.sampling is not None:
+            self._fill_uniforms(st, uniforms)
         post = lambda out, t: self._step_kernels(out, t, dec, st, max_len, ngram_step0, ctx)   # noqa: E731
         variant = None
         if prefix is not None:
@@ -439,6 +499,8 @@ class TrieBeamGenerator(SequenceGenerator):
     def __init__(self, tgt_dict, plan, *args, **kwargs):
         if kwargs.get("constraint_range") is not None:
             raise ValueError("TrieBeamGenerator: constraint_range cannot be combined with a constraint trie")
+        if kwargs.get("search_strategy") is not None:
+            raise NotImplementedError("TrieBeamGenerator: only beam search is implemented (search_strategy must be None)")
         super().__init__(tgt_dict, *args, **kwargs)
         if (plan.bos, plan.eos, plan.pad) != (self.bos, self.eos, self.pad):
             raise ValueError("TrieBeamGenerator: the plan was built with other BOS / EOS / PAD ids than the dictionary's")

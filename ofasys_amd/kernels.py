@@ -1482,6 +1482,39 @@ def closed_set_score(h2d, weight, bias, plan, bsz, ws=None):
     return scores
 
 
+# ------------------------------------------------------------------ sampling (csrc/sample.hip)
+def sample_ws_bytes(rows, V, K):
+    return int(lib().cdll.ofa_sample_ws_bytes(int(rows), int(V), int(K)))
+
+
+def sample_draw(logits2d, K, step, ws, uniforms, topk=-1, topp=-1.0, tokens=None, done=None, temperature=1.0, constraint_range=None,
+                min_len=1, max_len=256, pad=1, unk=3, eos=2, unk_penalty=0.0, ngram=0):
+    """Row pass of one sampling step: logits2d [rows, V] as beam_topk takes them, uniforms fp32 [rows] (this step's number in
+    [0, 1) per row) -> every row's drawn (lprob, token) in `ws` (sample_ws_bytes).  topp > 0 wins over topk > 0; neither: the
+    whole vocabulary.  The draw is the inverse CDF of the kept weights in vocabulary order."""
+    rows, V = logits2d.shape
+    if logits2d.stride(1) != 1:
+        raise OfaError("sample_draw: the logits' last dimension must be contiguous")
+    if uniforms.dtype != torch.float32 or uniforms.numel() != rows or not uniforms.is_contiguous():
+        raise OfaError("sample_draw: uniforms must be a contiguous float32 [rows]")
+    cs, ce = (-1, -1) if constraint_range is None else (int(constraint_range[0]), int(constraint_range[1]))
+    tok_ld = tokens.stride(0) if tokens is not None else 0
+    lib().call("ofa_sample_draw", ptr(logits2d), logits2d.stride(0), rows, V, int(K), float(temperature), cs, ce, int(step),
+               int(min_len), int(max_len), int(pad), int(unk), int(eos), float(unk_penalty), int(ngram), ptr(tokens), tok_ld,
+               ptr(done), int(topk), float(topp), ptr(uniforms), ptr(ws), dtype_code(logits2d), stream())
+
+
+def sample_select(ws, st, K, step, max_len, eos=2, normalize=False, len_penalty=1.0):
+    """Sentence pass of one sampling step over the state dict `st` (as beam_select): finalises the EOS draws, compacts the slots
+    that go on to the front, gathers the histories in place and writes the reorder index."""
+    tokens, scores = st["tokens"], st["scores"]
+    bsz = st["done"].numel()
+    lib().call("ofa_sample_select", ptr(ws), bsz, int(K), int(step), int(max_len), int(eos), int(bool(normalize)),
+               float(len_penalty), ptr(tokens), tokens.stride(0), tokens.shape[1], ptr(scores), scores.stride(0), ptr(st["ignore"]),
+               ptr(st["done"]), ptr(st["nfin"]), ptr(st["reorder"]), ptr(st["fin_tok"]), ptr(st["fin_pos"]),
+               st["fin_tok"].stride(1), ptr(st["fin_score"]), ptr(st["fin_len"]), ptr(st["fin_cnt"]), stream())
+
+
 # ------------------------------------------------------------------ trie-constrained beam search (csrc/trie_beam.hip)
 def trie_beam_splits(max_degree, V):
     """Workgroups per row of trie_beam_topk for a plan (the grid's x extent)."""

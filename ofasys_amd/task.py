@@ -131,6 +131,7 @@ class Task:
         self.general_preprocess: Optional[GeneralPreprocess] = None
         self._iters = {}
         self._generator = None
+        self._sampling_gens: Dict[Any, Any] = {}
 
     # ------------------------------------------------------------------ identity / datasets (task/base.py:256-273)
     @property
@@ -224,8 +225,9 @@ class Task:
     # ------------------------------------------------------------------ generation (task/base.py:232-246, 470-556, 727-793)
     def generator_kwargs(self, **gen_kwargs) -> Dict[str, Any]:
         """The reference's generator arguments (task/base.py:475-486: its pops and defaults; normalize_scores defaults to False
-        here, unlike the generator's own default) as SequenceGenerator keywords.  Only plain beam search exists: sampling, diverse
-        beam, diverse siblings, match_source_len and lexical constraints raise NotImplementedError."""
+        here, unlike the generator's own default) as SequenceGenerator keywords.  Beam search only: diverse beam, diverse siblings,
+        match_source_len and lexical constraints raise NotImplementedError, and so do the sampling arguments -- a sampling
+        generator comes from `sampling_generator`."""
         args = dict(
             beam_size=gen_kwargs.pop("beam", 5), return_n_best=gen_kwargs.pop("return_n_best", 1),
             max_len_a=gen_kwargs.pop("max_len_a", 0), max_len_b=gen_kwargs.pop("max_len_b", 200),
@@ -238,7 +240,8 @@ class Task:
         for k, default in unsupported.items():
             v = gen_kwargs.pop(k, default)
             if v != default:
-                raise NotImplementedError(f"build_generator: {k}={v!r} -- only plain beam search is implemented")
+                hint = "; for sampling call Task.sampling_generator(...)" if k.startswith("sampling") else ""
+                raise NotImplementedError(f"build_generator: {k}={v!r} -- only plain beam search is implemented{hint}")
         gen_kwargs.pop("diverse_beam_strength", None)
         return dict(args, **gen_kwargs)
 
@@ -248,6 +251,32 @@ class Task:
         if self.global_dict is None:
             raise ValueError(f"task {self.name}: initialize(global_dict) before building a generator")
         return SequenceGenerator(self.global_dict, **self.generator_kwargs(**gen_kwargs))
+
+    def sampling_generator(self, **gen_kwargs):
+        """SequenceGenerator(search_strategy=Sampling(...)) from the reference's generator arguments: `sampling`, `sampling_topk`,
+        `sampling_topp` (task/base.py:488-515, with its checks) and `seed` are taken out here, the rest goes through
+        `generator_kwargs`.  One generator is kept per option set, so its captured step graphs -- and its stream of random
+        numbers -- carry on over later batches.  `task.generator = task.sampling_generator(...)` makes `inference` sample."""
+        from .generator import Sampling, SequenceGenerator
+        if self.global_dict is None:
+            raise ValueError(f"task {self.name}: initialize(global_dict) before building a generator")
+        sampling = gen_kwargs.pop("sampling", True)
+        topk, topp = gen_kwargs.pop("sampling_topk", -1), gen_kwargs.pop("sampling_topp", -1.0)
+        seed = gen_kwargs.pop("seed", None)
+        others = [gen_kwargs.get("diverse_beam_groups", -1) > 0, gen_kwargs.get("match_source_len", False),
+                  gen_kwargs.get("diversity_rate", -1) > 0]
+        if sampling and any(others):
+            raise ValueError("Provided Search parameters are mutually exclusive.")
+        assert topk < 0 or sampling, "--sampling-topk requires --sampling"
+        assert topp < 0 or sampling, "--sampling-topp requires --sampling"
+        if not sampling:
+            raise ValueError("sampling_generator: sampling=False -- build_generator makes the beam-search generator")
+        kw = self.generator_kwargs(**gen_kwargs)
+        key = tuple(sorted((k, repr(v)) for k, v in dict(kw, sampling_topk=topk, sampling_topp=topp, seed=seed).items()))
+        if key not in self._sampling_gens:
+            self._sampling_gens[key] = SequenceGenerator(self.global_dict, search_strategy=Sampling(self.global_dict, topk, topp),
+                                                         seed=seed, **kw)
+        return self._sampling_gens[key]
 
     @property
     def generator(self):
