@@ -452,6 +452,19 @@ int ofa_ls_cross_entropy_bwd(const void* logits, const int64_t* target, const fl
                              const float* row_w, const float* grad_scale, void* dlogits, int64_t rows, int64_t V, int64_t ld,
                              int64_t ignore_index, float eps, int64_t cstart, int64_t cend, const uint8_t* cmask, int dtype,
                              void* stream);
+/* self-critical sequence training (engine/criterion/scst_loss.py:24-36, 214-233): reward-weighted NLL of the generated tokens, forward
+ * AND gradient in one call.  Row r belongs to sentence s = row_seq ? row_seq[r] : r / rows_per_seq and carries the weight
+ * w = reward[s] (fp32 [nseq]; an s outside [0, nseq) reads nothing and weighs 0).  Over the allowed vocabulary A -- all of it
+ * (cstart < 0), or [0,4) U [cstart,cend) -- it writes
+ *     lse = log sum_{v in A} exp(x_v),  row_loss = w (lse - x_t),  dlogits_v = w grad_scale[0] (exp(x_v - lse) - [v == t])   (v in A)
+ * and exactly 0 for v outside A, for columns V..ld-1, and for every column of a row whose target is ignore_index (row_loss 0) or whose
+ * weight is 0.  A target that is not an allowed column of [0, V) is a caller error the kernel survives: nothing is read out of bounds,
+ * row_loss = +inf, the gradient row is 0.  grad_scale: device scalar, NULL = 1.  16-bit logits with ld <= 65536 are held in the
+ * registers of a 1024-thread block (one read, one write); fp32 logits and longer rows are read twice.  logits finite, as above. */
+int ofa_scst_loss_fwd_grad(const void* logits, const int64_t* target, const float* reward, const int32_t* row_seq,
+                           int64_t rows_per_seq, const float* grad_scale, float* lse, float* row_loss, void* dlogits, int64_t rows,
+                           int64_t nseq, int64_t V, int64_t ld, int64_t ignore_index, int64_t cstart, int64_t cend, int dtype,
+                           void* stream);
 /* get_normalized_probs (model/ofa.py:287-299, module/utils.py:451-462): out fp32 [rows, V] = (log-)softmax_fp32(logits);
  * backward writes dlogits [rows, ld] in `dtype` (columns V..ld-1 zero). */
 int ofa_probs_fwd(const void* logits, float* out, int64_t rows, int64_t V, int64_t ld, int log_probs, int dtype,

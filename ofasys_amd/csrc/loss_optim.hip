@@ -269,6 +269,207 @@ __global__ __launch_bounds__(256) void lsce_bwd_kernel(const T* __restrict__ log
   }
 }
 
+// ---- self-critical sequence training (engine/criterion/scst_loss.py:24-36, 214-233): per row the NLL of the GENERATED token times the
+// reward of the row's sentence, over the allowed vocabulary (all of it, or [0,4) U [cstart,cend): the reference sets the other logits
+// to -inf, :215-217).  The logits are [B*K rows, V] -- K times the cross-entropy step's -- so forward and gradient share one pass:
+//     w = reward[s],  s = row_seq ? row_seq[r] : r / rows_per_seq      (a sentence index outside [0, nseq) reads nothing: w = 0)
+//     lse = log sum_{v in A} exp(x_v);   row_loss = w (lse - x_t);   dlogits_v = w g (exp(x_v - lse) - [v == t]) on A, exactly 0 elsewhere
+// An ignored row, a row of weight 0 and a row whose target is not an allowed column of [0, V) (a caller error: row_loss = +inf, as the
+// reference's -lprob) get a zero gradient row.
+__device__ __forceinline__ bool scst_ok(int64_t c, int64_t V, int64_t cs, int64_t ce) {
+  return c < V && (cs < 0 || c < 4 || (c >= cs && c < ce));
+}
+// a vector of N columns from c0: 2 = every column allowed, 0 = none, 1 = cut (by V, by cstart / cend, or the [0,4) vector)
+__device__ __forceinline__ int scst_vec_class(int64_t c0, int N, int64_t V, int64_t cs, int64_t ce) {
+  if (c0 >= V) return 0;
+  if (cs < 0) return c0 + N <= V ? 2 : 1;
+  if (c0 >= cs && c0 + N <= ce) return c0 + N <= V ? 2 : 1;
+  if (c0 >= 4 && (c0 + N <= cs || c0 >= ce)) return 0;
+  return 1;
+}
+struct ScstRow { float w; int64_t t; bool ignored, valid; };
+__device__ __forceinline__ ScstRow scst_row(int64_t row, const int64_t* target, const float* reward, const int32_t* row_seq,
+                                            int64_t rows_per_seq, int64_t nseq, int64_t V, int64_t cs, int64_t ce, int64_t ignore_index) {
+  ScstRow r;
+  const int64_t s = row_seq ? (int64_t)row_seq[row] : row / rows_per_seq;
+  r.w = (s >= 0 && s < nseq) ? reward[s] : 0.f;
+  r.t = target[row];
+  r.ignored = r.t == ignore_index;
+  r.valid = r.t >= 0 && scst_ok(r.t, V, cs, ce);
+  return r;
+}
+
+// Registers form (16-bit logits, ld <= 65536): ce_fwd_grad_kernel's block -- 1024 threads hold the row in NV x 8 registers each, one
+// read and one write -- with the allowed-set test made per VECTOR: a vector wholly inside the range takes the plain path, one wholly
+// outside is skipped (and written as zeros), and only the cut ones (the [0,4) vector, the two that cstart / cend cut, the one V cuts)
+// go element by element.
+template <typename T, int NV>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void scst_fwd_grad_kernel(
+    const T* __restrict__ logits, const int64_t* __restrict__ target, const float* __restrict__ reward,
+    const int32_t* __restrict__ row_seq, int rows_per_seq, const float* __restrict__ gscale, float* __restrict__ lse,
+    float* __restrict__ row_loss, T* __restrict__ dlogits, int nseq, int V, int ld, int64_t ignore_index, int cs, int ce) {
+  constexpr int N = Vec<T>::N;
+  static_assert(N == 8, "16-bit element types");
+  constexpr float L2E = 1.4426950408889634f;
+  auto ex2 = [](float v) { return __builtin_amdgcn_exp2f(v); };     // one v_exp_f32 behind an FMA, as in ce_fwd_grad_kernel
+  __shared__ float sm[16], ss[16];
+  const int64_t row = blockIdx.x;
+  const char* xb = reinterpret_cast<const char*>(logits + row * ld);
+  char* db = reinterpret_cast<char*>(dlogits + row * ld);
+  const int nvec = ld / N;
+  const int tid = threadIdx.x;
+  uint4 raw[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i)      // (past the row's end the last vector is loaded again, in bounds, and never used: no branch per slab)
+    raw[i] = *reinterpret_cast<const uint4*>(xb + (uint32_t)min(tid + i * 1024, nvec - 1) * 16u);
+  // the allowed set by VECTOR index (uniform bounds; the host hands cs = 0, ce = V for "no range"): every column allowed in [f_lo, f_hi),
+  // some column allowed in [a_lo, a_hi) and in vector 0 -- so a wave meets the per-element test only where cstart, cend or V cut
+  const int f_lo = (cs + 7) >> 3, f_hi = ce >> 3, a_lo = cs >> 3, a_hi = (ce + 7) >> 3;
+  // (one bit per slab in two registers, worked out once)
+  uint32_t some_bits = 0, full_bits = 0;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int v = tid + i * 1024;
+    some_bits |= (uint32_t)(((v >= a_lo) & (v < a_hi)) | (v == 0)) << i;
+    full_bits |= (uint32_t)((v >= f_lo) & (v < f_hi)) << i;
+  }
+  auto some = [&](uint32_t bits, int i) { return (bits >> i) & 1u; };
+  auto okc = [&](int th8, int k) {                       // column th8 + k, k = slab * 8192 + element: again against moved uniform bounds
+    return (th8 < V - k) & ((th8 < 4 - k) | ((th8 >= cs - k) & (th8 < ce - k)));
+  };
+  const int tid8 = tid * N;
+  float m = -INFINITY, s = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    if (!some(some_bits, i)) continue;
+    float a[N];
+    unpack16<T>(raw[i], a);
+    if (!some(full_bits, i)) {                           // a cut vector: its disallowed columns enter the sums as -inf
+#pragma unroll
+      for (int j = 0; j < N; ++j) a[j] = okc(tid8, i * 8192 + j) ? a[j] : -INFINITY;
+    }
+    float lm = a[0];
+#pragma unroll
+    for (int j = 1; j < N; ++j) lm = fmaxf(lm, a[j]);
+    const float mm = fmaxf(m, lm), mk = -mm * L2E;       // (every vector that gets here holds an allowed column: mm is finite)
+    float acc = s * ex2(fmaf(m, L2E, mk));
+#pragma unroll
+    for (int j = 0; j < N; ++j) acc += ex2(fmaf(a[j], L2E, mk));
+    m = mm;
+    s = acc;
+  }
+  const float mw = wave_max(m);                                      // max first, then one rescale per partial sum
+  const float sw = wave_sum(mw == -INFINITY ? 0.f : s * ex2((m - mw) * L2E));
+  const int wave = tid >> 6;
+  if ((tid & 63) == 0) { sm[wave] = mw; ss[wave] = sw; }
+  __syncthreads();
+  // the 16 wave results, one per lane, reduced by every wave in the same order (ce_fwd_grad_kernel reads all 32 values into registers of
+  // every thread, which with the row's 28 is where it spills); the results come back through a lane read: uniform from here on
+  const int lane = tid & 63;
+  const float mv = lane < 16 ? sm[lane] : -INFINITY, sv = lane < 16 ? ss[lane] : 0.f;
+  const float M = wave_max(mv);
+  const float S = wave_sum(sv * ex2((mv - M) * L2E));      // (a wave of disallowed columns only, and lanes 16..63: 0 * 2^-inf = 0)
+  const float l = M + logf(S);
+  const ScstRow r = scst_row(row, target, reward, row_seq, rows_per_seq, nseq, V, cs, ce, ignore_index);
+  if (tid == 0) {
+    lse[row] = l;
+    row_loss[row] = r.ignored ? 0.f : !r.valid ? INFINITY : r.w * (l - ld1<T>(reinterpret_cast<const T*>(xb) + r.t));
+  }
+  const float g = (r.ignored || !r.valid) ? 0.f : r.w * (gscale ? gscale[0] : 1.0f);
+  const int trel = (r.valid ? (int)r.t : -1) - tid8;     // the target's column relative to this thread's first: slab i, element j is i * 8192 + j
+  const float lk = -l * L2E;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    if (tid >= nvec - i * 1024) continue;
+    uint4 w = make_uint4(0, 0, 0, 0);
+    if ((g != 0.f) & (some(some_bits, i) != 0)) {
+      float a[N], o[N];
+      unpack16<T>(raw[i], a);
+#pragma unroll
+      for (int j = 0; j < N; ++j) o[j] = (ex2(fmaf(a[j], L2E, lk)) - (trel == i * 8192 + j ? 1.f : 0.f)) * g;
+      if (!some(full_bits, i)) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) o[j] = okc(tid8, i * 8192 + j) ? o[j] : 0.f;
+      }
+      w.x = pack2<T>(o[0], o[1]); w.y = pack2<T>(o[2], o[3]); w.z = pack2<T>(o[4], o[5]); w.w = pack2<T>(o[6], o[7]);
+    }
+    *reinterpret_cast<uint4*>(db + (uint32_t)(tid + i * 1024) * 16u) = w;
+  }
+}
+
+// Streaming form (fp32 logits, or rows longer than the registers form holds): one 256-thread block per row reads the row twice.
+template <typename T>
+__global__ __launch_bounds__(256) void scst_stream_kernel(
+    const T* __restrict__ logits, const int64_t* __restrict__ target, const float* __restrict__ reward,
+    const int32_t* __restrict__ row_seq, int64_t rows_per_seq, const float* __restrict__ gscale, float* __restrict__ lse,
+    float* __restrict__ row_loss, T* __restrict__ dlogits, int64_t nseq, int64_t V, int64_t ld, int64_t ignore_index, int64_t cs,
+    int64_t ce) {
+  constexpr int N = Vec<T>::N;
+  __shared__ float sm[4], ss[4], sl;
+  const int64_t row = blockIdx.x;
+  const T* x = logits + row * ld;
+  T* dx = dlogits + row * ld;
+  const int64_t nvec = ld / N;                             // ld is a multiple of the vector width (launch precondition)
+  float m = -INFINITY, s = 0.f;
+  for (int64_t v = threadIdx.x; v < nvec; v += 256) {
+    const int64_t c0 = v * N;
+    const int cls = scst_vec_class(c0, N, V, cs, ce);
+    if (cls == 0) continue;
+    float a[N];
+    load_vec<T>(x + c0, a);
+    if (cls == 2) {
+      float lm = a[0];
+#pragma unroll
+      for (int j = 1; j < N; ++j) lm = fmaxf(lm, a[j]);
+      const float mm = fmaxf(m, lm);
+      float acc = s * expf(m - mm);
+#pragma unroll
+      for (int j = 0; j < N; ++j) acc += expf(a[j] - mm);
+      m = mm;
+      s = acc;
+    } else {
+#pragma unroll
+      for (int j = 0; j < N; ++j)
+        if (scst_ok(c0 + j, V, cs, ce)) online_merge(m, s, a[j], 1.f);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+    online_merge(m, s, m2, s2);
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { sm[wave] = m; ss[wave] = s; }
+  __syncthreads();
+  const ScstRow r = scst_row(row, target, reward, row_seq, rows_per_seq, nseq, V, cs, ce, ignore_index);
+  if (threadIdx.x == 0) {
+    float M = sm[0], S = ss[0];
+    for (int w = 1; w < 4; ++w) online_merge(M, S, sm[w], ss[w]);
+    const float l = M + logf(S);
+    sl = l;
+    lse[row] = l;
+    row_loss[row] = r.ignored ? 0.f : !r.valid ? INFINITY : r.w * (l - ld1<T>(x + r.t));
+  }
+  __syncthreads();
+  const float l = sl;
+  const float g = (r.ignored || !r.valid) ? 0.f : r.w * (gscale ? gscale[0] : 1.0f);
+  for (int64_t v = threadIdx.x; v < nvec; v += 256) {
+    const int64_t c0 = v * N;
+    const int cls = g == 0.f ? 0 : scst_vec_class(c0, N, V, cs, ce);
+    float o[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) o[j] = 0.f;
+    if (cls != 0) {
+      float a[N];
+      load_vec<T>(x + c0, a);
+#pragma unroll
+      for (int j = 0; j < N; ++j)
+        if (cls == 2 || scst_ok(c0 + j, V, cs, ce)) o[j] = (expf(a[j] - l) - (c0 + j == r.t ? 1.f : 0.f)) * g;
+    }
+    store_vec<T>(dx + c0, o);
+  }
+}
+
 // get_normalized_probs (model/ofa.py:287-299): fp32 softmax / log-softmax of the logits, one block per row.
 __device__ __forceinline__ float block_sum(float v, float* sw) {
   v = wave_sum(v);
@@ -797,6 +998,48 @@ extern "C" int ofa_ls_cross_entropy_bwd(const void* logits, const int64_t* targe
     hipLaunchKernelGGL((lsce_bwd_kernel<T>), dim3((unsigned)rows), dim3(256), 0, st, (const T*)logits, target, lse, row_cnt, row_w, grad_scale, (T*)dlogits, V, ld, ignore_index, cfg);
   });
   return check_launch("ls_cross_entropy_bwd");
+}
+
+// the registers form holds 16-bit rows of at most 8 slabs x 1024 threads x 8 columns; everything else streams
+template <typename T>
+static void scst_launch(const T* logits, const int64_t* target, const float* reward, const int32_t* row_seq, int64_t rows_per_seq,
+                        const float* gs, float* lse, float* row_loss, T* dlogits, int64_t rows, int64_t nseq, int64_t V, int64_t ld,
+                        int64_t ignore_index, int64_t cs, int64_t ce, hipStream_t st) {
+  if constexpr (sizeof(T) == 2) {
+    const int64_t per_thread = (ld / 8 + 1023) / 1024;
+#define SCST_FG(NV) hipLaunchKernelGGL((scst_fwd_grad_kernel<T, NV>), dim3((unsigned)rows), dim3(1024), 0, st, logits, target, reward, row_seq, (int)rows_per_seq, gs, lse, row_loss, dlogits, (int)nseq, (int)V, (int)ld, ignore_index, (int)cs, (int)ce)
+    if (per_thread <= 1) { SCST_FG(1); return; }
+    if (per_thread <= 2) { SCST_FG(2); return; }
+    if (per_thread <= 4) { SCST_FG(4); return; }
+    if (per_thread <= 7) { SCST_FG(7); return; }
+    if (per_thread <= 8) { SCST_FG(8); return; }
+#undef SCST_FG
+  }
+  hipLaunchKernelGGL((scst_stream_kernel<T>), dim3((unsigned)rows), dim3(256), 0, st, logits, target, reward, row_seq, rows_per_seq, gs,
+                     lse, row_loss, dlogits, nseq, V, ld, ignore_index, cs, ce);
+}
+
+extern "C" int ofa_scst_loss_fwd_grad(const void* logits, const int64_t* target, const float* reward, const int32_t* row_seq,
+                                      int64_t rows_per_seq, const float* grad_scale, float* lse, float* row_loss, void* dlogits,
+                                      int64_t rows, int64_t nseq, int64_t V, int64_t ld, int64_t ignore_index, int64_t cstart,
+                                      int64_t cend, int dtype, void* stream) {
+  OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "scst_loss_fwd_grad: bad dtype %d", dtype);
+  OFA_REQUIRE(rows >= 0 && rows < ((int64_t)1 << 31) && nseq > 0 && nseq < ((int64_t)1 << 31) && V > 1 && ld >= V && logits && target &&
+                  reward && lse && row_loss && dlogits,
+              OFA_ERR_INVALID, "scst_loss_fwd_grad: bad argument");
+  OFA_REQUIRE(row_seq || (rows_per_seq >= 1 && rows_per_seq < ((int64_t)1 << 31)), OFA_ERR_INVALID,
+              "scst_loss_fwd_grad: rows_per_seq=%lld without a row_seq map", (long long)rows_per_seq);
+  OFA_REQUIRE(ld % dt_vecn(dtype) == 0, OFA_ERR_INVALID, "scst_loss_fwd_grad: ld=%lld must be a multiple of the 16-byte vector width", (long long)ld);
+  OFA_REQUIRE(cstart < 0 || (cstart >= 4 && cend > cstart && cend <= V), OFA_ERR_INVALID,
+              "scst_loss_fwd_grad: bad constraint range [%lld, %lld)", (long long)cstart, (long long)cend);
+  if (rows == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    scst_launch<T>((const T*)logits, target, reward, row_seq, row_seq ? 1 : rows_per_seq, grad_scale, lse, row_loss, (T*)dlogits, rows, nseq,
+                   V, ld, ignore_index, cstart < 0 ? 0 : cstart, cstart < 0 ? V : cend, st);      // (no range: [0, V))
+  });
+  return check_launch("scst_loss_fwd_grad");
 }
 
 extern "C" int ofa_probs_fwd(const void* logits, float* out, int64_t rows, int64_t V, int64_t ld, int log_probs, int dtype,

@@ -132,6 +132,8 @@ class Trainer:
         self.global_dict = None
         self.step_engine: Optional[TrainStep] = None
         self.history = []
+        self._scst = {}                             # task name -> scst.ScstRewardCriterion (tasks with cfg.scst)
+        self._score_sum, self._score_n = 0.0, 0     # CIDEr-D of this rank's hypotheses since the last history record
 
     @property
     def ema(self):
@@ -174,8 +176,9 @@ class Trainer:
             for task in tasks:
                 if task.cfg.text.pad_to_multiple == 1:
                     task.cfg.text.pad_to_multiple = cfg.common.graph_pad_to_multiple
-        crit = tasks[0].cfg.criterion
-        for task in tasks[1:]:
+        plain = [t for t in tasks if not t.cfg.scst]          # (an SCST task's micro-batches carry their own criterion: the reward)
+        crit = (plain or tasks)[0].cfg.criterion
+        for task in plain[1:]:
             # the reference builds one criterion per task (task/base.py:213-216); the step engine holds one: refuse a mix it would
             # silently flatten
             c = task.cfg.criterion
@@ -204,12 +207,27 @@ class Trainer:
         return {"init_scale": float(c.fp16_init_scale), "scale_factor": 2.0, "scale_window": window,
                 "tolerance": c.fp16_scale_tolerance, "threshold": c.threshold_loss_scale, "min_loss_scale": c.min_loss_scale}
 
+    def _scst_criterion(self, task):
+        crit = self._scst.get(task.name)
+        if crit is None:
+            from .scst import ScstRewardCriterion
+            crit = self._scst[task.name] = ScstRewardCriterion(task, task.cfg.criterion)
+        return crit
+
     def _micro_batches(self, tasks):
         """samples[task][i] of engine/trainer.py:747-766, flattened: update_freq micro-batches of every task, on the device."""
         out = []
         for task in tasks:
             for _ in range(task.cfg.dataset.update_freq):
                 s = to_device(task.get_sample("train"), self._device, self._float_dtype)
+                if task.cfg.scst:
+                    # self-critical sequence training: the criterion generates K hypotheses per sentence with the current weights,
+                    # scores them, and hands back the batch of hypotheses with their rewards (scst.ScstRewardCriterion)
+                    mb, log = self._scst_criterion(task)(self.step_engine.model, s)
+                    self._score_sum += log["score"]
+                    self._score_n += log["nsentences"]
+                    out.append(mb)
+                    continue
                 mb = {"slots": s["net_input"]["slots"], "target": s["target"], "task": task.name}
                 if s.get("constraint_masks") is not None:
                     mb["constraint_masks"] = s["constraint_masks"]
@@ -242,6 +260,9 @@ class Trainer:
                 n, loss = float(out["stats"][0]), float(out["stats"][1])
                 rec = {"update": attempts - skipped, "loss": loss / max(n, 1.0) / 0.6931471805599453, "sample_size": n,
                        "gnorm": float(out["gnorm"]), "lr": engine.lr}
+                if self._score_n:                                    # SCST: the mean CIDEr-D of this rank's hypotheses since the last record
+                    rec["score"] = self._score_sum / self._score_n
+                    self._score_sum, self._score_n = 0.0, 0
                 self.history.append(rec)
                 if self._rank == 0:
                     logger.info("update %(update)d | loss %(loss).4f (base 2 per token) | sample_size %(sample_size)d | "

@@ -961,6 +961,28 @@ def ls_cross_entropy_bwd(logits2d, target, lse, row_cnt, row_w, grad_scale, V, i
     return dlogits
 
 
+def scst_loss_fwd_grad(logits2d, target, reward, grad_scale, V, ignore_index, rows_per_seq=1, row_seq=None, cstart=-1, cend=-1,
+                       dlogits=None):
+    """Reward-weighted NLL rows and their gradient in one call (ofa_scst_loss_fwd_grad): returns lse, row_loss (fp32 [rows]) and
+    dlogits [rows, ld] = reward[sentence] * grad_scale[0] * (softmax - onehot) over the allowed vocabulary.  reward: fp32 [nseq];
+    the sentence of row r is row_seq[r] (int32 [rows]) or r // rows_per_seq; grad_scale: fp32 device scalar (None: 1)."""
+    rows, ld = logits2d.shape[0], logits2d.stride(0)
+    assert reward.dtype == torch.float32 and reward.is_contiguous() and target.dtype == torch.int64 and target.is_contiguous()
+    assert target.numel() == rows, (target.shape, rows)
+    if row_seq is not None:
+        assert row_seq.dtype == torch.int32 and row_seq.is_contiguous() and row_seq.numel() == rows, (row_seq.dtype, row_seq.shape)
+    else:
+        assert rows <= reward.numel() * int(rows_per_seq), (rows, reward.numel(), rows_per_seq)
+    lse = torch.empty(rows, dtype=torch.float32, device=logits2d.device)
+    row_loss = torch.empty(rows, dtype=torch.float32, device=logits2d.device)
+    if dlogits is None:
+        dlogits = torch.empty(rows, ld, dtype=logits2d.dtype, device=logits2d.device)
+    lib().call("ofa_scst_loss_fwd_grad", ptr(logits2d), ptr(target), ptr(reward), ptr(row_seq), int(rows_per_seq), ptr(grad_scale),
+               ptr(lse), ptr(row_loss), ptr(dlogits), rows, reward.numel(), V, ld, ignore_index, int(cstart), int(cend),
+               dtype_code(logits2d), stream())
+    return lse, row_loss, dlogits
+
+
 def probs_fwd(logits2d, V, ld, log_probs):
     rows = logits2d.shape[0]
     y = torch.empty(rows, V, dtype=torch.float32, device=logits2d.device)

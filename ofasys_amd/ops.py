@@ -1870,6 +1870,63 @@ def label_smoothed_cross_entropy(logits, target, ignore_index, eps, constraint_r
                                              drop_worst_ratio)
 
 
+class ScstLossFn(torch.autograd.Function):
+    """Self-critical sequence training loss (engine/criterion/scst_loss.py:24-36, 214-233): sum over rows of
+    reward[sentence] * NLL(log_softmax_fp32(logits over the allowed vocabulary), target), ignore_index rows contributing 0; returns
+    (loss_sum, ntokens).  The kernel writes the logits' gradient in the pass that computes the loss (kernels.scst_loss_fwd_grad)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, reward, ignore_index, constraint_range, row_seq, seed):
+        V = logits.shape[-1]
+        l2d = _ce_rows(logits)
+        t = target.reshape(-1).contiguous()
+        w = reward.reshape(-1).to(device=l2d.device, dtype=torch.float32).contiguous()
+        rows = l2d.shape[0]
+        if row_seq is not None:
+            row_seq = row_seq.reshape(-1).to(device=l2d.device, dtype=torch.int32).contiguous()
+            if row_seq.numel() != rows:
+                raise ValueError(f"scst_loss: row_seq has {row_seq.numel()} entries for {rows} rows")
+            rps = 1
+        else:
+            if w.numel() == 0 or rows % w.numel() != 0:
+                raise ValueError(f"scst_loss: {rows} rows do not divide into {w.numel()} sentences (pass row_seq)")
+            rps = rows // w.numel()
+        cs, ce = constraint_range if constraint_range is not None else (-1, -1)
+        seeded = (seed is not None and ctx.needs_input_grad[0] and seed.dtype == torch.float32 and seed.numel() == 1
+                  and seed.device == l2d.device)
+        lse, row_loss, d = K.scst_loss_fwd_grad(l2d, t, w, seed if seeded else None, V, ignore_index, rps, row_seq, cs, ce)
+        # the gradient at the seed's scale, handed out by the FIRST backward that receives that very tensor, unchanged; every other
+        # backward (another seed, a seed written to since, a repeated call) runs the same entry again at the scale it is given
+        ctx.seed, ctx.seed_version, ctx.pre = (seed, seed._version, d) if seeded else (None, None, None)
+        ctx.handed_out = False
+        ctx.save_for_backward(l2d, t, w, row_seq)
+        ctx.cfg = (ignore_index, rps, cs, ce, logits.shape)
+        ntok = t.ne(ignore_index).sum()
+        ctx.mark_non_differentiable(ntok)
+        return K.sum_f32(row_loss), ntok
+
+    @staticmethod
+    def backward(ctx, dloss, dntok):
+        l2d, t, w, row_seq = ctx.saved_tensors
+        ignore_index, rps, cs, ce, shape = ctx.cfg
+        V = l2d.shape[1]
+        seed = ctx.seed
+        if (seed is not None and not ctx.handed_out and dloss.data_ptr() == seed.data_ptr() and dloss.dtype == seed.dtype
+                and seed._version == ctx.seed_version):
+            ctx.handed_out = True
+            d = ctx.pre
+        else:
+            gs = dloss.reshape(1).float().contiguous()
+            _, _, d = K.scst_loss_fwd_grad(l2d, t, w, gs, V, ignore_index, rps, row_seq, cs, ce)
+        return d[:, :V].view(shape), None, None, None, None, None, None
+
+
+def scst_loss(logits, target, reward, ignore_index, constraint_range=None, row_seq=None, seed=None):
+    """-> (loss_sum, ntokens).  reward: one value per sentence; row r of the [rows, V] view of `logits` belongs to sentence row_seq[r],
+    or to r // (rows / sentences) without a map (logits [sentences, Tt, V]).  seed: as in `cross_entropy_sum`."""
+    return ScstLossFn.apply(logits, target, reward, ignore_index, constraint_range, row_seq, seed)
+
+
 def _rows_padded(logits):
     """[..., V] tensor -> ([rows, V] view with last dim contiguous, ld)."""
     V = logits.shape[-1]

@@ -48,6 +48,12 @@ class InstructionConfig:                              # task/base.py:123-137
 class CriterionConfig:                                # engine/criterion/label_smoothed_cross_entropy.py:27-59 / cross_entropy.py
     label_smoothing: float = 0.0
     drop_worst_ratio: float = 0.0
+    # "scst_reward_criterion" (engine/criterion/scst_loss.py:39-56; used by a task with cfg.scst): the fields below are its own
+    name: str = "label_smoothed_cross_entropy"
+    scst_cider_cached_tokens: Any = "corpus"          # a pickle path (ref_len, document_frequency), such a dict, or "corpus"
+    sentence_avg: bool = False
+    ignore_prefix_size: int = 0
+    constraint_range: Optional[str] = None
 
 
 @dataclass
@@ -74,6 +80,8 @@ class TaskConfig:                                     # task/base.py:157-189
     max_src_length: int = 128
     max_tgt_length: int = 30
     constraint_range: Optional[str] = None
+    scst: bool = False                                # self-critical sequence training (task/base.py:170-174)
+    scst_args: str = "{}"                             # generation arguments of the SCST generator, as JSON
     _name: Optional[str] = None
 
     def update(self, **kwargs):
@@ -131,6 +139,7 @@ class Task:
         self.general_preprocess: Optional[GeneralPreprocess] = None
         self._iters = {}
         self._generator = None
+        self._scst_generator = None
         self._sampling_gens: Dict[Any, Any] = {}
 
     # ------------------------------------------------------------------ identity / datasets (task/base.py:256-273)
@@ -296,6 +305,20 @@ class Task:
     @generator.setter
     def generator(self, generator):
         self._generator = generator
+
+    @property
+    def scst_generator(self):
+        """Built on first use from cfg.scst_args (task/base.py:249-253): every hypothesis of the beam is returned (SCST scores all K
+        of a sentence); with "sampling": true the K rows are K independent samples (`sampling_generator`)."""
+        if self._scst_generator is None:
+            args = json.loads(self.cfg.scst_args)
+            args.setdefault("return_n_best", args.get("beam", 5))
+            if args.get("sampling", False):
+                self._scst_generator = self.sampling_generator(**args)
+            else:
+                args.pop("sampling", None)
+                self._scst_generator = self.build_generator(**args)
+        return self._scst_generator
 
     def inference(self, model, sample, **kwargs):
         """Beam search on `sample` (a collated batch); for TEXT targets every hypothesis gets `.text` through the task's text

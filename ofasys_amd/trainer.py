@@ -371,7 +371,25 @@ class TrainStep:
             if plan is not None and cm is not None:
                 raise NotImplementedError("constraint masks are laid out by padded position: run such samples without a pack plan")
             counted = False
-            if self.label_smoothing > 0 or self.constraint_range is not None or self.drop_worst_ratio > 0 or cm is not None:
+            size = None
+            if s.get("reward") is not None:
+                # self-critical sequence training (scst.ScstRewardCriterion builds such a micro-batch): the generated tokens' NLL
+                # weighted by the sentence's reward, loss and logits gradient in one pass (engine/criterion/scst_loss.py:24-36)
+                if cm is not None:
+                    raise NotImplementedError("an SCST micro-batch (reward) cannot carry constraint_masks: its criterion takes a "
+                                              "constraint range only (engine/criterion/scst_loss.py:214-217)")
+                row_seq = None
+                if plan is not None:                 # packed decoder rows: the sentence of padded row i is i // Tt (filler rows: -1)
+                    row_seq = torch.div(plan.dec_index, s["target"].shape[1], rounding_mode="floor").to(torch.int32)
+                cr = s.get("constraint_range")
+                cr = tuple(int(v) for v in cr.split(",")) if cr is not None else self.constraint_range
+                if self.loss_scale_cfg is None and (self._seed is None or self._seed.device != logits.device):
+                    self._seed = torch.ones((), dtype=torch.float32, device=logits.device)
+                loss, n = ops.scst_loss(logits, target, s["reward"], self.pad, cr, row_seq,
+                                        seed=self._seed if self.loss_scale_cfg is None else None)
+                if s.get("sentence_avg"):            # sample_size = nsentences (scst_loss.py:93)
+                    size = s["reward"].numel()
+            elif self.label_smoothing > 0 or self.constraint_range is not None or self.drop_worst_ratio > 0 or cm is not None:
                 loss, _, n = ops.label_smoothed_cross_entropy(logits, target, self.pad, self.label_smoothing,
                                                               self.constraint_range, cm, self.drop_worst_ratio)
             else:
@@ -393,7 +411,7 @@ class TrainStep:
             else:                                    # FP16Optimizer.backward: loss * loss_scale (fp16_optimizer.py:92-102)
                 loss.backward(self._ls[0].to(loss.dtype))
             if not counted:
-                self._stats[0] += n
+                self._stats[0] += n if size is None else size
                 self._stats[1] += loss.detach().double()
                 self._stats[2] += n
         ops.flush_folds()
@@ -513,7 +531,8 @@ class TrainStep:
 
     def train_step(self, samples: List[dict], eager: bool = False):
         """samples: one dict per (task, micro-batch): {"slots": [...], "target": LongTensor[B,Tt], optional
-        "constraint_masks", "task"}."""
+        "constraint_masks", "task"}.  With "reward" (fp32, one value per row of `target`) the micro-batch takes the SCST criterion
+        (ops.scst_loss; optional "constraint_range": "start,end" and "sentence_avg": True)."""
         done = False
         structure = None
         if (self.use_graph and not eager) or self.world > 1:
