@@ -643,30 +643,62 @@ enum {
 };
 int ofa_gemm_plan(int M, int N, int K, int transA, int transB, int batch, int flags, int dtype, int64_t ws_bytes, int* plan);
 
-/* ---- beam search (csrc/beam_search.hip): the policy of SequenceGenerator.generate / BeamSearch.step
- * (generator/sequence_generator.py:283-492, finalize_hypos :530-627; utils/search.py:107-142) in two launches per decoding
- * step that take fixed device addresses and the step number only, so they are recorded inside the per-step hipGraph.
- * Rows are bsz sentences x K beams (K <= 16, K * V < 2^24).  ws: ofa_beam_ws_bytes(rows, V, K) bytes, written by
- * ofa_beam_topk and read by ofa_beam_select of the same step.
- * ofa_beam_topk: one read of logits [rows, ld] (V valid columns, fp32 / bf16 / fp16): the fp32 log-softmax normaliser of
- * x / temperature with constraint_range ([4, cstart) and [cend, V) -inf, cstart < 0: off; :724, 742-745) applied first, then
- * the reference's post-normaliser masks in order (EOS at step < min_len, NaN, PAD, unk_penalty, step >= max_len, n-gram bans over
- * tokens[row, 0..step] when ngram > 0; :296-343) and each row's best 2K candidates per 4096-column chunk.  done: optional int
- * [bsz] -- rows of finished sentences are skipped.
- * ofa_beam_select: one workgroup per sentence.  tokens int64 [rows, tok_ld] (tok_cap valid columns; column 0 = BOS) and scores
- * fp32 [rows, score_ld] are the histories, gathered in place; the next token goes to column step + 1 and the cumulative score
- * to column step; reorder int64 [rows] receives the source row of every row (the identity for a finished sentence); ignore int
- * [bsz, K] is cands_to_ignore; done int [bsz]; nfin int [1] counts finished sentences.  Finalised hypotheses: fin_tok int64
- * [bsz, K, fin_ld] (tokens 1..step, then EOS), fin_pos fp32 [bsz, K, fin_ld] (positional scores), fin_score fp32 [bsz, K]
- * (divided by (step + 1)^len_penalty when normalize), fin_len / fin_cnt int [bsz, K] / [bsz]. */
+/* ---- generation steps: beam search (csrc/beam_search.hip), beam search under a forced prefix, trie-constrained beam search
+ * (csrc/trie_beam.hip) and sampling (csrc/sample.hip).  Every step is a ROW PASS over the rows' distributions followed by a
+ * SENTENCE PASS over a sentence's candidates; both take fixed device addresses and the step number only, so they are recorded inside
+ * the per-step hipGraph.  Rows are bsz sentences x K beams (K <= 16, K * V < 2^24).  The two descriptors below are copied by value
+ * into the kernel arguments before an entry point returns: nothing on the device reads the caller's host memory.
+ *
+ * ofa_gen_policy: what a row pass applies to a row's logits.  The fp32 log-softmax normaliser is taken of x / temperature with
+ * constraint_range ([4, cstart) and [cend, V) -inf, cstart < 0: off; generator/sequence_generator.py:724, 742-745) applied first;
+ * then the reference's post-normaliser masks in order (:296-343): EOS at step < min_len, NaN, PAD, unk_penalty, step >= max_len (all
+ * but EOS), n-gram bans over tokens[row, 0..step] (int64 [rows, tok_ld], the token history) when ngram > 0.  done: optional int
+ * [bsz] -- rows of finished sentences are skipped. */
+typedef struct ofa_gen_policy {
+  float temperature;
+  int32_t cstart, cend;
+  int32_t step, min_len, max_len;
+  int32_t pad, unk, eos;
+  float unk_penalty;
+  int32_t ngram;
+  const int64_t* tokens;
+  int64_t tok_ld;
+  const int32_t* done;
+} ofa_gen_policy;
+
+/* ofa_gen_state: what a sentence pass works on.  tokens int64 [rows, tok_ld] (tok_cap valid columns; column 0 = BOS) and scores
+ * fp32 [rows, score_ld] are the histories, gathered in place; the next token goes to column step + 1 and the cumulative score to
+ * column step.  ignore int [bsz, K] is cands_to_ignore; done int [bsz]; nfin int [1] counts finished sentences; reorder int64 [rows]
+ * receives the source row of every row (the identity for a finished sentence).  Finalised hypotheses: fin_tok int64
+ * [bsz, K, fin_ld] (tokens 1..step, then EOS), fin_pos fp32 [bsz, K, fin_ld] (positional scores), fin_score fp32 [bsz, K] (divided
+ * by (step + 1)^len_penalty when normalize), fin_len / fin_cnt int [bsz, K] / [bsz]. */
+typedef struct ofa_gen_state {
+  int64_t* tokens;
+  int64_t tok_ld;
+  int32_t tok_cap;
+  float* scores;
+  int64_t score_ld;
+  int32_t *ignore, *done, *nfin;
+  int64_t* reorder;
+  int64_t* fin_tok;
+  float* fin_pos;
+  int64_t fin_ld;
+  float* fin_score;
+  int32_t *fin_len, *fin_cnt;
+} ofa_gen_state;
+
+/* Beam search: the policy of SequenceGenerator.generate / BeamSearch.step (generator/sequence_generator.py:283-492,
+ * finalize_hypos :530-627; utils/search.py:107-142) in two launches per decoding step.  ws: ofa_beam_ws_bytes(rows, V, K) bytes,
+ * written by ofa_beam_topk and read by ofa_beam_select of the same step.
+ * ofa_beam_topk: one read of logits [rows, ld] (V valid columns, fp32 / bf16 / fp16): the normaliser parts and each row's best 2K
+ * candidates per 4096-column chunk under `pol`.
+ * ofa_beam_select: one workgroup per sentence: the sentence's top min(2K, K * V - 1) candidates (beam 0 only at step 0), then the
+ * bookkeeping of the step on `st`. */
 int64_t ofa_beam_ws_bytes(int rows, int V, int K);
-int ofa_beam_topk(const void* logits, int64_t ld, int rows, int V, int K, float temperature, int cstart, int cend, int step,
-                  int min_len, int max_len, int pad, int unk, int eos, float unk_penalty, int ngram, const int64_t* tokens,
-                  int64_t tok_ld, const int* done, void* ws, int dtype, void* stream);
-int ofa_beam_select(const void* ws, int bsz, int K, int V, int step, int max_len, int eos, int unk, float unk_penalty,
-                    int normalize, float len_penalty, int64_t* tokens, int64_t tok_ld, int tok_cap, float* scores,
-                    int64_t score_ld, int* ignore, int* done, int* nfin, int64_t* reorder, int64_t* fin_tok, float* fin_pos,
-                    int64_t fin_ld, float* fin_score, int* fin_len, int* fin_cnt, void* stream);
+int ofa_beam_topk(const void* logits, int64_t ld, int rows, int V, int K, const ofa_gen_policy* pol, void* ws, int dtype,
+                  void* stream);
+int ofa_beam_select(const void* ws, const ofa_gen_state* st, int bsz, int K, int V, int step, int max_len, int eos, int unk,
+                    float unk_penalty, int normalize, float len_penalty, void* stream);
 
 /* ---- beam search under a forced target prefix (sample["prefix_tokens"], generator/sequence_generator.py:297-343, 497-523).
  * prefix int64 [bsz, prefix_ld]: the prefix tokens, <pad> where a sentence's prefix has ended; plen int [bsz]: its non-pad
@@ -679,20 +711,16 @@ int ofa_beam_select(const void* ws, int bsz, int K, int V, int step, int max_len
  * ofa_beam_prefix_fill: one workgroup per forced row.  f = min over the rows of the unfinished sentences of
  * (glogit - normaliser) - 1, NaN if any is NaN; the row's candidates under the tie rule (value descending, token ascending) --
  * its prefix token with its own lprob, then the lowest unmasked tokens at f, unk at f - unk_penalty; NaN / -inf f: -inf -- are
- * written to ws as lprobs.  Needs 2K + step + 4 <= min(V, 1024).
+ * written to ws as lprobs.  Needs 2K + step + 4 <= min(V, 1024).  Of `pol` it reads step, pad, unk, unk_penalty, ngram, tokens,
+ * tok_ld and done.
  * ofa_beam_prefix_select: ofa_beam_select, taking the candidate values of forced rows as lprobs already. */
-int ofa_beam_prefix_topk(const void* logits, int64_t ld, int rows, int V, int K, float temperature, int cstart, int cend, int step,
-                         int min_len, int max_len, int pad, int unk, int eos, float unk_penalty, int ngram, const int64_t* tokens,
-                         int64_t tok_ld, const int* done, const int64_t* prefix, int64_t prefix_ld, const int* plen, float* glogit,
-                         void* ws, int dtype, void* stream);
-int ofa_beam_prefix_fill(void* ws, int rows, int V, int K, int step, int pad, int unk, float unk_penalty, int ngram,
-                         const int64_t* tokens, int64_t tok_ld, const int* done, const int64_t* prefix, int64_t prefix_ld,
+int ofa_beam_prefix_topk(const void* logits, int64_t ld, int rows, int V, int K, const ofa_gen_policy* pol, const int64_t* prefix,
+                         int64_t prefix_ld, const int* plen, float* glogit, void* ws, int dtype, void* stream);
+int ofa_beam_prefix_fill(void* ws, int rows, int V, int K, const ofa_gen_policy* pol, const int64_t* prefix, int64_t prefix_ld,
                          const int* plen, const float* glogit, void* stream);
-int ofa_beam_prefix_select(const void* ws, int bsz, int K, int V, int step, int max_len, int eos, int unk, float unk_penalty,
-                           int normalize, float len_penalty, int64_t* tokens, int64_t tok_ld, int tok_cap, float* scores,
-                           int64_t score_ld, int* ignore, int* done, int* nfin, int64_t* reorder, int64_t* fin_tok, float* fin_pos,
-                           int64_t fin_ld, float* fin_score, int* fin_len, int* fin_cnt, const int64_t* prefix, int64_t prefix_ld,
-                           int pad, void* stream);
+int ofa_beam_prefix_select(const void* ws, const ofa_gen_state* st, int bsz, int K, int V, int step, int max_len, int eos, int unk,
+                           float unk_penalty, int normalize, float len_penalty, const int64_t* prefix, int64_t prefix_ld, int pad,
+                           void* stream);
 
 /* ---- closed-set scoring (csrc/closed_set_score.hip): TraverseTask.inference (task/traverse_task.py:63-110) without the
  * full-vocabulary projection.  The answer trie arrives as flat int arrays (ofasys_amd/traverse.py TraversePlan): N nodes, E edges
@@ -724,30 +752,28 @@ int ofa_closed_set_score(const void* h, int64_t ld_h, int dtype, const void* W, 
  * row, -1 = dead (its whole distribution is -inf).
  * ofa_trie_beam_topk replaces ofa_beam_topk: h [rows, ld_h] are the decoder's last-position features, W [V, ld_w] / bias [V] or NULL
  * the output projection (one dtype, rows 16-byte aligned); per row one dot product per child edge of node[row] (fp32 accumulation,
- * + bias, / temperature), the fp32 normaliser parts and the best 2K FINITE candidates after the post-normaliser masks of
- * ofa_beam_topk, written in ofa_beam_topk's layout of ws (ofa_beam_ws_bytes(rows, V, K) bytes) for ofa_beam_select of the same
- * step.  Grid (ofa_trie_beam_splits(max_degree, V), rows); a row with fewer than 2K finite candidates is completed with -inf
- * candidates at the lowest token ids not listed, as torch.topk breaks the reference's ties.  At step 0 only beam 0 of a sentence
- * is computed (the sentence pass reads no other).
+ * + bias, / temperature), the fp32 normaliser parts and the best 2K FINITE candidates after the post-normaliser masks of `pol`,
+ * written in ofa_beam_topk's layout of ws (ofa_beam_ws_bytes(rows, V, K) bytes) for ofa_beam_select of the same step.  The trie is
+ * the only constraint: a `pol` with a constraint range (cstart >= 0) is refused.  Grid (ofa_trie_beam_splits(max_degree, V), rows);
+ * a row with fewer than 2K finite candidates is completed with -inf candidates at the lowest token ids not listed, as torch.topk
+ * breaks the reference's ties.  At step 0 only beam 0 of a sentence is computed (the sentence pass reads no other).
  * ofa_trie_beam_advance runs after ofa_beam_select: node[row] <- the child of node[reorder[row]] through tokens[row, step + 1]
- * (dead: dead parent, score -inf, EOS edge); a sentence whose K slots are all ignored or at -inf gets done = 1 and bumps nfin.
+ * (dead: dead parent, score -inf, EOS edge); a sentence whose K slots are all ignored or at -inf gets done = 1 and bumps nfin.  Of
+ * `st` it reads the histories, ignore, reorder, done and nfin; the fin_* fields may be NULL.
  * ofa_trie_beam_splits: the grid's x extent for a plan (0: invalid arguments). */
 int ofa_trie_beam_splits(int max_degree, int V);
 int ofa_trie_beam_topk(const void* h, int64_t ld_h, int dtype, const void* W, int64_t ld_w, const void* bias, int D, int V,
                        int rows, int K, const int* node, const int* node_edge_off, const int* edge_token, int N, int E,
-                       int max_degree, float temperature, int step, int min_len, int max_len, int pad, int unk, int eos,
-                       float unk_penalty, int ngram, const int64_t* tokens, int64_t tok_ld, const int* done, void* ws,
-                       void* stream);
+                       int max_degree, const ofa_gen_policy* pol, void* ws, void* stream);
 int ofa_trie_beam_advance(int* node, const int* node_edge_off, const int* edge_token, const int* edge_child, int N, int E,
-                          int bsz, int K, int step, const int64_t* tokens, int64_t tok_ld, int tok_cap, const float* scores,
-                          int64_t score_ld, const int* ignore, const int64_t* reorder, int* done, int* nfin, void* stream);
+                          const ofa_gen_state* st, int bsz, int K, int step, void* stream);
 
 /* ---- sampling (csrc/sample.hip): Sampling.step (utils/search.py:596-715) under SequenceGenerator's bookkeeping
  * (generator/sequence_generator.py:283-492), two launches per decoding step, recorded in the step graph like the beam launches.
  * Rows are bsz sentences x K slots (K <= 16, V <= 65536); a sentence's K slots are K independent samples.  No random numbers
  * are made: uniforms fp32 [rows] holds this step's one number in [0, 1) per row.  ws: ofa_sample_ws_bytes(rows, V, K) = 8 * rows
  * bytes (the drawn lprob fp32 [rows], then the drawn token int [rows]), written by ofa_sample_draw and read by ofa_sample_select.
- * ofa_sample_draw: one workgroup per row.  lprobs as ofa_beam_topk computes them (same arguments: the fp32 log-softmax of
+ * ofa_sample_draw: one workgroup per row.  lprobs as ofa_beam_topk computes them under the same `pol` (the fp32 log-softmax of
  * x / temperature under constraint_range, then the post-normaliser masks); weights w = expf(lprob), not renormalised.  Kept set:
  * topp > 0: the tokens whose weight ranked strictly ahead (lprob descending, token ascending) is < topp (everything when the
  * row's total is below topp; topp <= 1); else topk > 0: the topk first of that ranking; else every token.  The draw is the kept
@@ -759,17 +785,12 @@ int ofa_trie_beam_advance(int* node, const int* node_edge_off, const int* edge_t
  * ofa_sample_select: one workgroup per sentence over the K draws: slot j continues itself (slot 0 at step 0) with
  * score = scores[row, step - 1] + lprob; an EOS draw with a finite score in a slot not ignored is finalised; ignored slots stay
  * ignored; the slots that go on are compacted to the front in column order (reorder is not the identity once a slot has ended);
- * a sentence is finished with K hypotheses or at step == max_len.  Histories, fin_* buffers, ignore, done, nfin and reorder as in
- * ofa_beam_select. */
+ * a sentence is finished with K hypotheses or at step == max_len.  The bookkeeping on `st` is ofa_beam_select's. */
 int64_t ofa_sample_ws_bytes(int rows, int V, int K);
-int ofa_sample_draw(const void* logits, int64_t ld, int rows, int V, int K, float temperature, int cstart, int cend, int step,
-                    int min_len, int max_len, int pad, int unk, int eos, float unk_penalty, int ngram, const int64_t* tokens,
-                    int64_t tok_ld, const int* done, int topk, float topp, const float* uniforms, void* ws, int dtype,
-                    void* stream);
-int ofa_sample_select(const void* ws, int bsz, int K, int step, int max_len, int eos, int normalize, float len_penalty,
-                      int64_t* tokens, int64_t tok_ld, int tok_cap, float* scores, int64_t score_ld, int* ignore, int* done,
-                      int* nfin, int64_t* reorder, int64_t* fin_tok, float* fin_pos, int64_t fin_ld, float* fin_score,
-                      int* fin_len, int* fin_cnt, void* stream);
+int ofa_sample_draw(const void* logits, int64_t ld, int rows, int V, int K, const ofa_gen_policy* pol, int topk, float topp,
+                    const float* uniforms, void* ws, int dtype, void* stream);
+int ofa_sample_select(const void* ws, const ofa_gen_state* st, int bsz, int K, int step, int max_len, int eos, int normalize,
+                      float len_penalty, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,9 +1,10 @@
-// What the two beam-search row passes (beam_search.hip: ofa_beam_topk over [rows, V] logits; trie_beam.hip: ofa_trie_beam_topk over
-// the child edges of a trie node) and the sentence pass (ofa_beam_select) have in common, defined once: the limits, the workspace
-// layout the row passes write and the sentence pass reads, the reference's post-normaliser masks in its order, the tie rules
-// (value descending, token ascending, NaN = empty) and the candidate-list machinery around the per-wave selection loops, which
-// stay with their kernels (one selects over 16 register-held values per lane, the other over an LDS array strided by thread).
-// Device helpers and host helpers only: no kernels, no entry points.
+// What the beam-search row passes (beam_search.hip: ofa_beam_topk over [rows, V] logits; trie_beam.hip: ofa_trie_beam_topk over
+// the child edges of a trie node; sample.hip: ofa_sample_draw) and the sentence passes (ofa_beam_select, ofa_sample_select) have
+// in common, defined once: the limits, the workspace layout the row passes write and the sentence pass reads, the checks of the
+// two descriptors of the C ABI (ofa_gen_policy, ofa_gen_state), the reference's post-normaliser masks in its order, the tie rules
+// (value descending, token ascending, NaN = empty), the candidate-list machinery around the per-wave selection loops, which stay
+// with their kernels (one selects over 16 register-held values per lane, the other over an LDS array strided by thread), and the
+// bookkeeping of a step over a sentence's candidate list.  Device helpers and host helpers only: no kernels, no entry points.
 #pragma once
 #include "common.h"
 
@@ -30,24 +31,31 @@ static inline BeamWs beam_ws_carve(const void* ws, int64_t rows, int64_t S, int6
   return BeamWs{p, p + beam_ws_cval_off(rows, S), (int*)(p + beam_ws_ctok_off(rows, S, K))};
 }
 
-// ---------------------------------------------------------------- the policy arguments both row passes take
-struct BeamPolicy {
-  float temperature;
-  int step, min_len, max_len, pad, unk, eos; float unk_pen;
-  int ngram; const int64_t* tokens; int64_t tok_ld;
-  const int* done;
-};
-
-// The arguments both row passes share, checked before any launch; `who` is the entry point's name.
-static inline int beam_check_row_pass(const char* who, int rows, int V, int K, float temperature, int step, int ngram,
-                                      const int64_t* tokens, int64_t tok_ld) {
+// ---------------------------------------------------------------- the descriptors' checks, before any launch; `who`: the entry point
+// The policy of a row pass (ofa_gen_policy: it crosses the C ABI and, by value, the kernel arguments as it is).
+static inline int beam_check_row_pass(const char* who, int rows, int V, int K, const ofa_gen_policy& p) {
   OFA_REQUIRE(K >= 1 && K <= BEAM_MAX_K, OFA_ERR_UNSUPPORTED, "%s: beam size %d outside [1, %d]", who, K, BEAM_MAX_K);
   OFA_REQUIRE(rows % K == 0, OFA_ERR_INVALID, "%s: rows %d not a multiple of the beam size %d", who, rows, K);
   OFA_REQUIRE((int64_t)K * V < (1 << 24), OFA_ERR_UNSUPPORTED, "%s: beam * vocabulary must stay below 2^24", who);
-  OFA_REQUIRE(temperature > 0.f, OFA_ERR_INVALID, "%s: temperature must be > 0", who);
-  OFA_REQUIRE(ngram <= 0 || (tokens && tok_ld > step), OFA_ERR_INVALID, "%s: n-gram bans need the token history", who);
+  OFA_REQUIRE(p.temperature > 0.f, OFA_ERR_INVALID, "%s: temperature must be > 0", who);
+  OFA_REQUIRE(p.ngram <= 0 || (p.tokens && p.tok_ld > p.step), OFA_ERR_INVALID, "%s: n-gram bans need the token history", who);
   return OFA_OK;
 }
+
+// The sentence state at `step` (>= 0).  fin: the caller finalises hypotheses, so the fin_* buffers are needed as well.
+static inline int beam_check_state(const char* who, const ofa_gen_state* st, int K, int step, bool fin) {
+  OFA_REQUIRE(st && st->tokens && st->scores && st->ignore && st->done && st->nfin && st->reorder &&
+                  (!fin || (st->fin_tok && st->fin_pos && st->fin_score && st->fin_len && st->fin_cnt)),
+              OFA_ERR_INVALID, "%s: null pointer", who);
+  OFA_REQUIRE(K >= 1 && K <= BEAM_MAX_K, OFA_ERR_UNSUPPORTED, "%s: beam size %d outside [1, %d]", who, K, BEAM_MAX_K);
+  OFA_REQUIRE(st->tok_cap >= step + 1 && st->tok_ld >= st->tok_cap && st->score_ld > step && (!fin || st->fin_ld > step), OFA_ERR_INVALID,
+              "%s: history buffers too short for step %d (tok_cap=%d tok_ld=%lld score_ld=%lld fin_ld=%lld)", who, step, st->tok_cap,
+              (long long)st->tok_ld, (long long)st->score_ld, (long long)st->fin_ld);
+  return OFA_OK;
+}
+
+// dynamic LDS of the sentence pass's in-place history gather: K rows of step + 1 tokens and step scores
+static inline size_t beam_history_lds(int K, int step) { return (size_t)K * (step + 1) * 8 + (size_t)K * step * 4; }
 
 // ---------------------------------------------------------------- device side
 // wave arg-max of (key desc, idx asc) over the lanes; NaN keys are empty.  Returns false when every lane is empty.
@@ -73,7 +81,7 @@ static_assert(sizeof(BeamListScratch) % 16 == 0, "embedded in front of 16-byte a
 // plen >= 0: the sample carries prefix_tokens and the row's prefix has plen tokens -- the reference then skips the rows with
 // plen >= step + n - 1 (sequence_generator.py:327-334).
 template <typename Sink>
-__device__ __forceinline__ void beam_ngram_scan(const BeamPolicy& p, int row, int tid, Sink ban, int plen = -1) {
+__device__ __forceinline__ void beam_ngram_scan(const ofa_gen_policy& p, int row, int tid, Sink ban, int plen = -1) {
   const int n = p.ngram;
   if (n > 0 && p.step + 2 - n >= 0 && plen < p.step + n - 1) {
     const int64_t* h = p.tokens + (int64_t)row * p.tok_ld;
@@ -130,13 +138,13 @@ __device__ __forceinline__ void beam_normaliser_part(BeamListScratch& sh, int ti
 // EOS at step < min_len, NaN -> -inf, PAD, step >= max_len: all but EOS, n-gram bans, unk -= unk_penalty.  Returns the
 // ordering key; the penalty orders only -- unk_val keeps the value of unk, and the sentence pass subtracts the penalty after
 // the normaliser.
-__device__ __forceinline__ float beam_mask_key(const BeamPolicy& p, float v, int c, bool banned, float& unk_val) {
+__device__ __forceinline__ float beam_mask_key(const ofa_gen_policy& p, float v, int c, bool banned, float& unk_val) {
   if (c == p.eos && p.step < p.min_len) v = -INFINITY;
   if (v != v) v = -INFINITY;
   if (c == p.pad) v = -INFINITY;
   if (p.step >= p.max_len && c != p.eos) v = -INFINITY;
   if (banned) v = -INFINITY;
-  if (c == p.unk) { unk_val = v; v = v - p.unk_pen; }
+  if (c == p.unk) { unk_val = v; v = v - p.unk_penalty; }
   return v;
 }
 
@@ -169,6 +177,120 @@ __device__ __forceinline__ int beam_merge_lists(const BeamListScratch& sh, int l
     }
   }
   return it;
+}
+
+// ---------------------------------------------------------------- the sentence pass after its candidate list
+// LDS of one sentence: the caller stages the list -- n entries of (cumulative score, source beam, token), best first -- in sel_*
+struct BeamSentScratch {
+  float sel_sc[2 * BEAM_MAX_K];
+  int sel_beam[2 * BEAM_MAX_K], sel_tok[2 * BEAM_MAX_K];
+  int act_beam[BEAM_MAX_K], act_tok[BEAM_MAX_K], new_ign[BEAM_MAX_K];
+  float act_sc[BEAM_MAX_K];
+  int fin_beam[BEAM_MAX_K], fin_slot[BEAM_MAX_K];
+  float fin_sc[BEAM_MAX_K];
+  int nfin_jobs, finished;
+};
+
+// The bookkeeping of one step (sequence_generator.py:345-492, finalize_hypos :530-627) for sentence `sent` over the n <= 2K
+// candidates staged in sh (n = K for sampling: slot j's one draw): the EOS candidates among the first K are finalised, the K
+// active candidates picked (the active_mask topk), cands_to_ignore carried, the token / score histories gathered in place through
+// `lds` (beam_history_lds bytes, free to overwrite), reorder written.  A sentence with K hypotheses or at step == max_len sets its
+// done flag, bumps the all-finished counter and keeps the identity reorder.  Call it after the barrier that publishes the list.
+__device__ __forceinline__ void beam_sentence_step(const ofa_gen_state& a, BeamSentScratch& sh, int sent, int K, int step, int max_len,
+                                                   int eos, int normalize, float len_pen, int n, void* lds) {
+  const int tid = threadIdx.x, r0 = sent * K;
+  if (tid == 0) {                                            // one thread, <= 2K candidates
+    bool eosm[2 * BEAM_MAX_K];
+    for (int j = 0; j < n; ++j) {
+      eosm[j] = sh.sel_tok[j] == eos && sh.sel_sc[j] != -INFINITY;
+      if (j < K && a.ignore[r0 + j]) eosm[j] = false;
+    }
+    int cnt = a.fin_cnt[sent], jobs = 0;
+    for (int j = 0; j < n && j < K; ++j) {
+      if (!eosm[j]) continue;
+      if (cnt < K) {
+        sh.fin_beam[jobs] = sh.sel_beam[j];
+        sh.fin_slot[jobs] = cnt;
+        sh.fin_sc[jobs] = sh.sel_sc[j];
+        ++jobs;
+        ++cnt;
+      }
+    }
+    a.fin_cnt[sent] = cnt;
+    sh.nfin_jobs = jobs;
+    const int fin = (cnt == K || step >= max_len) ? 1 : 0;
+    sh.finished = fin;
+    if (fin) {
+      a.done[sent] = 1;
+      atomicAdd(a.nfin, 1);
+    } else {
+      // active_mask = eos_mask * cand_size + offset; its K smallest: the first K unmasked candidates, then the masked ones
+      int nb = 0;
+      for (int pass = 0; pass < 2 && nb < K; ++pass)
+        for (int j = 0; j < n && nb < K; ++j) {
+          const bool masked = eosm[j] || (j < K && a.ignore[r0 + j]);
+          if (masked != (pass == 1)) continue;
+          sh.act_beam[nb] = sh.sel_beam[j];
+          sh.act_tok[nb] = sh.sel_tok[j];
+          sh.act_sc[nb] = sh.sel_sc[j];
+          sh.new_ign[nb] = masked ? 1 : 0;
+          ++nb;
+        }
+    }
+  }
+  __syncthreads();
+  // ---- finalised hypotheses: tokens 1..step then EOS, positional scores as differences of the cumulative scores
+  const int jobs = sh.nfin_jobs;
+  const int len = step + 1;
+  for (int e = tid; e < jobs * len; e += BEAM_THREADS) {
+    const int q = e / len, i = e % len;
+    const int64_t row = r0 + sh.fin_beam[q];
+    const int slot = sh.fin_slot[q];
+    const int64_t o = ((int64_t)sent * K + slot) * a.fin_ld + i;
+    a.fin_tok[o] = i < step ? a.tokens[row * a.tok_ld + i + 1] : (int64_t)eos;
+    const float cur = i < step ? a.scores[row * a.score_ld + i] : sh.fin_sc[q];
+    const float prev = i > 0 ? a.scores[row * a.score_ld + i - 1] : 0.f;
+    a.fin_pos[o] = i > 0 ? cur - prev : cur;
+  }
+  if (tid < jobs) {
+    const int slot = sh.fin_slot[tid];
+    float sc = sh.fin_sc[tid];
+    if (normalize) sc = sc / (float)pow((double)len, (double)len_pen);
+    a.fin_score[sent * K + slot] = sc;
+    a.fin_len[sent * K + slot] = len;
+  }
+  if (sh.finished) {
+    if (tid < K) a.reorder[r0 + tid] = r0 + tid;
+    return;
+  }
+  __syncthreads();                                           // finalisation read the old histories
+  // ---- gather the K rows' histories in place: LDS copy of the sentence's rows, then the selected rows back
+  int64_t* htok = (int64_t*)lds;                             // [K][step + 1]
+  float* hsc = (float*)(htok + K * len);                     // [K][step]
+  for (int e = tid; e < K * len; e += BEAM_THREADS) {
+    const int b = e / len, i = e % len;
+    htok[e] = a.tokens[(int64_t)(r0 + b) * a.tok_ld + i];
+  }
+  for (int e = tid; e < K * step; e += BEAM_THREADS) {
+    const int b = e / step, i = e % step;
+    hsc[e] = a.scores[(int64_t)(r0 + b) * a.score_ld + i];
+  }
+  __syncthreads();
+  for (int e = tid; e < K * len; e += BEAM_THREADS) {
+    const int b = e / len, i = e % len;
+    a.tokens[(int64_t)(r0 + b) * a.tok_ld + i] = htok[sh.act_beam[b] * len + i];
+  }
+  for (int e = tid; e < K * step; e += BEAM_THREADS) {
+    const int b = e / step, i = e % step;
+    a.scores[(int64_t)(r0 + b) * a.score_ld + i] = hsc[sh.act_beam[b] * step + i];
+  }
+  if (tid < K) {
+    const int64_t row = r0 + tid;
+    if (step + 1 < a.tok_cap) a.tokens[row * a.tok_ld + step + 1] = sh.act_tok[tid];
+    a.scores[row * a.score_ld + step] = sh.act_sc[tid];
+    a.reorder[row] = r0 + sh.act_beam[tid];
+    a.ignore[row] = sh.new_ign[tid];
+  }
 }
 
 }  // namespace ofa

@@ -18,7 +18,8 @@
 //    reference's CPU path), finalises the EOS candidates among the first K (finalize_hypos), picks the K active candidates
 //    (the active_mask topk), carries cands_to_ignore, and gathers the token / score histories in place.  A finished sentence
 //    (K hypotheses or step == max_len) sets its done flag, bumps the all-finished counter and is a no-op afterwards; its rows
-//    keep the identity reorder.
+//    keep the identity reorder.  Everything after the merge is beam_common.h's beam_sentence_step, which ofa_sample_select
+//    (sample.hip) runs over its K-wide list as well.
 // 3. Steps under a forced target prefix (sample["prefix_tokens"], sequence_generator.py:297-343, 497-523), three launches:
 //    ofa_beam_prefix_topk -- the row pass above without the min_len mask; it also stores every row's scaled logit at its prefix
 //    token, and a forced row (prefix token != pad) stops after its normaliser part: no selection loop.  ofa_beam_prefix_fill --
@@ -32,8 +33,7 @@ namespace ofa {
 struct BeamTopkArgs {
   const void* logits; int64_t ld;
   int rows, V, K, S;
-  int cstart, cend;
-  BeamPolicy p;
+  ofa_gen_policy p;
   BeamWs ws;
   // ofa_beam_prefix_topk only (PREFIX): the forced tokens of this step (null: a free step), the prefix lengths, g's logit
   const int64_t* prefix; int64_t prefix_ld;
@@ -47,7 +47,7 @@ struct BeamTopkArgs {
 template <typename T, bool PREFIX>
 __device__ __forceinline__ void beam_row_pass(const BeamTopkArgs& a) {
   const int split = blockIdx.x, row = blockIdx.y;
-  const BeamPolicy& p = a.p;
+  const ofa_gen_policy& p = a.p;
   if (p.done && p.done[row / a.K]) return;
   int64_t ftok = -1;                                         // the row's prefix token at this step (PREFIX, prefix step)
   bool forced = false;
@@ -89,7 +89,7 @@ __device__ __forceinline__ void beam_row_pass(const BeamTopkArgs& a) {
     const int c = base + wave * (64 * BEAM_PER_LANE) + j * 64 + lane;
     float v = x[j];
     if (p.temperature != 1.f) v = v / p.temperature;
-    if (a.cstart >= 0 && ((c >= 4 && c < a.cstart) || c >= a.cend)) v = -INFINITY;
+    if (p.cstart >= 0 && ((c >= 4 && c < p.cstart) || c >= p.cend)) v = -INFINITY;
     x[j] = v;
     if (c < a.V) {
       if (v != v) has_nan = 1;
@@ -169,12 +169,12 @@ struct BeamFillArgs {
   const int64_t* prefix; int64_t prefix_ld;
   const int* plen;
   const float* glogit;
-  BeamPolicy p;
+  ofa_gen_policy p;
 };
 
 __global__ __launch_bounds__(BEAM_THREADS) void beam_prefix_fill_kernel(BeamFillArgs a) {
   const int row = blockIdx.x, sent = row / a.K;
-  const BeamPolicy& p = a.p;
+  const ofa_gen_policy& p = a.p;
   if (p.done && p.done[sent]) return;
   const int64_t ftok = a.prefix[(int64_t)sent * a.prefix_ld + p.step];
   if (ftok == p.pad) return;                                 // a free row: ofa_beam_prefix_topk listed its candidates
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_prefix_fill_kernel(BeamFill
   }, a.plen[sent]);
   __syncthreads();
   // ---- the 2K lowest tokens that stay at f: not the prefix token and, unless f is -inf anyway, not masked and not unk
-  const bool unk_apart = fin && p.unk_pen != 0.f && p.unk != ftok && p.unk >= 0 && p.unk < a.V;
+  const bool unk_apart = fin && p.unk_penalty != 0.f && p.unk != ftok && p.unk >= 0 && p.unk < a.V;
   int have = 0;
   for (int base = 0; base < BEAM_FILL_POOL && base < a.V && have < K2; base += BEAM_THREADS) {
     const int c = base + tid;
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_prefix_fill_kernel(BeamFill
       if ((ban[tok >> 5] >> (tok & 31)) & 1u) v = -INFINITY;
     }
     eval_[tid] = v;                                          // (before the unk penalty, as the layout has it)
-    ekey[tid] = tok == p.unk ? v - p.unk_pen : v;
+    ekey[tid] = tok == p.unk ? v - p.unk_penalty : v;
     etok[tid] = tok;
   }
   __syncthreads();
@@ -267,16 +267,13 @@ struct BeamSelectArgs {
   BeamWs ws;
   int bsz, K, V, S, step, max_len, eos, unk; float unk_pen;
   int normalize; float len_pen;
-  int64_t* tokens; int64_t tok_ld; int tok_cap;
-  float* scores; int64_t score_ld;
-  int* ignore; int* done; int* nfin; int64_t* reorder;
-  int64_t* fin_tok; float* fin_pos; int64_t fin_ld; float* fin_score; int* fin_len; int* fin_cnt;
+  ofa_gen_state st;
   const int64_t* prefix; int64_t prefix_ld; int pad;        // ofa_beam_prefix_select: the forced tokens of this step (else null)
 };
 
 __global__ __launch_bounds__(BEAM_THREADS) void beam_select_kernel(BeamSelectArgs a) {
   const int sent = blockIdx.x;
-  if (a.done[sent]) return;                                  // finished: a no-op from then on
+  if (a.st.done[sent]) return;                               // finished: a no-op from then on
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = a.K, K2 = 2 * K, step = a.step, r0 = sent * K;
   const int nr = step == 0 ? 1 : K;                          // step 0: beam 0 only (search.py:126-129)
@@ -287,13 +284,8 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_select_kernel(BeamSelectArg
   int* pos = cfl + L * K2;                                   // [L] list heads
   __shared__ float lse[BEAM_MAX_K], cum[BEAM_MAX_K];
   __shared__ int bad[BEAM_MAX_K];
-  __shared__ float sel_sc[2 * BEAM_MAX_K];
-  __shared__ int sel_fl[2 * BEAM_MAX_K];
-  __shared__ int act_beam[BEAM_MAX_K], act_tok[BEAM_MAX_K], new_ign[BEAM_MAX_K];
-  __shared__ float act_sc[BEAM_MAX_K];
-  __shared__ int fin_beam[BEAM_MAX_K], fin_slot[BEAM_MAX_K];
-  __shared__ float fin_sc[BEAM_MAX_K];
-  __shared__ int nfin_jobs, finished, nsel;
+  __shared__ BeamSentScratch sh;
+  __shared__ int nsel;
 
   // ---- each beam row's normaliser from its splits' parts
   if (tid < nr) {
@@ -302,7 +294,7 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_select_kernel(BeamSelectArg
     if (a.prefix && a.prefix[(int64_t)sent * a.prefix_ld + step] != a.pad) { l = 0.f; b = false; }   // a forced row's list is normalised
     lse[tid] = l;
     bad[tid] = b;                                            // NaN or infinite: the whole row is -inf (log_softmax -> NaN -> -inf)
-    cum[tid] = step > 0 ? a.scores[(int64_t)(r0 + tid) * a.score_ld + step - 1] : 0.f;
+    cum[tid] = step > 0 ? a.st.scores[(int64_t)(r0 + tid) * a.st.score_ld + step - 1] : 0.f;
   }
   __syncthreads();
   // ---- candidates -> scores (lprob + cumulative score, search.py:131), staged in LDS
@@ -347,115 +339,23 @@ __global__ __launch_bounds__(BEAM_THREADS) void beam_select_kernel(BeamSelectArg
       if (!wave_argmax(lb, lf, mx, mf)) break;
       if (lli >= 0 && lf == mf) {
         pos[lli] += 1;
-        sel_sc[it] = mx;
-        sel_fl[it] = mf;
+        sh.sel_sc[it] = mx;
+        sh.sel_beam[it] = mf / a.V;
+        sh.sel_tok[it] = mf % a.V;
       }
       ++got;
     }
     if (lane == 0) nsel = got;
   }
   __syncthreads();
-  // ---- bookkeeping of one step (sequence_generator.py:345-492, finalize_hypos :530-627): one thread, <= 2K candidates
-  if (tid == 0) {
-    const int k = nsel;
-    bool eosm[2 * BEAM_MAX_K];
-    for (int j = 0; j < k; ++j) {
-      const int tok = sel_fl[j] % a.V;
-      eosm[j] = tok == a.eos && sel_sc[j] != -INFINITY;
-      if (j < K && a.ignore[r0 + j]) eosm[j] = false;
-    }
-    int cnt = a.fin_cnt[sent], jobs = 0;
-    for (int j = 0; j < k && j < K; ++j) {
-      if (!eosm[j]) continue;
-      if (cnt < K) {
-        fin_beam[jobs] = sel_fl[j] / a.V;
-        fin_slot[jobs] = cnt;
-        fin_sc[jobs] = sel_sc[j];
-        ++jobs;
-        ++cnt;
-      }
-    }
-    a.fin_cnt[sent] = cnt;
-    nfin_jobs = jobs;
-    const int fin = (cnt == K || step >= a.max_len) ? 1 : 0;
-    finished = fin;
-    if (fin) {
-      a.done[sent] = 1;
-      atomicAdd(a.nfin, 1);
-    } else {
-      // active_mask = eos_mask * cand_size + offset; its K smallest: the first K unmasked candidates, then the masked ones
-      int nb = 0;
-      for (int pass = 0; pass < 2 && nb < K; ++pass)
-        for (int j = 0; j < k && nb < K; ++j) {
-          const bool masked = eosm[j] || (j < K && a.ignore[r0 + j]);
-          if (masked != (pass == 1)) continue;
-          act_beam[nb] = sel_fl[j] / a.V;
-          act_tok[nb] = sel_fl[j] % a.V;
-          act_sc[nb] = sel_sc[j];
-          new_ign[nb] = masked ? 1 : 0;
-          ++nb;
-        }
-    }
-  }
-  __syncthreads();
-  // ---- finalised hypotheses: tokens 1..step then EOS, positional scores as differences of the cumulative scores
-  const int jobs = nfin_jobs;
-  const int len = step + 1;
-  for (int e = tid; e < jobs * len; e += BEAM_THREADS) {
-    const int q = e / len, i = e % len;
-    const int64_t row = r0 + fin_beam[q];
-    const int slot = fin_slot[q];
-    const int64_t o = ((int64_t)sent * K + slot) * a.fin_ld + i;
-    a.fin_tok[o] = i < step ? a.tokens[row * a.tok_ld + i + 1] : (int64_t)a.eos;
-    const float cur = i < step ? a.scores[row * a.score_ld + i] : fin_sc[q];
-    const float prev = i > 0 ? a.scores[row * a.score_ld + i - 1] : 0.f;
-    a.fin_pos[o] = i > 0 ? cur - prev : cur;
-  }
-  if (tid < jobs) {
-    const int slot = fin_slot[tid];
-    float sc = fin_sc[tid];
-    if (a.normalize) sc = sc / (float)pow((double)len, (double)a.len_pen);
-    a.fin_score[sent * K + slot] = sc;
-    a.fin_len[sent * K + slot] = len;
-  }
-  if (finished) {
-    if (tid < K) a.reorder[r0 + tid] = r0 + tid;
-    return;
-  }
-  __syncthreads();                                           // finalisation read the old histories
-  // ---- gather the K rows' histories in place: LDS copy of the sentence's rows, then the selected rows back
-  int64_t* htok = (int64_t*)smem;                            // [K][step + 1]
-  float* hsc = (float*)(htok + K * len);                     // [K][step]
-  for (int e = tid; e < K * len; e += BEAM_THREADS) {
-    const int b = e / len, i = e % len;
-    htok[e] = a.tokens[(int64_t)(r0 + b) * a.tok_ld + i];
-  }
-  for (int e = tid; e < K * step; e += BEAM_THREADS) {
-    const int b = e / step, i = e % step;
-    hsc[e] = a.scores[(int64_t)(r0 + b) * a.score_ld + i];
-  }
-  __syncthreads();
-  for (int e = tid; e < K * len; e += BEAM_THREADS) {
-    const int b = e / len, i = e % len;
-    a.tokens[(int64_t)(r0 + b) * a.tok_ld + i] = htok[act_beam[b] * len + i];
-  }
-  for (int e = tid; e < K * step; e += BEAM_THREADS) {
-    const int b = e / step, i = e % step;
-    a.scores[(int64_t)(r0 + b) * a.score_ld + i] = hsc[act_beam[b] * step + i];
-  }
-  if (tid < K) {
-    const int64_t row = r0 + tid;
-    if (step + 1 < a.tok_cap) a.tokens[row * a.tok_ld + step + 1] = act_tok[tid];
-    a.scores[row * a.score_ld + step] = act_sc[tid];
-    a.reorder[row] = r0 + act_beam[tid];
-    a.ignore[row] = new_ign[tid];
-  }
+  beam_sentence_step(a.st, sh, sent, K, step, a.max_len, a.eos, a.normalize, a.len_pen, nsel, smem);
 }
 
+// the sentence pass's dynamic LDS: the candidate lists, then (over them) the history gather
 static size_t select_smem(int K, int S, int step) {
   const int nr = step == 0 ? 1 : K, L = nr * S;
   const size_t cand = (size_t)L * 2 * K * 8 + (size_t)L * 4;
-  const size_t hist = (size_t)K * (step + 1) * 8 + (size_t)K * step * 4;
+  const size_t hist = beam_history_lds(K, step);
   return cand > hist ? cand : hist;
 }
 
@@ -463,119 +363,105 @@ static size_t select_smem(int K, int S, int step) {
 
 using namespace ofa;
 
+// the two descriptors of the generation steps as kernels._GenPolicy / _GenState mirror them (natural alignment on both sides)
+static_assert(sizeof(ofa_gen_policy) == 72, "ofa_gen_policy: 2 floats and 9 int32 (44 bytes, padded to 48), then 2 pointers and 1 int64");
+static_assert(sizeof(ofa_gen_state) == 120, "ofa_gen_state: 11 pointers and 3 int64; tok_cap (int32) sits in an 8-byte slot");
+
 extern "C" int64_t ofa_beam_ws_bytes(int rows, int V, int K) {
   if (rows <= 0 || V <= 0 || K <= 0) return 0;
   return beam_ws_words(rows, beam_splits(V), K) * 4;
 }
 
-extern "C" int ofa_beam_topk(const void* logits, int64_t ld, int rows, int V, int K, float temperature, int cstart, int cend,
-                             int step, int min_len, int max_len, int pad, int unk, int eos, float unk_penalty, int ngram,
-                             const int64_t* tokens, int64_t tok_ld, const int* done, void* ws, int dtype, void* stream) {
-  OFA_REQUIRE(logits && ws, OFA_ERR_INVALID, "ofa_beam_topk: null pointer");
-  OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "ofa_beam_topk: bad dtype %d", dtype);
-  OFA_REQUIRE(rows > 0 && V > 1 && ld >= V && step >= 0, OFA_ERR_INVALID, "ofa_beam_topk: rows=%d V=%d ld=%lld step=%d", rows, V,
-              (long long)ld, step);
-  if (const int rc = beam_check_row_pass("ofa_beam_topk", rows, V, K, temperature, step, ngram, tokens, tok_ld)) return rc;
+// the row pass of ofa_beam_topk and ofa_beam_prefix_topk (plen: the latter's prefix lengths; prefix: a prefix step's forced tokens)
+static int beam_topk_launch(const char* who, const void* logits, int64_t ld, int rows, int V, int K, const ofa_gen_policy* pol,
+                            const int64_t* prefix, int64_t prefix_ld, const int* plen, float* glogit, void* ws, int dtype,
+                            void* stream) {
+  OFA_REQUIRE(logits && ws && pol, OFA_ERR_INVALID, "%s: null pointer", who);
+  OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "%s: bad dtype %d", who, dtype);
+  OFA_REQUIRE(rows > 0 && V > 1 && ld >= V && pol->step >= 0, OFA_ERR_INVALID, "%s: rows=%d V=%d ld=%lld step=%d", who, rows, V,
+              (long long)ld, pol->step);
+  if (const int rc = beam_check_row_pass(who, rows, V, K, *pol)) return rc;
   const int S = beam_splits(V);
-  BeamTopkArgs a{logits, ld, rows, V, K, S, cstart, cend,
-                 BeamPolicy{temperature, step, min_len, max_len, pad, unk, eos, unk_penalty, ngram, tokens, tok_ld, done},
-                 beam_ws_carve(ws, rows, S, K), nullptr, 0, nullptr, nullptr};
+  BeamTopkArgs a{logits, ld, rows, V, K, S, *pol, beam_ws_carve(ws, rows, S, K), prefix, prefix_ld, plen, glogit};
+  if (prefix) a.p.min_len = 0;       // a prefix step applies the min_len mask to no row (the `elif` of sequence_generator.py:297-301)
   dim3 grid(S, rows);
   hipStream_t st = (hipStream_t)stream;
   dispatch_dtype(dtype, [&](auto tag) {
-    hipLaunchKernelGGL(beam_topk_kernel<typename decltype(tag)::type>, grid, dim3(BEAM_THREADS), 0, st, a);
+    using T = typename decltype(tag)::type;
+    if (plen) hipLaunchKernelGGL(beam_prefix_row_kernel<T>, grid, dim3(BEAM_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(beam_topk_kernel<T>, grid, dim3(BEAM_THREADS), 0, st, a);
   });
-  return check_launch("ofa_beam_topk");
+  return check_launch(who);
+}
+
+extern "C" int ofa_beam_topk(const void* logits, int64_t ld, int rows, int V, int K, const ofa_gen_policy* pol, void* ws, int dtype,
+                             void* stream) {
+  return beam_topk_launch("ofa_beam_topk", logits, ld, rows, V, K, pol, nullptr, 0, nullptr, nullptr, ws, dtype, stream);
 }
 
 // the sentence pass of ofa_beam_select and ofa_beam_prefix_select (prefix: the forced tokens of a prefix step, else null)
-static int beam_select_launch(const char* who, const void* ws, int bsz, int K, int V, int step, int max_len, int eos, int unk,
-                              float unk_penalty, int normalize, float len_penalty, int64_t* tokens, int64_t tok_ld, int tok_cap,
-                              float* scores, int64_t score_ld, int* ignore, int* done, int* nfin, int64_t* reorder, int64_t* fin_tok,
-                              float* fin_pos, int64_t fin_ld, float* fin_score, int* fin_len, int* fin_cnt, const int64_t* prefix,
+static int beam_select_launch(const char* who, const void* ws, const ofa_gen_state* st, int bsz, int K, int V, int step, int max_len,
+                              int eos, int unk, float unk_penalty, int normalize, float len_penalty, const int64_t* prefix,
                               int64_t prefix_ld, int pad, void* stream) {
-  OFA_REQUIRE(ws && tokens && scores && ignore && done && nfin && reorder && fin_tok && fin_pos && fin_score && fin_len && fin_cnt,
-              OFA_ERR_INVALID, "%s: null pointer", who);
+  OFA_REQUIRE(ws, OFA_ERR_INVALID, "%s: null pointer", who);
   OFA_REQUIRE(bsz > 0 && V > 1 && step >= 0 && step <= max_len, OFA_ERR_INVALID, "%s: bsz=%d V=%d step=%d max_len=%d", who,
               bsz, V, step, max_len);
-  OFA_REQUIRE(K >= 1 && K <= BEAM_MAX_K, OFA_ERR_UNSUPPORTED, "%s: beam size %d outside [1, %d]", who, K, BEAM_MAX_K);
+  if (const int rc = beam_check_state(who, st, K, step, true)) return rc;
   OFA_REQUIRE((int64_t)K * V < (1 << 24), OFA_ERR_UNSUPPORTED, "%s: beam * vocabulary must stay below 2^24", who);
-  OFA_REQUIRE(tok_cap >= step + 1 && tok_ld >= tok_cap && score_ld > step && fin_ld > step, OFA_ERR_INVALID,
-              "%s: history buffers too short for step %d (tok_cap=%d tok_ld=%lld score_ld=%lld fin_ld=%lld)", who, step,
-              tok_cap, (long long)tok_ld, (long long)score_ld, (long long)fin_ld);
   const int S = beam_splits(V);
   const size_t smem = select_smem(K, S, step);
   OFA_REQUIRE(smem <= 65536, OFA_ERR_UNSUPPORTED, "%s: beam %d x %d vocabulary splits x step %d needs %zu bytes of LDS", who,
               K, S, step, smem);
   BeamSelectArgs a{beam_ws_carve(ws, (int64_t)bsz * K, S, K), bsz, K, V, S, step, max_len, eos, unk, unk_penalty, normalize, len_penalty,
-                   tokens, tok_ld, tok_cap, scores, score_ld, ignore, done, nfin, reorder, fin_tok, fin_pos, fin_ld, fin_score,
-                   fin_len, fin_cnt, prefix, prefix_ld, pad};
+                   *st, prefix, prefix_ld, pad};
   hipLaunchKernelGGL(beam_select_kernel, dim3(bsz), dim3(BEAM_THREADS), smem, (hipStream_t)stream, a);
   return check_launch(who);
 }
 
-extern "C" int ofa_beam_select(const void* ws, int bsz, int K, int V, int step, int max_len, int eos, int unk, float unk_penalty,
-                               int normalize, float len_penalty, int64_t* tokens, int64_t tok_ld, int tok_cap, float* scores,
-                               int64_t score_ld, int* ignore, int* done, int* nfin, int64_t* reorder, int64_t* fin_tok,
-                               float* fin_pos, int64_t fin_ld, float* fin_score, int* fin_len, int* fin_cnt, void* stream) {
-  return beam_select_launch("ofa_beam_select", ws, bsz, K, V, step, max_len, eos, unk, unk_penalty, normalize, len_penalty, tokens,
-                            tok_ld, tok_cap, scores, score_ld, ignore, done, nfin, reorder, fin_tok, fin_pos, fin_ld, fin_score,
-                            fin_len, fin_cnt, nullptr, 0, 0, stream);
+extern "C" int ofa_beam_select(const void* ws, const ofa_gen_state* st, int bsz, int K, int V, int step, int max_len, int eos, int unk,
+                               float unk_penalty, int normalize, float len_penalty, void* stream) {
+  return beam_select_launch("ofa_beam_select", ws, st, bsz, K, V, step, max_len, eos, unk, unk_penalty, normalize, len_penalty, nullptr,
+                            0, 0, stream);
 }
 
 // ---------------------------------------------------------------- steps under a forced target prefix
-extern "C" int ofa_beam_prefix_topk(const void* logits, int64_t ld, int rows, int V, int K, float temperature, int cstart, int cend,
-                                    int step, int min_len, int max_len, int pad, int unk, int eos, float unk_penalty, int ngram,
-                                    const int64_t* tokens, int64_t tok_ld, const int* done, const int64_t* prefix,
-                                    int64_t prefix_ld, const int* plen, float* glogit, void* ws, int dtype, void* stream) {
-  OFA_REQUIRE(logits && ws && plen, OFA_ERR_INVALID, "ofa_beam_prefix_topk: null pointer");
-  OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "ofa_beam_prefix_topk: bad dtype %d", dtype);
-  OFA_REQUIRE(rows > 0 && V > 1 && ld >= V && step >= 0, OFA_ERR_INVALID, "ofa_beam_prefix_topk: rows=%d V=%d ld=%lld step=%d", rows,
-              V, (long long)ld, step);
-  OFA_REQUIRE(!prefix || (glogit && prefix_ld > step && step < max_len), OFA_ERR_INVALID,
+extern "C" int ofa_beam_prefix_topk(const void* logits, int64_t ld, int rows, int V, int K, const ofa_gen_policy* pol,
+                                    const int64_t* prefix, int64_t prefix_ld, const int* plen, float* glogit, void* ws, int dtype,
+                                    void* stream) {
+  OFA_REQUIRE(pol && plen, OFA_ERR_INVALID, "ofa_beam_prefix_topk: null pointer");
+  OFA_REQUIRE(!prefix || (glogit && prefix_ld > pol->step && pol->step < pol->max_len), OFA_ERR_INVALID,
               "ofa_beam_prefix_topk: a prefix step needs glogit, prefix_ld=%lld > step=%d and step < max_len=%d", (long long)prefix_ld,
-              step, max_len);
-  if (const int rc = beam_check_row_pass("ofa_beam_prefix_topk", rows, V, K, temperature, step, ngram, tokens, tok_ld)) return rc;
-  const int S = beam_splits(V);
-  // a prefix step applies the min_len mask to no row (the `elif` of sequence_generator.py:297-301)
-  BeamTopkArgs a{logits, ld, rows, V, K, S, cstart, cend,
-                 BeamPolicy{temperature, step, prefix ? 0 : min_len, max_len, pad, unk, eos, unk_penalty, ngram, tokens, tok_ld, done},
-                 beam_ws_carve(ws, rows, S, K), prefix, prefix_ld, plen, glogit};
-  dim3 grid(S, rows);
-  hipStream_t st = (hipStream_t)stream;
-  dispatch_dtype(dtype, [&](auto tag) {
-    hipLaunchKernelGGL(beam_prefix_row_kernel<typename decltype(tag)::type>, grid, dim3(BEAM_THREADS), 0, st, a);
-  });
-  return check_launch("ofa_beam_prefix_topk");
+              pol->step, pol->max_len);
+  return beam_topk_launch("ofa_beam_prefix_topk", logits, ld, rows, V, K, pol, prefix, prefix_ld, plen, glogit, ws, dtype, stream);
 }
 
-extern "C" int ofa_beam_prefix_fill(void* ws, int rows, int V, int K, int step, int pad, int unk, float unk_penalty, int ngram,
-                                    const int64_t* tokens, int64_t tok_ld, const int* done, const int64_t* prefix,
+extern "C" int ofa_beam_prefix_fill(void* ws, int rows, int V, int K, const ofa_gen_policy* pol, const int64_t* prefix,
                                     int64_t prefix_ld, const int* plen, const float* glogit, void* stream) {
-  OFA_REQUIRE(ws && prefix && plen && glogit, OFA_ERR_INVALID, "ofa_beam_prefix_fill: null pointer");
+  OFA_REQUIRE(ws && pol && prefix && plen && glogit, OFA_ERR_INVALID, "ofa_beam_prefix_fill: null pointer");
+  ofa_gen_policy p = *pol;                                   // its subset; what it does not read is out of the checks' way
+  p.temperature = 1.f;
+  p.cstart = p.cend = p.eos = -1;
+  p.min_len = p.max_len = 0;
+  const int step = p.step;
   OFA_REQUIRE(rows > 0 && V > 1 && step >= 0 && prefix_ld > step, OFA_ERR_INVALID, "ofa_beam_prefix_fill: rows=%d V=%d step=%d prefix_ld=%lld",
               rows, V, step, (long long)prefix_ld);
-  if (const int rc = beam_check_row_pass("ofa_beam_prefix_fill", rows, V, K, 1.f, step, ngram, tokens, tok_ld)) return rc;
+  if (const int rc = beam_check_row_pass("ofa_beam_prefix_fill", rows, V, K, p)) return rc;
   // at most step + 4 of the lowest tokens are not at f (the prefix token, pad, unk, step + 1 banned ones): 2K more are there
   const int pool = V < BEAM_FILL_POOL ? V : BEAM_FILL_POOL;
-  OFA_REQUIRE(2 * K + step + 4 <= pool && unk < pool, OFA_ERR_UNSUPPORTED,
+  OFA_REQUIRE(2 * K + step + 4 <= pool && p.unk < pool, OFA_ERR_UNSUPPORTED,
               "ofa_beam_prefix_fill: beam %d at step %d needs %d tokens among the first %d of the vocabulary", K, step,
               2 * K + step + 4, pool);
   const int S = beam_splits(V);
-  BeamFillArgs a{beam_ws_carve(ws, rows, S, K), rows, V, K, S, prefix, prefix_ld, plen, glogit,
-                 BeamPolicy{1.f, step, 0, 0, pad, unk, -1, unk_penalty, ngram, tokens, tok_ld, done}};
+  BeamFillArgs a{beam_ws_carve(ws, rows, S, K), rows, V, K, S, prefix, prefix_ld, plen, glogit, p};
   hipLaunchKernelGGL(beam_prefix_fill_kernel, dim3(rows), dim3(BEAM_THREADS), 0, (hipStream_t)stream, a);
   return check_launch("ofa_beam_prefix_fill");
 }
 
-extern "C" int ofa_beam_prefix_select(const void* ws, int bsz, int K, int V, int step, int max_len, int eos, int unk,
-                                      float unk_penalty, int normalize, float len_penalty, int64_t* tokens, int64_t tok_ld,
-                                      int tok_cap, float* scores, int64_t score_ld, int* ignore, int* done, int* nfin,
-                                      int64_t* reorder, int64_t* fin_tok, float* fin_pos, int64_t fin_ld, float* fin_score,
-                                      int* fin_len, int* fin_cnt, const int64_t* prefix, int64_t prefix_ld, int pad, void* stream) {
+extern "C" int ofa_beam_prefix_select(const void* ws, const ofa_gen_state* st, int bsz, int K, int V, int step, int max_len, int eos,
+                                      int unk, float unk_penalty, int normalize, float len_penalty, const int64_t* prefix,
+                                      int64_t prefix_ld, int pad, void* stream) {
   OFA_REQUIRE(prefix && prefix_ld > step, OFA_ERR_INVALID, "ofa_beam_prefix_select: prefix=%p prefix_ld=%lld step=%d", (const void*)prefix,
               (long long)prefix_ld, step);
-  return beam_select_launch("ofa_beam_prefix_select", ws, bsz, K, V, step, max_len, eos, unk, unk_penalty, normalize, len_penalty,
-                            tokens, tok_ld, tok_cap, scores, score_ld, ignore, done, nfin, reorder, fin_tok, fin_pos, fin_ld,
-                            fin_score, fin_len, fin_cnt, prefix, prefix_ld, pad, stream);
+  return beam_select_launch("ofa_beam_prefix_select", ws, st, bsz, K, V, step, max_len, eos, unk, unk_penalty, normalize, len_penalty,
+                            prefix, prefix_ld, pad, stream);
 }

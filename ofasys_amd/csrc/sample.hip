@@ -23,7 +23,7 @@
 // 2. ofa_sample_select -- the sentence pass, one workgroup per sentence, over the K-wide candidate list (slot j draws once, with
 //    itself as parent; parent 0 at step 0): score = scores[row, step - 1] + lprob, EOS draws of slots not ignored are finalised,
 //    ignored slots stay ignored, the active slots are compacted to the front in column order, histories gathered in place, reorder
-//    written.  Buffers as ofa_beam_select.
+//    written: beam_common.h's beam_sentence_step, the bookkeeping ofa_beam_select runs, over a list of exactly K.
 #include "beam_common.h"
 
 namespace ofa {
@@ -47,8 +47,7 @@ static inline SampleWs sample_ws_carve(const void* ws, int64_t rows) { return Sa
 struct SampleDrawArgs {
   const void* logits; int64_t ld;
   int rows, V, K, S;
-  int cstart, cend;
-  BeamPolicy p;
+  ofa_gen_policy p;
   int mode;                               // 0 plain, 1 top-k, 2 top-p
   u64 limit;                              // k, or p in units of 2^-40
   const float* uniforms;
@@ -93,7 +92,7 @@ __device__ __forceinline__ u64 wave_scan_u64(u64 v, int lane) {       // inclusi
 template <typename T>
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_draw_kernel(SampleDrawArgs a) {
   const int row = blockIdx.x, sent = row / a.K;
-  const BeamPolicy& p = a.p;
+  const ofa_gen_policy& p = a.p;
   if (p.done && p.done[sent]) return;
   const int src_row = p.step == 0 ? sent * a.K : row;       // step 0: the sentence's first row only (search.py:661-664)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -120,7 +119,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_draw_kernel(SampleDrawA
   // x / T under constraint_range: what the normaliser sees
   auto scaled = [&](float v, int c) -> float {
     if (p.temperature != 1.f) v = v / p.temperature;
-    if (a.cstart >= 0 && ((c >= 4 && c < a.cstart) || c >= a.cend)) v = -INFINITY;
+    if (p.cstart >= 0 && ((c >= 4 && c < p.cstart) || c >= p.cend)) v = -INFINITY;
     return v;
   };
   // ---- the fp32 normaliser, built as ofa_beam_topk builds it: a wave's (max, sum) of its quarter of every 4096-column part
@@ -335,123 +334,26 @@ struct SampleSelectArgs {
   SampleWs ws;
   int bsz, K, step, max_len, eos;
   int normalize; float len_pen;
-  int64_t* tokens; int64_t tok_ld; int tok_cap;
-  float* scores; int64_t score_ld;
-  int* ignore; int* done; int* nfin; int64_t* reorder;
-  int64_t* fin_tok; float* fin_pos; int64_t fin_ld; float* fin_score; int* fin_len; int* fin_cnt;
+  ofa_gen_state st;
 };
 
 __global__ __launch_bounds__(BEAM_THREADS) void sample_select_kernel(SampleSelectArgs a) {
   const int sent = blockIdx.x;
-  if (a.done[sent]) return;                                  // finished: a no-op from then on
+  if (a.st.done[sent]) return;                               // finished: a no-op from then on
   const int tid = threadIdx.x;
   const int K = a.K, step = a.step, r0 = sent * K;
   extern __shared__ float smem[];
-  __shared__ float sel_sc[BEAM_MAX_K];
-  __shared__ int sel_tok[BEAM_MAX_K];
-  __shared__ int act_beam[BEAM_MAX_K], act_tok[BEAM_MAX_K], new_ign[BEAM_MAX_K];
-  __shared__ float act_sc[BEAM_MAX_K];
-  __shared__ int fin_beam[BEAM_MAX_K], fin_slot[BEAM_MAX_K];
-  __shared__ float fin_sc[BEAM_MAX_K];
-  __shared__ int nfin_jobs, finished;
+  __shared__ BeamSentScratch sh;
 
-  // ---- the K candidates: slot j's draw, cumulative (search.py:708-713)
+  // ---- the K candidates: slot j's draw, cumulative (search.py:708-713), with itself as parent (slot 0 at step 0)
   if (tid < K) {
     const float lp = a.ws.lprob[r0 + tid];
-    sel_sc[tid] = step > 0 ? lp + a.scores[(int64_t)(r0 + tid) * a.score_ld + step - 1] : lp;
-    sel_tok[tid] = a.ws.tok[r0 + tid];
+    sh.sel_sc[tid] = step > 0 ? lp + a.st.scores[(int64_t)(r0 + tid) * a.st.score_ld + step - 1] : lp;
+    sh.sel_beam[tid] = step == 0 ? 0 : tid;
+    sh.sel_tok[tid] = a.ws.tok[r0 + tid];
   }
   __syncthreads();
-  // ---- bookkeeping of one step (sequence_generator.py:345-492, finalize_hypos :530-627) for a K-wide list: one thread
-  if (tid == 0) {
-    bool eosm[BEAM_MAX_K];
-    for (int j = 0; j < K; ++j) eosm[j] = sel_tok[j] == a.eos && sel_sc[j] != -INFINITY && !a.ignore[r0 + j];
-    int cnt = a.fin_cnt[sent], jobs = 0;
-    for (int j = 0; j < K; ++j) {
-      if (!eosm[j]) continue;
-      if (cnt < K) {
-        fin_beam[jobs] = step == 0 ? 0 : j;
-        fin_slot[jobs] = cnt;
-        fin_sc[jobs] = sel_sc[j];
-        ++jobs;
-        ++cnt;
-      }
-    }
-    a.fin_cnt[sent] = cnt;
-    nfin_jobs = jobs;
-    const int fin = (cnt == K || step >= a.max_len) ? 1 : 0;
-    finished = fin;
-    if (fin) {
-      a.done[sent] = 1;
-      atomicAdd(a.nfin, 1);
-    } else {
-      // active_mask over K columns: the slots that go on, in column order, then the ended and ignored ones (:438-452)
-      int nb = 0;
-      for (int pass = 0; pass < 2; ++pass)
-        for (int j = 0; j < K; ++j) {
-          const bool masked = eosm[j] || a.ignore[r0 + j];
-          if (masked != (pass == 1)) continue;
-          act_beam[nb] = step == 0 ? 0 : j;
-          act_tok[nb] = sel_tok[j];
-          act_sc[nb] = sel_sc[j];
-          new_ign[nb] = masked ? 1 : 0;
-          ++nb;
-        }
-    }
-  }
-  __syncthreads();
-  // ---- finalised hypotheses: tokens 1..step then EOS, positional scores as differences of the cumulative scores
-  const int jobs = nfin_jobs;
-  const int len = step + 1;
-  for (int e = tid; e < jobs * len; e += BEAM_THREADS) {
-    const int q = e / len, i = e % len;
-    const int64_t row = r0 + fin_beam[q];
-    const int slot = fin_slot[q];
-    const int64_t o = ((int64_t)sent * K + slot) * a.fin_ld + i;
-    a.fin_tok[o] = i < step ? a.tokens[row * a.tok_ld + i + 1] : (int64_t)a.eos;
-    const float cur = i < step ? a.scores[row * a.score_ld + i] : fin_sc[q];
-    const float prev = i > 0 ? a.scores[row * a.score_ld + i - 1] : 0.f;
-    a.fin_pos[o] = i > 0 ? cur - prev : cur;
-  }
-  if (tid < jobs) {
-    const int slot = fin_slot[tid];
-    float sc = fin_sc[tid];
-    if (a.normalize) sc = sc / (float)pow((double)len, (double)a.len_pen);
-    a.fin_score[sent * K + slot] = sc;
-    a.fin_len[sent * K + slot] = len;
-  }
-  if (finished) {
-    if (tid < K) a.reorder[r0 + tid] = r0 + tid;
-    return;
-  }
-  __syncthreads();                                           // finalisation read the old histories
-  // ---- gather the K rows' histories in place: LDS copy of the sentence's rows, then the selected rows back
-  int64_t* htok = (int64_t*)smem;                            // [K][step + 1]
-  float* hsc = (float*)(htok + K * len);                     // [K][step]
-  for (int e = tid; e < K * len; e += BEAM_THREADS) {
-    const int b = e / len, i = e % len;
-    htok[e] = a.tokens[(int64_t)(r0 + b) * a.tok_ld + i];
-  }
-  for (int e = tid; e < K * step; e += BEAM_THREADS) {
-    const int b = e / step, i = e % step;
-    hsc[e] = a.scores[(int64_t)(r0 + b) * a.score_ld + i];
-  }
-  __syncthreads();
-  for (int e = tid; e < K * len; e += BEAM_THREADS) {
-    const int b = e / len, i = e % len;
-    a.tokens[(int64_t)(r0 + b) * a.tok_ld + i] = htok[act_beam[b] * len + i];
-  }
-  for (int e = tid; e < K * step; e += BEAM_THREADS) {
-    const int b = e / step, i = e % step;
-    a.scores[(int64_t)(r0 + b) * a.score_ld + i] = hsc[act_beam[b] * step + i];
-  }
-  if (tid < K) {
-    const int64_t row = r0 + tid;
-    if (step + 1 < a.tok_cap) a.tokens[row * a.tok_ld + step + 1] = act_tok[tid];
-    a.scores[row * a.score_ld + step] = act_sc[tid];
-    a.reorder[row] = r0 + act_beam[tid];
-    a.ignore[row] = new_ign[tid];
-  }
+  beam_sentence_step(a.st, sh, sent, K, step, a.max_len, a.eos, a.normalize, a.len_pen, K, smem);
 }
 
 }  // namespace ofa
@@ -463,24 +365,20 @@ extern "C" int64_t ofa_sample_ws_bytes(int rows, int V, int K) {
   return (int64_t)rows * 8;
 }
 
-extern "C" int ofa_sample_draw(const void* logits, int64_t ld, int rows, int V, int K, float temperature, int cstart, int cend,
-                               int step, int min_len, int max_len, int pad, int unk, int eos, float unk_penalty, int ngram,
-                               const int64_t* tokens, int64_t tok_ld, const int* done, int topk, float topp, const float* uniforms,
-                               void* ws, int dtype, void* stream) {
-  OFA_REQUIRE(logits && ws && uniforms, OFA_ERR_INVALID, "ofa_sample_draw: null pointer");
+extern "C" int ofa_sample_draw(const void* logits, int64_t ld, int rows, int V, int K, const ofa_gen_policy* pol, int topk, float topp,
+                               const float* uniforms, void* ws, int dtype, void* stream) {
+  OFA_REQUIRE(logits && ws && uniforms && pol, OFA_ERR_INVALID, "ofa_sample_draw: null pointer");
   OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "ofa_sample_draw: bad dtype %d", dtype);
-  OFA_REQUIRE(rows > 0 && V > 1 && ld >= V && step >= 0, OFA_ERR_INVALID, "ofa_sample_draw: rows=%d V=%d ld=%lld step=%d", rows, V,
-              (long long)ld, step);
+  OFA_REQUIRE(rows > 0 && V > 1 && ld >= V && pol->step >= 0, OFA_ERR_INVALID, "ofa_sample_draw: rows=%d V=%d ld=%lld step=%d", rows, V,
+              (long long)ld, pol->step);
   OFA_REQUIRE(V <= SAMPLE_MAX_V, OFA_ERR_UNSUPPORTED, "ofa_sample_draw: vocabulary %d > %d", V, SAMPLE_MAX_V);
   OFA_REQUIRE(!(topp > 1.f) && topp == topp, OFA_ERR_INVALID, "ofa_sample_draw: top-p %g above 1", (double)topp);
-  if (const int rc = beam_check_row_pass("ofa_sample_draw", rows, V, K, temperature, step, ngram, tokens, tok_ld)) return rc;
+  if (const int rc = beam_check_row_pass("ofa_sample_draw", rows, V, K, *pol)) return rc;
   int mode = 0;
   u64 limit = 0;
   if (topp > 0.f) { mode = 2; limit = (u64)((double)topp * (double)SAMPLE_FIX_ONE); }   // top-p wins (search.py:666-672)
   else if (topk > 0 && topk < V) { mode = 1; limit = (u64)topk; }
-  SampleDrawArgs a{logits, ld, rows, V, K, beam_splits(V), cstart, cend,
-                   BeamPolicy{temperature, step, min_len, max_len, pad, unk, eos, unk_penalty, ngram, tokens, tok_ld, done},
-                   mode, limit, uniforms, sample_ws_carve(ws, rows)};
+  SampleDrawArgs a{logits, ld, rows, V, K, beam_splits(V), *pol, mode, limit, uniforms, sample_ws_carve(ws, rows)};
   hipStream_t st = (hipStream_t)stream;
   dispatch_dtype(dtype, [&](auto tag) {
     hipLaunchKernelGGL(sample_draw_kernel<typename decltype(tag)::type>, dim3(rows), dim3(SAMPLE_THREADS), 0, st, a);
@@ -488,22 +386,15 @@ extern "C" int ofa_sample_draw(const void* logits, int64_t ld, int rows, int V, 
   return check_launch("ofa_sample_draw");
 }
 
-extern "C" int ofa_sample_select(const void* ws, int bsz, int K, int step, int max_len, int eos, int normalize, float len_penalty,
-                                 int64_t* tokens, int64_t tok_ld, int tok_cap, float* scores, int64_t score_ld, int* ignore,
-                                 int* done, int* nfin, int64_t* reorder, int64_t* fin_tok, float* fin_pos, int64_t fin_ld,
-                                 float* fin_score, int* fin_len, int* fin_cnt, void* stream) {
-  OFA_REQUIRE(ws && tokens && scores && ignore && done && nfin && reorder && fin_tok && fin_pos && fin_score && fin_len && fin_cnt,
-              OFA_ERR_INVALID, "ofa_sample_select: null pointer");
+extern "C" int ofa_sample_select(const void* ws, const ofa_gen_state* st, int bsz, int K, int step, int max_len, int eos, int normalize,
+                                 float len_penalty, void* stream) {
+  OFA_REQUIRE(ws, OFA_ERR_INVALID, "ofa_sample_select: null pointer");
   OFA_REQUIRE(bsz > 0 && step >= 0 && step <= max_len, OFA_ERR_INVALID, "ofa_sample_select: bsz=%d step=%d max_len=%d", bsz, step,
               max_len);
-  OFA_REQUIRE(K >= 1 && K <= BEAM_MAX_K, OFA_ERR_UNSUPPORTED, "ofa_sample_select: beam size %d outside [1, %d]", K, BEAM_MAX_K);
-  OFA_REQUIRE(tok_cap >= step + 1 && tok_ld >= tok_cap && score_ld > step && fin_ld > step, OFA_ERR_INVALID,
-              "ofa_sample_select: history buffers too short for step %d (tok_cap=%d tok_ld=%lld score_ld=%lld fin_ld=%lld)", step,
-              tok_cap, (long long)tok_ld, (long long)score_ld, (long long)fin_ld);
-  const size_t smem = (size_t)K * (step + 1) * 8 + (size_t)K * step * 4;
+  if (const int rc = beam_check_state("ofa_sample_select", st, K, step, true)) return rc;
+  const size_t smem = beam_history_lds(K, step);
   OFA_REQUIRE(smem <= 65536, OFA_ERR_UNSUPPORTED, "ofa_sample_select: beam %d x step %d needs %zu bytes of LDS", K, step, smem);
-  SampleSelectArgs a{sample_ws_carve(ws, (int64_t)bsz * K), bsz, K, step, max_len, eos, normalize, len_penalty, tokens, tok_ld, tok_cap,
-                     scores, score_ld, ignore, done, nfin, reorder, fin_tok, fin_pos, fin_ld, fin_score, fin_len, fin_cnt};
+  SampleSelectArgs a{sample_ws_carve(ws, (int64_t)bsz * K), bsz, K, step, max_len, eos, normalize, len_penalty, *st};
   hipLaunchKernelGGL(sample_select_kernel, dim3(bsz), dim3(BEAM_THREADS), smem, (hipStream_t)stream, a);
   return check_launch("ofa_sample_select");
 }

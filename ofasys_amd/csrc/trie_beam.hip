@@ -50,7 +50,7 @@ struct TrieTopkArgs {
   const void* W; int64_t ld_w; const void* bias;
   int D, V, rows, K, S, Su, epw;
   const int* node; const int* node_edge_off; const int* edge_token; int N, E;
-  BeamPolicy p;
+  ofa_gen_policy p;
   BeamWs ws;
 };
 
@@ -68,7 +68,7 @@ template <typename T>
 __global__ __launch_bounds__(BEAM_THREADS) void trie_beam_topk_kernel(TrieTopkArgs a) {
   constexpr int NV = Vec<T>::N;
   const int split = blockIdx.x, row = blockIdx.y;
-  const BeamPolicy& p = a.p;
+  const ofa_gen_policy& p = a.p;
   if (p.done && p.done[row / a.K]) return;
   if (p.step == 0 && row % a.K != 0) return;                  // the sentence pass reads beam 0 only at step 0
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -232,14 +232,13 @@ __global__ __launch_bounds__(BEAM_THREADS) void trie_beam_topk_kernel(TrieTopkAr
 struct TrieAdvanceArgs {
   int* node; const int* node_edge_off; const int* edge_token; const int* edge_child; int N, E;
   int bsz, K, step;
-  const int64_t* tokens; int64_t tok_ld; int tok_cap;
-  const float* scores; int64_t score_ld;
-  const int* ignore; const int64_t* reorder; int* done; int* nfin;
+  ofa_gen_state st;                       // read: the histories, ignore, reorder; written: done, nfin
 };
 
 __global__ __launch_bounds__(BEAM_THREADS) void trie_beam_advance_kernel(TrieAdvanceArgs a) {
   const int sent = blockIdx.x;
-  if (a.done[sent]) return;                                   // finished (possibly by this step's sentence pass): its nodes are not read again
+  const ofa_gen_state& st = a.st;
+  if (st.done[sent]) return;                                  // finished (possibly by this step's sentence pass): its nodes are not read again
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = a.K, r0 = sent * K;
   __shared__ int old[BEAM_MAX_K];
@@ -249,14 +248,14 @@ __global__ __launch_bounds__(BEAM_THREADS) void trie_beam_advance_kernel(TrieAdv
   __syncthreads();                                            // every old node is read before any is written
   for (int b = wave; b < K; b += 4) {
     const int64_t row = r0 + b;
-    const int64_t parent = a.reorder[row] - r0;
-    const float sc = a.scores[row * a.score_ld + a.step];
+    const int64_t parent = st.reorder[row] - r0;
+    const float sc = st.scores[row * st.score_ld + a.step];
     const bool finite = sc == sc && sc != -INFINITY;
     int child = -1;
-    if (finite && parent >= 0 && parent < K && a.step + 1 < a.tok_cap) {
+    if (finite && parent >= 0 && parent < K && a.step + 1 < st.tok_cap) {
       const int pn = old[parent];
       if ((unsigned)pn < (unsigned)a.N) {
-        const int64_t tok = a.tokens[row * a.tok_ld + a.step + 1];
+        const int64_t tok = st.tokens[row * st.tok_ld + a.step + 1];
         const int e0 = max(a.node_edge_off[pn], 0), e1 = min(a.node_edge_off[pn + 1], a.E);
         float found = -1.f;                                   // node ids < 2^24: exact as float
         for (int e = e0 + lane; e < e1; e += WAVE)
@@ -267,13 +266,13 @@ __global__ __launch_bounds__(BEAM_THREADS) void trie_beam_advance_kernel(TrieAdv
     }
     if (lane == 0) {
       a.node[row] = child;
-      if (finite && !a.ignore[row]) atomicOr(&alive, 1);
+      if (finite && !st.ignore[row]) atomicOr(&alive, 1);
     }
   }
   __syncthreads();
   if (tid == 0 && !alive) {                                   // every slot ignored or at -inf: nothing more can be finalised
-    a.done[sent] = 1;
-    atomicAdd(a.nfin, 1);
+    st.done[sent] = 1;
+    atomicAdd(st.nfin, 1);
   }
 }
 
@@ -288,22 +287,22 @@ extern "C" int ofa_trie_beam_splits(int max_degree, int V) {
 
 extern "C" int ofa_trie_beam_topk(const void* h, int64_t ld_h, int dtype, const void* W, int64_t ld_w, const void* bias, int D, int V,
                                   int rows, int K, const int* node, const int* node_edge_off, const int* edge_token, int N, int E,
-                                  int max_degree, float temperature, int step, int min_len, int max_len, int pad, int unk, int eos,
-                                  float unk_penalty, int ngram, const int64_t* tokens, int64_t tok_ld, const int* done, void* ws,
-                                  void* stream) {
-  OFA_REQUIRE(h && W && node && node_edge_off && edge_token && ws, OFA_ERR_INVALID, "ofa_trie_beam_topk: null pointer");
+                                  int max_degree, const ofa_gen_policy* pol, void* ws, void* stream) {
+  OFA_REQUIRE(h && W && node && node_edge_off && edge_token && ws && pol, OFA_ERR_INVALID, "ofa_trie_beam_topk: null pointer");
   OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "ofa_trie_beam_topk: bad dtype %d", dtype);
+  const int step = pol->step;
   OFA_REQUIRE(rows > 0 && V > 1 && D > 0 && step >= 0 && N > 0 && E > 0, OFA_ERR_INVALID,
               "ofa_trie_beam_topk: rows=%d V=%d D=%d step=%d N=%d E=%d", rows, V, D, step, N, E);
-  if (const int rc = beam_check_row_pass("ofa_trie_beam_topk", rows, V, K, temperature, step, ngram, tokens, tok_ld)) return rc;
+  if (const int rc = beam_check_row_pass("ofa_trie_beam_topk", rows, V, K, *pol)) return rc;
+  OFA_REQUIRE(pol->cstart < 0, OFA_ERR_INVALID, "ofa_trie_beam_topk: a constraint range [%d, %d) cannot be combined with the trie",
+              pol->cstart, pol->cend);
   OFA_REQUIRE(max_degree >= 1 && max_degree <= V && max_degree <= E, OFA_ERR_INVALID,
               "ofa_trie_beam_topk: max_degree %d outside [1, min(V, E)]", max_degree);
-  OFA_REQUIRE(ngram <= 0 || step < TB_BAN_MAX, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: n-gram bans beyond step %d", TB_BAN_MAX);
+  OFA_REQUIRE(pol->ngram <= 0 || step < TB_BAN_MAX, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: n-gram bans beyond step %d", TB_BAN_MAX);
   if (const int rc = check_proj_operands("ofa_trie_beam_topk", dtype, D, h, ld_h, W, ld_w)) return rc;
   const int S = beam_splits(V), epw = tb_edges_per_wg(max_degree, V);
   TrieTopkArgs a{h, ld_h, W, ld_w, bias, D, V, rows, K, S, cdiv(max_degree, epw), epw, node, node_edge_off, edge_token, N, E,
-                 BeamPolicy{temperature, step, min_len, max_len, pad, unk, eos, unk_penalty, ngram, tokens, tok_ld, done},
-                 beam_ws_carve(ws, rows, S, K)};
+                 *pol, beam_ws_carve(ws, rows, S, K)};
   const size_t smem = sizeof(TrieTopkScratch) + (size_t)D * dt_size(dtype) + (size_t)a.epw * 8;
   OFA_REQUIRE(smem <= TB_LDS_MAX, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_topk: D=%d with %d edges per workgroup needs %zu bytes of LDS",
               D, a.epw, smem);
@@ -317,19 +316,12 @@ extern "C" int ofa_trie_beam_topk(const void* h, int64_t ld_h, int dtype, const 
 }
 
 extern "C" int ofa_trie_beam_advance(int* node, const int* node_edge_off, const int* edge_token, const int* edge_child, int N, int E,
-                                     int bsz, int K, int step, const int64_t* tokens, int64_t tok_ld, int tok_cap,
-                                     const float* scores, int64_t score_ld, const int* ignore, const int64_t* reorder, int* done,
-                                     int* nfin, void* stream) {
-  OFA_REQUIRE(node && node_edge_off && edge_token && edge_child && tokens && scores && ignore && reorder && done && nfin,
-              OFA_ERR_INVALID, "ofa_trie_beam_advance: null pointer");
+                                     const ofa_gen_state* st, int bsz, int K, int step, void* stream) {
+  OFA_REQUIRE(node && node_edge_off && edge_token && edge_child, OFA_ERR_INVALID, "ofa_trie_beam_advance: null pointer");
   OFA_REQUIRE(bsz > 0 && step >= 0 && N > 0 && E > 0 && N < (1 << 24), OFA_ERR_INVALID, "ofa_trie_beam_advance: bsz=%d step=%d N=%d E=%d",
               bsz, step, N, E);
-  OFA_REQUIRE(K >= 1 && K <= BEAM_MAX_K, OFA_ERR_UNSUPPORTED, "ofa_trie_beam_advance: beam size %d outside [1, %d]", K, BEAM_MAX_K);
-  OFA_REQUIRE(tok_cap >= step + 1 && tok_ld >= tok_cap && score_ld > step, OFA_ERR_INVALID,
-              "ofa_trie_beam_advance: history buffers too short for step %d (tok_cap=%d tok_ld=%lld score_ld=%lld)", step, tok_cap,
-              (long long)tok_ld, (long long)score_ld);
-  TrieAdvanceArgs a{node, node_edge_off, edge_token, edge_child, N, E, bsz, K, step, tokens, tok_ld, tok_cap, scores, score_ld,
-                    ignore, reorder, done, nfin};
+  if (const int rc = beam_check_state("ofa_trie_beam_advance", st, K, step, false)) return rc;
+  TrieAdvanceArgs a{node, node_edge_off, edge_token, edge_child, N, E, bsz, K, step, *st};
   hipLaunchKernelGGL(trie_beam_advance_kernel, dim3(bsz), dim3(BEAM_THREADS), 0, (hipStream_t)stream, a);
   return check_launch("ofa_trie_beam_advance");
 }

@@ -341,12 +341,20 @@ class SequenceGenerator:
         if logits.shape[1] > self.vocab_size:
             raise ValueError(f"decoder output width {logits.shape[1]} > dictionary size {self.vocab_size}")
 
+    def _policy(self, dec, st, max_len, ngram):
+        """The row passes' keywords (kernels._gen_policy)."""
+        return dict(tokens=dec.tokens, done=st["done"], temperature=self.temperature, min_len=self.min_len, max_len=max_len,
+                    constraint_range=None if self.constraint_start is None else (self.constraint_start, self.constraint_end),
+                    pad=self.pad, unk=self.unk, eos=self.eos, unk_penalty=self.unk_penalty, ngram=ngram)
+
+    def _select(self):
+        """The sentence passes' keywords; the plain and prefix beam passes take the unk penalty as well."""
+        kw = dict(eos=self.eos, normalize=self.normalize_scores, len_penalty=self.len_penalty)
+        return kw if self.sampling is not None else dict(kw, unk=self.unk, unk_penalty=self.unk_penalty)
+
     def _row_pass(self, logits, t, dec, st, max_len, ngram, ctx):
         """The step's row pass into st["ws"]; returns the vocabulary width the sentence pass works with."""
-        K.beam_topk(logits, self.beam_size, t, st["ws"], tokens=dec.tokens, done=st["done"], temperature=self.temperature,
-                    constraint_range=None if self.constraint_start is None else (self.constraint_start, self.constraint_end),
-                    min_len=self.min_len, max_len=max_len, pad=self.pad, unk=self.unk, eos=self.eos,
-                    unk_penalty=self.unk_penalty, ngram=ngram)
+        K.beam_topk(logits, self.beam_size, t, st["ws"], **self._policy(dec, st, max_len, ngram))
         return logits.shape[1]
 
     def _advance(self, t, st, ctx):
@@ -357,20 +365,14 @@ class SequenceGenerator:
         the min_len mask and without candidates for forced rows, the fill, and the sentence pass told which rows are normalised.
         Otherwise a free step: the plain two launches, with the n-gram bans following the prefix lengths."""
         beam, V = self.beam_size, out.shape[1]
-        policy = dict(tokens=dec.tokens, done=st["done"], pad=self.pad, unk=self.unk, unk_penalty=self.unk_penalty,
-                      ngram=self.no_repeat_ngram_size)
-        K.beam_prefix_topk(out, beam, t, st["ws"], st["plen"], prefix=st["prefix"] if forced else None, glogit=st["glogit"],
-                           temperature=self.temperature, min_len=self.min_len, max_len=max_len, eos=self.eos,
-                           constraint_range=None if self.constraint_start is None else (self.constraint_start, self.constraint_end),
-                           **policy)
+        policy = self._policy(dec, st, max_len, self.no_repeat_ngram_size)
+        K.beam_prefix_topk(out, beam, t, st["ws"], st["plen"], prefix=st["prefix"] if forced else None, glogit=st["glogit"], **policy)
         st["tokens"] = dec.tokens
-        sel = dict(eos=self.eos, unk=self.unk, unk_penalty=self.unk_penalty, normalize=self.normalize_scores,
-                   len_penalty=self.len_penalty)
         if forced:
             K.beam_prefix_fill(st["ws"], out.shape[0], V, beam, t, st["prefix"], st["plen"], st["glogit"], **policy)
-            K.beam_prefix_select(st["ws"], st, beam, V, t, max_len, st["prefix"], pad=self.pad, **sel)
+            K.beam_prefix_select(st["ws"], st, beam, V, t, max_len, st["prefix"], pad=self.pad, **self._select())
         else:
-            K.beam_select(st["ws"], st, beam, V, t, max_len, **sel)
+            K.beam_select(st["ws"], st, beam, V, t, max_len, **self._select())
         dec.reorder(st["reorder"], caches_only=True)
 
     def _step_kernels(self, out, t, dec, st, max_len, ngram_step0=True, ctx=None):
@@ -380,21 +382,16 @@ class SequenceGenerator:
             return self._sample_step_kernels(out, t, dec, st, max_len, ngram)
         V = self._row_pass(out, t, dec, st, max_len, ngram, ctx)
         st["tokens"] = dec.tokens
-        K.beam_select(st["ws"], st, self.beam_size, V, t, max_len, eos=self.eos, unk=self.unk, unk_penalty=self.unk_penalty,
-                      normalize=self.normalize_scores, len_penalty=self.len_penalty)
+        K.beam_select(st["ws"], st, self.beam_size, V, t, max_len, **self._select())
         self._advance(t, st, ctx)
         dec.reorder(st["reorder"], caches_only=True)
 
     def _sample_step_kernels(self, out, t, dec, st, max_len, ngram):
         """A sampling step: every row's draw from row t of the uniforms, then the K-wide sentence pass."""
         K.sample_draw(out, self.beam_size, t, st["sample_ws"], st["uniforms"][t], topk=self.sampling.sampling_topk,
-                      topp=self.sampling.sampling_topp, tokens=dec.tokens, done=st["done"], temperature=self.temperature,
-                      constraint_range=None if self.constraint_start is None else (self.constraint_start, self.constraint_end),
-                      min_len=self.min_len, max_len=max_len, pad=self.pad, unk=self.unk, eos=self.eos,
-                      unk_penalty=self.unk_penalty, ngram=ngram)
+                      topp=self.sampling.sampling_topp, **self._policy(dec, st, max_len, ngram))
         st["tokens"] = dec.tokens
-        K.sample_select(st["sample_ws"], st, self.beam_size, t, max_len, eos=self.eos, normalize=self.normalize_scores,
-                        len_penalty=self.len_penalty)
+        K.sample_select(st["sample_ws"], st, self.beam_size, t, max_len, **self._select())
         dec.reorder(st["reorder"], caches_only=True)
 
     def _fill_uniforms(self, st, uniforms):
@@ -550,9 +547,7 @@ class TrieBeamGenerator(SequenceGenerator):
         dev, weight, bias = ctx
         if feats.dtype != weight.dtype:
             feats = feats.to(weight.dtype)
-        K.trie_beam_topk(feats, weight, bias, dev, st["node"], self.beam_size, t, st["ws"], tokens=dec.tokens, done=st["done"],
-                         temperature=self.temperature, min_len=self.min_len, max_len=max_len, pad=self.pad, unk=self.unk,
-                         eos=self.eos, unk_penalty=self.unk_penalty, ngram=ngram)
+        K.trie_beam_topk(feats, weight, bias, dev, st["node"], self.beam_size, t, st["ws"], **self._policy(dec, st, max_len, ngram))
         return weight.shape[0]
 
     def _advance(self, t, st, ctx):

@@ -1371,40 +1371,64 @@ def join_bwd(dy, dz, x, y, ga, gb, stats, p, seed, offset, offset_base, grads, f
     return dres, dx
 
 
-# ------------------------------------------------------------------ beam search (csrc/beam_search.hip)
+# ------------------------------------------------------------------ generation steps (csrc/beam_search.hip, sample.hip, trie_beam.hip)
+class _GenPolicy(ctypes.Structure):     # ofa_gen_policy
+    _fields_ = [("temperature", ctypes.c_float), ("cstart", ctypes.c_int32), ("cend", ctypes.c_int32), ("step", ctypes.c_int32),
+                ("min_len", ctypes.c_int32), ("max_len", ctypes.c_int32), ("pad", ctypes.c_int32), ("unk", ctypes.c_int32),
+                ("eos", ctypes.c_int32), ("unk_penalty", ctypes.c_float), ("ngram", ctypes.c_int32), ("tokens", ctypes.c_void_p),
+                ("tok_ld", ctypes.c_int64), ("done", ctypes.c_void_p)]
+
+
+class _GenState(ctypes.Structure):      # ofa_gen_state
+    _fields_ = [("tokens", ctypes.c_void_p), ("tok_ld", ctypes.c_int64), ("tok_cap", ctypes.c_int32), ("scores", ctypes.c_void_p),
+                ("score_ld", ctypes.c_int64), ("ignore", ctypes.c_void_p), ("done", ctypes.c_void_p), ("nfin", ctypes.c_void_p),
+                ("reorder", ctypes.c_void_p), ("fin_tok", ctypes.c_void_p), ("fin_pos", ctypes.c_void_p), ("fin_ld", ctypes.c_int64),
+                ("fin_score", ctypes.c_void_p), ("fin_len", ctypes.c_void_p), ("fin_cnt", ctypes.c_void_p)]
+
+
+def _gen_policy(step, tokens=None, done=None, temperature=1.0, constraint_range=None, min_len=1, max_len=256, pad=1, unk=3, eos=2,
+                unk_penalty=0.0, ngram=0):
+    """The row passes' ofa_gen_policy -> its address (the entry point copies it before it returns).  tokens: int64
+    [rows, >= step + 1] history (n-gram bans); done: int32 [bsz] or None."""
+    cs, ce = (-1, -1) if constraint_range is None else (int(constraint_range[0]), int(constraint_range[1]))
+    p = _GenPolicy(float(temperature), cs, ce, int(step), int(min_len), int(max_len), int(pad), int(unk), int(eos), float(unk_penalty),
+                   int(ngram), ptr(tokens), tokens.stride(0) if tokens is not None else 0, ptr(done))
+    return ctypes.byref(p)
+
+
+def _gen_state(st):
+    """The sentence passes' ofa_gen_state from the state dict `st` (generator.SequenceGenerator._buffers, plus "tokens": the
+    decoder's token history) -> (its address, bsz)."""
+    tokens, scores, fin_tok = st["tokens"], st["scores"], st["fin_tok"]
+    s = _GenState(ptr(tokens), tokens.stride(0), tokens.shape[1], ptr(scores), scores.stride(0), ptr(st["ignore"]), ptr(st["done"]),
+                  ptr(st["nfin"]), ptr(st["reorder"]), ptr(fin_tok), ptr(st["fin_pos"]), fin_tok.stride(1), ptr(st["fin_score"]),
+                  ptr(st["fin_len"]), ptr(st["fin_cnt"]))
+    return ctypes.byref(s), st["done"].numel()
+
+
 def beam_ws_bytes(rows, V, K):
     return int(lib().cdll.ofa_beam_ws_bytes(int(rows), int(V), int(K)))
 
 
-def beam_topk(logits2d, K, step, ws, tokens=None, done=None, temperature=1.0, constraint_range=None, min_len=1, max_len=256,
-              pad=1, unk=3, eos=2, unk_penalty=0.0, ngram=0):
+def beam_topk(logits2d, K, step, ws, **policy):
     """Row pass of one beam-search step: logits2d [rows, V] (row stride ld, last dim contiguous) -> each row's normaliser parts and
-    best 2K candidates in `ws` (beam_ws_bytes).  tokens: int64 [rows, >= step + 1] history (n-gram bans); done: int32 [bsz] or None."""
+    best 2K candidates in `ws` (beam_ws_bytes).  policy: _gen_policy's keywords."""
     rows, V = logits2d.shape
     if logits2d.stride(1) != 1:
         raise OfaError("beam_topk: the logits' last dimension must be contiguous")
-    cs, ce = (-1, -1) if constraint_range is None else (int(constraint_range[0]), int(constraint_range[1]))
-    tok_ld = tokens.stride(0) if tokens is not None else 0
-    lib().call("ofa_beam_topk", ptr(logits2d), logits2d.stride(0), rows, V, int(K), float(temperature), cs, ce, int(step),
-               int(min_len), int(max_len), int(pad), int(unk), int(eos), float(unk_penalty), int(ngram), ptr(tokens), tok_ld,
-               ptr(done), ptr(ws), dtype_code(logits2d), stream())
+    lib().call("ofa_beam_topk", ptr(logits2d), logits2d.stride(0), rows, V, int(K), _gen_policy(step, **policy), ptr(ws),
+               dtype_code(logits2d), stream())
 
 
 def beam_select(ws, st, K, V, step, max_len, eos=2, unk=3, unk_penalty=0.0, normalize=False, len_penalty=1.0):
-    """Sentence pass of one beam-search step over the state dict `st` (generator.SequenceGenerator._buffers, plus "tokens": the
-    decoder's token history): finalises, selects the K active candidates, gathers the histories in place and writes the reorder
-    index."""
-    tokens, scores = st["tokens"], st["scores"]
-    bsz = st["done"].numel()
-    lib().call("ofa_beam_select", ptr(ws), bsz, int(K), int(V), int(step), int(max_len), int(eos), int(unk), float(unk_penalty),
-               int(bool(normalize)), float(len_penalty), ptr(tokens), tokens.stride(0), tokens.shape[1], ptr(scores),
-               scores.stride(0), ptr(st["ignore"]), ptr(st["done"]), ptr(st["nfin"]), ptr(st["reorder"]), ptr(st["fin_tok"]),
-               ptr(st["fin_pos"]), st["fin_tok"].stride(1), ptr(st["fin_score"]), ptr(st["fin_len"]), ptr(st["fin_cnt"]),
-               stream())
+    """Sentence pass of one beam-search step over the state dict `st` (_gen_state): finalises, selects the K active candidates,
+    gathers the histories in place and writes the reorder index."""
+    state, bsz = _gen_state(st)
+    lib().call("ofa_beam_select", ptr(ws), state, bsz, int(K), int(V), int(step), int(max_len), int(eos), int(unk),
+               float(unk_penalty), int(bool(normalize)), float(len_penalty), stream())
 
 
-def beam_prefix_topk(logits2d, K, step, ws, plen, prefix=None, glogit=None, tokens=None, done=None, temperature=1.0,
-                     constraint_range=None, min_len=1, max_len=256, pad=1, unk=3, eos=2, unk_penalty=0.0, ngram=0):
+def beam_prefix_topk(logits2d, K, step, ws, plen, prefix=None, glogit=None, **policy):
     """beam_topk for a sample that carries prefix_tokens.  plen: int32 [bsz] prefix lengths (the n-gram bans skip rows with
     plen >= step + ngram - 1).  prefix int64 [bsz, > step] (a prefix step; None: a free step): no min_len mask, every row's scaled
     logit at prefix[sentence, step] goes to glogit fp32 [rows], and forced rows (prefix token != pad) get their candidates from
@@ -1415,12 +1439,8 @@ def beam_prefix_topk(logits2d, K, step, ws, plen, prefix=None, glogit=None, toke
     if plen.dtype != torch.int32 or plen.numel() * int(K) != rows or not plen.is_contiguous():
         raise OfaError("beam_prefix_topk: plen must be a contiguous int32 [rows / K]")
     _check_prefix("beam_prefix_topk", prefix, glogit, rows, K)
-    cs, ce = (-1, -1) if constraint_range is None else (int(constraint_range[0]), int(constraint_range[1]))
-    tok_ld = tokens.stride(0) if tokens is not None else 0
-    lib().call("ofa_beam_prefix_topk", ptr(logits2d), logits2d.stride(0), rows, V, int(K), float(temperature), cs, ce, int(step),
-               int(min_len), int(max_len), int(pad), int(unk), int(eos), float(unk_penalty), int(ngram), ptr(tokens), tok_ld,
-               ptr(done), ptr(prefix), prefix.stride(0) if prefix is not None else 0, ptr(plen), ptr(glogit), ptr(ws),
-               dtype_code(logits2d), stream())
+    lib().call("ofa_beam_prefix_topk", ptr(logits2d), logits2d.stride(0), rows, V, int(K), _gen_policy(step, **policy), ptr(prefix),
+               prefix.stride(0) if prefix is not None else 0, ptr(plen), ptr(glogit), ptr(ws), dtype_code(logits2d), stream())
 
 
 def _check_prefix(who, prefix, glogit, rows, K):
@@ -1432,25 +1452,20 @@ def _check_prefix(who, prefix, glogit, rows, K):
         raise OfaError(f"{who}: glogit must be a contiguous float32 [rows]")
 
 
-def beam_prefix_fill(ws, rows, V, K, step, prefix, plen, glogit, tokens=None, done=None, pad=1, unk=3, unk_penalty=0.0, ngram=0):
+def beam_prefix_fill(ws, rows, V, K, step, prefix, plen, glogit, **policy):
     """Between beam_prefix_topk and beam_prefix_select of a prefix step: the batch-wide fill value and the candidates of every
-    forced row, written to `ws` as lprobs."""
+    forced row, written to `ws` as lprobs.  policy: the row pass's; tokens, done, pad, unk, unk_penalty and ngram are read."""
     _check_prefix("beam_prefix_fill", prefix, glogit, rows, K)
-    tok_ld = tokens.stride(0) if tokens is not None else 0
-    lib().call("ofa_beam_prefix_fill", ptr(ws), int(rows), int(V), int(K), int(step), int(pad), int(unk), float(unk_penalty),
-               int(ngram), ptr(tokens), tok_ld, ptr(done), ptr(prefix), prefix.stride(0), ptr(plen), ptr(glogit), stream())
+    lib().call("ofa_beam_prefix_fill", ptr(ws), int(rows), int(V), int(K), _gen_policy(step, **policy), ptr(prefix), prefix.stride(0),
+               ptr(plen), ptr(glogit), stream())
 
 
 def beam_prefix_select(ws, st, K, V, step, max_len, prefix, pad=1, eos=2, unk=3, unk_penalty=0.0, normalize=False, len_penalty=1.0):
     """beam_select of a prefix step: the candidate values of forced rows (prefix[sentence, step] != pad) are lprobs already."""
-    tokens, scores = st["tokens"], st["scores"]
-    bsz = st["done"].numel()
+    state, bsz = _gen_state(st)
     _check_prefix("beam_prefix_select", prefix, None, bsz * int(K), K)
-    lib().call("ofa_beam_prefix_select", ptr(ws), bsz, int(K), int(V), int(step), int(max_len), int(eos), int(unk),
-               float(unk_penalty), int(bool(normalize)), float(len_penalty), ptr(tokens), tokens.stride(0), tokens.shape[1],
-               ptr(scores), scores.stride(0), ptr(st["ignore"]), ptr(st["done"]), ptr(st["nfin"]), ptr(st["reorder"]),
-               ptr(st["fin_tok"]), ptr(st["fin_pos"]), st["fin_tok"].stride(1), ptr(st["fin_score"]), ptr(st["fin_len"]),
-               ptr(st["fin_cnt"]), ptr(prefix), prefix.stride(0), int(pad), stream())
+    lib().call("ofa_beam_prefix_select", ptr(ws), state, bsz, int(K), int(V), int(step), int(max_len), int(eos), int(unk),
+               float(unk_penalty), int(bool(normalize)), float(len_penalty), ptr(prefix), prefix.stride(0), int(pad), stream())
 
 
 # ------------------------------------------------------------------ closed-set scoring (csrc/closed_set_score.hip)
@@ -1509,32 +1524,25 @@ def sample_ws_bytes(rows, V, K):
     return int(lib().cdll.ofa_sample_ws_bytes(int(rows), int(V), int(K)))
 
 
-def sample_draw(logits2d, K, step, ws, uniforms, topk=-1, topp=-1.0, tokens=None, done=None, temperature=1.0, constraint_range=None,
-                min_len=1, max_len=256, pad=1, unk=3, eos=2, unk_penalty=0.0, ngram=0):
-    """Row pass of one sampling step: logits2d [rows, V] as beam_topk takes them, uniforms fp32 [rows] (this step's number in
-    [0, 1) per row) -> every row's drawn (lprob, token) in `ws` (sample_ws_bytes).  topp > 0 wins over topk > 0; neither: the
-    whole vocabulary.  The draw is the inverse CDF of the kept weights in vocabulary order."""
+def sample_draw(logits2d, K, step, ws, uniforms, topk=-1, topp=-1.0, **policy):
+    """Row pass of one sampling step: logits2d [rows, V] and the policy as beam_topk takes them, uniforms fp32 [rows] (this step's
+    number in [0, 1) per row) -> every row's drawn (lprob, token) in `ws` (sample_ws_bytes).  topp > 0 wins over topk > 0; neither:
+    the whole vocabulary.  The draw is the inverse CDF of the kept weights in vocabulary order."""
     rows, V = logits2d.shape
     if logits2d.stride(1) != 1:
         raise OfaError("sample_draw: the logits' last dimension must be contiguous")
     if uniforms.dtype != torch.float32 or uniforms.numel() != rows or not uniforms.is_contiguous():
         raise OfaError("sample_draw: uniforms must be a contiguous float32 [rows]")
-    cs, ce = (-1, -1) if constraint_range is None else (int(constraint_range[0]), int(constraint_range[1]))
-    tok_ld = tokens.stride(0) if tokens is not None else 0
-    lib().call("ofa_sample_draw", ptr(logits2d), logits2d.stride(0), rows, V, int(K), float(temperature), cs, ce, int(step),
-               int(min_len), int(max_len), int(pad), int(unk), int(eos), float(unk_penalty), int(ngram), ptr(tokens), tok_ld,
-               ptr(done), int(topk), float(topp), ptr(uniforms), ptr(ws), dtype_code(logits2d), stream())
+    lib().call("ofa_sample_draw", ptr(logits2d), logits2d.stride(0), rows, V, int(K), _gen_policy(step, **policy), int(topk),
+               float(topp), ptr(uniforms), ptr(ws), dtype_code(logits2d), stream())
 
 
 def sample_select(ws, st, K, step, max_len, eos=2, normalize=False, len_penalty=1.0):
     """Sentence pass of one sampling step over the state dict `st` (as beam_select): finalises the EOS draws, compacts the slots
     that go on to the front, gathers the histories in place and writes the reorder index."""
-    tokens, scores = st["tokens"], st["scores"]
-    bsz = st["done"].numel()
-    lib().call("ofa_sample_select", ptr(ws), bsz, int(K), int(step), int(max_len), int(eos), int(bool(normalize)),
-               float(len_penalty), ptr(tokens), tokens.stride(0), tokens.shape[1], ptr(scores), scores.stride(0), ptr(st["ignore"]),
-               ptr(st["done"]), ptr(st["nfin"]), ptr(st["reorder"]), ptr(st["fin_tok"]), ptr(st["fin_pos"]),
-               st["fin_tok"].stride(1), ptr(st["fin_score"]), ptr(st["fin_len"]), ptr(st["fin_cnt"]), stream())
+    state, bsz = _gen_state(st)
+    lib().call("ofa_sample_select", ptr(ws), state, bsz, int(K), int(step), int(max_len), int(eos), int(bool(normalize)),
+               float(len_penalty), stream())
 
 
 # ------------------------------------------------------------------ trie-constrained beam search (csrc/trie_beam.hip)
@@ -1546,26 +1554,23 @@ def trie_beam_splits(max_degree, V):
     return n
 
 
-def trie_beam_topk(h2d, weight, bias, plan, node, K, step, ws, tokens=None, done=None, temperature=1.0, min_len=1, max_len=256,
-                   pad=1, unk=3, eos=2, unk_penalty=0.0, ngram=0):
+def trie_beam_topk(h2d, weight, bias, plan, node, K, step, ws, **policy):
     """Row pass of one trie-constrained beam-search step, in place of beam_topk: h2d [rows, D] last-position features, weight
     [V, D] / bias the output projection, `plan` the device arrays of a traverse.TraversePlan, node int32 [rows] the trie node of
-    every row (-1: dead).  Writes `ws` (beam_ws_bytes(rows, V, K)) for beam_select of the same step."""
+    every row (-1: dead); policy: _gen_policy's keywords but constraint_range (the trie is the constraint).  Writes `ws`
+    (beam_ws_bytes(rows, V, K)) for beam_select of the same step."""
     _closed_set_proj(h2d, weight, bias)
     rows = h2d.shape[0]
     if node.dtype != torch.int32 or node.numel() != rows or not node.is_contiguous():
         raise OfaError("trie_beam_topk: node must be a contiguous int32 [rows]")
-    tok_ld = tokens.stride(0) if tokens is not None else 0
     lib().call("ofa_trie_beam_topk", ptr(h2d), h2d.stride(0), dtype_code(h2d), ptr(weight), weight.stride(0), ptr(bias),
                h2d.shape[1], weight.shape[0], rows, int(K), ptr(node), ptr(plan["node_edge_off"]), ptr(plan["edge_token"]),
-               plan["N"], plan["E"], plan["max_degree"], float(temperature), int(step), int(min_len), int(max_len), int(pad),
-               int(unk), int(eos), float(unk_penalty), int(ngram), ptr(tokens), tok_ld, ptr(done), ptr(ws), stream())
+               plan["N"], plan["E"], plan["max_degree"], _gen_policy(step, **policy), ptr(ws), stream())
 
 
 def trie_beam_advance(plan, node, st, K, step):
     """After beam_select: every row's trie node follows its parent (st["reorder"]) through the token chosen at `step`; sentences
     with nothing left to finalise are marked done.  `st`: the state dict beam_select works on."""
-    tokens, scores = st["tokens"], st["scores"]
+    state, bsz = _gen_state(st)
     lib().call("ofa_trie_beam_advance", ptr(node), ptr(plan["node_edge_off"]), ptr(plan["edge_token"]), ptr(plan["edge_child"]),
-               plan["N"], plan["E"], st["done"].numel(), int(K), int(step), ptr(tokens), tokens.stride(0), tokens.shape[1],
-               ptr(scores), scores.stride(0), ptr(st["ignore"]), ptr(st["reorder"]), ptr(st["done"]), ptr(st["nfin"]), stream())
+               plan["N"], plan["E"], state, bsz, int(K), int(step), stream())

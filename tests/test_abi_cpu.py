@@ -103,6 +103,20 @@ def test_attn_call_mirrors_the_c_struct():
     assert ctypes.sizeof(K._AttnCall) == int(re.search(r"static_assert\(sizeof\(ofa_attn_call\) == (\d+)", src).group(1)) == 280
 
 
+def test_generation_descriptors_mirror_the_c_structs():
+    """kernels._GenPolicy / _GenState are as large as the static_asserts in csrc/beam_search.hip say ofa_gen_policy / ofa_gen_state
+    are, and carry the header's fields in the header's order."""
+    import re
+    from ofasys_amd import kernels as K
+    src = open(os.path.join(os.path.dirname(L.LIB_PATH), "csrc", "beam_search.hip")).read()
+    header = re.sub(r"/\*.*?\*/", " ", open(L.HEADER).read(), flags=re.S)
+    for mirror, name, size in ((K._GenPolicy, "ofa_gen_policy", 72), (K._GenState, "ofa_gen_state", 120)):
+        assert ctypes.sizeof(mirror) == int(re.search(r"static_assert\(sizeof\(%s\) == (\d+)" % name, src).group(1)) == size
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), header, flags=re.S).group(1)
+        assert re.findall(r"(\w+)\s*[,;]", body) == [f[0] for f in mirror._fields_], name
+    assert len(K._GenPolicy._fields_) == 14 and len(K._GenState._fields_) == 15
+
+
 _P = 4096                     # a fake, 16-byte aligned device address: every descriptor below is refused before any launch
 _SEG = dict(seg=_P, rows_q=64, rows_k=64)
 _DSUM = dict(bias=_P, dbias=_P, ws=_P)

@@ -35,8 +35,10 @@ def test_header_declares_and_library_exports_sampling_entry_points():
 
 def _draw(h, rows=10, V=204, K=5, temperature=1.0, step=0, ngram=0, tokens=None, tok_ld=0, topp=-1.0, logits=0x1000, ld=None):
     """ofa_sample_draw with made-up addresses: refused calls return before anything is launched or read."""
-    return h.cdll.ofa_sample_draw(logits, V if ld is None else ld, rows, V, K, temperature, -1, -1, step, 1, 10, 1, 3, 2, 0.0, ngram,
-                                  tokens, tok_ld, None, -1, topp, 0x2000, 0x3000, 0, None)
+    from ofasys_amd import kernels as Kn
+    pol = Kn._GenPolicy(temperature=temperature, cstart=-1, cend=-1, step=step, min_len=1, max_len=10, pad=1, unk=3, eos=2,
+                        unk_penalty=0.0, ngram=ngram, tokens=tokens, tok_ld=tok_ld, done=None)
+    return h.cdll.ofa_sample_draw(logits, V if ld is None else ld, rows, V, K, ctypes.byref(pol), -1, topp, 0x2000, 0x3000, 0, None)
 
 
 def test_sampling_entry_points_validate_before_any_launch():
@@ -53,12 +55,22 @@ def test_sampling_entry_points_validate_before_any_launch():
         rc = _draw(h, **kwargs)
         assert rc == code and what in h.cdll.ofa_last_error(), (kwargs, rc, h.cdll.ofa_last_error())
     # the sentence pass: K outside [1, 16], a null buffer, histories too short for the step
+    from ofasys_amd import kernels as Kn
     p = 0x1000
-    sel = lambda K=3, step=2, cap=8, ws=p: h.cdll.ofa_sample_select(ws, 2, K, step, 10, 2, 0, 1.0, p, cap, cap, p, cap, p, p, p, p, p,   # noqa: E731
-                                                                    p, cap, p, p, p, None)
-    assert sel(K=17) == UNSUPPORTED and sel(K=0) == UNSUPPORTED
-    assert sel(ws=None) == INVALID and sel(step=8, cap=8) == INVALID and sel(step=11) == INVALID
 
+    def sel(K=3, step=2, cap=8, ws=p, **fields):
+        st = Kn._GenState(p, cap, cap, p, cap, p, p, p, p, p, p, cap, p, p, p)
+        for name, value in fields.items():
+            setattr(st, name, value)
+        return h.cdll.ofa_sample_select(ws, ctypes.byref(st), 2, K, step, 10, 2, 0, 1.0, None)
+
+    assert sel(K=17) == UNSUPPORTED and b"beam size 17 outside" in h.cdll.ofa_last_error()
+    assert sel(K=0) == UNSUPPORTED
+    assert sel(ws=None) == INVALID and b"null pointer" in h.cdll.ofa_last_error()
+    assert sel(fin_cnt=None) == INVALID and b"null pointer" in h.cdll.ofa_last_error()
+    assert sel(step=8, cap=8) == INVALID and b"history buffers too short for step 8" in h.cdll.ofa_last_error()
+    assert sel(step=11) == INVALID
+    assert h.cdll.ofa_sample_select(p, None, 2, 3, 2, 10, 2, 0, 1.0, None) == INVALID and b"null pointer" in h.cdll.ofa_last_error()
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 def test_sampling_kernels_compile_without_spills(tmp_path):

@@ -275,6 +275,63 @@ def test_sentence_pass_matches_restated_bookkeeping(normalize):
     assert want["fin_cnt"].tolist() == [3, 3, 2, 3] and bool(want["ignore"][0].any())
 
 
+@pytest.mark.gpu
+def test_beam_and_sampling_sentence_passes_share_their_bookkeeping():
+    """The same K (score, beam, token) candidates through sample_select (scripted draws) and through beam_select (a hand-built
+    workspace, V = 8: one normaliser part per row) leave the same state, bit for bit: bsz 2, K 3, max_len 3, steps 0 .. 3.
+    Step 0 reads beam 0 only (the beam workspace lists the K candidates in row 0's list, sampling gives every slot parent 0);
+    sentence 0 finalises an EOS at step 0, so one of its slots is ignored from step 1 on -- where it draws an EOS that must not be
+    finalised -- and at step 2 its first slot ends, so the reorder is no identity; sentence 1 draws an EOS at -inf at step 1, which
+    is not finalised and goes on at -inf; step 3 = max_len finishes both.  Every candidate list descends in slot order, as the
+    beam pass's merge sorts it; the values are multiples of 1/8 and every row's normaliser is exactly 2 (max 2, sum 1), so both
+    routes hold identical floats before the shared bookkeeping starts."""
+    from ofasys_amd import kernels as Kn
+    K, bsz, V, max_len, E, NI = 3, 2, 8, 3, EOS, -math.inf
+    rows, K2, LSE = bsz * K, 2 * K, 2.0
+    script = [   # per step: (tokens, lprobs) [bsz][K] in the slot order of that step
+        ([[5, E, 6], [7, 4, 6]], [[-0.25, -0.5, -1.0], [-0.125, -0.375, -0.75]]),
+        ([[4, 5, E], [5, 6, E]], [[-0.25, -0.5, -2.0], [-0.25, -0.25, NI]]),
+        ([[E, 7, 4], [4, 5, 6]], [[-0.25, -0.25, -0.5], [-0.5, -0.5, -0.5]]),
+        ([[E, E, E], [E, E, E]], [[-0.125, -1.5, -0.5], [-0.125, -0.125, -0.125]]),
+    ]
+    cfg = dict(max_len=max_len, normalize=True, len_penalty=1.3)
+    want = sc.empty_state(bsz, K, max_len + 2)
+    samp = {k: v.to(DEV) for k, v in want.items()}
+    beam = {k: v.to(DEV) for k, v in want.items()}
+    assert Kn.beam_ws_bytes(rows, V, K) == rows * (2 + 2 * K2) * 4
+    for step, (toks, lps) in enumerate(script):
+        tok, lp = torch.tensor(toks).view(-1), torch.tensor(lps).view(-1)
+        cum = lp + want["scores"][:, step - 1] if step > 0 else lp
+        assert bool((cum.view(bsz, K)[:, :-1] >= cum.view(bsz, K)[:, 1:]).all()), step      # the order the beam merge would give
+        # ---- sampling: the draws as sample_draw leaves them
+        sws = torch.cat([lp, tok.to(torch.int32).view(torch.float32)]).to(DEV)
+        Kn.sample_select(sws, samp, K, step, max_len, eos=E, normalize=True, len_penalty=cfg["len_penalty"])
+        # ---- beam: stats [rows, 1, 2], values [rows, 1, 2K], tokens [rows, 1, 2K] (-1: none); value = lprob + normaliser
+        stats = torch.tensor([LSE, 1.0]).repeat(rows, 1)
+        cval, ctok = torch.full((rows, K2), NI), torch.full((rows, K2), -1, dtype=torch.int32)
+        if step == 0:                                          # one row is read: its list holds the sentence's K candidates
+            cval.view(bsz, K, K2)[:, 0, :K], ctok.view(bsz, K, K2)[:, 0, :K] = (lp + LSE).view(bsz, K), tok.to(torch.int32).view(bsz, K)
+        else:                                                  # one candidate per row: beam j continues as slot j
+            cval[:, 0], ctok[:, 0] = lp + LSE, tok.to(torch.int32)
+        bws = torch.cat([stats.view(-1), cval.view(-1), ctok.view(-1).view(torch.float32)]).to(DEV)
+        Kn.beam_select(bws, beam, K, V, step, max_len, eos=E, unk=sc.UNK, unk_penalty=0.0, normalize=True, len_penalty=cfg["len_penalty"])
+        torch.cuda.synchronize()
+        for name in want:
+            a, b = samp[name].cpu(), beam[name].cpu()
+            same = torch.equal(a.view(torch.int32), b.view(torch.int32)) if a.dtype == torch.float32 else torch.equal(a, b)
+            assert same, (step, name, a, b)
+        want = sc.select_step(want, tok, lp, K, step, cfg)
+        compare_state({k: v.cpu() for k, v in samp.items()}, want, step)
+        if step == 0:
+            assert want["ignore"].tolist() == [[0, 0, 1], [0, 0, 0]] and want["fin_cnt"].tolist() == [1, 0]
+            assert want["reorder"].tolist() == [0, 0, 0, 3, 3, 3]                            # every slot continues beam 0
+        if step == 1:                                          # neither the ignored slot's EOS nor the EOS at -inf is finalised
+            assert want["fin_cnt"].tolist() == [1, 0] and want["scores"][5, 1] == NI and want["tokens"][5, 2] == E
+        if step == 2:
+            assert want["reorder"].tolist() == [1, 0, 2, 3, 4, 5] and want["ignore"].tolist() == [[0, 1, 1], [0, 0, 0]]
+    assert want["done"].tolist() == [1, 1] and int(want["nfin"]) == 2 and want["fin_cnt"].tolist() == [3, 2]
+
+
 # ------------------------------------------------------------------------------------------------ generate() against the reference
 def _model(dtype=torch.float32):
     model, d = build_model(CASES["tiny_text"], DEV, dtype)

@@ -102,18 +102,27 @@ def test_status_codes_before_any_launch():
     never dereferenced)."""
     from ofasys_amd import lib as L
     h = L.lib()
+    import ctypes
+    from ofasys_amd import kernels as Kn
     p = 4096                                                                        # a 16-byte aligned stand-in for a pointer
 
+    def split(kw, struct, defaults):
+        """A descriptor from its defaults and the keywords that name its fields; the other keywords are the call's own."""
+        fields = dict(defaults, **{k: kw.pop(k) for k in list(kw) if k in defaults})
+        return struct(**fields)
+
     def topk(**kw):
+        pol = split(kw, Kn._GenPolicy, dict(temperature=1.0, cstart=-1, cend=-1, step=0, min_len=1, max_len=10, pad=1, unk=3, eos=2,
+                                            unk_penalty=0.0, ngram=0, tokens=None, tok_ld=0, done=None))
         a = dict(h=p, ld_h=64, dtype=L.F32, W=p, ld_w=64, bias=None, D=64, V=204, rows=10, K=5, node=p, off=p, tok=p, N=7, E=20,
-                 max_degree=6, temperature=1.0, step=0, min_len=1, max_len=10, pad=1, unk=3, eos=2, unk_penalty=0.0, ngram=0,
-                 tokens=None, tok_ld=0, done=None, ws=p, stream=None)
+                 max_degree=6, pol=ctypes.byref(pol), ws=p, stream=None)
         a.update(kw)
         h.call("ofa_trie_beam_topk", *a.values())
 
     def advance(**kw):
-        a = dict(node=p, off=p, tok=p, child=p, N=7, E=20, bsz=2, K=5, step=0, tokens=p, tok_ld=11, tok_cap=11, scores=p,
-                 score_ld=11, ignore=p, reorder=p, done=p, nfin=p, stream=None)
+        # the fin_* fields stay NULL: the advance pass does not read them
+        st = split(kw, Kn._GenState, dict(tokens=p, tok_ld=11, tok_cap=11, scores=p, score_ld=11, ignore=p, reorder=p, done=p, nfin=p))
+        a = dict(node=p, off=p, tok=p, child=p, N=7, E=20, st=ctypes.byref(st), bsz=2, K=5, step=0, stream=None)
         a.update(kw)
         h.call("ofa_trie_beam_advance", *a.values())
 
@@ -124,10 +133,12 @@ def test_status_codes_before_any_launch():
                        (dict(ngram=2), "token history"), (dict(ngram=2, tokens=p, tok_ld=400, step=300), "n-gram bans beyond"),
                        (dict(D=66), "16-byte"), (dict(ld_w=60), "16-byte"), (dict(h=p + 4), "16-byte"),
                        (dict(dtype=L.BF16, D=68, ld_h=68, ld_w=68), "16-byte"), (dict(D=16384, ld_h=16384, ld_w=16384), "LDS"),
-                       (dict(N=0), "N=0"), (dict(step=-1), "step=-1")):
+                       (dict(N=0), "N=0"), (dict(step=-1), "step=-1"), (dict(pol=None), "null pointer"),
+                       (dict(cstart=4, cend=100), "status 1.*constraint range")):     # the trie is the only constraint
         with pytest.raises(L.OfaError, match=match):
             topk(**bad)
-    for bad, match in ((dict(child=None), "null pointer"), (dict(nfin=None), "null pointer"), (dict(K=17), "beam size"),
+    for bad, match in ((dict(child=None), "null pointer"), (dict(nfin=None), "null pointer"), (dict(st=None), "null pointer"),
+                       (dict(K=17), "beam size"),
                        (dict(bsz=0), "bsz=0"), (dict(step=11), "too short"), (dict(score_ld=0), "too short"),
                        (dict(tok_ld=5), "too short"), (dict(N=1 << 24), "N=")):
         with pytest.raises(L.OfaError, match=match):
