@@ -792,6 +792,23 @@ int ofa_sample_draw(const void* logits, int64_t ld, int rows, int V, int K, cons
 int ofa_sample_select(const void* ws, const ofa_gen_state* st, int bsz, int K, int step, int max_len, int eos, int normalize,
                       float len_penalty, void* stream);
 
+/* ---- diverse decoding (csrc/diverse_beam.hip): DiverseBeamSearch.step (utils/search.py:549-593) and DiverseSiblingsSearch.step
+ * (:738-787) as sentence passes that replace ofa_beam_select after ofa_beam_topk of the same step: same ws, same arguments, same
+ * bookkeeping on `st`, one workgroup per sentence.  Both first reduce every row to its own top 2K by lprob, which needs
+ * parts(V) * 2K <= 512.  Ties: value descending, then beam * V + token ascending.  The rewritten scores are the cumulative scores
+ * from then on, so hypothesis scores and positional scores contain the penalties, as the reference's do.
+ * ofa_diverse_group_select: `groups` G divides K (1 <= G <= K); group g owns beams g, g + G, ... and takes, after the groups before
+ * it, its top min(2 K/G, rows * V - 1) of (lprob - strength * count[token]) + cumulative, count = the tokens those groups took
+ * (duplicates and -inf picks included); at step 0 it reads row g alone.  The list handed to the bookkeeping is the reference's
+ * interleave, rank j of group g at j * G + g.  strength must be finite and >= 0: a penalised top 2 K/G then lies inside the row's
+ * unpenalised top 2K, which a reward would leave.
+ * ofa_diverse_sibling_select: step 0 is ofa_beam_select's; afterwards the top 2K of ((lprob + cumulative) - (rank + 1) * rate) over
+ * every beam's own top 2K, rank counted from 0 inside the beam.  Needs V > 2K; rate finite. */
+int ofa_diverse_group_select(const void* ws, const ofa_gen_state* st, int bsz, int K, int V, int step, int max_len, int eos, int unk,
+                             float unk_penalty, int normalize, float len_penalty, int groups, float strength, void* stream);
+int ofa_diverse_sibling_select(const void* ws, const ofa_gen_state* st, int bsz, int K, int V, int step, int max_len, int eos, int unk,
+                               float unk_penalty, int normalize, float len_penalty, float rate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 // What the beam-search row passes (beam_search.hip: ofa_beam_topk over [rows, V] logits; trie_beam.hip: ofa_trie_beam_topk over
-// the child edges of a trie node; sample.hip: ofa_sample_draw) and the sentence passes (ofa_beam_select, ofa_sample_select) have
-// in common, defined once: the limits, the workspace layout the row passes write and the sentence pass reads, the checks of the
+// the child edges of a trie node; sample.hip: ofa_sample_draw) and the sentence passes (ofa_beam_select, ofa_sample_select,
+// diverse_beam.hip: ofa_diverse_group_select / ofa_diverse_sibling_select) have in common, defined once: the limits, the workspace layout the row passes write and the sentence pass reads, the checks of the
 // two descriptors of the C ABI (ofa_gen_policy, ofa_gen_state), the reference's post-normaliser masks in its order, the tie rules
 // (value descending, token ascending, NaN = empty), the candidate-list machinery around the per-wave selection loops, which stay
 // with their kernels (one selects over 16 register-held values per lane, the other over an LDS array strided by thread), and the

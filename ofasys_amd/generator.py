@@ -29,6 +29,10 @@ advances every row's node.
 `SequenceGenerator(search_strategy=Sampling(...))` samples instead (utils/search.py:596-715): a sentence's K rows are K independent
 samples, drawn by csrc/sample.hip from uniform numbers held in `st["uniforms"]` -- supplied by the caller (`generate(uniforms=U)`) or
 filled once per generate, outside the step graphs, from a seeded torch.Generator.
+
+`SequenceGenerator(search_strategy=DiverseBeamSearch(...) | DiverseSiblingsSearch(...))` decodes diversely (utils/search.py:532-593,
+718-787): the row pass, the decoder step and the cache reorder are the plain ones, and the sentence pass is csrc/diverse_beam.hip's,
+which works on the candidates the row pass already lists.
 """
 import math
 from dataclasses import dataclass
@@ -204,11 +208,37 @@ class Sampling:
             raise ValueError(f"Sampling: sampling_topp={sampling_topp} is above 1")
 
 
+class DiverseBeamSearch:
+    """The reference's diverse beam search (utils/search.py:532-547; Hamming diversity between `num_groups` groups of beams) as a
+    plain options holder.  The step is csrc/diverse_beam.hip's ofa_diverse_group_select, which needs a strength >= 0."""
+
+    def __init__(self, tgt_dict, num_groups, diversity_strength):
+        self.pad, self.unk, self.eos, self.vocab_size = tgt_dict.pad(), tgt_dict.unk(), tgt_dict.eos(), len(tgt_dict)
+        self.num_groups, self.diversity_strength = int(num_groups), float(diversity_strength)
+        if self.num_groups < 1:
+            raise ValueError(f"DiverseBeamSearch: num_groups={num_groups} is below 1")
+        if not (0.0 <= self.diversity_strength < math.inf):
+            raise ValueError(f"DiverseBeamSearch: diversity_strength={diversity_strength} must be finite and >= 0 (a negative "
+                             "strength rewards repeated tokens; the step then needs more than each row's top 2K candidates)")
+
+
+class DiverseSiblingsSearch:
+    """The reference's diverse-siblings search (utils/search.py:718-736) as a plain options holder; rate 0 is plain beam search.
+    The step is csrc/diverse_beam.hip's ofa_diverse_sibling_select."""
+
+    def __init__(self, tgt_dict, diversity_rate):
+        self.pad, self.unk, self.eos, self.vocab_size = tgt_dict.pad(), tgt_dict.unk(), tgt_dict.eos(), len(tgt_dict)
+        self.diversity_rate = float(diversity_rate)
+        if not math.isfinite(self.diversity_rate):
+            raise ValueError(f"DiverseSiblingsSearch: diversity_rate={diversity_rate} is not finite")
+
+
 class SequenceGenerator:
     """Beam search with the reference's constructor and defaults (generator/sequence_generator.py:66-159), or sampling with
     `search_strategy=Sampling(...)` (`seed`: of the uniform numbers `generate` draws when it is given none; None: taken from
-    torch's global generator).  Unsupported options of the reference raise NotImplementedError: other search strategies, an LM,
-    a constraint trie, match_source_len, lexical constraints, a prefix that holds <eos>, and any prefix under sampling."""
+    torch's global generator), or diverse decoding with `search_strategy=DiverseBeamSearch(...)` / `DiverseSiblingsSearch(...)`.
+    Unsupported options of the reference raise NotImplementedError: other search strategies, an LM, a constraint trie,
+    match_source_len, lexical constraints, a prefix that holds <eos>, and any prefix under sampling or diverse decoding."""
 
     MAX_BEAM = 16
 
@@ -218,10 +248,12 @@ class SequenceGenerator:
                  no_repeat_ngram_size: int = 0, search_strategy=None, lm_model=None, lm_weight: float = 1.0,
                  constraint_trie=None, constraint_range: Optional[str] = None, use_graph: bool = True, seed: Optional[int] = None,
                  **unused_kwargs):
-        if search_strategy is not None and not isinstance(search_strategy, Sampling):
-            raise NotImplementedError("SequenceGenerator: only plain beam search and sampling are implemented (search_strategy must "
-                                      "be None or a Sampling; diverse beam and constrained search are not)")
-        self.sampling: Optional[Sampling] = search_strategy
+        if search_strategy is not None and not isinstance(search_strategy, (Sampling, DiverseBeamSearch, DiverseSiblingsSearch)):
+            raise NotImplementedError("SequenceGenerator: only plain beam search, sampling and diverse decoding are implemented "
+                                      "(search_strategy must be None, a Sampling, a DiverseBeamSearch or a DiverseSiblingsSearch; "
+                                      "constrained search is not)")
+        self.sampling: Optional[Sampling] = search_strategy if isinstance(search_strategy, Sampling) else None
+        self.diverse = search_strategy if isinstance(search_strategy, (DiverseBeamSearch, DiverseSiblingsSearch)) else None
         self.seed, self._rng = seed, None
         if lm_model is not None:
             raise NotImplementedError("SequenceGenerator: LM fusion (lm_model) is not implemented")
@@ -240,6 +272,11 @@ class SequenceGenerator:
         if return_n_best == -1:
             return_n_best = self.beam_size
         self.return_n_best = min(self.beam_size, return_n_best)
+        if isinstance(self.diverse, DiverseBeamSearch) and self.beam_size % self.diverse.num_groups != 0:
+            raise ValueError("DiverseBeamSearch requires --beam to be divisible by the number of groups")
+        if isinstance(self.diverse, DiverseSiblingsSearch) and self.vocab_size <= 2 * self.beam_size:
+            raise ValueError(f"DiverseSiblingsSearch: every beam lists its own top 2 * beam = {2 * self.beam_size} tokens, the "
+                             f"dictionary has {self.vocab_size}")
         self.max_len_a, self.max_len_b, self.max_len, self.min_len = max_len_a, max_len_b, max_len, min_len
         self.normalize_scores, self.len_penalty, self.unk_penalty = normalize_scores, len_penalty, unk_penalty
         self.temperature, self.no_repeat_ngram_size = temperature, no_repeat_ngram_size
@@ -280,6 +317,9 @@ class SequenceGenerator:
         if self.sampling is not None:
             raise NotImplementedError("SequenceGenerator: prefix_tokens under sampling are not implemented (got a prefix of "
                                       f"{prefix.size(1)} columns)")
+        if self.diverse is not None:
+            raise NotImplementedError("SequenceGenerator: prefix_tokens under a diverse search strategy are not implemented (got a "
+                                      f"prefix of {prefix.size(1)} columns)")
         prefix = prefix.long()
         keep = prefix.ne(self.pad)
         plen = keep.sum(1)
@@ -357,6 +397,16 @@ class SequenceGenerator:
         K.beam_topk(logits, self.beam_size, t, st["ws"], **self._policy(dec, st, max_len, ngram))
         return logits.shape[1]
 
+    def _sentence_pass(self, t, st, V, max_len):
+        """The step's sentence pass over st["ws"]: plain beam search, or the diverse strategy's over the same candidates."""
+        if isinstance(self.diverse, DiverseBeamSearch):
+            K.diverse_group_select(st["ws"], st, self.beam_size, V, t, max_len, self.diverse.num_groups,
+                                   self.diverse.diversity_strength, **self._select())
+        elif isinstance(self.diverse, DiverseSiblingsSearch):
+            K.diverse_sibling_select(st["ws"], st, self.beam_size, V, t, max_len, self.diverse.diversity_rate, **self._select())
+        else:
+            K.beam_select(st["ws"], st, self.beam_size, V, t, max_len, **self._select())
+
     def _advance(self, t, st, ctx):
         """Device work between the sentence pass and the cache reorder."""
 
@@ -382,7 +432,7 @@ class SequenceGenerator:
             return self._sample_step_kernels(out, t, dec, st, max_len, ngram)
         V = self._row_pass(out, t, dec, st, max_len, ngram, ctx)
         st["tokens"] = dec.tokens
-        K.beam_select(st["ws"], st, self.beam_size, V, t, max_len, **self._select())
+        self._sentence_pass(t, st, V, max_len)
         self._advance(t, st, ctx)
         dec.reorder(st["reorder"], caches_only=True)
 
@@ -412,6 +462,9 @@ class SequenceGenerator:
     @torch.no_grad()
     def generate(self, model, sample, uniforms=None, **kwargs):
         """uniforms (sampling only): fp32 [steps + 1, rows], row t the numbers of step t -- the draws are a function of them."""
+        if uniforms is not None and self.diverse is not None:
+            raise NotImplementedError("generate: uniforms together with a diverse search strategy are not implemented (they are "
+                                      "read by sampling only)")
         if uniforms is not None and self.sampling is None:
             raise ValueError("generate: uniforms are read by sampling only (search_strategy=Sampling(...))")
         ngram_step0 = self.check_sample(sample, **kwargs)
@@ -496,6 +549,9 @@ class TrieBeamGenerator(SequenceGenerator):
     def __init__(self, tgt_dict, plan, *args, **kwargs):
         if kwargs.get("constraint_range") is not None:
             raise ValueError("TrieBeamGenerator: constraint_range cannot be combined with a constraint trie")
+        if isinstance(kwargs.get("search_strategy"), (DiverseBeamSearch, DiverseSiblingsSearch)):
+            raise NotImplementedError("TrieBeamGenerator: a diverse search strategy over the answer trie is not implemented "
+                                      "(search_strategy must be None)")
         if kwargs.get("search_strategy") is not None:
             raise NotImplementedError("TrieBeamGenerator: only beam search is implemented (search_strategy must be None)")
         super().__init__(tgt_dict, *args, **kwargs)

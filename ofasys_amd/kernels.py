@@ -1545,6 +1545,24 @@ def sample_select(ws, st, K, step, max_len, eos=2, normalize=False, len_penalty=
                float(len_penalty), stream())
 
 
+# ------------------------------------------------------------------ diverse decoding (csrc/diverse_beam.hip)
+def diverse_group_select(ws, st, K, V, step, max_len, groups, strength, eos=2, unk=3, unk_penalty=0.0, normalize=False,
+                         len_penalty=1.0):
+    """Sentence pass of one diverse-beam-search step, in place of beam_select after beam_topk: `groups` groups of K / groups beams
+    (group g owns beams g, g + groups, ...), each penalised by strength (>= 0) times how often the groups before it took a token."""
+    state, bsz = _gen_state(st)
+    lib().call("ofa_diverse_group_select", ptr(ws), state, bsz, int(K), int(V), int(step), int(max_len), int(eos), int(unk),
+               float(unk_penalty), int(bool(normalize)), float(len_penalty), int(groups), float(strength), stream())
+
+
+def diverse_sibling_select(ws, st, K, V, step, max_len, rate, eos=2, unk=3, unk_penalty=0.0, normalize=False, len_penalty=1.0):
+    """Sentence pass of one diverse-siblings step, in place of beam_select after beam_topk: after step 0 every beam's own top 2K
+    continuations lose (rank + 1) * rate before the sentence's top 2K are taken."""
+    state, bsz = _gen_state(st)
+    lib().call("ofa_diverse_sibling_select", ptr(ws), state, bsz, int(K), int(V), int(step), int(max_len), int(eos), int(unk),
+               float(unk_penalty), int(bool(normalize)), float(len_penalty), float(rate), stream())
+
+
 # ------------------------------------------------------------------ trie-constrained beam search (csrc/trie_beam.hip)
 def trie_beam_splits(max_degree, V):
     """Workgroups per row of trie_beam_topk for a plan (the grid's x extent)."""

@@ -141,6 +141,7 @@ class Task:
         self._generator = None
         self._scst_generator = None
         self._sampling_gens: Dict[Any, Any] = {}
+        self._diverse_gens: Dict[Any, Any] = {}
 
     # ------------------------------------------------------------------ identity / datasets (task/base.py:256-273)
     @property
@@ -236,7 +237,7 @@ class Task:
         """The reference's generator arguments (task/base.py:475-486: its pops and defaults; normalize_scores defaults to False
         here, unlike the generator's own default) as SequenceGenerator keywords.  Beam search only: diverse beam, diverse siblings,
         match_source_len and lexical constraints raise NotImplementedError, and so do the sampling arguments -- a sampling
-        generator comes from `sampling_generator`."""
+        generator comes from `sampling_generator`, a diverse one from `diverse_generator`."""
         args = dict(
             beam_size=gen_kwargs.pop("beam", 5), return_n_best=gen_kwargs.pop("return_n_best", 1),
             max_len_a=gen_kwargs.pop("max_len_a", 0), max_len_b=gen_kwargs.pop("max_len_b", 200),
@@ -249,7 +250,8 @@ class Task:
         for k, default in unsupported.items():
             v = gen_kwargs.pop(k, default)
             if v != default:
-                hint = "; for sampling call Task.sampling_generator(...)" if k.startswith("sampling") else ""
+                hint = "; for sampling call Task.sampling_generator(...)" if k.startswith("sampling") else \
+                    "; for diverse decoding call Task.diverse_generator(...)" if k.startswith("divers") else ""
                 raise NotImplementedError(f"build_generator: {k}={v!r} -- only plain beam search is implemented{hint}")
         gen_kwargs.pop("diverse_beam_strength", None)
         return dict(args, **gen_kwargs)
@@ -287,6 +289,32 @@ class Task:
                                                          seed=seed, **kw)
         return self._sampling_gens[key]
 
+    def diverse_generator(self, **gen_kwargs):
+        """SequenceGenerator(search_strategy=DiverseBeamSearch(...) or DiverseSiblingsSearch(...)) from the reference's generator
+        arguments: `diverse_beam_groups`, `diverse_beam_strength` (default 0.5) and `diversity_rate` are taken out here with the
+        reference's exclusivity check and selection order (task/base.py:491-532: groups when > 0, else siblings when the rate is
+        > -1), the rest goes through `generator_kwargs`.  One generator is kept per option set, so its captured step graphs carry
+        on over later batches.  `task.generator = task.diverse_generator(...)` makes `inference` decode diversely."""
+        from .generator import DiverseBeamSearch, DiverseSiblingsSearch, SequenceGenerator
+        if self.global_dict is None:
+            raise ValueError(f"task {self.name}: initialize(global_dict) before building a generator")
+        groups, strength = gen_kwargs.pop("diverse_beam_groups", -1), gen_kwargs.pop("diverse_beam_strength", 0.5)
+        rate = gen_kwargs.pop("diversity_rate", -1)
+        if sum(int(bool(c)) for c in (gen_kwargs.get("sampling", False), groups > 0, gen_kwargs.get("match_source_len", False),
+                                      rate > 0)) > 1:
+            raise ValueError("Provided Search parameters are mutually exclusive.")
+        if not (groups > 0 or rate > -1):
+            raise ValueError("diverse_generator: neither diverse_beam_groups > 0 nor diversity_rate > -1 -- build_generator makes "
+                             "the beam-search generator")
+        kw = self.generator_kwargs(**gen_kwargs)
+        chosen = dict(diverse_beam_groups=groups, diverse_beam_strength=strength) if groups > 0 else dict(diversity_rate=rate)
+        key = tuple(sorted((k, repr(v)) for k, v in dict(kw, **chosen).items()))
+        if key not in self._diverse_gens:
+            strategy = DiverseBeamSearch(self.global_dict, groups, strength) if groups > 0 else \
+                DiverseSiblingsSearch(self.global_dict, rate)
+            self._diverse_gens[key] = SequenceGenerator(self.global_dict, search_strategy=strategy, **kw)
+        return self._diverse_gens[key]
+
     @property
     def generator(self):
         """Built on first use from cfg.evaluation.generator_args (JSON) and cfg.constraint_range (text targets)."""
@@ -309,12 +337,15 @@ class Task:
     @property
     def scst_generator(self):
         """Built on first use from cfg.scst_args (task/base.py:249-253): every hypothesis of the beam is returned (SCST scores all K
-        of a sentence); with "sampling": true the K rows are K independent samples (`sampling_generator`)."""
+        of a sentence); with "sampling": true the K rows are K independent samples (`sampling_generator`), and with
+        "diverse_beam_groups" > 0 or "diversity_rate" > -1 they come from diverse decoding (`diverse_generator`)."""
         if self._scst_generator is None:
             args = json.loads(self.cfg.scst_args)
             args.setdefault("return_n_best", args.get("beam", 5))
             if args.get("sampling", False):
                 self._scst_generator = self.sampling_generator(**args)
+            elif args.get("diverse_beam_groups", -1) > 0 or args.get("diversity_rate", -1) > -1:
+                self._scst_generator = self.diverse_generator(**args)
             else:
                 args.pop("sampling", None)
                 self._scst_generator = self.build_generator(**args)
