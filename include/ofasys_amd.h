@@ -431,7 +431,9 @@ int ofa_cross_entropy_fwd(const void* logits, const int64_t* target, float* lse,
 /* Both in ONE pass over the logits (one read, one write instead of two reads and a write): lse, row_loss AND
  * dlogits = (softmax - onehot) * grad_scale[0] (grad_scale: device scalar known before the forward -- the backward seed or the loss
  * scale; NULL = 1; zero for ignored rows and for columns V..ld-1).  16-bit logits of at most 65536 padded columns
- * (ofa_cross_entropy_fwd_grad_ok != 0), the row is held in the registers of a 1024-thread block. */
+ * (ofa_cross_entropy_fwd_grad_ok != 0), the row is held in the registers of a 1024-thread block.  A non-ignored target outside [0, V)
+ * is a caller error this entry survives as ofa_scst_loss_fwd_grad does: nothing is read out of bounds, row_loss = +inf, the gradient row
+ * is 0.  (ofa_cross_entropy_fwd / _bwd read x[target] unchecked.) */
 int ofa_cross_entropy_fwd_grad_ok(int64_t V, int64_t ld, int dtype);
 int ofa_cross_entropy_fwd_grad(const void* logits, const int64_t* target, const float* grad_scale, float* lse, float* row_loss,
                                void* dlogits, int64_t rows, int64_t V, int64_t ld, int64_t ignore_index, int dtype, void* stream);

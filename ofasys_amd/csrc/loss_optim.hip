@@ -14,13 +14,62 @@ __device__ __forceinline__ void online_merge(float& m, float& s, float m2, float
   m = mm;
 }
 
+// ---- the row core of every fused loss kernel below: a running (max, sum of exp(x - max)) per thread, fed a vector at a time.
+// The exponential exp(v - c) about a centre c, in the two forms the kernels use:
+struct ExpLib {                                          // the library expf (~12 instructions): the 256-thread streaming kernels
+  float c;
+  __device__ __forceinline__ explicit ExpLib(float centre) : c(centre) {}
+  __device__ __forceinline__ float operator()(float v) const { return expf(v - c); }
+};
+// ONE v_exp_f32 behind an FMA (2^(v log2 e - c log2 e), 1 ulp): with two exponentials per logit (one for the sum, one for the
+// probability) the library's arithmetic, not HBM, set the time of the one-pass kernel
+constexpr float L2E = 1.4426950408889634f;
+__device__ __forceinline__ float ex2(float v) { return __builtin_amdgcn_exp2f(v); }
+struct Exp2Fma {
+  float k;
+  __device__ __forceinline__ explicit Exp2Fma(float centre) : k(-centre * L2E) {}
+  __device__ __forceinline__ float operator()(float v) const { return ex2(fmaf(v, L2E, k)); }
+};
+// one vector into (m, s): the vector's max, ONE rescale of s, N exponentials about the new max (m == -inf before the first: exp(-inf) = 0)
+template <typename Exp, int N>
+__device__ __forceinline__ void vec_merge(float& m, float& s, const float (&a)[N]) {
+  float lm = a[0];
+#pragma unroll
+  for (int j = 1; j < N; ++j) lm = fmaxf(lm, a[j]);
+  const float mm = fmaxf(m, lm);
+  const Exp e(mm);
+  float acc = s * e(m);
+#pragma unroll
+  for (int j = 0; j < N; ++j) acc += e(a[j]);
+  m = mm;
+  s = acc;
+}
+// the (m, s) of a 256-thread block's threads -> the row's log-sum-exp, handed to `row_done(lse)` in thread 0 ONLY: lanes by xor 32..1,
+// one (m, s) per wave through LDS, then thread 0 merges waves 0..3 in order.  (That order is part of these kernels' results, bit for bit.)
+// Call it at most once per kernel, from all 256 threads: the LDS below is the helper's own, and its early `return` for threads 1..255
+// leaves the helper, after its barrier, not the kernel.
+template <typename F>
+__device__ __forceinline__ void block256_lse(float m, float s, F&& row_done) {
+  __shared__ float sm[4], ss[4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+    online_merge(m, s, m2, s2);
+  }
+  if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = m; ss[threadIdx.x >> 6] = s; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  float M = sm[0], S = ss[0];
+  for (int w = 1; w < 4; ++w) online_merge(M, S, sm[w], ss[w]);
+  row_done(M + logf(S));
+}
+
 // one 256-thread block per row
 template <typename T>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logits, const int64_t* __restrict__ target,
                                                      float* __restrict__ lse, float* __restrict__ row_loss, int64_t V,
                                                      int64_t ld, int64_t ignore_index) {
   constexpr int N = Vec<T>::N;
-  __shared__ float sm[4], ss[4];
   const int64_t row = blockIdx.x;
   const T* x = logits + row * ld;
   float m = -INFINITY, s = 0.f;
@@ -28,33 +77,14 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const T* __restrict__ logit
   for (int64_t v = threadIdx.x; v < nvec; v += 256) {
     float a[N];
     load_vec<T>(x + v * N, a);
-    float lm = a[0];
-#pragma unroll
-    for (int j = 1; j < N; ++j) lm = fmaxf(lm, a[j]);
-    const float mm = fmaxf(m, lm);
-    float acc = s * expf(m - mm);
-#pragma unroll
-    for (int j = 0; j < N; ++j) acc += expf(a[j] - mm);
-    m = mm;
-    s = acc;
+    vec_merge<ExpLib>(m, s, a);
   }
   for (int64_t e = nvec * N + threadIdx.x; e < V; e += 256) online_merge(m, s, ld1<T>(x + e), 1.f);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    online_merge(m, s, m2, s2);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sm[wave] = m; ss[wave] = s; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float M = sm[0], S = ss[0];
-    for (int w = 1; w < 4; ++w) online_merge(M, S, sm[w], ss[w]);
-    const float l = M + logf(S);
+  block256_lse(m, s, [&](float l) {
     lse[row] = l;
     const int64_t t = target[row];
     row_loss[row] = (t == ignore_index) ? 0.f : l - ld1<T>(x + t);
-  }
+  });
 }
 
 template <typename T>
@@ -89,7 +119,6 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const T* __restrict__ logit
 // criterion is the LAST node of the forward graph and its upstream gradient is a scalar the caller knows before the forward runs (the
 // backward seed 1, or the loss scale), so one kernel can do both: a 1024-thread block holds its whole row in registers (NV x 8 elements
 // per thread), reduces max / sum-exp (waves by shuffles, the 16 waves through LDS), and writes lse, the row's loss and
-// dlogits = (softmax - onehot) * grad_scale from the same registers: one read, one write.  Same arithmetic per element as
 // dlogits = (softmax - onehot) * grad_scale from the same registers: one read, one write.  Exponentials by v_exp_f32 (1 ulp), a 1024-wide
 // reduction tree: lse and the probabilities agree with ce_fwd_kernel / ce_bwd_kernel to fp32 rounding, not bit for bit.
 template <typename T, int NV>
@@ -100,10 +129,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void 
   // against 118 for the two kernels it replaces.  32-bit indices and scalar-base + 32-bit-offset addressing keep it there.)
   constexpr int N = Vec<T>::N;
   static_assert(N == 8, "16-bit element types");
-  // exponentials as ONE v_exp_f32 behind an FMA (2^(x log2 e - m log2 e), 1 ulp): the library expf the two-kernel route uses is ~12
-  // instructions, and with two exponentials per logit (one for the sum, one for the probability) that arithmetic, not HBM, set the time
-  constexpr float L2E = 1.4426950408889634f;
-  auto ex2 = [](float v) { return __builtin_amdgcn_exp2f(v); };
   __shared__ float sm[16], ss[16];
   const int64_t row = blockIdx.x;
   const char* xb = reinterpret_cast<const char*>(logits + row * ld);       // (uniform: scalar registers)
@@ -124,15 +149,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void 
     float a[N];
     unpack16<T>(raw[i], a);
     if (c0 + N <= V) {
-      float lm = a[0];
-#pragma unroll
-      for (int j = 1; j < N; ++j) lm = fmaxf(lm, a[j]);
-      const float mm = fmaxf(m, lm), mk = -mm * L2E;
-      float acc = s * ex2(fmaf(m, L2E, mk));             // (m == -inf on the first vector: 2^-inf = 0)
-#pragma unroll
-      for (int j = 0; j < N; ++j) acc += ex2(fmaf(a[j], L2E, mk));
-      m = mm;
-      s = acc;
+      vec_merge<Exp2Fma>(m, s, a);
     } else {
 #pragma unroll
       for (int j = 0; j < N; ++j)
@@ -156,12 +173,15 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void 
   const int64_t t64 = target[row];
   const bool ignored = t64 == ignore_index;
   const int t = (t64 >= 0 && t64 < V) ? (int)t64 : -1;
+  // a target outside [0, V) that is not ignore_index is a caller error the kernel survives as the SCST entry does: x[t] is not read,
+  // row_loss = +inf (the -lprob of a column that does not exist), the gradient row is zero
+  const bool dead = ignored || t < 0;
   if (tid == 0) {
     lse[row] = l;
-    row_loss[row] = ignored ? 0.f : l - ld1<T>(reinterpret_cast<const T*>(xb) + t64);
+    row_loss[row] = ignored ? 0.f : t < 0 ? INFINITY : l - ld1<T>(reinterpret_cast<const T*>(xb) + t);
   }
-  const float g = ignored ? 0.f : (gscale ? gscale[0] : 1.0f);
-  const float lk = -l * L2E;
+  const float g = dead ? 0.f : (gscale ? gscale[0] : 1.0f);
+  const Exp2Fma prob(l);                                 // exp(x - lse)
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int v = tid + i * 1024;
@@ -172,7 +192,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void 
 #pragma unroll
     for (int j = 0; j < N; ++j) {
       float d = 0.f;
-      if (!ignored && c0 + j < V) d = (ex2(fmaf(a[j], L2E, lk)) - (c0 + j == t ? 1.f : 0.f)) * g;
+      if (!dead && c0 + j < V) d = (prob(a[j]) - (c0 + j == t ? 1.f : 0.f)) * g;
       o[j] = d;
     }
     uint4 w;
@@ -199,7 +219,7 @@ __global__ __launch_bounds__(256) void lsce_fwd_kernel(const T* __restrict__ log
                                                        float* __restrict__ lse, float* __restrict__ row_loss,
                                                        float* __restrict__ row_nll, float* __restrict__ row_cnt, int64_t V,
                                                        int64_t ld, int64_t ignore_index, LsCfg cfg) {
-  __shared__ float sm[4], ss[4], sx[4], sc[4];
+  __shared__ float sx[4], sc[4];
   const int64_t row = blockIdx.x;
   const T* x = logits + row * ld;
   float m = -INFINITY, s = 0.f, sumx = 0.f, cnt = 0.f;
@@ -210,20 +230,10 @@ __global__ __launch_bounds__(256) void lsce_fwd_kernel(const T* __restrict__ log
     sumx += a;
     cnt += 1.f;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    online_merge(m, s, m2, s2);
-  }
   sumx = wave_sum(sumx);
   cnt = wave_sum(cnt);
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sm[wave] = m; ss[wave] = s; sx[wave] = sumx; sc[wave] = cnt; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float M = sm[0], S = ss[0];
-    for (int w = 1; w < 4; ++w) online_merge(M, S, sm[w], ss[w]);
-    const float l = M + logf(S);
+  if ((threadIdx.x & 63) == 0) { sx[threadIdx.x >> 6] = sumx; sc[threadIdx.x >> 6] = cnt; }
+  block256_lse(m, s, [&](float l) {                      // (its barrier orders sx / sc too)
     const float X = sx[0] + sx[1] + sx[2] + sx[3], C = sc[0] + sc[1] + sc[2] + sc[3];
     lse[row] = l;
     row_cnt[row] = C;
@@ -238,7 +248,7 @@ __global__ __launch_bounds__(256) void lsce_fwd_kernel(const T* __restrict__ log
       row_nll[row] = nll;
       row_loss[row] = (1.f - cfg.eps - eps_i) * nll + eps_i * smooth;
     }
-  }
+  });
 }
 
 // d loss_row / d x[v] = (1 - eps - eps_i)(p_v - [v == t]) + eps_i (C p_v - 1)   for allowed v, 0 elsewhere; times
@@ -310,8 +320,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void 
     float* __restrict__ row_loss, T* __restrict__ dlogits, int nseq, int V, int ld, int64_t ignore_index, int cs, int ce) {
   constexpr int N = Vec<T>::N;
   static_assert(N == 8, "16-bit element types");
-  constexpr float L2E = 1.4426950408889634f;
-  auto ex2 = [](float v) { return __builtin_amdgcn_exp2f(v); };     // one v_exp_f32 behind an FMA, as in ce_fwd_grad_kernel
   __shared__ float sm[16], ss[16];
   const int64_t row = blockIdx.x;
   const char* xb = reinterpret_cast<const char*>(logits + row * ld);
@@ -348,17 +356,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void 
 #pragma unroll
       for (int j = 0; j < N; ++j) a[j] = okc(tid8, i * 8192 + j) ? a[j] : -INFINITY;
     }
-    float lm = a[0];
-#pragma unroll
-    for (int j = 1; j < N; ++j) lm = fmaxf(lm, a[j]);
-    const float mm = fmaxf(m, lm), mk = -mm * L2E;       // (every vector that gets here holds an allowed column: mm is finite)
-    float acc = s * ex2(fmaf(m, L2E, mk));
-#pragma unroll
-    for (int j = 0; j < N; ++j) acc += ex2(fmaf(a[j], L2E, mk));
-    m = mm;
-    s = acc;
+    vec_merge<Exp2Fma>(m, s, a);                         // (every vector that gets here holds an allowed column: the new max is finite)
   }
-  const float mw = wave_max(m);                                      // max first, then one rescale per partial sum
+  // max first, then ONE rescale per partial sum: the pairwise online merges of block256_lse (two expf each, six shuffle levels and the
+  // serial merges of the wave results) would be this block's critical path -- nothing else runs on the CU while it reduces
+  const float mw = wave_max(m);
   const float sw = wave_sum(mw == -INFINITY ? 0.f : s * ex2((m - mw) * L2E));
   const int wave = tid >> 6;
   if ((tid & 63) == 0) { sm[wave] = mw; ss[wave] = sw; }
@@ -377,7 +379,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void 
   }
   const float g = (r.ignored || !r.valid) ? 0.f : r.w * (gscale ? gscale[0] : 1.0f);
   const int trel = (r.valid ? (int)r.t : -1) - tid8;     // the target's column relative to this thread's first: slab i, element j is i * 8192 + j
-  const float lk = -l * L2E;
+  const Exp2Fma prob(l);                                 // exp(x - lse)
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     if (tid >= nvec - i * 1024) continue;
@@ -386,7 +388,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void 
       float a[N], o[N];
       unpack16<T>(raw[i], a);
 #pragma unroll
-      for (int j = 0; j < N; ++j) o[j] = (ex2(fmaf(a[j], L2E, lk)) - (trel == i * 8192 + j ? 1.f : 0.f)) * g;
+      for (int j = 0; j < N; ++j) o[j] = (prob(a[j]) - (trel == i * 8192 + j ? 1.f : 0.f)) * g;
       if (!some(full_bits, i)) {
 #pragma unroll
         for (int j = 0; j < N; ++j) o[j] = okc(tid8, i * 8192 + j) ? o[j] : 0.f;
@@ -405,7 +407,7 @@ __global__ __launch_bounds__(256) void scst_stream_kernel(
     float* __restrict__ row_loss, T* __restrict__ dlogits, int64_t nseq, int64_t V, int64_t ld, int64_t ignore_index, int64_t cs,
     int64_t ce) {
   constexpr int N = Vec<T>::N;
-  __shared__ float sm[4], ss[4], sl;
+  __shared__ float sl;
   const int64_t row = blockIdx.x;
   const T* x = logits + row * ld;
   T* dx = dlogits + row * ld;
@@ -418,38 +420,19 @@ __global__ __launch_bounds__(256) void scst_stream_kernel(
     float a[N];
     load_vec<T>(x + c0, a);
     if (cls == 2) {
-      float lm = a[0];
-#pragma unroll
-      for (int j = 1; j < N; ++j) lm = fmaxf(lm, a[j]);
-      const float mm = fmaxf(m, lm);
-      float acc = s * expf(m - mm);
-#pragma unroll
-      for (int j = 0; j < N; ++j) acc += expf(a[j] - mm);
-      m = mm;
-      s = acc;
+      vec_merge<ExpLib>(m, s, a);
     } else {
 #pragma unroll
       for (int j = 0; j < N; ++j)
         if (scst_ok(c0 + j, V, cs, ce)) online_merge(m, s, a[j], 1.f);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    online_merge(m, s, m2, s2);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sm[wave] = m; ss[wave] = s; }
-  __syncthreads();
   const ScstRow r = scst_row(row, target, reward, row_seq, rows_per_seq, nseq, V, cs, ce, ignore_index);
-  if (threadIdx.x == 0) {
-    float M = sm[0], S = ss[0];
-    for (int w = 1; w < 4; ++w) online_merge(M, S, sm[w], ss[w]);
-    const float l = M + logf(S);
+  block256_lse(m, s, [&](float l) {
     sl = l;
     lse[row] = l;
     row_loss[row] = r.ignored ? 0.f : !r.valid ? INFINITY : r.w * (l - ld1<T>(x + r.t));
-  }
+  });
   __syncthreads();
   const float l = sl;
   const float g = (r.ignored || !r.valid) ? 0.f : r.w * (gscale ? gscale[0] : 1.0f);

@@ -1750,75 +1750,86 @@ def patch_embed(img, weight, bias, p, cls_token=None):
 
 
 # ---------------------------------------------------------------------------------------------- criterion
-class CrossEntropyFn(torch.autograd.Function):
-    """sum over rows of NLL(log_softmax_fp32(logits), target), ignore_index rows contribute 0
-    (engine/criterion/cross_entropy.py:27-67).  logits: [..., V] view of storage whose row stride is a multiple of 8."""
-
-    @staticmethod
-    def forward(ctx, logits, target, ignore_index, seed=None):
-        """seed: the fp32 device scalar the caller WILL hand to `loss.backward(seed)` (trainer.TrainStep: its constant ones tensor).
-        With it the logits' gradient is computed by the forward kernel from the row it already holds (one pass over the logits
-        instead of three); backward returns it when it is handed that very tensor, and otherwise takes the two-kernel route."""
-        V = logits.shape[-1]
-        if logits.is_contiguous():
-            l2d = logits.reshape(-1, V)
-        else:
-            try:
-                l2d = logits.view(-1, V)                       # a padded-stride view of row storage: no copy
-            except RuntimeError:
-                l2d = logits.contiguous().view(-1, V)          # a transposed [T, B, V] layout (op-by-op layer stacks)
-        if l2d.stride(1) != 1 or l2d.stride(0) % (4 if l2d.dtype == torch.float32 else 8) != 0:
-            pad = (-V) % 8
-            store = torch.zeros(l2d.shape[0], V + pad, dtype=l2d.dtype, device=l2d.device)
-            store[:, :V].copy_(l2d)
-            l2d = store[:, :V]
-        t = target.reshape(-1).contiguous()
-        ctx.ignore_index, ctx.shape = ignore_index, logits.shape
-        ctx.seed = ctx.pre = None
-        if (seed is not None and ctx.needs_input_grad[0] and seed.dtype == torch.float32 and seed.numel() == 1 and seed.device == l2d.device
-                and K.cross_entropy_fwd_grad_ok(l2d, V)):
-            lse, row_loss, d = K.cross_entropy_fwd_grad(l2d, t, seed, V, ignore_index)
-            ctx.seed, ctx.pre = seed, d                  # (the logits themselves are not kept: nothing reads them again)
-            ctx.save_for_backward(t, lse)
-            ctx.l2d = l2d                                # kept only for the fallback below (a view of the projection's output)
-            return K.sum_f32(row_loss)
-        lse, row_loss = K.cross_entropy_fwd(l2d, t, V, ignore_index)
-        ctx.save_for_backward(l2d, t, lse)
-        return K.sum_f32(row_loss)
-
-    @staticmethod
-    def backward(ctx, dloss):
-        if ctx.pre is not None:
-            t, lse = ctx.saved_tensors
-            d, seed, l2d = ctx.pre, ctx.seed, ctx.l2d
-            ctx.pre = ctx.seed = ctx.l2d = None
-            V = ctx.shape[-1]
-            if dloss.data_ptr() == seed.data_ptr() and dloss.dtype == seed.dtype:
-                return d[:, :V].view(ctx.shape), None, None, None
-            gs = dloss.reshape(1).float().contiguous()   # seeded with something else after all: the two-kernel route
-            d = K.cross_entropy_bwd(l2d, t, lse, gs, V, ctx.ignore_index, dlogits=d)
-            return d[:, :V].view(ctx.shape), None, None, None
-        l2d, t, lse = ctx.saved_tensors
-        V = l2d.shape[1]
-        gs = dloss.reshape(1).float().contiguous()
-        d = K.cross_entropy_bwd(l2d, t, lse, gs, V, ctx.ignore_index)
-        return d[:, :V].view(ctx.shape), None, None, None
-
-
-def cross_entropy_sum(logits, target, ignore_index, seed=None):
-    return CrossEntropyFn.apply(logits, target, ignore_index, seed)
-
-
 def _ce_rows(logits):
     """[..., V] logits -> [rows, V] view whose row stride is a multiple of the 16-byte vector width (copy only if needed)."""
     V = logits.shape[-1]
-    l2d = logits.reshape(-1, V) if logits.is_contiguous() else logits.view(-1, V)
+    if logits.is_contiguous():
+        l2d = logits.reshape(-1, V)
+    else:
+        try:
+            l2d = logits.view(-1, V)                       # a padded-stride view of row storage: no copy
+        except RuntimeError:
+            l2d = logits.contiguous().view(-1, V)          # a transposed [T, B, V] layout (op-by-op layer stacks)
     if l2d.stride(1) != 1 or l2d.stride(0) % (4 if l2d.dtype == torch.float32 else 8) != 0:
         pad = (-V) % 8
         store = torch.zeros(l2d.shape[0], V + pad, dtype=l2d.dtype, device=l2d.device)
         store[:, :V].copy_(l2d)
         l2d = store[:, :V]
     return l2d
+
+
+class _SeededGrad:
+    """The logits' gradient a criterion's forward wrote at the scale of `seed`: the fp32 device scalar the caller says it WILL hand to
+    `loss.backward(seed)` (trainer.TrainStep: its constant ones tensor).  It is handed out once, and only to a backward that receives
+    that very tensor, unwritten since the forward; every other backward (another tensor, a seed written to since, a repeated call under
+    retain_graph) recomputes at the scale it is given -- from tensors the Function saved with save_for_backward, none of which this
+    object holds or clears.  Of the seed only its identity and version are read, so it lives here, outside autograd's version check
+    (which would raise where a recomputation is the right answer)."""
+
+    @staticmethod
+    def usable(seed, device):
+        return seed is not None and seed.dtype == torch.float32 and seed.numel() == 1 and seed.device == device
+
+    def __init__(self, seed=None, pre=None):                 # (no arguments: nothing precomputed, every backward computes)
+        self.seed, self.version, self.pre = seed, None if seed is None else seed._version, pre
+
+    def take(self, dloss):
+        """the precomputed gradient if `dloss` is the backward it was computed for (None: recompute); it is handed out once"""
+        seed = self.seed
+        if self.pre is None or dloss.data_ptr() != seed.data_ptr() or dloss.dtype != seed.dtype or seed._version != self.version:
+            return None
+        return self.spare()
+
+    def spare(self):
+        """the precomputed buffer, if it was never handed out, to write a recomputed gradient into (None: allocate)"""
+        d, self.pre = self.pre, None
+        return d
+
+
+class CrossEntropyFn(torch.autograd.Function):
+    """sum over rows of NLL(log_softmax_fp32(logits), target), ignore_index rows contribute 0
+    (engine/criterion/cross_entropy.py:27-67).  logits: [..., V]; a row stride that is no multiple of the vector width is padded here."""
+
+    @staticmethod
+    def forward(ctx, logits, target, ignore_index, seed=None):
+        """seed: see _SeededGrad.  With it the logits' gradient is computed by the forward kernel from the row it already holds (one
+        pass over the logits instead of three); a backward that cannot take it runs ce_bwd on the saved logits view."""
+        V = logits.shape[-1]
+        l2d = _ce_rows(logits)
+        t = target.reshape(-1).contiguous()
+        ctx.ignore_index, ctx.shape = ignore_index, logits.shape
+        ctx.seeded = _SeededGrad()
+        if ctx.needs_input_grad[0] and _SeededGrad.usable(seed, l2d.device) and K.cross_entropy_fwd_grad_ok(l2d, V):
+            lse, row_loss, d = K.cross_entropy_fwd_grad(l2d, t, seed, V, ignore_index)
+            ctx.seeded = _SeededGrad(seed, d)
+        else:
+            lse, row_loss = K.cross_entropy_fwd(l2d, t, V, ignore_index)     # (no seed known: the forward does not write a gradient)
+        ctx.save_for_backward(l2d, t, lse)
+        return K.sum_f32(row_loss)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        l2d, t, lse = ctx.saved_tensors
+        V = l2d.shape[1]
+        d = ctx.seeded.take(dloss)
+        if d is None:
+            gs = dloss.reshape(1).float().contiguous()
+            d = K.cross_entropy_bwd(l2d, t, lse, gs, V, ctx.ignore_index, dlogits=ctx.seeded.spare())
+        return d[:, :V].view(ctx.shape), None, None, None
+
+
+def cross_entropy_sum(logits, target, ignore_index, seed=None):
+    return CrossEntropyFn.apply(logits, target, ignore_index, seed)
 
 
 class LabelSmoothedCrossEntropyFn(torch.autograd.Function):
@@ -1892,13 +1903,9 @@ class ScstLossFn(torch.autograd.Function):
                 raise ValueError(f"scst_loss: {rows} rows do not divide into {w.numel()} sentences (pass row_seq)")
             rps = rows // w.numel()
         cs, ce = constraint_range if constraint_range is not None else (-1, -1)
-        seeded = (seed is not None and ctx.needs_input_grad[0] and seed.dtype == torch.float32 and seed.numel() == 1
-                  and seed.device == l2d.device)
+        seeded = ctx.needs_input_grad[0] and _SeededGrad.usable(seed, l2d.device)
         lse, row_loss, d = K.scst_loss_fwd_grad(l2d, t, w, seed if seeded else None, V, ignore_index, rps, row_seq, cs, ce)
-        # the gradient at the seed's scale, handed out by the FIRST backward that receives that very tensor, unchanged; every other
-        # backward (another seed, a seed written to since, a repeated call) runs the same entry again at the scale it is given
-        ctx.seed, ctx.seed_version, ctx.pre = (seed, seed._version, d) if seeded else (None, None, None)
-        ctx.handed_out = False
+        ctx.seeded = _SeededGrad(seed, d) if seeded else _SeededGrad()      # (a backward that cannot take it runs the same entry again)
         ctx.save_for_backward(l2d, t, w, row_seq)
         ctx.cfg = (ignore_index, rps, cs, ce, logits.shape)
         ntok = t.ne(ignore_index).sum()
@@ -1910,12 +1917,8 @@ class ScstLossFn(torch.autograd.Function):
         l2d, t, w, row_seq = ctx.saved_tensors
         ignore_index, rps, cs, ce, shape = ctx.cfg
         V = l2d.shape[1]
-        seed = ctx.seed
-        if (seed is not None and not ctx.handed_out and dloss.data_ptr() == seed.data_ptr() and dloss.dtype == seed.dtype
-                and seed._version == ctx.seed_version):
-            ctx.handed_out = True
-            d = ctx.pre
-        else:
+        d = ctx.seeded.take(dloss)
+        if d is None:
             gs = dloss.reshape(1).float().contiguous()
             _, _, d = K.scst_loss_fwd_grad(l2d, t, w, gs, V, ignore_index, rps, row_seq, cs, ce)
         return d[:, :V].view(shape), None, None, None, None, None, None

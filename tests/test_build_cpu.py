@@ -52,6 +52,8 @@ def _kernel_meta(src, tmp_path):
     # load / MFMA segments would also put scratch traffic on the vmcnt counter the loop's LDS-DMA waits are counted on
     ("gemm_pp.hip", r"gemm_pp_kernel", 0),
     ("gemm_pp.hip", r"gemm_group_tn_pp_kernel", 0),
+    # the one-pass SCST loss row: the row's NV x 4 registers at two blocks of 1024 threads per CU (64 registers), every NV, bf16 and fp16
+    ("loss_optim.hip", r"scst_fwd_grad_kernel", 0),
 ])
 def test_hot_kernels_do_not_spill(tmp_path, src, pattern, max_spill):
     meta = _kernel_meta(src, tmp_path)

@@ -10,7 +10,9 @@ What each test pins (the gaps the suite had):
   ce_fwd_grad_kernel<T, 2> never ran ................. ld = 8200, 16384 (and 8256 as a view of wider storage)
   the two-kernel route never saw fp16 or a tail ...... test_two_kernel_cross_entropy: fp32 / bf16 / fp16, targets inside the scalar tail
   softmax and label smoothing thin ................... test_probs (second trip, V = 1), test_label_smoothed_cross_entropy (ranges, masks, row_w)
-  random rows cannot show a dropped column ........... the `planted` regime: the row's dominant logit sits on each seam column in turn"""
+  random rows cannot show a dropped column ........... the `planted` regime: the row's dominant logit sits on each seam column in turn
+  a target outside [0, V) through the fused entry .... test_fused_cross_entropy_survives_targets_outside_the_vocabulary
+  a stale or repeated seeded backward ................ test_seeded_backward_of_cross_entropy_sum"""
 import pytest
 import torch
 
@@ -127,6 +129,87 @@ def test_fused_cross_entropy(K, dtype, ld):
             lse2, _ = K.cross_entropy_fwd(x, t, V, co.IGNORE)
             assert float((lse2 - lse).abs().max()) <= 2 * co.LSE_TOL, (case, "the two routes' lse")
     _report(f"fused cross entropy ld={ld}")
+
+
+def test_fused_cross_entropy_survives_targets_outside_the_vocabulary(K):
+    """A non-ignored target outside [0, V) handed to ofa_cross_entropy_fwd_grad is a caller error the kernel survives as
+    ofa_scst_loss_fwd_grad does (test_scst_kernel_gpu.test_disallowed_targets_are_survived): nothing read out of bounds, row_loss = +inf,
+    a zero gradient row -- and the other rows meet the float64 reference."""
+    from tests import scst_oracle as so
+    dtype, V, ld, g = torch.bfloat16, 8193, 8200, 0.37
+    b = so.build(so.ScstCase("planted", V, ld, None, g, False, 78, 0), dtype, DEV)
+    x, t = b["x"], b["t"].clone()
+    R = so.ROWS
+    bad = {8: V + 1, 9: -7, 10: 10 ** 12, 11: ld}                        # padding, < 0, huge, one past the storage row
+    assert R == 12 and so.IGNORED_ROW < 8
+    for r, v in bad.items():
+        t[r] = v
+    _poison(((R,), F32), ((R,), F32), ((R, ld), dtype))
+    lse, row_loss, d = K.cross_entropy_fwd_grad(x, t, _gs(g), V, co.IGNORE)
+    torch.cuda.synchronize()
+    for r in bad:
+        assert float(row_loss[r]) == float("inf") and float(d[r].float().abs().max()) == 0.0, r
+    assert bool(torch.isfinite(d).all())
+    good = dict(x=x[:8], t=t[:8], g=g, ignored=so.IGNORED_ROW)
+    _check_ce(dict(lse=lse[:8], row_loss=row_loss[:8], d=d[:8]), good, dtype, "targets outside [0, V)", "fused")
+    check_f32("fused lse", lse[8:], co.ce_reference(x[8:], torch.zeros(4, dtype=torch.int64, device=DEV), g)[0]["lse"], co.LSE_TOL, dtype,
+              "lse of the rows with a bad target")
+
+
+def _bf16_neighbours(a, b):
+    """a and b are roundings to bf16 of two fp32 values a few fp32 ulps apart (the same gradient by v_exp_f32 and by expf): equal, or
+    adjacent bf16 values -- at most one bf16 ulp, 2^-7 of the larger magnitude, apart; exactly equal where one is 0."""
+    a, b = a.double(), b.double()
+    return bool(((a - b).abs() <= 2.0 ** -7 * torch.maximum(a.abs(), b.abs())).all())
+
+
+def test_seeded_backward_of_cross_entropy_sum(K):
+    """ops.cross_entropy_sum with a seed (tests/test_scst_gpu.py::test_seeded_backward for the SCST op): the gradient precomputed at the
+    seed's scale is what the backward seeded with that very tensor returns; a second backward (retain_graph), another tensor of the same
+    value and a seed written to since the forward all recompute through ce_bwd_kernel -- to equal numbers on these inputs (the two
+    kernels' exponentials differ by fp32 ulps, which no element's bf16 rounding sees here), or, within one bf16 rounding, to the new scale.  Each gradient meets the float64 reference at its scale."""
+    from ofasys_amd import ops
+    dtype, R, V = torch.bfloat16, 6, 257
+    x = co.make_case("randn3", R, V, V, None, 640).to(dtype).to(DEV)
+    t = torch.randint(0, V, (R,), generator=torch.Generator(device="cpu").manual_seed(641))
+    t[2] = co.IGNORE
+    t = t.to(DEV)
+    logits = x.clone().requires_grad_(True)                  # dense [6, 257]: the op pads the rows to 264 itself
+    padded = torch.zeros(R, 264, dtype=dtype, device=DEV)
+    padded[:, :V] = x
+
+    def meets_reference(d, g, tag):
+        assert d.shape == (R, V) and d.dtype == dtype
+        ref, bd = co.ce_reference(padded[:, :V], t, g)
+        check_grad("ce op d", torch.nn.functional.pad(d, (0, 264 - V)), ref["d"], bd, dtype, g, tag)
+
+    seed = torch.ones((), dtype=F32, device=DEV)
+    _poison(((R,), F32), ((R,), F32), ((R, 264), dtype))
+    loss = ops.cross_entropy_sum(logits, t, co.IGNORE, seed=seed)
+    want = K.cross_entropy_fwd_grad(padded[:, :V], t, seed.reshape(1), V, co.IGNORE)[2][:, :V]
+    first, = torch.autograd.grad(loss, logits, seed, retain_graph=True)
+    torch.cuda.synchronize()
+    assert torch.equal(first, want) and float(first.float().abs().max()) > 0, "the first backward returns the forward kernel's gradient"
+    meets_reference(first, 1.0, "first")
+    kept = first.clone()
+    _poison(((R, 264), dtype))
+    again, = torch.autograd.grad(loss, logits, seed, retain_graph=True)                                  # a second time: recomputed
+    assert again.data_ptr() != first.data_ptr() and torch.equal(first, kept) and torch.equal(again, first)
+    meets_reference(again, 1.0, "again")
+    _poison(((R, 264), dtype))
+    other, = torch.autograd.grad(loss, logits, torch.ones((), device=DEV), retain_graph=True)            # another tensor: recomputed
+    assert other.data_ptr() != first.data_ptr() and torch.equal(first, kept) and torch.equal(other, first)
+    meets_reference(other, 1.0, "other")
+    # a seed changed in place between forward and backward: the stale gradient is not handed out
+    seed2 = torch.ones((), dtype=F32, device=DEV)
+    loss2 = ops.cross_entropy_sum(logits, t, co.IGNORE, seed=seed2)
+    seed2.mul_(2.0)
+    changed, = torch.autograd.grad(loss2, logits, seed2)
+    torch.cuda.synchronize()
+    print("elements that differ from the first gradient: again", int((again != first).sum()), "other", int((other != first).sum()),
+          "changed", int((changed.float() != first.float() * 2).sum()), "of", first.numel())
+    assert _bf16_neighbours(changed.float(), first.float() * 2)
+    meets_reference(changed, 2.0, "changed")
 
 
 def test_fused_route_is_offered_up_to_65536_columns(K):
