@@ -9,6 +9,11 @@
 
 namespace ofa {
 
+// The widest rows (NV = 32: more than 8192 columns of a 16-bit type, 4096 of fp32) sum a lane's share of the row statistics in three
+// levels: the elements of a 16-byte vector, four vectors, the groups.  ONE running sum over the lane's up to 256 elements rounds the
+// same way at every step when the row is (nearly) constant: the mean of a constant GELU row of 16384 columns came out 2.6e-6 of its
+// magnitude off, sixteen times what float32 owes (tests/rownorm_oracle.py: `fwd NV32 m2048 ... gelu`).  Narrower rows keep the running
+// sum, bit for bit: join_fwd_kernel (csrc/join.hip, at most 8 vectors per lane) promises the bits of this kernel.
 template <typename T, int NV, bool GELU>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, const T* __restrict__ gamma,
                                                      const T* __restrict__ beta, T* __restrict__ y,
@@ -19,11 +24,13 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const T* xr = x + row * cols;
+  constexpr bool GROUPED = NV == 32;
   float v[NV][N];
-  float s = 0.f;
+  float s = 0.f, sg = 0.f;                         // sg: the open group of four vectors (GROUPED)
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = (i * 64 + lane) * N;
+    float t = 0.f;
     if (c < cols) {
       load_vec<T>(xr + c, v[i]);
 #pragma unroll
@@ -33,24 +40,35 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* __restrict__ x, co
           gauss_cdf<!__is_same(T, bf16_t)>(v[i][j], cdf, e);
           v[i][j] *= cdf;
         }
-        s += v[i][j];
+        if (GROUPED) t += v[i][j];
+        else s += v[i][j];
       }
     } else {
 #pragma unroll
       for (int j = 0; j < N; ++j) v[i][j] = 0.f;
     }
+    if (GROUPED) {
+      sg += t;
+      if ((i & 3) == 3) { s += sg; sg = 0.f; }
+    }
   }
   const float mu = wave_sum(s) / (float)cols;
-  float q = 0.f;
+  float q = 0.f, qg = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = (i * 64 + lane) * N;
+    float t = 0.f;
     if (c < cols) {
 #pragma unroll
       for (int j = 0; j < N; ++j) {
         const float d = v[i][j] - mu;
-        q += d * d;
+        if (GROUPED) t += d * d;
+        else q += d * d;
       }
+    }
+    if (GROUPED) {
+      qg += t;
+      if ((i & 3) == 3) { q += qg; qg = 0.f; }
     }
   }
   const float var = wave_sum(q) / (float)cols;
