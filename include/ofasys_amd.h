@@ -156,6 +156,9 @@ typedef struct ofa_gemm_group_item {
   void* out;         /* optional, with out_alpha / ldo: when the plan leaves this product ONE K-slice (splits == 1) the kernel adds */
   int64_t ldo;       /* out_alpha * a^T b straight onto out [m, n] (16-bit, row stride ldo, 16-byte aligned) in its epilogue -- no slab, */
   float out_alpha;   /* no fold launch (the weight gradients of a small micro-batch: every product is one slice).  NULL: always slabs */
+  int32_t store;     /* with out, one slice: != 0 WRITES out_alpha * a^T b (the first writer of a gradient in a step: out is not read, the
+                      * value is the one adding onto zeros gives); 0 adds onto out.  A product that goes through slabs hands the mode to
+                      * its fold job (ofa_fold_job.accumulate) instead. */
 } ofa_gemm_group_item;
 /* host only: validates the items and fills `splits` (one K-slice length for the group: <= 256 workgroups in total) */
 int ofa_gemm_group_plan(ofa_gemm_group_item* items, int n, int dtype);
@@ -342,6 +345,12 @@ int ofa_embedding_range_bwd(const void* dout, void* dweight, int batch, int64_t 
  * one-launch forms above existed?  Always 0 in the product library. */
 enum { OFA_EDGE_POS_RANGE = 0, OFA_EDGE_TOKEN_BWD = 1, OFA_EDGE_COLSUM_FOLD = 2, OFA_EDGE_IM2COL = 3 };
 int ofa_step_edges_old(int item);
+/* Debug library only (OFA_STEP_TAIL_OLD = bit mask over the items below): the gradient plumbing around the optimizer as it ran before
+ * -- bit 0: a zero fill of the whole gradient arena, every sink adding (no first-touch writes); bit 1: ofa_sumsq + ofa_step_schedule[_scaled]
+ * + the counter add as launches of their own (no ofa_sumsq_schedule); bit 2: ofa_reduce_sum_f32 + ofa_step_stats_add behind the
+ * criterion (no ofa_cross_entropy_fwd_grad_stats).  The product library has one path: always 0. */
+enum { OFA_TAIL_FIRST_TOUCH = 0, OFA_TAIL_NORM_SCHEDULE = 1, OFA_TAIL_CRITERION_STATS = 2 };
+int ofa_step_tail_old(int item);
 
 /* ---- elementwise pieces of the layer (transformer_layer.py:167-208): */
 int ofa_gelu_fwd(const void* x, void* y, int64_t n, int dtype, void* stream);                  /* module/gelu.py:18-19 */
@@ -437,6 +446,13 @@ int ofa_cross_entropy_fwd(const void* logits, const int64_t* target, float* lse,
 int ofa_cross_entropy_fwd_grad_ok(int64_t V, int64_t ld, int dtype);
 int ofa_cross_entropy_fwd_grad(const void* logits, const int64_t* target, const float* grad_scale, float* lse, float* row_loss,
                                void* dlogits, int64_t rows, int64_t V, int64_t ld, int64_t ignore_index, int dtype, void* stream);
+/* ofa_cross_entropy_fwd_grad plus the bookkeeping that followed it as two single-block launches: the last block to finish (a ticket:
+ * `ticket` is one device word that is 0 before the first call; the kernel resets it) writes loss[0] = sum of row_loss in
+ * ofa_reduce_sum_f32's order and adds [count of target != ignore_index, loss[0], the same count] to stats (fp64[3]) as
+ * ofa_step_stats_add does: the same bits.  rows >= 1. */
+int ofa_cross_entropy_fwd_grad_stats(const void* logits, const int64_t* target, const float* grad_scale, float* lse, float* row_loss,
+                                     void* dlogits, int64_t rows, int64_t V, int64_t ld, int64_t ignore_index, int dtype, float* loss,
+                                     double* stats, unsigned int* ticket, void* stream);
 /* dlogits = (softmax - onehot) * grad_scale[0] (device scalar), zero for ignored rows and for columns V..ld-1. */
 int ofa_cross_entropy_bwd(const void* logits, const int64_t* target, const float* lse, const float* grad_scale,
                           void* dlogits, int64_t rows, int64_t V, int64_t ld, int64_t ignore_index, int dtype,
@@ -486,6 +502,14 @@ int ofa_sumsq(const void* x, float* out /* fp32[1], accumulated into */, float* 
  * otherwise sched[3] = 0. */
 int ofa_step_schedule(const float* gsq, const double* sample_size, double* step, const double* lr, float* sched,
                       float* gnorm, float clip_norm, double beta1, double beta2, void* stream);
+/* ofa_sumsq, then ofa_step_schedule (loss_scaler NULL) or ofa_step_schedule_scaled, then counter[0] += counter_add (counter NULL: none;
+ * the Philox stream position of the step) in ONE launch: the last block to finish (`ticket`: one device word, 0 before the first call,
+ * reset by the kernel) folds the block partials in ofa_sumsq's order and runs the schedule -- the same bits as the separate launches.
+ * gsq[0] is WRITTEN (the sum of squares of x alone; it needs no clearing).  n >= 1; ws: ofa_sumsq_ws_floats() floats. */
+int ofa_sumsq_schedule(const void* x, float* gsq, float* ws, unsigned int* ticket, int64_t n, int dtype, const double* sample_size,
+                       double* step, const double* lr, float* sched, float* gnorm, double* loss_scaler, int64_t* counter,
+                       int64_t counter_add, float clip_norm, double beta1, double beta2, double scale_factor, double scale_window,
+                       double tolerance, double threshold, double min_loss_scale, void* stream);
 /* stats [3] fp64 += [count of target != pad, loss[0], the same count]: one micro-batch's share of the update's logging sums
  * [sample_size, loss_sum, ntokens] (engine/trainer.py:842-860, criterion/cross_entropy.py:55-67 with sentence_avg = False); loss: a
  * device fp32 scalar; target: int64 [n].  One launch, nothing on the host. */
@@ -607,6 +631,9 @@ typedef struct ofa_copy_job {
   int64_t bytes;
 } ofa_copy_job;
 int ofa_copy_batched(const ofa_copy_job* jobs, int njobs, void* stream);
+/* Batched zero fill, the sibling of ofa_copy_batched: dst_i[0 .. bytes_i) = 0 (src is ignored) -- the gradient-arena views a train
+ * step has to clear because no full writer stores to them first (partial writers: embedding rows; parameters nobody wrote). */
+int ofa_zero_batched(const ofa_copy_job* jobs, int njobs, void* stream);
 #define OFA_DEFER_FOLD 2
 /* partial-row count (`nslots`) the corresponding call writes; ws layouts: LayerNorm [q][nslots][cols] with q = dgamma,
  * dbeta(, dbias); colsum [nslots][cols]; split-K GEMM [splits][M][(N+3)&~3] (ofa_gemm_splits == 1: no partials). */

@@ -855,6 +855,15 @@ extern "C" int ofa_step_edges_old(int item) {
   return 0;
 }
 
+// debug builds: OFA_STEP_TAIL_OLD = a bit mask of OFA_TAIL_* items (the gradient plumbing around the optimizer) that run as they did
+// before; the product library has one path
+extern "C" int ofa_step_tail_old(int item) {
+#ifdef OFA_DEBUG_SWITCHES
+  if (const char* e = getenv("OFA_STEP_TAIL_OLD")) return (atoi(e) >> item) & 1;
+#endif
+  return 0;
+}
+
 extern "C" int ofa_embedding_bwd_ids_ok(int64_t n, int D, int64_t V, int dtype) {
   const int vecn = dt_vecn(dtype);
   return OFA_DT_OK(dtype) && n >= 0 && n <= OFA_EMBEDDING_IDS_MAX && V > 0 && V < ((int64_t)1 << 31) && D > 0 && D % vecn == 0 &&

@@ -223,15 +223,23 @@ struct CopyJobs {
   int njobs;
 };
 
-__global__ __launch_bounds__(256) void copy_batched_kernel(CopyJobs J) {
-  int lo = 0, hi = J.njobs - 1;                             // the job of this block: the last one whose first block is <= blockIdx.x
+// the job of this block (the last one whose first block is <= blockIdx.x), its byte offset inside the job and the bytes it handles
+__device__ __forceinline__ int copy_job_of(const CopyJobs& J, int64_t& off, int& n) {
+  int lo = 0, hi = J.njobs - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
     if (J.block0[mid] <= blockIdx.x) lo = mid; else hi = mid - 1;
   }
-  const int64_t off = (int64_t)(blockIdx.x - J.block0[lo]) * COPY_CHUNK;
+  off = (int64_t)(blockIdx.x - J.block0[lo]) * COPY_CHUNK;
   const int64_t left = J.bytes[lo] - off;
-  const int n = (int)(left < COPY_CHUNK ? left : COPY_CHUNK);
+  n = (int)(left < COPY_CHUNK ? left : COPY_CHUNK);
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void copy_batched_kernel(CopyJobs J) {
+  int64_t off;
+  int n;
+  const int lo = copy_job_of(J, off, n);
   const unsigned char* s = J.src[lo] + off;
   unsigned char* d = J.dst[lo] + off;
   if ((((uintptr_t)s | (uintptr_t)d) & 15) == 0) {
@@ -243,11 +251,30 @@ __global__ __launch_bounds__(256) void copy_batched_kernel(CopyJobs J) {
   }
 }
 
+// ---- batched zero fill: the gradient-arena views of a train step that no full writer stores to first (a few small tensors; the
+// arena-wide fill they replace wrote 286 MB per cfg-2 step).  The copy's job table and block map; src is not read.  A chunk that does
+// not start on a 16-byte boundary (ranges are element-granular) is zeroed bytewise up to the first one and by 16-byte stores from there.
+__global__ __launch_bounds__(256) void zero_batched_kernel(CopyJobs J) {
+  int64_t off;
+  int n;
+  const int lo = copy_job_of(J, off, n);
+  unsigned char* d = J.dst[lo] + off;
+  int head = (int)((16 - ((uintptr_t)d & 15)) & 15);
+  head = head < n ? head : n;
+  for (int i = threadIdx.x; i < head; i += 256) d[i] = 0;
+  const int nv = (n - head) >> 4;
+  uint4* v = reinterpret_cast<uint4*>(d + head);
+  for (int i = threadIdx.x; i < nv; i += 256) v[i] = make_uint4(0, 0, 0, 0);
+  for (int i = head + (nv << 4) + threadIdx.x; i < n; i += 256) d[i] = 0;
+}
+
 }  // namespace ofa
 using namespace ofa;
 
-extern "C" int ofa_copy_batched(const ofa_copy_job* jobs, int njobs, void* stream) {
-  OFA_REQUIRE(njobs >= 0 && (njobs == 0 || jobs), OFA_ERR_INVALID, "copy_batched: bad argument");
+// one launch per COPY_MAX_JOBS jobs of a HOST job array; ZERO: the zero fill (src is ignored), else the copy
+template <bool ZERO>
+static int copy_jobs_launch(const ofa_copy_job* jobs, int njobs, void* stream, const char* what) {
+  OFA_REQUIRE(njobs >= 0 && (njobs == 0 || jobs), OFA_ERR_INVALID, "%s: bad argument", what);
   hipStream_t st = (hipStream_t)stream;
   for (int base = 0; base < njobs; base += COPY_MAX_JOBS) {
     CopyJobs J;
@@ -256,9 +283,9 @@ extern "C" int ofa_copy_batched(const ofa_copy_job* jobs, int njobs, void* strea
     unsigned blocks = 0;
     for (int i = 0; i < n; ++i) {
       const ofa_copy_job& b = jobs[base + i];
-      OFA_REQUIRE(b.bytes >= 0 && (b.bytes == 0 || (b.src && b.dst)), OFA_ERR_INVALID, "copy_batched: bad job %d", base + i);
+      OFA_REQUIRE(b.bytes >= 0 && (b.bytes == 0 || (b.dst && (ZERO || b.src))), OFA_ERR_INVALID, "%s: bad job %d", what, base + i);
       if (b.bytes == 0) continue;
-      J.src[m] = (const unsigned char*)b.src; J.dst[m] = (unsigned char*)b.dst; J.bytes[m] = b.bytes;
+      J.src[m] = ZERO ? nullptr : (const unsigned char*)b.src; J.dst[m] = (unsigned char*)b.dst; J.bytes[m] = b.bytes;
       J.block0[m] = blocks;
       blocks += (unsigned)((b.bytes + COPY_CHUNK - 1) / COPY_CHUNK);
       ++m;
@@ -266,11 +293,20 @@ extern "C" int ofa_copy_batched(const ofa_copy_job* jobs, int njobs, void* strea
     if (m == 0) continue;
     J.block0[m] = blocks;
     J.njobs = m;
-    hipLaunchKernelGGL(copy_batched_kernel, dim3(blocks), dim3(256), 0, st, J);
-    int rc = check_launch("copy_batched");
+    if (ZERO) hipLaunchKernelGGL(zero_batched_kernel, dim3(blocks), dim3(256), 0, st, J);
+    else hipLaunchKernelGGL(copy_batched_kernel, dim3(blocks), dim3(256), 0, st, J);
+    int rc = check_launch(what);
     if (rc) return rc;
   }
   return 0;
+}
+
+extern "C" int ofa_zero_batched(const ofa_copy_job* jobs, int njobs, void* stream) {
+  return copy_jobs_launch<true>(jobs, njobs, stream, "zero_batched");
+}
+
+extern "C" int ofa_copy_batched(const ofa_copy_job* jobs, int njobs, void* stream) {
+  return copy_jobs_launch<false>(jobs, njobs, stream, "copy_batched");
 }
 
 extern "C" int ofa_fold_batched(const ofa_fold_job* jobs, int njobs, void* stream) {

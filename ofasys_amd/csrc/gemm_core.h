@@ -543,7 +543,8 @@ __host__ __device__ constexpr int big_read_after(int t, int nr) { return t < nr 
 constexpr int GROUP_MAX = 16;                  // (two layers' worth of weight gradients: 2 x 6 for a decoder layer)
 struct GroupItem {
   const void* A; const void* B; float* ws;
-  void* out; int64_t ldo; float alpha;     // out != nullptr: ONE K-slice, accumulated straight onto out (16-bit) in the epilogue
+  void* out; int64_t ldo; float alpha;     // out != nullptr: ONE K-slice, straight onto out (16-bit) in the epilogue ...
+  int store;                               // ... added to what is there (0) or written over it (1: the gradient's first writer of the step)
   int64_t lda, ldb;
   int M, N, K, krows, ksplit, splits, tiles_m, tiles_n, first;   // K: rounded up to whole K tiles, krows: the real row count; first: index of the item's first workgroup
 };
@@ -564,7 +565,7 @@ __device__ __forceinline__ const GroupItem* group_enter(const GroupArgs& ga, Gem
   g.A = it.A; g.B = it.B; g.C = it.out; g.bias = nullptr;
   g.M = it.M; g.N = it.N; g.K = it.K; g.transA = 1; g.transB = 0;
   g.lda = it.lda; g.ldb = it.ldb; g.ldc = it.ldo; g.strideA = g.strideB = g.strideC = 0;
-  g.alpha = it.out ? it.alpha : 1.f; g.flags = it.out ? OFA_GEMM_ACCUM : 0; g.batch_inner = 1; g.strideA2 = g.strideB2 = g.strideC2 = 0; g.a_krows = g.b_krows = it.krows;
+  g.alpha = it.out ? it.alpha : 1.f; g.flags = (it.out && !it.store) ? OFA_GEMM_ACCUM : 0; g.batch_inner = 1; g.strideA2 = g.strideB2 = g.strideC2 = 0; g.a_krows = g.b_krows = it.krows;
   g.colstat = nullptr; g.colstat_rows = 0;
   const int ntiles = it.tiles_m * it.tiles_n, local = id - it.first;
   ks = local / ntiles;

@@ -1242,7 +1242,7 @@ extern "C" int ofa_gemm_group_tn(const ofa_gemm_group_item* items, int n, int dt
     OFA_REQUIRE(it.splits >= 1 && it.splits <= 32, OFA_ERR_INVALID, "gemm_group: product %d: splits %d (run ofa_gemm_group_plan)", p, it.splits);
     GroupItem& d = ga.it[p];
     d.A = it.a; d.B = it.b; d.ws = it.slabs; d.lda = it.lda; d.ldb = it.ldb;
-    d.out = direct ? it.out : nullptr; d.ldo = it.ldo; d.alpha = it.out_alpha;
+    d.out = direct ? it.out : nullptr; d.ldo = it.ldo; d.alpha = it.out_alpha; d.store = it.store != 0;
     d.M = it.m; d.N = it.n; d.K = cdiv(it.k, BK) * BK; d.krows = it.k;
     d.ksplit = cdiv(cdiv(it.k, BK), it.splits) * BK;
     d.splits = it.splits;

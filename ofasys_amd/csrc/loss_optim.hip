@@ -124,12 +124,13 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const T* __restrict__ logit
 template <typename T, int NV>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void ce_fwd_grad_kernel(
     const T* __restrict__ logits, const int64_t* __restrict__ target, const float* __restrict__ gscale, float* __restrict__ lse,
-    float* __restrict__ row_loss, T* __restrict__ dlogits, int V, int ld, int64_t ignore_index) {
+    float* __restrict__ row_loss, T* __restrict__ dlogits, int V, int ld, int64_t ignore_index, float* __restrict__ loss_out,
+    double* __restrict__ stats, unsigned* __restrict__ ticket) {
   // (two blocks per CU -- 64 registers -- so that one block's loads and stores overlap the other's arithmetic: with one, 141 us at cfg-2
   // against 118 for the two kernels it replaces.  32-bit indices and scalar-base + 32-bit-offset addressing keep it there.)
   constexpr int N = Vec<T>::N;
   static_assert(N == 8, "16-bit element types");
-  __shared__ float sm[16], ss[16];
+  __shared__ float sm[17], ss[16];                       // (sm[16]: the fused statistics' "this block drew the last ticket")
   const int64_t row = blockIdx.x;
   const char* xb = reinterpret_cast<const char*>(logits + row * ld);       // (uniform: scalar registers)
   char* db = reinterpret_cast<char*>(dlogits + row * ld);
@@ -178,7 +179,18 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void 
   const bool dead = ignored || t < 0;
   if (tid == 0) {
     lse[row] = l;
-    row_loss[row] = ignored ? 0.f : t < 0 ? INFINITY : l - ld1<T>(reinterpret_cast<const T*>(xb) + t);
+    const float rl = ignored ? 0.f : t < 0 ? INFINITY : l - ld1<T>(reinterpret_cast<const T*>(xb) + t);
+    // (fused statistics: a write-through store, which the last block's agent-scope loads see without a fence in every block)
+    if (ticket) {
+      // The ticket counts PUBLISHED ROW LOSSES, not finished blocks: it is drawn here, before the gradient row is written, so that its
+      // round trip (and the store's acknowledgement before it) hides under this block's stores instead of lengthening every block by
+      // it (ticket at the end: 67.4 -> 71.0 us at cfg-2).  The statistics need the row losses and the targets, nothing else.
+      __hip_atomic_store(row_loss + row, rl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      sm[16] = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1.f : 0.f;
+    } else {
+      row_loss[row] = rl;
+    }
   }
   const float g = dead ? 0.f : (gscale ? gscale[0] : 1.0f);
   const Exp2Fma prob(l);                                 // exp(x - lse)
@@ -198,6 +210,41 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void 
     uint4 w;
     w.x = pack2<T>(o[0], o[1]); w.y = pack2<T>(o[2], o[3]); w.z = pack2<T>(o[4], o[5]); w.w = pack2<T>(o[6], o[7]);
     *reinterpret_cast<uint4*>(db + (uint32_t)v * 16u) = w;
+  }
+  if (!ticket) return;
+  // Fused statistics (ticket != NULL): the block that drew the LAST ticket (above) sums the row losses in reduce_sum_f32_kernel's order
+  // (256 lanes striding the rows, wave sums, the four wave results in order), writes the loss and adds [count of target != ignore_index,
+  // loss, the same count] to stats as step_stats_add_kernel does -- two single-block launches less -- and resets the ticket.  Thread 0
+  // stored its row loss write-through and had the store acknowledged before it drew; the rows are read with agent-scope loads.  No
+  // __threadfence(): a release fence in each of the 1792 cfg-2 blocks writes back an L2 full of gradient rows -- measured 67 -> 155 us.
+  // What this rests on: on gfx950 an agent-scope relaxed atomic store is a write-through (sc1) store and an agent-scope relaxed atomic
+  // load an sc1 load, which is served from the memory side of the XCDs' L2s, never from a line another XCD's store left stale; EVERY
+  // load of row_loss below is such a load, so no acquire (cache invalidate) is needed for them.  That is this part's measured behaviour
+  // and what hipcc emits for these builtins today, not a guarantee of the memory model: relaxed atomics order nothing by themselves,
+  // the s_waitcnt between the store's acknowledgement and the ticket does.
+  __syncthreads();                                       // (sm[16] is written; every thread is long done with sm[0..15] / ss)
+  if (sm[16] == 0.f) return;                             // (uniform over the block)
+  const int64_t rows = gridDim.x;
+  float ls_ = 0.f;
+  int cnt = 0;
+  if (tid < 256)
+    for (int64_t i = tid; i < rows; i += 256) {
+      ls_ += __hip_atomic_load(row_loss + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      cnt += target[i] != ignore_index;
+    }
+  ls_ = wave_sum(ls_);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  if (tid < 256 && (tid & 63) == 0) { ss[tid >> 6] = ls_; sm[tid >> 6] = __int_as_float(cnt); }
+  __syncthreads();
+  if (tid == 0) {
+    const float loss = ss[0] + ss[1] + ss[2] + ss[3];
+    const double c = (double)(__float_as_int(sm[0]) + __float_as_int(sm[1]) + __float_as_int(sm[2]) + __float_as_int(sm[3]));
+    loss_out[0] = loss;
+    stats[0] += c;
+    stats[1] += (double)loss;
+    stats[2] += c;
+    *ticket = 0u;
   }
 }
 
@@ -780,13 +827,12 @@ __global__ __launch_bounds__(256) void ema_segments_kernel(S* __restrict__ state
 // gradient norm is not finite or the step saw no target token (sample_size <= 0), sched = [0, 0, lr, 1] -- ofa_adam_step(step = 0)
 // then returns without touching master weights or moments -- the update counter does not advance, and sched[4] (a running count
 // of skipped updates) is incremented for the host to poll.
-__global__ void step_schedule_kernel(const float* __restrict__ gsq, const double* __restrict__ sample_size,
-                                     double* __restrict__ step, const double* __restrict__ lr, float* __restrict__ sched,
-                                     float* __restrict__ gnorm, float clip_norm, double beta1, double beta2) {
-  if (threadIdx.x || blockIdx.x) return;
+__device__ __forceinline__ void step_schedule_one(float gsq0, const double* __restrict__ sample_size, double* __restrict__ step,
+                                                  const double* __restrict__ lr, float* __restrict__ sched, float* __restrict__ gnorm,
+                                                  float clip_norm, double beta1, double beta2) {
   const double n = sample_size[0];
   const float inv_n = n > 0.0 ? (float)(1.0 / n) : 0.f;
-  const float gn = sqrtf(gsq[0]) * inv_n;
+  const float gn = sqrtf(gsq0) * inv_n;
   gnorm[0] = n > 0.0 ? gn : __builtin_nanf("");
   if (!(n > 0.0) || !isfinite(gn)) {
     sched[0] = 0.f;
@@ -807,6 +853,12 @@ __global__ void step_schedule_kernel(const float* __restrict__ gsq, const double
   sched[2] = (float)lr[0];
   gnorm[0] = gn;
 }
+__global__ void step_schedule_kernel(const float* __restrict__ gsq, const double* __restrict__ sample_size,
+                                     double* __restrict__ step, const double* __restrict__ lr, float* __restrict__ sched,
+                                     float* __restrict__ gnorm, float clip_norm, double beta1, double beta2) {
+  if (threadIdx.x || blockIdx.x) return;
+  step_schedule_one(gsq[0], sample_size, step, lr, sched, gnorm, clip_norm, beta1, beta2);
+}
 
 // The scaled-loss variant of step_schedule_kernel: engine/optim/fp16_optimizer.py:170-204 + dynamic_loss_scaler.py:9-70 in one
 // device thread.  `ls` (fp64[8]) = [loss_scale, iter, last_overflow_iter, last_rescale_iter, overflows_since_rescale, fatal,
@@ -820,16 +872,15 @@ __global__ void step_schedule_kernel(const float* __restrict__ gsq, const double
 //       ++iter; the update is SKIPPED (trainer.py catches OverflowError and zeroes the grads)
 //   otherwise update() (:33-37): if (iter - last_overflow_iter) % scale_window == 0: loss_scale *= factor,
 //       last_rescale_iter = iter; ++iter.
-__global__ void step_schedule_scaled_kernel(const float* __restrict__ gsq, const double* __restrict__ sample_size,
-                                            double* __restrict__ step, const double* __restrict__ lr, float* __restrict__ sched,
-                                            float* __restrict__ gnorm, double* __restrict__ ls, float clip_norm, double beta1,
-                                            double beta2, double scale_factor, double scale_window, double tolerance,
-                                            double threshold, double min_loss_scale) {
-  if (threadIdx.x || blockIdx.x) return;
+__device__ __forceinline__ void step_schedule_scaled_one(float gsq0, const double* __restrict__ sample_size, double* __restrict__ step,
+                                                         const double* __restrict__ lr, float* __restrict__ sched,
+                                                         float* __restrict__ gnorm, double* __restrict__ ls, float clip_norm,
+                                                         double beta1, double beta2, double scale_factor, double scale_window,
+                                                         double tolerance, double threshold, double min_loss_scale) {
   const double n = sample_size[0];
   const double scale = ls[0];
   double mf = n > 0.0 ? 1.0 / (scale * n) : 0.0;
-  const float gn = (float)(mf * sqrt((double)gsq[0]));
+  const float gn = (float)(mf * sqrt((double)gsq0));
   gnorm[0] = n > 0.0 ? gn : __builtin_nanf("");
   if (!(n > 0.0)) {                              // an EMPTY batch is not an overflow: skip the update, leave the scaler's state alone
     sched[0] = 0.f;                              // (the reference's scaler only reacts to an inf / nan norm, dynamic_loss_scaler.py:44-70)
@@ -880,6 +931,72 @@ __global__ void step_schedule_scaled_kernel(const float* __restrict__ gsq, const
   }
   ls[1] = it + 1.0;
 }
+__global__ void step_schedule_scaled_kernel(const float* __restrict__ gsq, const double* __restrict__ sample_size,
+                                            double* __restrict__ step, const double* __restrict__ lr, float* __restrict__ sched,
+                                            float* __restrict__ gnorm, double* __restrict__ ls, float clip_norm, double beta1,
+                                            double beta2, double scale_factor, double scale_window, double tolerance,
+                                            double threshold, double min_loss_scale) {
+  if (threadIdx.x || blockIdx.x) return;
+  step_schedule_scaled_one(gsq[0], sample_size, step, lr, sched, gnorm, ls, clip_norm, beta1, beta2, scale_factor, scale_window,
+                           tolerance, threshold, min_loss_scale);
+}
+
+// The gradient norm's sum of squares, its final fold and the step's scalar schedule in ONE launch: sumsq_kernel's blocks, and the
+// LAST block to finish (a ticket drawn once the block's write-through partial is acknowledged; it resets the ticket itself) folds the block partials in
+// sumsq_final_kernel's order, then runs step_schedule_one / step_schedule_scaled_one and the Philox counter add that followed as
+// launches of their own.  gsq[0] is written, not added to: it needs no clearing and holds what the separate launches leave there.
+struct SchedArgs {
+  const double* sample_size; double* step; const double* lr; float* sched; float* gnorm; double* ls;   // ls NULL: no loss scaler
+  int64_t* counter; int64_t counter_add;                                                                // counter NULL: none
+  float clip_norm; double beta1, beta2, scale_factor, scale_window, tolerance, threshold, min_loss_scale;
+};
+template <typename T>
+__global__ __launch_bounds__(256) void sumsq_schedule_kernel(const T* __restrict__ x, float* __restrict__ partial,
+                                                             float* __restrict__ gsq, unsigned* __restrict__ ticket, int64_t n,
+                                                             SchedArgs a) {
+  constexpr int N = Vec<T>::N;
+  __shared__ float sw[4];
+  __shared__ float fin[4];
+  float s = 0.f;
+  const int64_t nvec = n / N;
+  for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * 256) {
+    float e[N];
+    load_vec<T>(x + v * N, e);
+#pragma unroll
+    for (int j = 0; j < N; ++j) s += e[j] * e[j];
+  }
+  if (blockIdx.x == 0)
+    for (int64_t e = nvec * N + threadIdx.x; e < n; e += 256) { const float q = ld1<T>(x + e); s += q * q; }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    // a write-through store of the partial, its acknowledgement, then the ticket (relaxed, agent scope): the last arriver reads the
+    // partials with agent-scope loads.  (With __threadfence() on both sides the kernel took 105 us instead of 58: DESIGN.md 5p.
+    // The same hand-off, resting on the same measured gfx950 behaviour, as ce_fwd_grad_kernel's statistics tail: see there.)
+    __hip_atomic_store(partial + blockIdx.x, sw[0] + sw[1] + sw[2] + sw[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const bool last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1;
+    fin[0] = last ? 1.f : 0.f;
+  }
+  __syncthreads();
+  if (fin[0] == 0.f) return;                               // (uniform over the block)
+  const int nb = (int)gridDim.x;
+  float t = 0.f;
+  for (int i = threadIdx.x; i < nb; i += 256) t += __hip_atomic_load(partial + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  t = wave_sum(t);
+  if ((threadIdx.x & 63) == 0) sw[threadIdx.x >> 6] = t;   // (sw was last read before the barrier above)
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float total = 0.f + (sw[0] + sw[1] + sw[2] + sw[3]);   // (sumsq_final_kernel adds onto a cleared gsq)
+    gsq[0] = total;
+    if (a.ls) step_schedule_scaled_one(total, a.sample_size, a.step, a.lr, a.sched, a.gnorm, a.ls, a.clip_norm, a.beta1, a.beta2,
+                                       a.scale_factor, a.scale_window, a.tolerance, a.threshold, a.min_loss_scale);
+    else step_schedule_one(total, a.sample_size, a.step, a.lr, a.sched, a.gnorm, a.clip_norm, a.beta1, a.beta2);
+    if (a.counter) a.counter[0] += a.counter_add;
+    *ticket = 0u;
+  }
+}
 }  // namespace ofa
 using namespace ofa;
 
@@ -900,9 +1017,10 @@ extern "C" int ofa_cross_entropy_fwd(const void* logits, const int64_t* target, 
 // the whole row lives in the block's registers: NV vectors of 8 per thread, 1024 threads
 template <typename T>
 static bool ce_fwd_grad_launch(const T* logits, const int64_t* target, const float* gs, float* lse, float* row_loss, T* dlogits,
-                               int64_t rows, int64_t V, int64_t ld, int64_t ignore_index, hipStream_t st) {
+                               int64_t rows, int64_t V, int64_t ld, int64_t ignore_index, hipStream_t st, float* loss_out = nullptr,
+                               double* stats = nullptr, unsigned* ticket = nullptr) {
   const int64_t per_thread = (ld / 8 + 1023) / 1024;
-#define CE_FG(NV) hipLaunchKernelGGL((ce_fwd_grad_kernel<T, NV>), dim3((unsigned)rows), dim3(1024), 0, st, logits, target, gs, lse, row_loss, dlogits, (int)V, (int)ld, ignore_index)
+#define CE_FG(NV) hipLaunchKernelGGL((ce_fwd_grad_kernel<T, NV>), dim3((unsigned)rows), dim3(1024), 0, st, logits, target, gs, lse, row_loss, dlogits, (int)V, (int)ld, ignore_index, loss_out, stats, ticket)
   if (per_thread <= 1) CE_FG(1);
   else if (per_thread <= 2) CE_FG(2);
   else if (per_thread <= 4) CE_FG(4);
@@ -931,6 +1049,24 @@ extern "C" int ofa_cross_entropy_fwd_grad(const void* logits, const int64_t* tar
   });
   OFA_REQUIRE(ok, OFA_ERR_UNSUPPORTED, "cross_entropy_fwd_grad: row too long");
   return check_launch("cross_entropy_fwd_grad");
+}
+
+extern "C" int ofa_cross_entropy_fwd_grad_stats(const void* logits, const int64_t* target, const float* grad_scale, float* lse,
+                                                float* row_loss, void* dlogits, int64_t rows, int64_t V, int64_t ld,
+                                                int64_t ignore_index, int dtype, float* loss, double* stats, unsigned int* ticket,
+                                                void* stream) {
+  OFA_REQUIRE(ofa_cross_entropy_fwd_grad_ok(V, ld, dtype), OFA_ERR_UNSUPPORTED,
+              "cross_entropy_fwd_grad_stats: 16-bit logits of at most 65536 (padded) columns, ld a multiple of 8 (V=%lld ld=%lld dtype=%d)", (long long)V, (long long)ld, dtype);
+  OFA_REQUIRE(rows >= 1 && logits && target && lse && row_loss && dlogits && loss && stats && ticket, OFA_ERR_INVALID,
+              "cross_entropy_fwd_grad_stats: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  const bool ok = dispatch_dtype16(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return ce_fwd_grad_launch<T>((const T*)logits, target, grad_scale, lse, row_loss, (T*)dlogits, rows, V, ld, ignore_index, st, loss,
+                                 stats, ticket);
+  });
+  OFA_REQUIRE(ok, OFA_ERR_UNSUPPORTED, "cross_entropy_fwd_grad_stats: row too long");
+  return check_launch("cross_entropy_fwd_grad_stats");
 }
 
 extern "C" int ofa_cross_entropy_bwd(const void* logits, const int64_t* target, const float* lse, const float* grad_scale,
@@ -1069,6 +1205,29 @@ extern "C" int ofa_sumsq(const void* x, float* out, float* ws, int64_t n, int dt
   if (rc) return rc;
   hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, st, (const float*)ws, out, nb);
   return check_launch("sumsq_final");
+}
+
+extern "C" int ofa_sumsq_schedule(const void* x, float* gsq, float* ws, unsigned int* ticket, int64_t n, int dtype,
+                                  const double* sample_size, double* step, const double* lr, float* sched, float* gnorm,
+                                  double* loss_scaler, int64_t* counter, int64_t counter_add, float clip_norm, double beta1,
+                                  double beta2, double scale_factor, double scale_window, double tolerance, double threshold,
+                                  double min_loss_scale, void* stream) {
+  OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "sumsq_schedule: bad dtype %d", dtype);
+  OFA_REQUIRE(n >= 1 && x && gsq && ws && ticket && sample_size && step && lr && sched && gnorm, OFA_ERR_INVALID,
+              "sumsq_schedule: bad argument");
+  OFA_REQUIRE(!loss_scaler || (scale_factor > 1.0 && scale_window >= 1.0 && min_loss_scale >= 0.0), OFA_ERR_INVALID,
+              "sumsq_schedule: bad scaler configuration");
+  hipStream_t st = (hipStream_t)stream;
+  const int vecw = dt_vecn(dtype);
+  int64_t nbl = (n / vecw + 255) / 256;
+  const int nb = (int)(nbl < 1 ? 1 : (nbl > 1024 ? 1024 : nbl));                 // (ofa_sumsq's grid: the same partials)
+  SchedArgs a{sample_size, step, lr, sched, gnorm, loss_scaler, counter, counter_add, clip_norm, beta1, beta2,
+              scale_factor, scale_window, tolerance, threshold, min_loss_scale};
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((sumsq_schedule_kernel<T>), dim3(nb), dim3(256), 0, st, (const T*)x, ws, gsq, ticket, n, a);
+  });
+  return check_launch("sumsq_schedule");
 }
 
 extern "C" int ofa_adam_step(float* master, float* exp_avg, float* exp_avg_sq, const void* grad, void* model_param,

@@ -70,6 +70,45 @@ def copy_batched(pairs):
         lib().call("ofa_copy_batched", ctypes.addressof(arr), len(jobs), stream())
 
 
+def zero_batched(bufs):
+    """Zero fill of every (device address, bytes) in `bufs` in ONE launch per 96 (ofa_zero_batched)."""
+    if bufs:
+        arr = (_CopyJob * len(bufs))()
+        for it, (d_, n) in zip(arr, bufs):
+            it.src, it.dst, it.bytes = None, d_, n
+        lib().call("ofa_zero_batched", ctypes.addressof(arr), len(bufs), stream())
+
+
+# First-touch gradient writes.  A launch that ADDS its result to `out` (accumulate=True) asks `grad_mode(out, full)` -- installed by
+# ops.py, which keeps the step's touched set -- at the moment it is issued: False = this launch is the first full writer of that
+# gradient-arena view in the step and STORES (what is there is not read); True = add.  full=False: the launch writes only part of
+# `out`.  Outputs that are no arena gradient (and everything outside a train step) always add.  None: nothing installed, always add.
+grad_mode = None
+
+
+def _accum(out, accumulate, full=True):
+    if grad_mode is None:
+        return bool(accumulate)
+    if accumulate:
+        return bool(grad_mode(out, full))
+    grad_mode(out, full, store=True)                 # a plain store into an arena gradient is a writer too: the range is marked
+    return False
+
+
+def _accum_all(outs):
+    """_accum for a launch with ONE accumulate flag over several gradient outputs: they store only together (an output that alone
+    would have stored is cleared first and added to)."""
+    if grad_mode is None:
+        return True
+    if all(grad_mode(o, True, peek=True) is False for o in outs):
+        for o in outs:
+            grad_mode(o, True)
+        return False
+    for o in outs:                                   # mixed: each asks as a partial writer (cleared on demand, learned for the next step)
+        grad_mode(o, False)
+    return True
+
+
 DEFER_FOLD = 2            # OFA_DEFER_FOLD
 FOLD_LANES16 = 4          # OFA_FOLD_LANES16
 GEMM_DEFER_REDUCE = 128   # OFA_GEMM_DEFER_REDUCE
@@ -86,6 +125,7 @@ class FoldQueue:
 
     def __init__(self):
         self.jobs, self.keep, self.bytes, self.outs, self.want_flush = [], [], 0, set(), False
+        self.modes = []                              # per job: (accumulate asked for, the other flag bits)
 
     def add(self, part, part_off, out, cols, stride, nslots, alpha=1.0, accumulate=True, flush_ok=True, lanes16=False):
         """lanes16: sum the slots in the order of ofa_colsum's own final pass (OFA_FOLD_LANES16)."""
@@ -97,6 +137,7 @@ class FoldQueue:
         self.outs.add(out.data_ptr())
         self.jobs.append(_FoldJob(dptr(part) + part_off * 4, dptr(out), cols, stride, nslots,
                                   int(bool(accumulate)) | (FOLD_LANES16 if lanes16 else 0), float(alpha), dtype_code(out)))
+        self.modes.append((bool(accumulate), FOLD_LANES16 if lanes16 else 0))
         self.keep.append((part, out))
         self.bytes += nslots * stride * 4
         self.want_flush = self.bytes > self.MAX_PENDING_BYTES
@@ -109,9 +150,12 @@ class FoldQueue:
     def flush(self):
         if not self.jobs:
             return
+        for job, (_, out), (want, bits) in zip(self.jobs, self.keep, self.modes):     # store or add: decided HERE, where the launch is issued
+            job.accumulate = int(_accum(out, want)) | bits
         arr = (_FoldJob * len(self.jobs))(*self.jobs)
         lib().call("ofa_fold_batched", ctypes.addressof(arr), len(self.jobs), stream())
         self.jobs, self.keep, self.bytes, self.want_flush = [], [], 0, False   # (same stream: buffers may be reused)
+        self.modes = []
         self.outs = set()
 
 
@@ -122,7 +166,7 @@ class ImmediateFold:
     def add(self, part, part_off, out, cols, stride, nslots, alpha=1.0, accumulate=True, flush_ok=True, lanes16=False):
         assert part.dtype == torch.float32 and out.is_contiguous()
         job = (_FoldJob * 1)(_FoldJob(dptr(part) + part_off * 4, dptr(out), cols, stride, nslots,
-                                      int(bool(accumulate)) | (FOLD_LANES16 if lanes16 else 0), float(alpha), dtype_code(out)))
+                                      int(_accum(out, accumulate)) | (FOLD_LANES16 if lanes16 else 0), float(alpha), dtype_code(out)))
         lib().call("ofa_fold_batched", ctypes.addressof(job), 1, stream())
 
     def flush_if_large(self):
@@ -178,6 +222,8 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, fuse_gelu=False, dgamma=None, dbeta=
         acc = DEFER_FOLD
     else:
         ws = workspace(wsr * cols * 4, x.device, "ln")
+        if acc:
+            acc = _accum_all([o for o in (dgamma, dbeta, dbias if fuse_gelu else None) if o is not None])
     if fuse_gelu:
         lib().call("ofa_gelu_layernorm_bwd", ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx), ptr(dgamma),
                    ptr(dbeta), ptr(dbias), ptr(ws), rows, cols, int(acc), dtype_code(x), stream())
@@ -237,12 +283,14 @@ def gemm(a, b, trans_a=False, trans_b=False, bias=None, bias_row=False, alpha=1.
         nsp = lib().cdll.ofa_gemm_splits(M, N, K, int(trans_a), int(trans_b), 1, flags, dt, 256 << 20)
         if nsp > 1:
             ws = torch.empty(nsp * M * N, dtype=torch.float32, device=a.device)
-            fold.add(ws, 0, out, M * N, M * N, nsp, alpha, accumulate)
+            fold.add(ws, 0, out, M * N, M * N, nsp, alpha, accumulate)      # (store or add: the fold's decision, at its flush)
             flags |= GEMM_DEFER_REDUCE
             ws_bytes = 256 << 20            # (the planner saw this budget; the slabs themselves fit by construction)
     if ws is None:
         ws = workspace(256 << 20, a.device, "gemm")
         ws_bytes = ws.numel() * 4
+        if not _accum(out, accumulate, full=ldc == N and (not batched or sc == M * N)):
+            flags &= ~GEMM_ACCUM            # the first full writer of an arena gradient in this step (or a plain store): store
     args = ("ofa_gemm", ptr(a), ptr(b), ptr(out), ptr(bias), M, N, K, int(trans_a), int(trans_b), lda, ldb, ldc, batch,
             sa, sb, sc, 0, 0, 0, 0, float(alpha), flags, dt, ptr(ws), ws_bytes, stream())
     if _prof is not None:
@@ -296,7 +344,8 @@ def gemm_colstat(a, b, bias=None, max_groups=512):
 class _GroupItem(ctypes.Structure):     # ofa_gemm_group_item
     _fields_ = [("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("slabs", ctypes.c_void_p), ("lda", ctypes.c_int64),
                 ("ldb", ctypes.c_int64), ("m", ctypes.c_int32), ("n", ctypes.c_int32), ("k", ctypes.c_int32),
-                ("splits", ctypes.c_int32), ("out", ctypes.c_void_p), ("ldo", ctypes.c_int64), ("out_alpha", ctypes.c_float)]
+                ("splits", ctypes.c_int32), ("out", ctypes.c_void_p), ("ldo", ctypes.c_int64), ("out_alpha", ctypes.c_float),
+                ("store", ctypes.c_int32)]
 
 
 GROUP_MAX = 16
@@ -336,6 +385,7 @@ def gemm_group_tn(products, fold):
         if direct:                                                                         #  must not share a launch)
             direct_outs.add(out.data_ptr())
             it.out, it.ldo, it.out_alpha = dptr(out), out.stride(0), float(alpha)
+            it.store = int(not _accum(out, True, full=out.is_contiguous()))      # (a slab product's fold job decides at its flush)
             slabs.append(None)
         else:
             sl = torch.empty(it.splits * it.m * it.n, dtype=torch.float32, device=dy.device)
@@ -512,7 +562,7 @@ def c_attn_grad(delta, c_attn, B, heads, T, out=None, accumulate=False):
     if out is None:
         out = torch.empty_like(c_attn)
         accumulate = False
-    lib().call("ofa_c_attn_grad", ptr(delta), ptr(c_attn), ptr(out), B, heads, T, delta.stride(0), int(accumulate),
+    lib().call("ofa_c_attn_grad", ptr(delta), ptr(c_attn), ptr(out), B, heads, T, delta.stride(0), int(_accum(out, accumulate)),
                dtype_code(c_attn), stream())
     return out
 
@@ -779,7 +829,7 @@ def batch_sum(x, batch, out=None, accumulate=False):
     if out is None:
         out = torch.empty(n, dtype=x.dtype, device=x.device)
         accumulate = False
-    lib().call("ofa_batch_sum", ptr(x), ptr(out), int(batch), n, int(bool(accumulate)), dtype_code(x), stream())
+    lib().call("ofa_batch_sum", ptr(x), ptr(out), int(batch), n, int(_accum(out, accumulate)), dtype_code(x), stream())
     return out
 
 
@@ -829,6 +879,15 @@ def scatter_rows_part(dpacked, inverse, B, nk, Ttot, start):
     return out
 
 
+# items of the debug library's OFA_STEP_TAIL_OLD mask (include/ofasys_amd.h: OFA_TAIL_*)
+TAIL_FIRST_TOUCH, TAIL_NORM_SCHEDULE, TAIL_CRITERION_STATS = 0, 1, 2
+
+
+def tail_old(item):
+    """Debug library with OFA_STEP_TAIL_OLD set: the gradient plumbing around the optimizer as it ran before (A/B runs); else False."""
+    return bool(lib().cdll.ofa_step_tail_old(int(item)))
+
+
 # items of the debug library's OFA_STEP_EDGES_OLD mask (include/ofasys_amd.h: OFA_EDGE_*)
 EDGE_POS_RANGE, EDGE_TOKEN_BWD, EDGE_COLSUM_FOLD, EDGE_IM2COL = 0, 1, 2, 3
 
@@ -846,6 +905,8 @@ def embedding_bwd(dout, ids, V, padding_idx=-1, dweight=None, id_major=None):
     D = dout.shape[-1]
     if dweight is None:
         dweight = torch.zeros(V, D, dtype=dout.dtype, device=dout.device)
+    else:
+        _accum(dweight, True, full=False)            # touches the rows of the ids only: a partial writer always adds
     S = lib().cdll.ofa_embedding_bwd_slices(V, D)
     pad = -1 if padding_idx is None else padding_idx
     if id_major is None:
@@ -873,6 +934,7 @@ def embedding_range_bwd(dout, dweight, r0, T):
     V, D = dweight.shape
     batch = dout.numel() // (T * D)
     assert dweight.is_contiguous() and dweight.dtype == dout.dtype and batch * T * D == dout.numel()
+    _accum(dweight, True, full=False)                # rows r0 .. r0 + T - 1 only: a partial writer always adds
     lib().call("ofa_embedding_range_bwd", ptr(dout), ptr(dweight), batch, T, D, V, int(r0), dtype_code(dout), stream())
     return dweight
 
@@ -880,6 +942,8 @@ def embedding_range_bwd(dout, dweight, r0, T):
 def segment_rowsum(dout2d, plan, dweight, accumulate):
     """dweight[plan.rows[s]] (+)= sum of the rows of dout2d in segment s (ofa_segment_rowsum); plan: ops.SegmentPlan."""
     assert dout2d.dim() == 2 and dout2d.is_contiguous() and dweight.is_contiguous() and dout2d.dtype == dweight.dtype
+    if accumulate:
+        _accum(dweight, True, full=False)            # the rows of the plan's ids only: a partial writer always adds
     lib().call("ofa_segment_rowsum", ptr(dout2d), ptr(plan.order), ptr(plan.seg_off), ptr(plan.seg_row), ptr(dweight), plan.nseg,
                dout2d.shape[1], int(accumulate), dtype_code(dout2d), stream())
     return dweight
@@ -917,13 +981,22 @@ def cross_entropy_fwd_grad_ok(logits2d, V):
     return logits2d.is_cuda and bool(lib().cdll.ofa_cross_entropy_fwd_grad_ok(int(V), int(logits2d.stride(0)), dtype_code(logits2d)))
 
 
-def cross_entropy_fwd_grad(logits2d, target, grad_scale, V, ignore_index):
+def cross_entropy_fwd_grad(logits2d, target, grad_scale, V, ignore_index, stats=None, ticket=None):
     """lse, row_loss AND dlogits = (softmax - onehot) * grad_scale[0] in one pass over the logits (ofa_cross_entropy_fwd_grad):
-    grad_scale is the fp32 device scalar the backward pass will be seeded with (None: 1)."""
+    grad_scale is the fp32 device scalar the backward pass will be seeded with (None: 1).
+    stats (fp64[3]) + ticket (one int32 device word, 0 before the first call): the kernel's last block also sums the row losses and adds
+    [non-ignored targets, loss, non-ignored targets] to stats (ofa_cross_entropy_fwd_grad_stats); returns (lse, row_loss, dlogits, loss)."""
     rows, ld = logits2d.shape[0], logits2d.stride(0)
     lse = torch.empty(rows, dtype=torch.float32, device=logits2d.device)
     row_loss = torch.empty(rows, dtype=torch.float32, device=logits2d.device)
     dlogits = torch.empty(rows, ld, dtype=logits2d.dtype, device=logits2d.device)
+    if stats is not None:
+        assert stats.dtype == torch.float64 and stats.numel() >= 3 and ticket.dtype == torch.int32 and rows >= 1
+        assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == rows
+        loss = torch.empty((), dtype=torch.float32, device=logits2d.device)
+        lib().call("ofa_cross_entropy_fwd_grad_stats", ptr(logits2d), ptr(target), ptr(grad_scale), ptr(lse), ptr(row_loss), ptr(dlogits),
+                   rows, V, ld, ignore_index, dtype_code(logits2d), ptr(loss), ptr(stats), ptr(ticket), stream())
+        return lse, row_loss, dlogits, loss
     lib().call("ofa_cross_entropy_fwd_grad", ptr(logits2d), ptr(target), ptr(grad_scale), ptr(lse), ptr(row_loss), ptr(dlogits), rows, V,
                ld, ignore_index, dtype_code(logits2d), stream())
     return lse, row_loss, dlogits
@@ -1006,6 +1079,19 @@ def sumsq(x, out):
     return out
 
 
+def sumsq_schedule(x, gsq, ticket, sample_size, step, lr, sched, gnorm, clip_norm, beta1, beta2, loss_scaler=None, scale_factor=2.0,
+                   scale_window=2000, tolerance=0.0, threshold=None, min_loss_scale=1e-4, counter=None, counter_add=0):
+    """sumsq(x) -> gsq (written), then step_schedule / step_schedule_scaled (loss_scaler given) and counter += counter_add (an int64
+    device scalar, optional), all in ONE launch (ofa_sumsq_schedule): the same bits as the separate launches.  ticket: one int32 device
+    word, 0 before the first call (the kernel resets it)."""
+    assert x.is_contiguous() and x.numel() >= 1 and ticket.dtype == torch.int32 and (counter is None or counter.dtype == torch.int64)
+    ws = workspace(lib().cdll.ofa_sumsq_ws_floats() * 4, x.device, "sumsq")
+    lib().call("ofa_sumsq_schedule", ptr(x), ptr(gsq), ptr(ws), ptr(ticket), x.numel(), dtype_code(x), ptr(sample_size), ptr(step),
+               ptr(lr), ptr(sched), ptr(gnorm), ptr(loss_scaler), ptr(counter), int(counter_add), float(clip_norm), float(beta1),
+               float(beta2), float(scale_factor), float(scale_window), float(tolerance), float(threshold or 0.0), float(min_loss_scale),
+               stream())
+
+
 def step_schedule(gsq, sample_size, step, lr, sched, gnorm, clip_norm, beta1, beta2):
     """Device-side scalar schedule of one update (see ofa_step_schedule); all arguments are 1-element device tensors
     (gsq fp32, sample_size / step / lr fp64, sched fp32[3], gnorm fp32)."""
@@ -1081,8 +1167,8 @@ def colsum(x, alpha=1.0, out=None, accumulate=False, out_dtype=torch.float32, fo
         fold.flush_if_large()
         return out
     ws = workspace(lib().cdll.ofa_colsum_ws_floats(cols) * 4, x.device, "colsum")
-    lib().call("ofa_colsum", ptr(x), ptr(out), ptr(ws), rows, cols, x.stride(0), float(alpha), int(accumulate),
-               dtype_code(x), dtype_code(out), stream())
+    lib().call("ofa_colsum", ptr(x), ptr(out), ptr(ws), rows, cols, x.stride(0), float(alpha),
+               int(_accum(out, accumulate, full=out.is_contiguous())), dtype_code(x), dtype_code(out), stream())
     return out
 
 
@@ -1245,6 +1331,8 @@ def batchnorm_bwd(dy, y, x, gamma, mean, rstd, batch_stats, relu, want_dres=Fals
         dgamma = torch.empty(C, dtype=gamma.dtype, device=x.device)
         dbeta = torch.empty(C, dtype=gamma.dtype, device=x.device)
     ws = workspace(lib().cdll.ofa_batchnorm_ws_floats(C) * 4, x.device, "bn")
+    if acc:
+        acc = _accum_all([dgamma, dbeta])
     lib().call("ofa_batchnorm_bwd", ptr(dy), ptr(y), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dx), ptr(dres), ptr(dgamma),
                ptr(dbeta), ptr(ws), rows, C, int(batch_stats), int(relu), int(acc), ptr(beta) if (relu and not want_dres) else None,
                dtype_code(x), stream())
@@ -1288,6 +1376,8 @@ def batchnorm_bwd_stats(dy, y, x, gamma, mean, rstd, relu, regate_beta=None, dga
         dbeta = torch.empty(C, dtype=gamma.dtype, device=x.device)
     sums = torch.empty(2, C, dtype=torch.float32, device=x.device)
     ws = workspace(lib().cdll.ofa_batchnorm_ws_floats(C) * 4, x.device, "bn")
+    if acc:
+        acc = _accum_all([dgamma, dbeta])
     lib().call("ofa_batchnorm_bwd_stats", ptr(dy), ptr(y), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(sums), ptr(dgamma), ptr(dbeta),
                ptr(ws), rows, C, int(relu), int(acc), ptr(regate_beta), dtype_code(x), stream())
     return sums, dgamma, dbeta

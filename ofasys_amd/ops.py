@@ -84,8 +84,21 @@ class _Rng:
             cls.offset = 0
 
 
+    @classmethod
+    def defer(cls):
+        """advance() handed to a kernel that runs anyway: -> (base, offset) for the caller to add on the device (the relative offset is
+        folded here), or None when there is nothing to add or more than one device's base (then advance() has run)."""
+        if cls.offset and len(cls.base) == 1:
+            (b,) = cls.base.values()
+            o, cls.offset = cls.offset, 0
+            return b, o
+        cls.advance()
+        return None
+
+
 manual_seed = _Rng.manual_seed
 rng_advance = _Rng.advance
+rng_defer = _Rng.defer
 
 
 # ---------------------------------------------------------------------------------------------- gradient sinks
@@ -101,6 +114,139 @@ def _sink_done(param):
     cb = getattr(param, "_ofa_grad_ready", None)
     if cb is not None:
         cb()
+
+
+# First-touch gradient writes.  The train step does not clear the gradient arena.  Instead every launch that adds a result to a
+# gradient asks `grad_mode` -- the ONE place that decides, at the moment the launch is issued (kernels._accum: the GEMM epilogues, the
+# grouped launch's items, the fold jobs at their flush, the column sums and reduces) -- whether it stores or adds:
+#   * the first FULL writer of a range of the arena in a step (a launch that writes every element of its view) stores;
+#   * every later contribution adds: a second writer of a tied or shared parameter, a second micro-batch, a second chunk;
+#   * a PARTIAL writer (embedding rows, a strided view) always adds; what nobody has written under it is cleared first;
+#   * what nobody wrote at all by the end of backward is cleared then (`grad_end`): the unused-parameter rule.
+# The touched set is a sorted list of disjoint element ranges of the arena, cleared per step (`grad_begin`).  The ranges a step had to
+# clear on demand are handed back by `grad_end`; the next step of the same batch structure clears them up front in ONE launch.
+# Values: storing round(x) and adding round(x) onto +0 give the same number (-0.0 stored where 0 + -0.0 gave +0.0 is the one difference in
+# bits), so a step computes what it computed after an arena-wide zero fill.
+class _Touched:
+    arena = None         # the gradient arena of the running step (None: no step is running -- every sink adds)
+    spans = []           # sorted, disjoint [lo, hi) element ranges written (or cleared) so far in this step
+    demand = []          # ranges cleared on demand in this step, in order
+    unused = []          # ranges nobody wrote (grad_end)
+
+
+def _zero_ranges(arena, ranges, also=()):
+    """Clear the element ranges of the arena (and the whole of every contiguous tensor in `also`) in one batched launch."""
+    es = arena.element_size()
+    K.zero_batched([(K.dptr(arena) + lo * es, (hi - lo) * es) for lo, hi in ranges] +
+                   [(K.dptr(t), t.numel() * t.element_size()) for t in also])
+
+
+def _span_gaps(lo, hi):
+    """The parts of [lo, hi) outside the touched set."""
+    import bisect
+    spans, gaps = _Touched.spans, []
+    i = bisect.bisect_right(spans, (lo, float("inf"))) - 1
+    if i >= 0 and spans[i][1] > lo:
+        lo = spans[i][1]
+    i += 1
+    while lo < hi:
+        if i < len(spans) and spans[i][0] < hi:
+            if spans[i][0] > lo:
+                gaps.append((lo, spans[i][0]))
+            lo = max(lo, spans[i][1])
+            i += 1
+        else:
+            gaps.append((lo, hi))
+            break
+    return gaps
+
+
+def _span_mark(lo, hi):
+    import bisect
+    spans = _Touched.spans
+    i = bisect.bisect_left(spans, (lo, lo))
+    if i > 0 and spans[i - 1][1] >= lo:
+        i -= 1
+    j = i
+    while j < len(spans) and spans[j][0] <= hi:
+        lo, hi = min(lo, spans[j][0]), max(hi, spans[j][1])
+        j += 1
+    spans[i:j] = [(lo, hi)]
+
+
+def grad_begin(arena, prezero=(), also=()):
+    """Start of a train step over the gradient arena `arena` (1-D): nothing is touched; `prezero` -- the ranges the previous step of this
+    batch structure cleared on demand -- are cleared now, in one launch, before the first backward kernel.  also: small contiguous
+    tensors the step wants cleared at its start (its statistics, the sum of squares), which ride in the same launch."""
+    _Touched.arena, _Touched.spans, _Touched.demand, _Touched.unused = arena, [], [], []
+    prezero = [(max(0, lo), min(arena.numel(), hi)) for lo, hi in prezero if lo < hi]
+    if prezero or also:
+        _zero_ranges(arena, prezero, also)
+        for lo, hi in prezero:
+            _span_mark(lo, hi)
+
+
+def _dense(t):
+    """Does the view cover every element of its memory range exactly once (contiguous in some order of its dimensions)?"""
+    want = 1
+    for n, st in sorted(((n, st) for n, st in zip(t.shape, t.stride()) if n > 1), key=lambda p: p[1]):
+        if st != want:
+            return False
+        want *= n
+    return True
+
+
+def grad_mode(out, full=True, peek=False, store=False):
+    """Does the launch being issued ADD to `out` (True) or is it the first full writer of that gradient in this step and stores (False)?
+    Anything that is not a view of the running step's arena adds, as it always did.  peek: the answer alone, nothing is marked or cleared.
+    store: the launch overwrites `out` whatever is there (accumulate=False): its range is marked as written -- a full view as it is, the
+    unwritten rest under a strided one cleared first -- so that grad_end does not take it for a gradient nobody wrote."""
+    arena = _Touched.arena
+    if arena is None or out.dtype != arena.dtype or out.device != arena.device:
+        return True
+    es = arena.element_size()
+    off = out.data_ptr() - arena.data_ptr()
+    if off < 0 or off >= arena.numel() * es or out.numel() == 0:
+        return True
+    lo = off // es
+    reach = 1 + sum((n - 1) * st for n, st in zip(out.shape, out.stride()))
+    hi = lo + reach
+    gaps = _span_gaps(lo, hi)
+    if store and not peek and full and _dense(out):
+        _span_mark(lo, hi)
+        return False
+    if full and _dense(out) and gaps == [(lo, hi)]:
+        if not peek:
+            _span_mark(lo, hi)
+        return False
+    if peek:
+        return True
+    if gaps:                                         # a partial writer, or a range written in part: clear the rest, then add
+        _zero_ranges(arena, gaps)
+        _Touched.demand.extend(gaps)
+        _span_mark(lo, hi)
+    return True
+
+
+def grad_end():
+    """End of a step's backward (every queued fold and weight gradient launched): clears what nobody wrote and closes the step.
+    -> (ranges cleared on demand, ranges nobody wrote)."""
+    arena = _Touched.arena
+    if arena is None:
+        return [], []
+    _Touched.unused = _span_gaps(0, arena.numel())
+    if _Touched.unused:
+        _zero_ranges(arena, _Touched.unused)
+    _Touched.arena = None
+    return list(_Touched.demand), list(_Touched.unused)
+
+
+def grad_abort():
+    """A step that did not reach grad_end (backward raised): every sink adds again."""
+    _Touched.arena = None
+
+
+K.grad_mode = grad_mode
 
 
 # Deferred folds (kernels.FoldQueue): when enabled, arena-gradient producers leave their fp32 partial rows in place and the
@@ -1801,8 +1947,10 @@ class CrossEntropyFn(torch.autograd.Function):
     (engine/criterion/cross_entropy.py:27-67).  logits: [..., V]; a row stride that is no multiple of the vector width is padded here."""
 
     @staticmethod
-    def forward(ctx, logits, target, ignore_index, seed=None):
-        """seed: see _SeededGrad.  With it the logits' gradient is computed by the forward kernel from the row it already holds (one
+    def forward(ctx, logits, target, ignore_index, seed=None, stats=None):
+        """stats: a StepStats or None.  With it, and on the one-pass path, the kernel's last block also adds the micro-batch's share of
+        the step statistics (stats.done is then set: the caller launches nothing more for them).
+        seed: see _SeededGrad.  With it the logits' gradient is computed by the forward kernel from the row it already holds (one
         pass over the logits instead of three); a backward that cannot take it runs ce_bwd on the saved logits view."""
         V = logits.shape[-1]
         l2d = _ce_rows(logits)
@@ -1810,6 +1958,12 @@ class CrossEntropyFn(torch.autograd.Function):
         ctx.ignore_index, ctx.shape = ignore_index, logits.shape
         ctx.seeded = _SeededGrad()
         if ctx.needs_input_grad[0] and _SeededGrad.usable(seed, l2d.device) and K.cross_entropy_fwd_grad_ok(l2d, V):
+            if stats is not None and t.dtype == torch.int64 and t.numel() >= 1:
+                lse, row_loss, d, loss = K.cross_entropy_fwd_grad(l2d, t, seed, V, ignore_index, stats.stats, stats.ticket)
+                stats.done = True
+                ctx.seeded = _SeededGrad(seed, d)
+                ctx.save_for_backward(l2d, t, lse)
+                return loss
             lse, row_loss, d = K.cross_entropy_fwd_grad(l2d, t, seed, V, ignore_index)
             ctx.seeded = _SeededGrad(seed, d)
         else:
@@ -1825,11 +1979,21 @@ class CrossEntropyFn(torch.autograd.Function):
         if d is None:
             gs = dloss.reshape(1).float().contiguous()
             d = K.cross_entropy_bwd(l2d, t, lse, gs, V, ctx.ignore_index, dlogits=ctx.seeded.spare())
-        return d[:, :V].view(ctx.shape), None, None, None
+        return d[:, :V].view(ctx.shape), None, None, None, None
 
 
-def cross_entropy_sum(logits, target, ignore_index, seed=None):
-    return CrossEntropyFn.apply(logits, target, ignore_index, seed)
+class StepStats:
+    """Where a criterion may add its micro-batch's [sample_size, loss_sum, ntokens] itself: stats fp64[3] and the ticket word of the
+    kernel that does it (int32, zero); done: the last forward did."""
+
+    def __init__(self, stats, ticket):
+        self.stats, self.ticket, self.done = stats, ticket, False
+
+
+def cross_entropy_sum(logits, target, ignore_index, seed=None, stats=None):
+    if stats is not None:
+        stats.done = False
+    return CrossEntropyFn.apply(logits, target, ignore_index, seed, stats)
 
 
 class LabelSmoothedCrossEntropyFn(torch.autograd.Function):

@@ -91,6 +91,13 @@ class FlatParams:
                 p.data = self._view(self.flat, o, p)
                 p.grad = self._view(self.grad, o, p)
                 p._ofa_grad = p.grad          # backward kernels accumulate straight into the arena (ops._sink)
+                # a gradient that autograd itself delivers (a parameter used through torch's own ops) is ADDED to the arena view by
+                # AccumulateGrad: a partial writer as far as the step's first-touch rule goes (ops.grad_mode) -- asked just before
+                # (the engine also runs the hook with no gradient at all -- the sinks' own `return None` -- which touches nothing)
+                old = getattr(p, "_ofa_grad_hook", None)
+                if old is not None:                  # (an earlier FlatParams over the same parameter: its hook goes)
+                    old.remove()
+                p._ofa_grad_hook = p.register_hook(lambda g, v=p._ofa_grad: None if g is None else (ops.grad_mode(v, False) and None))
         off_of = {id(p): o for p, o in zip(params, self.offsets)}
         for m in mhas:
             n = 3 if m.self_attention else 2
@@ -134,6 +141,9 @@ class FlatParams:
 
     def zero_grad(self):
         self.grad.zero_()
+        self.repoint()
+
+    def repoint(self):
         for p, o in zip(self.params, self.offsets):      # autograd may have replaced .grad; re-point it at the arena
             if p.grad is None or p.grad.data_ptr() != self.grad.data_ptr() + o * self.grad.element_size():
                 p.grad = self._view(self.grad, o, p)
@@ -323,6 +333,11 @@ class TrainStep:
             self.loss_scale_cfg = cfg
             self._ls = torch.tensor([cfg["init_scale"], 0, -1, -1, 0, 0, 0, 0], dtype=torch.float64, device=dev)
         self._graphs = {}                           # batch structure -> dict(graphs, static samples, seen count)
+        self._gsq_cleared = False
+        self._rng_pending = None                    # (Philox counter, its step's advance): added by the fused norm / schedule launch
+        self._tail_ticket = torch.zeros(2, dtype=torch.int32, device=dev)     # tickets of the two fused tails (they reset themselves)
+        self._ce_stats = ops.StepStats(self._stats, self._tail_ticket[1:2])
+        self._prezero = {}                          # batch structure -> gradient-arena ranges its partial writers need cleared up front
         # Every captured structure pins its activations: the captures share ONE memory pool (step graphs replay one at a time and
         # consume nothing of each other, so the pool's blocks are reused across them) and at most `max_graphs` structures are
         # captured -- the rest run eagerly.  Variable-length data should arrive bucketed (pad_to_multiple / packing buckets).
@@ -350,12 +365,47 @@ class TrainStep:
         model = self.model
         model.train()
         ops.drop_pending()
-        self.fp.zero_grad()
-        self._stats.zero_()
+        if self._rng_pending:                            # (a forward / backward whose update never ran: its counter advance is still due)
+            self._rng_pending[0].add_(self._rng_pending[1])
+            self._rng_pending = None
+        # gradients: no arena-wide fill.  The first full writer of a gradient in the step stores, every later one adds (ops.grad_mode);
+        # what this batch structure's partial writers need cleared is cleared here, in one launch, and what nobody writes at the end.
+        # (Data parallel: the reducer reads buckets from inside backward, unwritten parameters included -- the arena is filled as before.
+        #  The debug library's OFA_STEP_TAIL_OLD bit 0 selects the fill too.)
+        first_touch = self.world == 1 and not K.tail_old(K.TAIL_FIRST_TOUCH)
+        if first_touch:
+            self.fp.repoint()
+            # (structure None: eager steps share one list.  The step's statistics and the sum of squares are cleared by the same launch.)
+            ops.grad_begin(self.fp.grad, self._prezero.get(structure, ()), also=(self._stats, self._gsq))
+            self._gsq_cleared = True
+        else:
+            ops.grad_abort()
+            self.fp.zero_grad()
+            self._stats.zero_()
         self.reducer.overlap = overlap_reduce
         # gradients are only read after backward unless buckets are all-reduced from inside it: fold lazily, in batches
         ops.defer_reductions(self.world == 1 or not overlap_reduce)
         self.reducer.begin_step(structure, dynamic=self.dynamic_autograd or self.sync_collectives)
+        try:
+            self._micro_batches(samples)
+            ops.flush_folds()
+        except BaseException:
+            ops.grad_abort()                         # (every sink adds again: nothing of this step's touched set outlives it)
+            raise
+        if first_touch:
+            demand, _ = ops.grad_end()               # (before the gradient norm: clears what nobody wrote)
+            if demand:
+                if len(self._prezero) >= 256 and structure not in self._prezero:
+                    self._prezero.clear()
+                self._prezero[structure] = sorted(set(self._prezero.get(structure, ())) | set(demand))
+        # (one owned range and no collective between the norm and the schedule: the counter add rides in that launch, see _update)
+        self._rng_pending = ops.rng_defer() if self._fused_norm() else ops.rng_advance()
+
+    def _fused_norm(self):
+        return self.world == 1 and not K.tail_old(K.TAIL_NORM_SCHEDULE)
+
+    def _micro_batches(self, samples):
+        model = self.model
         for s in samples:
             plan = s.get("pack")
             target = s["target"]
@@ -396,9 +446,13 @@ class TrainStep:
                 # (the backward seed is known here: the criterion kernel writes the logits' gradient in its one pass over them)
                 if self.loss_scale_cfg is None and (self._seed is None or self._seed.device != logits.device):
                     self._seed = torch.ones((), dtype=torch.float32, device=logits.device)
-                loss = ops.cross_entropy_sum(logits, target, self.pad, seed=self._seed if self.loss_scale_cfg is None else None)
+                fused = self._ce_stats if (logits.is_cuda and not K.tail_old(K.TAIL_CRITERION_STATS)) else None
+                loss = ops.cross_entropy_sum(logits, target, self.pad, seed=self._seed if self.loss_scale_cfg is None else None,
+                                             stats=fused)
                 n = None
-                if loss.is_cuda and loss.dtype == torch.float32 and target.is_contiguous() and target.dtype == torch.int64:
+                if fused is not None and fused.done:     # (the criterion kernel's last block added the statistics)
+                    counted = True
+                elif loss.is_cuda and loss.dtype == torch.float32 and target.is_contiguous() and target.dtype == torch.int64:
                     # [sample_size, loss_sum, ntokens] += (non-pad targets, loss, non-pad targets) in one launch
                     K.step_stats_add(self._stats, loss.detach(), target, self.pad)
                     counted = True
@@ -414,8 +468,6 @@ class TrainStep:
                 self._stats[0] += n if size is None else size
                 self._stats[1] += loss.detach().double()
                 self._stats[2] += n
-        ops.flush_folds()
-        ops.rng_advance()
 
     def _reduce(self):
         self.reducer.finish()
@@ -424,8 +476,26 @@ class TrainStep:
     def _update(self):
         # coef = (1/sample_size) * min(1, clip / (||g/sample_size|| + 1e-6)), all on the device; a non-finite norm or an empty
         # batch sets the skip flag instead (ofa_step_schedule) and ofa_adam_step leaves weights and moments untouched
-        self._gsq.zero_()
         owned = self.reducer.owned_ranges()              # the whole arena, or (sharded optimizer) this rank's pieces of the buckets
+        pending, self._rng_pending = self._rng_pending, None
+        if self._fused_norm() and len(owned) == 1 and owned[0][2] and owned[0][1] > owned[0][0]:
+            # the sum of squares, its fold, the schedule and the Philox counter add in one launch (ofa_sumsq_schedule)
+            lo, hi, _ = owned[0]
+            c = self.loss_scale_cfg or {}
+            K.sumsq_schedule(self.fp.grad[lo:hi], self._gsq, self._tail_ticket[0:1], self._stats, self._step_t, self._lr_t, self._sched,
+                             self._gnorm_t, self.clip_norm, self.betas[0], self.betas[1],
+                             loss_scaler=self._ls if self.loss_scale_cfg is not None else None,
+                             scale_factor=c.get("scale_factor", 2.0), scale_window=c.get("scale_window", 2000),
+                             tolerance=c.get("tolerance", 0.0), threshold=c.get("threshold"), min_loss_scale=c.get("min_loss_scale", 1e-4),
+                             counter=pending[0] if pending else None, counter_add=pending[1] if pending else 0)
+            self._gsq_cleared = False
+            self._finish_update(owned)
+            return
+        if pending:
+            pending[0].add_(pending[1])
+        if not self._gsq_cleared:                        # (a first-touch step cleared it with its gradients: nothing wrote it since)
+            self._gsq.zero_()
+        self._gsq_cleared = False
         for lo, hi, counted in owned:
             if counted:
                 K.sumsq(self.fp.grad[lo:hi], self._gsq)
@@ -440,6 +510,9 @@ class TrainStep:
             K.step_schedule_scaled(self._gsq, self._stats, self._step_t, self._lr_t, self._sched, self._gnorm_t, self._ls,
                                    self.clip_norm, self.betas[0], self.betas[1], c["scale_factor"], c["scale_window"],
                                    c["tolerance"], c["threshold"], c["min_loss_scale"])
+        self._finish_update(owned)
+
+    def _finish_update(self, owned):
         for lo, hi, _ in owned:
             K.adam_step(self.master[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], self.fp.grad[lo:hi], self.fp.flat[lo:hi],
                         self._sched, 0.0, self.betas[0], self.betas[1], self.eps, self.weight_decay, 0)

@@ -29,6 +29,30 @@ def bench(fn, n=30):
 
 
 R, Rd = 13312, 1536          # encoder / decoder rows of the packed cfg-2 batch (B = 32; row buckets of 512 / 256)
+
+if len(sys.argv) > 1 and sys.argv[1] == "cold":
+    # python tools/gemm_bench.py cold: the vocabulary weight gradient (51272 x 768 over 1536 rows) storing against adding onto its
+    # output, with the output COLD -- every launch follows a 1 GiB fill that evicts it from the Infinity Cache, as the step's 79 MB
+    # gradient is when its writer runs -- and HIP events around the product alone.  What the accumulate epilogue's read costs in situ.
+    a = torch.randn(Rd, 51272, device=dev).bfloat16()
+    b = torch.randn(Rd, 768, device=dev).bfloat16()
+    out = torch.zeros(51272, 768, device=dev, dtype=torch.bfloat16)
+    evict = torch.empty(1 << 28, dtype=torch.float32, device=dev)
+    for acc in (False, True, False, True):
+        ts = []
+        for _ in range(12):
+            evict.fill_(0.0)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            K.gemm(a, b, True, False, out=out, accumulate=acc)
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e3)
+            out.zero_()
+        ts = sorted(ts[2:])
+        print(f"TN 51272 x 768 x K 1536 cold output, accumulate={acc!s:5}: median {ts[len(ts) // 2]:7.1f} us  min {ts[0]:7.1f}  max {ts[-1]:7.1f}",
+              flush=True)
+    sys.exit(0)
 shapes = [
     # forward (y = x W^T): rows x N x K
     ("NT", R, 2304, 768, "qkv forward"), ("NT", R, 768, 768, "out_proj forward"), ("NT", R, 3072, 768, "fc1 forward"),
