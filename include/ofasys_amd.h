@@ -470,6 +470,26 @@ int ofa_ls_cross_entropy_bwd(const void* logits, const int64_t* target, const fl
                              const float* row_w, const float* grad_scale, void* dlogits, int64_t rows, int64_t V, int64_t ld,
                              int64_t ignore_index, float eps, int64_t cstart, int64_t cend, const uint8_t* cmask, int dtype,
                              void* stream);
+/* The same criterion for closed-set targets, the per-row byte mask replaced by ONE trie node per row (traverse.TraversePlan's CSR:
+ * node_edge_off int32 [N + 1], edge_token int32 [E]).  Row r's allowed set A is {edge_token[e] : node_edge_off[n] <= e < node_edge_off[n + 1]},
+ * n = node[r], inside [0, V) and, with cstart >= 0, inside [0,4) U [cstart,cend); C = |A|, eps_i = eps / (C - 1 + 1e-6), and lse, row_loss,
+ * row_nll, row_cnt = C and the gradient are ofa_ls_cross_entropy_*'s over A.  An edge_token outside [0, V) is skipped, not read.
+ * target == ignore_index: row_loss = row_nll = 0 and a zero gradient row.  A live target on a node outside [0, N) (-1: no closed set at
+ * that position), on a node with no allowed child (lse = -inf), or that is no allowed child itself: row_loss = row_nll = +inf (the
+ * reference masks the target's log-probability to -inf) and a zero gradient row, as ofa_scst_loss_fwd_grad treats an invalid target.
+ * fwd: with dlogits != NULL the same launch also writes the gradient row [0, ld) at grad_scale[0] (device scalar, NULL = 1).
+ * bwd: the gradient at grad_scale[0] * row_w[r] (row_w optional; 0 drops a row -- drop_worst) from the forward's lse and row_cnt.
+ * One workgroup per row reads C logits, not V; every 16-byte vector of the gradient row is written.  dlogits 16-byte aligned. */
+int ofa_trie_ls_cross_entropy_fwd(const void* logits, const int64_t* target, const int32_t* node, const int32_t* node_edge_off,
+                                  const int32_t* edge_token, int64_t N, int64_t E, const float* grad_scale, float* lse,
+                                  float* row_loss, float* row_nll, float* row_cnt, void* dlogits, int64_t rows, int64_t V,
+                                  int64_t ld, int64_t ignore_index, float eps, int64_t cstart, int64_t cend, int dtype,
+                                  void* stream);
+int ofa_trie_ls_cross_entropy_bwd(const void* logits, const int64_t* target, const int32_t* node, const int32_t* node_edge_off,
+                                  const int32_t* edge_token, int64_t N, int64_t E, const float* lse, const float* row_cnt,
+                                  const float* row_w, const float* grad_scale, void* dlogits, int64_t rows, int64_t V,
+                                  int64_t ld, int64_t ignore_index, float eps, int64_t cstart, int64_t cend, int dtype,
+                                  void* stream);
 /* self-critical sequence training (engine/criterion/scst_loss.py:24-36, 214-233): reward-weighted NLL of the generated tokens, forward
  * AND gradient in one call.  Row r belongs to sentence s = row_seq ? row_seq[r] : r / rows_per_seq and carries the weight
  * w = reward[s] (fp32 [nseq]; an s outside [0, nseq) reads nothing and weighs 0).  Over the allowed vocabulary A -- all of it

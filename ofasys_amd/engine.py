@@ -231,6 +231,9 @@ class Trainer:
                 mb = {"slots": s["net_input"]["slots"], "target": s["target"], "task": task.name}
                 if s.get("constraint_masks") is not None:
                     mb["constraint_masks"] = s["constraint_masks"]
+                if s.get("constraint_nodes") is not None:         # cfg.text.closed_set_nodes: one trie node per target position
+                    mb["constraint_nodes"] = s["constraint_nodes"]
+                    mb["constraint_trie"] = task.constraint_trie_on(self._device)
                 out.append(mb)
         return out
 

@@ -1034,6 +1034,43 @@ def ls_cross_entropy_bwd(logits2d, target, lse, row_cnt, row_w, grad_scale, V, i
     return dlogits
 
 
+def _trie_args(logits2d, target, nodes, trie):
+    """The checked (node, node_edge_off, edge_token, N, E) arguments of ofa_trie_ls_cross_entropy_*; trie: a dict with the int32 device
+    arrays "node_edge_off" [N + 1], "edge_token" [E] and the ints "N", "E" (traverse.TraversePlan.to_device)."""
+    rows = logits2d.shape[0]
+    off, tok, N, E = trie["node_edge_off"], trie["edge_token"], int(trie["N"]), int(trie["E"])
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == rows, (target.dtype, target.shape, rows)
+    assert nodes.dtype == torch.int32 and nodes.is_contiguous() and nodes.numel() == rows, (nodes.dtype, nodes.shape, rows)
+    assert off.dtype == torch.int32 and off.is_contiguous() and off.numel() == N + 1, (off.dtype, off.shape, N)
+    assert tok.dtype == torch.int32 and tok.is_contiguous() and tok.numel() == E, (tok.dtype, tok.shape, E)
+    return ptr(nodes), ptr(off), ptr(tok), N, E
+
+
+def trie_ls_cross_entropy_fwd(logits2d, target, nodes, trie, V, ignore_index, eps, cstart=-1, cend=-1, grad_scale=None, want_grad=False):
+    """Label-smoothed CE rows whose allowed set is the children of the trie node nodes[row] (ofa_trie_ls_cross_entropy_fwd): returns
+    lse, row_loss, row_nll, row_cnt (fp32 [rows]) and, with want_grad, dlogits [rows, ld] at grad_scale[0] (fp32 device scalar, None: 1)
+    written by the same launch (else None)."""
+    rows, ld = logits2d.shape[0], logits2d.stride(0)
+    targs = _trie_args(logits2d, target, nodes, trie)
+    out = [torch.empty(rows, dtype=torch.float32, device=logits2d.device) for _ in range(4)]
+    dlogits = torch.empty(rows, ld, dtype=logits2d.dtype, device=logits2d.device) if want_grad else None
+    lib().call("ofa_trie_ls_cross_entropy_fwd", ptr(logits2d), ptr(target), *targs, ptr(grad_scale), *[ptr(o) for o in out],
+               ptr(dlogits), rows, V, ld, ignore_index, float(eps), int(cstart), int(cend), dtype_code(logits2d), stream())
+    return (*out, dlogits)
+
+
+def trie_ls_cross_entropy_bwd(logits2d, target, nodes, trie, lse, row_cnt, row_w, grad_scale, V, ignore_index, eps, cstart=-1, cend=-1,
+                              dlogits=None):
+    """dlogits [rows, ld] at grad_scale[0] * row_w[row] from the forward's lse and row_cnt (ofa_trie_ls_cross_entropy_bwd)."""
+    rows, ld = logits2d.shape[0], logits2d.stride(0)
+    targs = _trie_args(logits2d, target, nodes, trie)
+    if dlogits is None:
+        dlogits = torch.empty(rows, ld, dtype=logits2d.dtype, device=logits2d.device)
+    lib().call("ofa_trie_ls_cross_entropy_bwd", ptr(logits2d), ptr(target), *targs, ptr(lse), ptr(row_cnt), ptr(row_w), ptr(grad_scale),
+               ptr(dlogits), rows, V, ld, ignore_index, float(eps), int(cstart), int(cend), dtype_code(logits2d), stream())
+    return dlogits
+
+
 def scst_loss_fwd_grad(logits2d, target, reward, grad_scale, V, ignore_index, rows_per_seq=1, row_seq=None, cstart=-1, cend=-1,
                        dlogits=None):
     """Reward-weighted NLL rows and their gradient in one call (ofa_scst_loss_fwd_grad): returns lse, row_loss (fp32 [rows]) and

@@ -2045,6 +2045,70 @@ def label_smoothed_cross_entropy(logits, target, ignore_index, eps, constraint_r
                                              drop_worst_ratio)
 
 
+class TrieLabelSmoothedCrossEntropyFn(torch.autograd.Function):
+    """LabelSmoothedCrossEntropyFn for closed-set targets, the [rows, V] constraint mask replaced by one trie node per row: row r's
+    allowed set is the children of nodes[r] in `trie` (the dict of device arrays of traverse.TraversePlan.to_device: node_edge_off,
+    edge_token, N, E), a node of -1 allowing nothing.  Returns (loss_sum, nll_sum, ntokens).  A live target that is not an allowed
+    child of its node gives loss = +inf, as the reference's masked log-probability does, and no gradient.
+    seed: see _SeededGrad.  With it and without drop_worst the forward launch also writes the logits' gradient
+    (kernels.trie_ls_cross_entropy_fwd); every other backward runs kernels.trie_ls_cross_entropy_bwd on the saved rows."""
+
+    @staticmethod
+    def forward(ctx, logits, target, nodes, trie, ignore_index, eps, constraint_range, drop_worst_ratio, seed):
+        V = logits.shape[-1]
+        l2d = _ce_rows(logits)
+        t = target.reshape(-1).contiguous()
+        nd = nodes.reshape(-1).to(device=l2d.device, dtype=torch.int32).contiguous()
+        if nd.numel() != l2d.shape[0]:
+            raise ValueError(f"trie_label_smoothed_cross_entropy: {nd.numel()} nodes for {l2d.shape[0]} rows")
+        cs, ce = constraint_range if constraint_range is not None else (-1, -1)
+        seeded = drop_worst_ratio <= 0 and ctx.needs_input_grad[0] and _SeededGrad.usable(seed, l2d.device)
+        lse, row_loss, row_nll, row_cnt, d = K.trie_ls_cross_entropy_fwd(l2d, t, nd, trie, V, ignore_index, eps, cs, ce,
+                                                                         grad_scale=seed if seeded else None, want_grad=seeded)
+        ctx.seeded = _SeededGrad(seed, d) if seeded else _SeededGrad()
+        valid = t.ne(ignore_index)
+        row_w = None
+        if drop_worst_ratio > 0:
+            n = valid.sum()
+            k = (n.double() * (1 - drop_worst_ratio)).floor().long()                # int(n * (1 - ratio)), on the device
+            key = torch.where(valid, row_loss, torch.full_like(row_loss, float("inf")))
+            order = torch.argsort(key, stable=True)
+            rank = torch.empty_like(order)
+            rank[order] = torch.arange(order.numel(), device=order.device)
+            keep = rank < k
+            row_w = keep.float()
+            zero = torch.zeros_like(row_loss)
+            row_loss, row_nll = torch.where(keep, row_loss, zero), torch.where(keep, row_nll, zero)   # (a dropped +inf row: 0, not NaN)
+            ntok = k
+        else:
+            ntok = valid.sum()
+        ctx.save_for_backward(l2d, t, nd, lse, row_cnt, row_w, trie["node_edge_off"], trie["edge_token"])
+        ctx.cfg = (ignore_index, eps, cs, ce, logits.shape, int(trie["N"]), int(trie["E"]))
+        ctx.mark_non_differentiable(ntok)
+        return K.sum_f32(row_loss), K.sum_f32(row_nll).detach(), ntok
+
+    @staticmethod
+    def backward(ctx, dloss, dnll, dntok):
+        l2d, t, nd, lse, row_cnt, row_w, off, tok = ctx.saved_tensors
+        ignore_index, eps, cs, ce, shape, N, E = ctx.cfg
+        V = l2d.shape[1]
+        d = ctx.seeded.take(dloss)
+        if d is None:
+            gs = dloss.reshape(1).float().contiguous()
+            trie = {"node_edge_off": off, "edge_token": tok, "N": N, "E": E}
+            d = K.trie_ls_cross_entropy_bwd(l2d, t, nd, trie, lse, row_cnt, row_w, gs, V, ignore_index, eps, cs, ce,
+                                            dlogits=ctx.seeded.spare())
+        return d[:, :V].view(shape), None, None, None, None, None, None, None, None
+
+
+def trie_label_smoothed_cross_entropy(logits, target, nodes, trie, ignore_index, eps, constraint_range=None, drop_worst_ratio=0.0,
+                                      seed=None):
+    """-> (loss_sum, nll_sum, ntokens).  nodes: int32, one trie node per row of the [rows, V] view of `logits` (-1: no closed set at
+    that position); trie: the device arrays of the answer trie (Task.constraint_trie_on).  seed: as in `cross_entropy_sum`."""
+    return TrieLabelSmoothedCrossEntropyFn.apply(logits, target, nodes, trie, ignore_index, eps, constraint_range, drop_worst_ratio,
+                                                 seed)
+
+
 class ScstLossFn(torch.autograd.Function):
     """Self-critical sequence training loss (engine/criterion/scst_loss.py:24-36, 214-233): sum over rows of
     reward[sentence] * NLL(log_softmax_fp32(logits over the allowed vocabulary), target), ignore_index rows contributing 0; returns

@@ -142,6 +142,7 @@ class Task:
         self._scst_generator = None
         self._sampling_gens: Dict[Any, Any] = {}
         self._diverse_gens: Dict[Any, Any] = {}
+        self._trie_dev: Dict[Any, Any] = {}                  # device -> (plan, its device arrays): constraint_trie_on
 
     # ------------------------------------------------------------------ identity / datasets (task/base.py:256-273)
     @property
@@ -206,6 +207,20 @@ class Task:
     def collate(self, rows: List[Dict[str, Any]], split="train") -> Dict:
         samples = [s for s in (self.preprocess_data_and_instruction(dict(r), split) for r in rows) if s is not None]
         return self.general_preprocess.collate(samples)
+
+    def constraint_trie_on(self, device):
+        """The answer trie of the text preprocessor's closed set as the device arrays the node-form criterion reads
+        (ops.trie_label_smoothed_cross_entropy): {"node_edge_off" int32 [N + 1], "edge_token" int32 [E], "N", "E"}.  Built once per
+        device and handed out as the SAME tensors every time, so a captured step's replay finds nothing to copy.  Needs
+        cfg.text.closed_set_nodes and a prepared closed set (the preprocessor's `constraint_plan`)."""
+        plan = self.general_preprocess.name2pre["text"].constraint_plan if self.general_preprocess is not None else None
+        if plan is None:
+            raise ValueError(f"task {self.name}: no answer trie -- set cfg.text.closed_set_nodes and prepare a closed set")
+        cache, key = self._trie_dev, torch.device(device)
+        if key not in cache or cache[key][0] is not plan:      # (a closed set prepared again: a new plan, new arrays)
+            cache[key] = (plan, {"node_edge_off": torch.from_numpy(plan.node_edge_off).to(key),
+                                 "edge_token": torch.from_numpy(plan.edge_token).to(key), "N": plan.N, "E": plan.E})
+        return cache[key][1]
 
     # ------------------------------------------------------------------ iteration (task/base.py:396-449, in process)
     def _batches(self, split, rank, world):

@@ -420,9 +420,33 @@ class TrainStep:
             cm = s.get("constraint_masks")
             if plan is not None and cm is not None:
                 raise NotImplementedError("constraint masks are laid out by padded position: run such samples without a pack plan")
+            # closed-set targets by trie node (collate's closed_set_nodes): one int32 per target position instead of a mask row, and
+            # "constraint_trie", the task's device arrays of the answer trie; the nodes follow the targets into a packed layout
+            nodes = s.get("constraint_nodes")
+            if nodes is not None:
+                if cm is not None:
+                    raise ValueError("a micro-batch carries its closed set as constraint_masks or as constraint_nodes, not both")
+                if s.get("reward") is not None:
+                    raise NotImplementedError("an SCST micro-batch (reward) cannot carry constraint_nodes: its criterion takes a "
+                                              "constraint range only (engine/criterion/scst_loss.py:214-217)")
+                if s.get("constraint_trie") is None:
+                    raise ValueError("constraint_nodes need \"constraint_trie\": the device arrays of the answer trie "
+                                     "(Task.constraint_trie_on(device))")
+                if plan is not None:
+                    packed = s.get("constraint_nodes_packed")
+                    if packed is None:
+                        idx = plan.dec_index
+                        packed = nodes.reshape(-1)[idx.clamp_min(0)].masked_fill(idx < 0, -1)
+                    nodes = packed.view(1, -1)
             counted = False
             size = None
-            if s.get("reward") is not None:
+            if nodes is not None:
+                if self.loss_scale_cfg is None and (self._seed is None or self._seed.device != logits.device):
+                    self._seed = torch.ones((), dtype=torch.float32, device=logits.device)
+                loss, _, n = ops.trie_label_smoothed_cross_entropy(logits, target, nodes, s["constraint_trie"], self.pad,
+                                                                   self.label_smoothing, self.constraint_range, self.drop_worst_ratio,
+                                                                   seed=self._seed if self.loss_scale_cfg is None else None)
+            elif s.get("reward") is not None:
                 # self-critical sequence training (scst.ScstRewardCriterion builds such a micro-batch): the generated tokens' NLL
                 # weighted by the sentence's reward, loss and logits gradient in one pass (engine/criterion/scst_loss.py:24-36)
                 if cm is not None:
@@ -605,7 +629,10 @@ class TrainStep:
     def train_step(self, samples: List[dict], eager: bool = False):
         """samples: one dict per (task, micro-batch): {"slots": [...], "target": LongTensor[B,Tt], optional
         "constraint_masks", "task"}.  With "reward" (fp32, one value per row of `target`) the micro-batch takes the SCST criterion
-        (ops.scst_loss; optional "constraint_range": "start,end" and "sentence_avg": True)."""
+        (ops.scst_loss; optional "constraint_range": "start,end" and "sentence_avg": True).  With "constraint_nodes" (int32 [B, Tt],
+        -1 where no closed set applies) and "constraint_trie" (the answer trie's device arrays: Task.constraint_trie_on) it takes the
+        node form of the label-smoothed criterion (ops.trie_label_smoothed_cross_entropy), with or without a pack plan; optional
+        "constraint_nodes_packed" as "target_packed"."""
         done = False
         structure = None
         if (self.use_graph and not eager) or self.world > 1:

@@ -85,6 +85,7 @@ class TraversePlan:
             lo, hi = int(self.node_edge_off[n]), int(self.node_edge_off[n + 1])
             items.extend((n, e, min(e + self.ITEM_EDGES, hi)) for e in range(lo, hi, self.ITEM_EDGES))
         self.items = np.array(items, np.int32).reshape(-1, 3)
+        self._child_of = None                                # walk()'s (node, token) -> child map, built on first use
         assert E == len(self.edge_token) == len(self.edge_node) and int(self.path_off[-1]) == self.P
 
     def allowed(self, c: int, t: int) -> List[int]:
@@ -95,6 +96,28 @@ class TraversePlan:
     def node_of(self, c: int, t: int) -> int:
         """The node reached by the first t tokens of answer c (t <= its length): the node of its t-th path edge."""
         return int(self.edge_node[self.path_edge[self.path_off[c] + t]])
+
+    def walk(self, tokens) -> np.ndarray:
+        """int32 [len(tokens) + 1]: entry i is the node reached by tokens[:i] (node 0 for the empty prefix), so the children of entry i
+        are the tokens position i may take and the last entry is the node whose edge is EOS.  `tokens`: an answer of the closed set
+        without BOS / EOS; a token that is no child of the node reached so far raises ValueError (the reference's loss for such a
+        sample is +inf: the target's log-probability is masked to -inf)."""
+        if self._child_of is None:                            # (node, token) -> child, once
+            node = np.repeat(np.arange(self.N), np.diff(self.node_edge_off))
+            self._child_of = {(int(n), int(t)): int(c) for n, t, c in zip(node, self.edge_token, self.edge_child)}
+        tokens = [int(t) for t in tokens]
+        out = np.zeros(len(tokens) + 1, np.int32)
+        n = 0
+        for i, t in enumerate(tokens):
+            child = self._child_of.get((n, t), -1)
+            if child < 0:                                     # not a child at all, or EOS in the middle of an answer
+                raise ValueError(f"TraversePlan.walk: token {t} at position {i} of {tokens} is not a child of the trie node its "
+                                 f"prefix reaches: the answer is outside the closed set")
+            out[i + 1] = n = child
+        if (n, self.eos) not in self._child_of:
+            raise ValueError(f"TraversePlan.walk: {tokens} ends at position {len(tokens)} on a node without an EOS edge: the answer "
+                             f"is outside the closed set (a strict prefix of one of its answers)")
+        return out
 
     def chunk_items(self, c0: int, c1: int):
         """The rows [i0, i1) of `items` whose node is represented by an answer in [c0, c1), and the chunk's longest row."""
@@ -161,7 +184,8 @@ class TraverseTask(Task):
         ids = [pre.encode(a).tolist() if isinstance(a, str) else [int(t) for t in a] for a in answers]
         if any(t < 0 or t >= len(d) for a in ids for t in a):
             raise ValueError(f"task {self.name}: the closed set holds token ids outside the dictionary (size {len(d)})")
-        self.plan = TraversePlan(ids, d.bos(), d.eos(), d.pad())
+        # (closed_set_nodes: the text preprocessor already holds the plan of these answers for its collation -- one object, not two)
+        self.plan = pre.constraint_plan if pre.constraint_plan is not None else TraversePlan(ids, d.bos(), d.eos(), d.pad())
         self._dev, self._buf, self._trie_gens = {}, {}, {}
         self._seq2label = {}
         for i, a in enumerate(ids):                           # duplicates go to the lowest label
