@@ -503,6 +503,27 @@ int ofa_scst_loss_fwd_grad(const void* logits, const int64_t* target, const floa
                            int64_t rows_per_seq, const float* grad_scale, float* lse, float* row_loss, void* dlogits, int64_t rows,
                            int64_t nseq, int64_t V, int64_t ld, int64_t ignore_index, int64_t cstart, int64_t cend, int dtype,
                            void* stream);
+/* Validation (engine/criterion/label_smoothed_cross_entropy.py:114-198 in eval mode, compute_loss + compute_accuracy): ONE read of the
+ * [rows, V] logits gives, per row, row_loss and row_nll (fp32; ofa_ls_cross_entropy_fwd's formulas: eps = 0 without a constraint is plain
+ * cross entropy, row_loss == row_nll) and row_hit (int32: 1 iff the target is the arg-max of the stored logits over the allowed set A,
+ * ties to the lowest column -- compared as stored values, so exact).  No gradient, no lse, no log-probabilities are written.
+ * A is the whole vocabulary (cstart < 0), [0,4) U [cstart,cend), either intersected with the byte mask cmask [rows, V], or -- with
+ * node != NULL -- the children of trie node node[r] as in ofa_trie_ls_cross_entropy_fwd (optionally inside the range; a byte mask
+ * and nodes together are refused).  C = |A|; eps_i = eps / (C - 1) unconstrained, eps / (C - 1 + 1e-6) with any constraint.
+ * target == ignore_index: row_loss = row_nll = 0, row_hit = 0.  A live target outside [0, V) or outside A: the target column is not
+ * read, row_loss = row_nll = +inf, row_hit = 0.  Columns V..ld-1 and disallowed columns never enter a result.  Logits finite.
+ * 16-bit logits with ld <= 65536, ld a multiple of 8, a 16-byte aligned base and no byte mask are held in the registers of a 1024-thread
+ * block; everything else (fp32, a byte mask, longer rows, any other ld) streams through a 256-thread block, and the node form reads
+ * only a node's children.  rows == 0: nothing is launched. */
+int ofa_criterion_eval(const void* logits, const int64_t* target, const uint8_t* cmask, const int32_t* node,
+                       const int32_t* node_edge_off, const int32_t* edge_token, int64_t N, int64_t E, float* row_loss, float* row_nll,
+                       int32_t* row_hit, int64_t rows, int64_t V, int64_t ld, int64_t ignore_index, float eps, int64_t cstart,
+                       int64_t cend, int dtype, void* stream);
+/* acc fp64[4] = [ntokens, loss_sum, nll_sum, n_correct] += [count of target != ignore_index, sum row_loss, sum row_nll, count of
+ * row_hit != 0] of one batch: ONE single-block launch that sums in ofa_reduce_sum_f32's order -- no atomics, the same inputs give the
+ * same bits.  rows == 0: nothing is launched. */
+int ofa_eval_stats_add(double* acc, const float* row_loss, const float* row_nll, const int32_t* row_hit, const int64_t* target,
+                       int64_t rows, int64_t ignore_index, void* stream);
 /* get_normalized_probs (model/ofa.py:287-299, module/utils.py:451-462): out fp32 [rows, V] = (log-)softmax_fp32(logits);
  * backward writes dlogits [rows, ld] in `dtype` (columns V..ld-1 zero). */
 int ofa_probs_fwd(const void* logits, float* out, int64_t rows, int64_t V, int64_t ld, int log_probs, int dtype,

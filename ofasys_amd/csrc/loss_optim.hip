@@ -500,6 +500,240 @@ __global__ __launch_bounds__(256) void scst_stream_kernel(
   }
 }
 
+// ---- validation (engine/criterion/label_smoothed_cross_entropy.py:114-198 in eval mode: compute_loss + compute_accuracy): per row the
+// label-smoothed loss, the NLL and "the target is the arg-max of the allowed logits" from ONE read of the row -- no gradient, no lse, no
+// log-probabilities.  The formulas are lsce_fwd_kernel's; the arg-max is carried as (value, lowest column) next to (max, sum): a
+// thread meets its columns in rising order and takes a column only on a strictly larger stored value, the reductions take the largest
+// value and, among equal values, the smallest column as an int -- lprobs.argmax(1) of the reference on the CPU, exactly.
+constexpr int NO_COL = 0x7fffffff;
+__device__ __forceinline__ int wave_min_i(int v) {
+#ifndef OFA_WAVE_REDUCE_SHFL
+#define OFA_DPP_I(CTRL, MASK) __builtin_amdgcn_update_dpp(v, v, CTRL, MASK, 0xf, false)
+  v = min(v, OFA_DPP_I(0xB1, 0xf));                      // (wave_max's steps: lanes outside the row mask keep `old` = v)
+  v = min(v, OFA_DPP_I(0x4E, 0xf));
+  v = min(v, OFA_DPP_I(0x141, 0xf));
+  v = min(v, OFA_DPP_I(0x140, 0xf));
+  v = min(v, OFA_DPP_I(0x142, 0xa));
+  v = min(v, OFA_DPP_I(0x143, 0xc));
+#undef OFA_DPP_I
+  return __builtin_amdgcn_readlane(v, 63);
+#else
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+#endif
+}
+struct EvalCfg { float eps; int cs, ce, ranged; };          // ranged == 0: cs = 0, ce = V
+// the row's outputs from its reduced (lse, sum of allowed x, count, arg-max column); `valid`: the target is an allowed column of [0, V)
+template <typename T>
+__device__ __forceinline__ void eval_row_done(const T* x, int64_t row, int64_t t, bool ignored, bool valid, float l, float X, float C,
+                                              int amax, float eps, bool constrained, float* row_loss, float* row_nll, int32_t* row_hit) {
+  float rl = 0.f, rn = 0.f;
+  int hit = 0;
+  if (!ignored && !valid) {
+    rl = rn = INFINITY;                                  // (the -lprob of a column that is masked or does not exist; x[t] is not read)
+  } else if (!ignored) {
+    rn = l - ld1<T>(x + t);
+    const float eps_i = eps / (constrained ? (C - 1.f + 1e-6f) : (C - 1.f));
+    rl = (1.f - eps - eps_i) * rn + eps_i * (C * l - X);
+    hit = amax == (int)t;
+  }
+  row_loss[row] = rl;
+  row_nll[row] = rn;
+  row_hit[row] = hit;
+}
+
+// Registers form (16-bit logits, ld <= 65536, no byte mask): scst_fwd_grad_kernel's block and per-VECTOR range test, nothing written back.
+template <typename T, int NV>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8))) void criterion_eval_regs_kernel(
+    const T* __restrict__ logits, const int64_t* __restrict__ target, float* __restrict__ row_loss, float* __restrict__ row_nll,
+    int32_t* __restrict__ row_hit, int V, int ld, int64_t ignore_index, EvalCfg cfg) {
+  constexpr int N = Vec<T>::N;
+  static_assert(N == 8, "16-bit element types");
+  __shared__ float sm[16], ss[16], sx[16];
+  __shared__ int si[16];
+  const int64_t row = blockIdx.x;
+  const char* xb = reinterpret_cast<const char*>(logits + row * ld);
+  const int nvec = ld / N;
+  const int tid = threadIdx.x;
+  const int cs = cfg.cs, ce = cfg.ce;
+  uint4 raw[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i)      // (past the row's end the last vector is loaded again, in bounds, and never used: no branch per slab)
+    raw[i] = *reinterpret_cast<const uint4*>(xb + (uint32_t)min(tid + i * 1024, nvec - 1) * 16u);
+  const int f_lo = (cs + 7) >> 3, f_hi = ce >> 3, a_lo = cs >> 3, a_hi = (ce + 7) >> 3;
+  uint32_t some_bits = 0, full_bits = 0;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int v = tid + i * 1024;
+    some_bits |= (uint32_t)(((v >= a_lo) & (v < a_hi)) | (v == 0)) << i;
+    full_bits |= (uint32_t)((v >= f_lo) & (v < f_hi)) << i;
+  }
+  auto okc = [&](int th8, int k) {                       // column th8 + k, k = slab * 8192 + element, against moved uniform bounds
+    return (th8 < V - k) & ((th8 < 4 - k) | ((th8 >= cs - k) & (th8 < ce - k)));
+  };
+  const int tid8 = tid * N;
+  float m = -INFINITY, s = 0.f, sumx = 0.f;
+  int bi = NO_COL;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    if (!((some_bits >> i) & 1u)) continue;
+    float a[N];
+    unpack16<T>(raw[i], a);
+    if (!((full_bits >> i) & 1u)) {                      // a cut vector: its disallowed columns are -inf to the max, the sum and the arg-max
+#pragma unroll
+      for (int j = 0; j < N; ++j) a[j] = okc(tid8, i * 8192 + j) ? a[j] : -INFINITY;
+    }
+    float cur = m;                                       // (m IS the largest allowed value so far: the arg-max needs no copy of it)
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const bool gt = a[j] > cur;
+      cur = gt ? a[j] : cur;
+      bi = gt ? tid8 + i * 8192 + j : bi;
+      sumx += a[j] == -INFINITY ? 0.f : a[j];
+    }
+    vec_merge<Exp2Fma>(m, s, a);                         // (every vector that gets here holds an allowed column: the new max is finite)
+  }
+  const float mw = wave_max(m);
+  const float sw = wave_sum(mw == -INFINITY ? 0.f : s * ex2((m - mw) * L2E));
+  const float xw = wave_sum(sumx);
+  const int iw = wave_min_i(m == mw ? bi : NO_COL);
+  const int wave = tid >> 6;
+  if ((tid & 63) == 0) { sm[wave] = mw; ss[wave] = sw; sx[wave] = xw; si[wave] = iw; }
+  __syncthreads();
+  if (tid >= 64) return;                                 // (wave 0 finishes the row: one wave result per lane)
+  const int lane = tid;
+  const float mv = lane < 16 ? sm[lane] : -INFINITY, sv = lane < 16 ? ss[lane] : 0.f, xv = lane < 16 ? sx[lane] : 0.f;
+  const int iv = lane < 16 ? si[lane] : NO_COL;
+  const float M = wave_max(mv);
+  const float S = wave_sum(sv * ex2((mv - M) * L2E));      // (a wave of disallowed columns only, and lanes 16..63: 0 * 2^-inf = 0)
+  const float X = wave_sum(xv);
+  const int amax = wave_min_i(mv == M ? iv : NO_COL);
+  if (tid != 0) return;
+  const int64_t t = target[row];
+  const bool valid = t >= 0 && t < V && (t < 4 || (t >= cs && t < ce));
+  const float C = cfg.ranged ? (float)(4 + ce - cs) : (float)V;     // (cs >= 4, ce <= V: |[0,4) U [cs,ce)| needs no count)
+  eval_row_done<T>(reinterpret_cast<const T*>(xb), row, t, t == ignore_index, valid, M + logf(S), X, C, amax, cfg.eps, cfg.ranged != 0,
+                   row_loss, row_nll, row_hit);
+}
+
+// NN allowed-or-minus-infinity values of rising columns from c0 into a thread's (m, s, sum x, count, arg-max column)
+template <int NN>
+__device__ __forceinline__ void eval_merge(const float (&a)[NN], int c0, float& m, float& s, float& sumx, float& cnt, int& bi) {
+  float lm = a[0];
+#pragma unroll
+  for (int j = 1; j < NN; ++j) lm = fmaxf(lm, a[j]);
+  if (lm == -INFINITY) return;
+  float cur = m;
+#pragma unroll
+  for (int j = 0; j < NN; ++j) {
+    const bool gt = a[j] > cur;
+    cur = gt ? a[j] : cur;
+    bi = gt ? c0 + j : bi;
+  }
+  float acc = s * expf(m - cur);                         // max first, then ONE rescale (cur = the new max, finite; m = -inf: s = 0)
+#pragma unroll
+  for (int j = 0; j < NN; ++j) {
+    const bool on = a[j] != -INFINITY;
+    acc += expf(a[j] - cur);
+    sumx += on ? a[j] : 0.f;
+    cnt += on ? 1.f : 0.f;
+  }
+  m = cur;
+  s = acc;
+}
+
+// Streaming form (fp32 logits, a byte mask, rows the registers form does not hold, an ld that is no multiple of the vector): one
+// 256-thread block reads the row once, by 16-byte vectors where `vec_ok` (ld a multiple of the vector width, the base aligned).
+template <typename T, bool MASK>
+__global__ __launch_bounds__(256) void criterion_eval_stream_kernel(
+    const T* __restrict__ logits, const int64_t* __restrict__ target, const uint8_t* __restrict__ cmask, float* __restrict__ row_loss,
+    float* __restrict__ row_nll, int32_t* __restrict__ row_hit, int64_t V, int64_t ld, int64_t ignore_index, EvalCfg cfg, int vec_ok) {
+  constexpr int N = Vec<T>::N;
+  __shared__ float sm[4], ss[4], sx[4], sc[4];
+  __shared__ int si[4];
+  const int64_t row = blockIdx.x;
+  const int tid = threadIdx.x;
+  const T* x = logits + row * ld;
+  const uint8_t* mk = MASK ? cmask + row * V : nullptr;
+  const int64_t cs = cfg.ranged ? cfg.cs : -1, ce = cfg.ce;
+  float m = -INFINITY, s = 0.f, sumx = 0.f, cnt = 0.f;
+  int bi = NO_COL;
+  const int64_t nvec = vec_ok ? V / N : 0;                 // (whole vectors below V; the rest of the row goes column by column)
+  for (int64_t v = tid; v < nvec; v += 256) {
+    const int64_t c0 = v * N;
+    const int cls = scst_vec_class(c0, N, V, cs, ce);
+    if (cls == 0) continue;
+    float a[N];
+    load_vec<T>(x + c0, a);
+#pragma unroll
+    for (int j = 0; j < N; ++j) {                          // a disallowed column: -inf to the max, the sums and the arg-max (selects, no branches)
+      bool ok = (cls == 2) | scst_ok(c0 + j, V, cs, ce);
+      if constexpr (MASK) ok &= mk[c0 + j] != 0;
+      a[j] = ok ? a[j] : -INFINITY;
+    }
+    eval_merge<N>(a, (int)c0, m, s, sumx, cnt, bi);
+  }
+  for (int64_t c = nvec * N + tid; c < V; c += 256) {
+    bool ok = scst_ok(c, V, cs, ce);
+    if constexpr (MASK) ok &= mk[c] != 0;
+    const float a[1] = {ok ? ld1<T>(x + c) : -INFINITY};     // (c < V: the load is in bounds whatever `ok` says)
+    eval_merge<1>(a, (int)c, m, s, sumx, cnt, bi);
+  }
+  const float mw = wave_max(m);
+  const float sw = wave_sum(mw == -INFINITY ? 0.f : s * expf(m - mw));
+  const float xw = wave_sum(sumx), cw = wave_sum(cnt);
+  const int iw = wave_min_i(m == mw ? bi : NO_COL);
+  if ((tid & 63) == 0) { sm[tid >> 6] = mw; ss[tid >> 6] = sw; sx[tid >> 6] = xw; sc[tid >> 6] = cw; si[tid >> 6] = iw; }
+  __syncthreads();
+  if (tid != 0) return;
+  const float M = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+  float S = 0.f;
+  int amax = NO_COL;
+  if (M > -INFINITY) {
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      S += ss[w] * expf(sm[w] - M);
+      if (sm[w] == M) amax = min(amax, si[w]);
+    }
+  }
+  const int64_t t = target[row];
+  bool valid = t >= 0 && scst_ok(t, V, cs, ce);
+  if constexpr (MASK) valid = valid && mk[t] != 0;
+  eval_row_done<T>(x, row, t, t == ignore_index, valid, M > -INFINITY ? M + logf(S) : -INFINITY, sx[0] + sx[1] + sx[2] + sx[3],
+                   sc[0] + sc[1] + sc[2] + sc[3], amax, cfg.eps, cfg.ranged != 0 || MASK, row_loss, row_nll, row_hit);
+}
+
+// One validation batch into the running accumulator acc fp64[4] = [ntokens, loss_sum, nll_sum, n_correct]: a single block sums the
+// rows in reduce_sum_f32_kernel's order (256 lanes striding the rows, wave sums, the four wave results in order) and counts the
+// targets that are not ignore_index -- one block, one order, no atomics: the same inputs give the same bits.
+__global__ __launch_bounds__(256) void eval_stats_add_kernel(double* __restrict__ acc, const float* __restrict__ row_loss,
+                                                             const float* __restrict__ row_nll, const int32_t* __restrict__ row_hit,
+                                                             const int64_t* __restrict__ target, int64_t rows, int64_t ignore_index) {
+  __shared__ float sl[4], sn[4];
+  __shared__ int sh[4], st[4];
+  float l = 0.f, n = 0.f;
+  int h = 0, c = 0;
+  for (int64_t i = threadIdx.x; i < rows; i += 256) {
+    l += row_loss[i];
+    n += row_nll[i];
+    h += row_hit[i] != 0;
+    c += target[i] != ignore_index;
+  }
+  l = wave_sum(l);
+  n = wave_sum(n);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { h += __shfl_xor(h, o, 64); c += __shfl_xor(c, o, 64); }
+  if ((threadIdx.x & 63) == 0) { sl[threadIdx.x >> 6] = l; sn[threadIdx.x >> 6] = n; sh[threadIdx.x >> 6] = h; st[threadIdx.x >> 6] = c; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    acc[0] += (double)(st[0] + st[1] + st[2] + st[3]);
+    acc[1] += (double)(sl[0] + sl[1] + sl[2] + sl[3]);
+    acc[2] += (double)(sn[0] + sn[1] + sn[2] + sn[3]);
+    acc[3] += (double)(sh[0] + sh[1] + sh[2] + sh[3]);
+  }
+}
+
 // get_normalized_probs (model/ofa.py:287-299): fp32 softmax / log-softmax of the logits, one block per row.
 __device__ __forceinline__ float block_sum(float v, float* sw) {
   v = wave_sum(v);
@@ -1159,6 +1393,75 @@ extern "C" int ofa_scst_loss_fwd_grad(const void* logits, const int64_t* target,
                    V, ld, ignore_index, cstart < 0 ? 0 : cstart, cstart < 0 ? V : cend, st);      // (no range: [0, V))
   });
   return check_launch("scst_loss_fwd_grad");
+}
+
+namespace ofa {
+// the node form: trie_loss.hip, next to the row core whose formulas it shares (arguments checked by the caller below)
+void trie_criterion_eval_launch(const void* logits, const int64_t* target, const int32_t* node, const int32_t* node_edge_off,
+                                const int32_t* edge_token, int64_t N, int64_t E, float* row_loss, float* row_nll, int32_t* row_hit,
+                                int64_t rows, int64_t V, int64_t ld, int64_t ignore_index, float eps, int64_t cstart, int64_t cend,
+                                int dtype, hipStream_t st);
+}
+static bool criterion_eval_regs_ok(const void* logits, const uint8_t* cmask, int64_t V, int64_t ld, int dtype) {
+  return (dtype == OFA_BF16 || dtype == OFA_F16) && !cmask && ld % 8 == 0 && ld <= 8 * 1024 * 8 && aligned16(logits);
+}
+
+extern "C" int ofa_criterion_eval(const void* logits, const int64_t* target, const uint8_t* cmask, const int32_t* node,
+                                  const int32_t* node_edge_off, const int32_t* edge_token, int64_t N, int64_t E, float* row_loss,
+                                  float* row_nll, int32_t* row_hit, int64_t rows, int64_t V, int64_t ld, int64_t ignore_index, float eps,
+                                  int64_t cstart, int64_t cend, int dtype, void* stream) {
+  const int64_t lim = (int64_t)1 << 31;
+  OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "criterion_eval: bad dtype %d", dtype);
+  OFA_REQUIRE(rows >= 0 && rows < lim && V > 1 && V < lim && ld >= V && logits && target && row_loss && row_nll && row_hit, OFA_ERR_INVALID,
+              "criterion_eval: bad argument (rows=%lld V=%lld ld=%lld)", (long long)rows, (long long)V, (long long)ld);
+  OFA_REQUIRE(eps >= 0.f && eps < 1.f && (cstart < 0 || (cstart >= 4 && cend > cstart && cend <= V)), OFA_ERR_INVALID,
+              "criterion_eval: bad eps / constraint range [%lld, %lld)", (long long)cstart, (long long)cend);
+  OFA_REQUIRE(!(node && cmask), OFA_ERR_INVALID, "criterion_eval: a closed set comes as a byte mask or as trie nodes, not both");
+  // (E leaves room for the gather loop's 32-bit edge index to step past the last edge, as ofa_trie_ls_cross_entropy_fwd)
+  OFA_REQUIRE(!node || (node_edge_off && N >= 1 && N < lim && E >= 0 && E < lim - 4096 && (edge_token || E == 0)), OFA_ERR_INVALID,
+              "criterion_eval: nodes without a trie (N=%lld E=%lld)", (long long)N, (long long)E);
+  if (rows == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (node) {
+    trie_criterion_eval_launch(logits, target, node, node_edge_off, edge_token, N, E, row_loss, row_nll, row_hit, rows, V, ld, ignore_index,
+                               eps, cstart, cend, dtype, st);
+    return check_launch("criterion_eval");
+  }
+  const EvalCfg cfg{eps, cstart < 0 ? 0 : (int)cstart, cstart < 0 ? (int)V : (int)cend, cstart < 0 ? 0 : 1};      // (no range: [0, V))
+  const bool regs = criterion_eval_regs_ok(logits, cmask, V, ld, dtype);
+  const int vec_ok = ld % dt_vecn(dtype) == 0 && aligned16(logits);
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    if constexpr (sizeof(T) == 2) {
+      if (regs) {
+        const int64_t per_thread = (ld / 8 + 1023) / 1024;
+#define EVAL_RG(NV) hipLaunchKernelGGL((criterion_eval_regs_kernel<T, NV>), dim3((unsigned)rows), dim3(1024), 0, st, (const T*)logits, target, row_loss, row_nll, row_hit, (int)V, (int)ld, ignore_index, cfg)
+        if (per_thread <= 1) EVAL_RG(1);
+        else if (per_thread <= 2) EVAL_RG(2);
+        else if (per_thread <= 4) EVAL_RG(4);
+        else if (per_thread <= 7) EVAL_RG(7);
+        else EVAL_RG(8);
+#undef EVAL_RG
+        return;
+      }
+    }
+    if (cmask)
+      hipLaunchKernelGGL((criterion_eval_stream_kernel<T, true>), dim3((unsigned)rows), dim3(256), 0, st, (const T*)logits, target, cmask,
+                         row_loss, row_nll, row_hit, V, ld, ignore_index, cfg, vec_ok);
+    else
+      hipLaunchKernelGGL((criterion_eval_stream_kernel<T, false>), dim3((unsigned)rows), dim3(256), 0, st, (const T*)logits, target, cmask,
+                         row_loss, row_nll, row_hit, V, ld, ignore_index, cfg, vec_ok);
+  });
+  return check_launch("criterion_eval");
+}
+
+extern "C" int ofa_eval_stats_add(double* acc, const float* row_loss, const float* row_nll, const int32_t* row_hit, const int64_t* target,
+                                  int64_t rows, int64_t ignore_index, void* stream) {
+  OFA_REQUIRE(acc && rows >= 0 && (rows == 0 || (row_loss && row_nll && row_hit && target)), OFA_ERR_INVALID, "eval_stats_add: bad argument");
+  if (rows == 0) return 0;
+  hipLaunchKernelGGL(eval_stats_add_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, acc, row_loss, row_nll, row_hit, target, rows,
+                     ignore_index);
+  return check_launch("eval_stats_add");
 }
 
 extern "C" int ofa_probs_fwd(const void* logits, float* out, int64_t rows, int64_t V, int64_t ld, int log_probs, int dtype,

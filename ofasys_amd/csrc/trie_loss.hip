@@ -150,6 +150,111 @@ __global__ __launch_bounds__(TRIE_THREADS) void trie_lsce_kernel(const T* __rest
   }
 }
 
+// Validation's node form (ofa_criterion_eval with nodes): the forward half of the row core above -- the same gather, the same
+// max-then-rescale sums -- plus the arg-max over the children as (stored value, lowest token): a node's children come in edge order,
+// not token order, so an equal value takes the smaller token at every step.  Writes row_loss, row_nll and row_hit; nothing else.
+template <typename T>
+__global__ __launch_bounds__(TRIE_THREADS) void trie_eval_kernel(const T* __restrict__ logits, const int64_t* __restrict__ target,
+                                                                 float* __restrict__ row_loss, float* __restrict__ row_nll,
+                                                                 int32_t* __restrict__ row_hit, int64_t V, int64_t ld, int64_t ignore_index,
+                                                                 TrieCfg cfg) {
+  constexpr int NO_TOK = 0x7fffffff;
+  __shared__ float sm[4], ss[4], sx[4], sc[4];
+  __shared__ int sf[4], si[4];
+  const int64_t row = blockIdx.x;
+  const int tid = threadIdx.x;
+  const T* x = logits + row * ld;
+  const int64_t t = target[row];
+  const bool ignored = t == ignore_index;
+  const int n = cfg.node[row];
+  int lo = 0, hi = 0;
+  if (n >= 0 && n < cfg.N) {
+    lo = max(cfg.node_edge_off[n], 0);
+    hi = min(cfg.node_edge_off[n + 1], cfg.E);
+  }
+  auto allowed = [&](int tok) {
+    return tok >= 0 && tok < V && (cfg.cs < 0 || tok < 4 || (tok >= cfg.cs && tok < cfg.ce));
+  };
+  float m = -INFINITY, s = 0.f, sumx = 0.f, cnt = 0.f;
+  int found = 0, bi = NO_TOK;
+  for (int e0 = lo + tid; e0 < hi; e0 += TRIE_THREADS * TRIE_UNROLL) {
+    int tok[TRIE_UNROLL];
+    float a[TRIE_UNROLL];
+    float lm = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < TRIE_UNROLL; ++j) {
+      const int e = e0 + j * TRIE_THREADS;
+      tok[j] = e < hi ? cfg.edge_token[e] : -1;
+      if (!allowed(tok[j])) tok[j] = -1;                   // (an edge_token outside [0, V) is skipped, never dereferenced)
+      found |= tok[j] >= 0 && tok[j] == t;
+      a[j] = tok[j] >= 0 ? ld1<T>(x + tok[j]) : -INFINITY;
+      lm = fmaxf(lm, a[j]);
+    }
+    if (lm > -INFINITY) {
+      const float mm = fmaxf(m, lm);
+      float acc = s * expf(m - mm);
+#pragma unroll
+      for (int j = 0; j < TRIE_UNROLL; ++j) {
+        acc += expf(a[j] - mm);
+        sumx += tok[j] >= 0 ? a[j] : 0.f;
+        cnt += tok[j] >= 0 ? 1.f : 0.f;
+        if (tok[j] >= 0 && (a[j] > m || (a[j] == m && tok[j] < bi))) { m = a[j]; bi = tok[j]; }    // (m ends as mm: the largest of them)
+      }
+      m = mm;
+      s = acc;
+    }
+  }
+  const float mw = wave_max(m);
+  const float sw = wave_sum(mw == -INFINITY ? 0.f : s * expf(m - mw));
+  sumx = wave_sum(sumx);
+  cnt = wave_sum(cnt);
+  int iw = m == mw ? bi : NO_TOK;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) iw = min(iw, __shfl_xor(iw, o, 64));
+  found = __any(found) ? 1 : 0;
+  if ((tid & 63) == 0) { sm[tid >> 6] = mw; ss[tid >> 6] = sw; sx[tid >> 6] = sumx; sc[tid >> 6] = cnt; sf[tid >> 6] = found; si[tid >> 6] = iw; }
+  __syncthreads();
+  if (tid != 0) return;
+  found = sf[0] | sf[1] | sf[2] | sf[3];
+  const float M = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+  float S = 0.f;
+  int amax = NO_TOK;
+  if (M > -INFINITY) {
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      S += ss[w] * expf(sm[w] - M);
+      if (sm[w] == M) amax = min(amax, si[w]);
+    }
+  }
+  const float l = M > -INFINITY ? M + logf(S) : -INFINITY;
+  const float C = sc[0] + sc[1] + sc[2] + sc[3];
+  float rl = 0.f, rn = 0.f;
+  int hit = 0;
+  if (!ignored && !found) {
+    rl = rn = INFINITY;                                    // (no allowed child of the node: as the row core above)
+  } else if (!ignored) {
+    const float eps_i = cfg.eps / (C - 1.f + 1e-6f);
+    rn = l - ld1<T>(x + t);                                // (found: t is an allowed column of [0, V))
+    rl = (1.f - cfg.eps - eps_i) * rn + eps_i * (C * l - (sx[0] + sx[1] + sx[2] + sx[3]));
+    hit = amax == (int)t;
+  }
+  row_loss[row] = rl;
+  row_nll[row] = rn;
+  row_hit[row] = hit;
+}
+
+void trie_criterion_eval_launch(const void* logits, const int64_t* target, const int32_t* node, const int32_t* node_edge_off,
+                                const int32_t* edge_token, int64_t N, int64_t E, float* row_loss, float* row_nll, int32_t* row_hit,
+                                int64_t rows, int64_t V, int64_t ld, int64_t ignore_index, float eps, int64_t cstart, int64_t cend,
+                                int dtype, hipStream_t st) {
+  const TrieCfg cfg{node, node_edge_off, edge_token, (int)N, (int)E, eps, cstart < 0 ? -1 : (int)cstart, (int)cend};
+  dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((trie_eval_kernel<T>), dim3((unsigned)rows), dim3(TRIE_THREADS), 0, st, (const T*)logits, target, row_loss, row_nll,
+                       row_hit, V, ld, ignore_index, cfg);
+  });
+}
+
 static int trie_check(const char* who, const void* logits, const int64_t* target, const int32_t* node, const int32_t* node_edge_off,
                       const int32_t* edge_token, int64_t N, int64_t E, int64_t rows, int64_t V, int64_t ld, float eps, int64_t cstart,
                       int64_t cend, const void* dlogits, int dtype) {

@@ -10,8 +10,13 @@
 EMA (engine/ema/ema.py; `cfg.ema`, or store_ema= / ema_decay= / ... as flat options): kept on the device and updated inside the step
 (ofasys_amd/ema.py); `Trainer.ema` is the object -- get_model(), reverse(model), state_dict().
 
-Out of scope: CLI / hydra config tree, checkpoints (hence ema_seed_model), metrics / logging back-ends,
-validation loops, FSDP / BMUF.  One process per GPU: when WORLD_SIZE > 1 (torch.distributed.run) the process group is initialised on RCCL.
+Validation (engine/trainer.py:982-1030 `valid_step`, task/base.py:680-703): `Trainer.validate` walks a task's "valid" split once through
+the step engine's forward-only `valid_step` (one kernel pass per batch for loss, NLL and token accuracy, accumulated on the device, one
+synchronisation per pass) -- on request with the EMA weights; `validate_interval_updates=N` makes `fit` do so every N updates and at
+the end.  Training is untouched by it: the same run with and without validation computes the same weights, bit for bit.
+
+Out of scope: CLI / hydra config tree, checkpoints (hence ema_seed_model), generation metrics / logging back-ends,
+FSDP / BMUF.  One process per GPU: when WORLD_SIZE > 1 (torch.distributed.run) the process group is initialised on RCCL.
 """
 import logging
 import os
@@ -44,6 +49,9 @@ class CommonConfig:
     graph_pad_to_multiple: int = 16    # with use_graph: text batches are padded to a multiple of this (collate_tokens' own
                                        # pad_to_multiple, preprocessor/utils.py:75-113) so that a few hipGraphs cover the length
                                        # distribution and every DP rank meets the same few structures; 1 = the reference's padding
+    validate_interval_updates: int = 0 # fit() validates every N completed updates and once at the end (0: never; the reference's name)
+    max_valid_steps: Optional[int] = None      # at most this many batches per task and validation pass (None: the whole split)
+    validate_with_ema: bool = False    # fit()'s validation passes run on the EMA weights (needs store_ema)
 
 
 @dataclass
@@ -132,6 +140,8 @@ class Trainer:
         self.global_dict = None
         self.step_engine: Optional[TrainStep] = None
         self.history = []
+        self.valid_history = []                     # one record per validate(): {"update", "ema", task name: result dict}
+        self._tasks = []
         self._scst = {}                             # task name -> scst.ScstRewardCriterion (tasks with cfg.scst)
         self._score_sum, self._score_n = 0.0, 0     # CIDEr-D of this rank's hypotheses since the last history record
 
@@ -194,6 +204,7 @@ class Trainer:
             task.init_data_iterator("train", rank, world)
         self._device, self._rank, self._world = device, rank, world
         self._float_dtype = torch.float32 if cfg.common.fp32 else half
+        self._tasks = list(tasks)
         return self.step_engine
 
     def _loss_scale_cfg(self, world):
@@ -228,14 +239,62 @@ class Trainer:
                     self._score_n += log["nsentences"]
                     out.append(mb)
                     continue
-                mb = {"slots": s["net_input"]["slots"], "target": s["target"], "task": task.name}
-                if s.get("constraint_masks") is not None:
-                    mb["constraint_masks"] = s["constraint_masks"]
-                if s.get("constraint_nodes") is not None:         # cfg.text.closed_set_nodes: one trie node per target position
-                    mb["constraint_nodes"] = s["constraint_nodes"]
-                    mb["constraint_trie"] = task.constraint_trie_on(self._device)
-                out.append(mb)
+                out.append(self._plain_micro_batch(task, s))
         return out
+
+    def _plain_micro_batch(self, task, s):
+        """A collated sample on the device as the micro-batch dict TrainStep.train_step / valid_step take."""
+        mb = {"slots": s["net_input"]["slots"], "target": s["target"], "task": task.name}
+        if s.get("constraint_masks") is not None:
+            mb["constraint_masks"] = s["constraint_masks"]
+        if s.get("constraint_nodes") is not None:         # cfg.text.closed_set_nodes: one trie node per target position
+            mb["constraint_nodes"] = s["constraint_nodes"]
+            mb["constraint_trie"] = task.constraint_trie_on(self._device)
+        return mb
+
+    # ------------------------------------------------------------------ validation
+    @staticmethod
+    def _valid_tasks(tasks, split):
+        """The tasks a validation pass covers: those with a `split` dataset.  An SCST task is refused: the reference validates it by
+        generating, which the criterion pass cannot stand in for."""
+        out = []
+        for task in tasks:
+            if task.datasets.get(split) is None:
+                continue
+            if task.cfg.scst:
+                raise NotImplementedError(f"task {task.name}: an SCST task (cfg.scst) is validated by generating in the reference; "
+                                          "Trainer.validate runs the criterion only -- leave the task out of `tasks`")
+            out.append(task)
+        return out
+
+    def validate(self, tasks=None, split="valid", use_ema=False, max_steps=None):
+        """One pass over `split` of every task that has it (default: the tasks of setup() / fit()) -> {task name: result dict}:
+        loss, nll_loss (base 2 per token), ppl, ntokens, sample_size and -- for tasks with cfg.criterion.report_accuracy --
+        n_correct, total, accuracy (TrainStep.valid_result).  use_ema: with the averaged weights.  max_steps: at most that many
+        batches per task.  Appends {"update", "ema", **results} to `valid_history`; one synchronisation per task."""
+        if self.step_engine is None:
+            raise RuntimeError("Trainer.validate needs setup() or fit() first: the step engine owns the model")
+        engine = self.step_engine
+        results = {}
+        for task in self._valid_tasks(self._tasks if tasks is None else tasks, split):
+            engine.valid_begin()
+            for i, s in enumerate(task.valid_batches(split, self._rank, self._world)):
+                if max_steps is not None and i >= max_steps:
+                    break
+                s = to_device(s, self._device, self._float_dtype)
+                engine.valid_step([self._plain_micro_batch(task, s)], use_ema=use_ema)
+            res = engine.valid_result()
+            if not task.cfg.criterion.report_accuracy:
+                for k in ("n_correct", "total", "accuracy"):
+                    res.pop(k)
+            results[task.name] = res
+            if self._rank == 0:
+                acc = f" | accuracy {res['accuracy']:.2f}" if "accuracy" in res else ""
+                logger.info("valid on '%s' subset%s | task %s | update %d | loss %.4f | nll_loss %.4f | ppl %.2f | ntokens %d%s", split,
+                            " (ema)" if use_ema else "", task.name, engine.num_updates, res["loss"], res["nll_loss"], res["ppl"],
+                            int(res["ntokens"]), acc)
+        self.valid_history.append({"update": engine.num_updates, "ema": bool(use_ema), **results})
+        return results
 
     # ------------------------------------------------------------------ the loop
     def fit(self, model, tasks: List[Task]):
@@ -248,6 +307,9 @@ class Trainer:
         # one step) and reads it exactly at log time and before leaving the loop.
         poll = _SkipPoll() if self._device.type == "cuda" else None
         skipped, attempts, max_update = 0, 0, cfg.optimization.max_update
+        interval, validated_at = int(cfg.common.validate_interval_updates or 0), 0
+        if interval > 0:
+            self._valid_tasks(tasks, "valid")                        # (an SCST task with a valid split: refused before the first update)
         while attempts - skipped < max_update:
             attempts += 1
             update = attempts - skipped                              # the update this attempt will be if it is not skipped
@@ -272,5 +334,10 @@ class Trainer:
                                 "gnorm %(gnorm).3f | lr %(lr).3g", rec)
             if attempts > 4 * max_update + 64:                       # every step skipped and no scaler floor to stop at
                 raise FloatingPointError(f"{skipped} of {attempts} updates were skipped on the device (non-finite gradients)")
+            if interval > 0:
+                done = attempts - skipped                            # completed updates (as exact as the skip counter's last read)
+                if done > validated_at and (done % interval == 0 or last):
+                    validated_at = done
+                    self.validate(tasks, use_ema=cfg.common.validate_with_ema, max_steps=cfg.common.max_valid_steps)
         torch.cuda.synchronize()
         return self.history

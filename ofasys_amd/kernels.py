@@ -1071,6 +1071,40 @@ def trie_ls_cross_entropy_bwd(logits2d, target, nodes, trie, lse, row_cnt, row_w
     return dlogits
 
 
+def criterion_eval(logits2d, target, V, ignore_index, eps, cstart=-1, cend=-1, cmask=None, nodes=None, trie=None):
+    """Validation's criterion rows in one read of the logits (ofa_criterion_eval): returns row_loss, row_nll (fp32 [rows]) and row_hit
+    (int32 [rows]: the target is the arg-max over the allowed set).  The allowed set: the whole vocabulary, the range, a byte mask
+    [rows, V], or the children of trie node nodes[row] (`trie` as in trie_ls_cross_entropy_fwd).  The outputs are fresh tensors (inside
+    a capture: of the capturing graph's pool), there is no other scratch."""
+    rows, ld = logits2d.shape[0], logits2d.stride(0) if logits2d.shape[0] > 1 else max(logits2d.stride(0), V)
+    assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == rows, (target.dtype, target.shape, rows)
+    row_loss = torch.empty(rows, dtype=torch.float32, device=logits2d.device)
+    row_nll = torch.empty(rows, dtype=torch.float32, device=logits2d.device)
+    row_hit = torch.empty(rows, dtype=torch.int32, device=logits2d.device)
+    targs = (None, None, None, 0, 0)
+    if nodes is not None:
+        if trie is None:
+            raise ValueError("criterion_eval: nodes need the trie's device arrays")
+        targs = _trie_args(logits2d, target, nodes, trie)
+    if cmask is not None:
+        cmask = _u8(cmask)
+        assert cmask.is_contiguous() and cmask.numel() == rows * V, (cmask.shape, rows, V)
+    lib().call("ofa_criterion_eval", ptr(logits2d), ptr(target), ptr(cmask), *targs, ptr(row_loss), ptr(row_nll), ptr(row_hit), rows, V, ld,
+               int(ignore_index), float(eps), int(cstart), int(cend), dtype_code(logits2d), stream())
+    return row_loss, row_nll, row_hit
+
+
+def eval_stats_add(acc, row_loss, row_nll, row_hit, target, ignore_index):
+    """acc (fp64 [4]: ntokens, loss_sum, nll_sum, n_correct) += one batch's rows, summed in a fixed order by one block
+    (ofa_eval_stats_add): the same inputs give the same bits."""
+    assert acc.dtype == torch.float64 and acc.numel() >= 4 and acc.is_contiguous()
+    rows = row_loss.numel()
+    t = target.reshape(-1)
+    assert t.dtype == torch.int64 and t.is_contiguous() and t.numel() == rows
+    assert row_loss.dtype == row_nll.dtype == torch.float32 and row_hit.dtype == torch.int32 and row_nll.numel() == row_hit.numel() == rows
+    lib().call("ofa_eval_stats_add", ptr(acc), ptr(row_loss), ptr(row_nll), ptr(row_hit), ptr(t), rows, int(ignore_index), stream())
+
+
 def scst_loss_fwd_grad(logits2d, target, reward, grad_scale, V, ignore_index, rows_per_seq=1, row_seq=None, cstart=-1, cend=-1,
                        dlogits=None):
     """Reward-weighted NLL rows and their gradient in one call (ofa_scst_loss_fwd_grad): returns lse, row_loss (fp32 [rows]) and

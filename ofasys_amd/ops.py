@@ -2158,6 +2158,32 @@ def scst_loss(logits, target, reward, ignore_index, constraint_range=None, row_s
     return ScstLossFn.apply(logits, target, reward, ignore_index, constraint_range, row_seq, seed)
 
 
+def criterion_eval(logits, target, pad, eps, constraint_range=None, constraint_masks=None, nodes=None, trie=None, acc=None):
+    """Validation's criterion (engine/criterion/label_smoothed_cross_entropy.py:114-198 in eval mode), no autograd: one read of the
+    [..., V] logits gives per row the label-smoothed loss, the NLL and "the target is the arg-max of the allowed logits"
+    (kernels.criterion_eval), and a second, single-block launch adds [ntokens, loss_sum, nll_sum, n_correct] to `acc` (fp64 [4];
+    None: a fresh zero accumulator) in a fixed order.  The allowed set as in label_smoothed_cross_entropy (range, byte masks) or
+    trie_label_smoothed_cross_entropy (nodes + trie).  Returns (acc, row_loss, row_nll, row_hit); nothing is synchronised."""
+    V = logits.shape[-1]
+    with torch.no_grad():
+        l2d = _ce_rows(logits.detach())
+        t = target.reshape(-1).contiguous()
+        cs, ce = constraint_range if constraint_range is not None else (-1, -1)
+        cm = constraint_masks.reshape(-1, V).contiguous() if constraint_masks is not None else None
+        nd = None
+        if nodes is not None:
+            if cm is not None:
+                raise ValueError("criterion_eval: a closed set comes as constraint_masks or as nodes, not both")
+            nd = nodes.reshape(-1).to(device=l2d.device, dtype=torch.int32).contiguous()
+            if nd.numel() != l2d.shape[0]:
+                raise ValueError(f"criterion_eval: {nd.numel()} nodes for {l2d.shape[0]} rows")
+        row_loss, row_nll, row_hit = K.criterion_eval(l2d, t, V, pad, eps, cs, ce, cm, nd, trie)
+        if acc is None:
+            acc = torch.zeros(4, dtype=torch.float64, device=l2d.device)
+        K.eval_stats_add(acc, row_loss, row_nll, row_hit, t, pad)
+    return acc, row_loss, row_nll, row_hit
+
+
 def _rows_padded(logits):
     """[..., V] tensor -> ([rows, V] view with last dim contiguous, ld)."""
     V = logits.shape[-1]

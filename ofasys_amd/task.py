@@ -6,7 +6,9 @@
 
 Generation: `Task.generator` / `Task.inference` run beam search (ofasys_amd/generator.py SequenceGenerator; task/base.py:232-246,
 470-556, 727-793) for TEXT targets.
-What stays out: file / OSS readers, multi-worker prefetch, metrics, non-text generators, checkpoint state.  The
+Validation: `Task.valid_batches` walks a split once, in order; `Trainer.validate` (engine.py) runs it through the step engine's
+forward-only `valid_step` -- loss, NLL and, with `cfg.criterion.report_accuracy`, token accuracy (task/base.py:680-703).
+What stays out: file / OSS readers, multi-worker prefetch, generation metrics, non-text generators, checkpoint state.  The
 batch iterator is a plain in-process loop over the bound dataset: micro-batches of `micro_batch_size` rows, each rank of a
 data-parallel job reading its own contiguous shard (io/reader/dataset.py:49-53), reshuffled per epoch with a seeded permutation.
 """
@@ -48,6 +50,7 @@ class InstructionConfig:                              # task/base.py:123-137
 class CriterionConfig:                                # engine/criterion/label_smoothed_cross_entropy.py:27-59 / cross_entropy.py
     label_smoothing: float = 0.0
     drop_worst_ratio: float = 0.0
+    report_accuracy: bool = False                     # validation also reports n_correct / total / accuracy (:49-52, :180-198)
     # "scst_reward_criterion" (engine/criterion/scst_loss.py:39-56; used by a task with cfg.scst): the fields below are its own
     name: str = "label_smoothed_cross_entropy"
     scst_cider_cached_tokens: Any = "corpus"          # a pickle path (ref_len, document_frequency), such a dict, or "corpus"
@@ -238,6 +241,17 @@ class Task:
                 idx = order[i:i + bs]
                 yield self.collate([ds[int(j) % n] for j in idx], split)
             epoch += 1
+
+    def valid_batches(self, split="valid", rank=0, world=1):
+        """A FINITE iterator over the rank's shard of `split` for one validation pass (task/base.py:680-703 with the reference's
+        non-shuffled eval iterator): every row once, in dataset order, micro_batch_size rows per batch and the last, shorter batch
+        included.  The shards are contiguous and together cover the whole dataset: rank r reads rows [r n / world, (r + 1) n / world)."""
+        ds = self.datasets[split]
+        n = len(ds)
+        lo, hi = rank * n // world, (rank + 1) * n // world
+        bs = self.cfg.dataset.micro_batch_size
+        for i in range(lo, hi, bs):
+            yield self.collate([ds[int(j)] for j in range(i, min(i + bs, hi))], split)
 
     def init_data_iterator(self, split="train", rank=0, world=1):
         self._iters[split] = self._batches(split, rank, world)

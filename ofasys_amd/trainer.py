@@ -12,6 +12,7 @@ Step arithmetic reproduced:
 The multiply, the clip coefficient and Adam are ONE kernel pass over the flat arena (coef stays on the device: no host
 sync anywhere in the step).
 """
+import contextlib
 import os
 import warnings
 from typing import List
@@ -347,6 +348,11 @@ class TrainStep:
         self._skipped_seen = 0.0
         self._seed = torch.ones((), dtype=torch.float32, device=dev)   # the backward seed of a micro-batch's loss (autograd's default: one fill per call)
         self.last = {}
+        # validation (valid_begin / valid_step / valid_result): its accumulator [ntokens, loss_sum, nll_sum, n_correct] and its own
+        # table of forward-only graphs; nothing of the training state above is written by it
+        self._valid_acc = torch.zeros(4, dtype=torch.float64, device=dev)
+        self._valid_graphs = {}                     # (batch structure, use_ema) -> dict(graphs, static samples, seen count)
+        self._warned_valid_cap = False
         ema_cfg = as_config(ema)
         self.ema = EMA(model, self.fp, ema_cfg, step_t=self._step_t) if ema_cfg is not None else None
 
@@ -404,40 +410,46 @@ class TrainStep:
     def _fused_norm(self):
         return self.world == 1 and not K.tail_old(K.TAIL_NORM_SCHEDULE)
 
+    def _criterion_inputs(self, model, s):
+        """One micro-batch through `model` -> (logits, target, constraint masks, constraint nodes, pack plan) as the criterion takes
+        them: by padded position, or (pack plan) by packed decoder row.  The train step and the validation step share it."""
+        plan = s.get("pack")
+        target = s["target"]
+        if plan is None:
+            logits = model(s["slots"])[0]
+        else:                                    # ragged batch (packing.py): logits and targets by packed decoder row
+            logits = model(s["slots"], pack=plan)[0]
+            target = s.get("target_packed")
+            if target is None:
+                idx = plan.dec_index
+                target = s["target"].reshape(-1)[idx.clamp_min(0)].masked_fill(idx < 0, self.pad).view(1, -1)
+        cm = s.get("constraint_masks")
+        if plan is not None and cm is not None:
+            raise NotImplementedError("constraint masks are laid out by padded position: run such samples without a pack plan")
+        # closed-set targets by trie node (collate's closed_set_nodes): one int32 per target position instead of a mask row, and
+        # "constraint_trie", the task's device arrays of the answer trie; the nodes follow the targets into a packed layout
+        nodes = s.get("constraint_nodes")
+        if nodes is not None:
+            if cm is not None:
+                raise ValueError("a micro-batch carries its closed set as constraint_masks or as constraint_nodes, not both")
+            if s.get("reward") is not None:
+                raise NotImplementedError("an SCST micro-batch (reward) cannot carry constraint_nodes: its criterion takes a "
+                                          "constraint range only (engine/criterion/scst_loss.py:214-217)")
+            if s.get("constraint_trie") is None:
+                raise ValueError("constraint_nodes need \"constraint_trie\": the device arrays of the answer trie "
+                                 "(Task.constraint_trie_on(device))")
+            if plan is not None:
+                packed = s.get("constraint_nodes_packed")
+                if packed is None:
+                    idx = plan.dec_index
+                    packed = nodes.reshape(-1)[idx.clamp_min(0)].masked_fill(idx < 0, -1)
+                nodes = packed.view(1, -1)
+        return logits, target, cm, nodes, plan
+
     def _micro_batches(self, samples):
         model = self.model
         for s in samples:
-            plan = s.get("pack")
-            target = s["target"]
-            if plan is None:
-                logits = model(s["slots"])[0]
-            else:                                    # ragged batch (packing.py): logits and targets by packed decoder row
-                logits = model(s["slots"], pack=plan)[0]
-                target = s.get("target_packed")
-                if target is None:
-                    idx = plan.dec_index
-                    target = s["target"].reshape(-1)[idx.clamp_min(0)].masked_fill(idx < 0, self.pad).view(1, -1)
-            cm = s.get("constraint_masks")
-            if plan is not None and cm is not None:
-                raise NotImplementedError("constraint masks are laid out by padded position: run such samples without a pack plan")
-            # closed-set targets by trie node (collate's closed_set_nodes): one int32 per target position instead of a mask row, and
-            # "constraint_trie", the task's device arrays of the answer trie; the nodes follow the targets into a packed layout
-            nodes = s.get("constraint_nodes")
-            if nodes is not None:
-                if cm is not None:
-                    raise ValueError("a micro-batch carries its closed set as constraint_masks or as constraint_nodes, not both")
-                if s.get("reward") is not None:
-                    raise NotImplementedError("an SCST micro-batch (reward) cannot carry constraint_nodes: its criterion takes a "
-                                              "constraint range only (engine/criterion/scst_loss.py:214-217)")
-                if s.get("constraint_trie") is None:
-                    raise ValueError("constraint_nodes need \"constraint_trie\": the device arrays of the answer trie "
-                                     "(Task.constraint_trie_on(device))")
-                if plan is not None:
-                    packed = s.get("constraint_nodes_packed")
-                    if packed is None:
-                        idx = plan.dec_index
-                        packed = nodes.reshape(-1)[idx.clamp_min(0)].masked_fill(idx < 0, -1)
-                    nodes = packed.view(1, -1)
+            logits, target, cm, nodes, plan = self._criterion_inputs(model, s)
             counted = False
             size = None
             if nodes is not None:
@@ -603,7 +615,7 @@ class TrainStep:
         """Tensors whose lifetime is the step engine's / the model's own (what a capture may address without a pin)."""
         own = list(self.model.parameters()) + list(self.model.buffers())
         own += [self.fp.flat, self.fp.grad, self.master, self.exp_avg, self.exp_avg_sq, self._stats, self._gsq, self._gnorm_t,
-                self._step_t, self._lr_t, self._sched, self._seed, getattr(self, "_ls", None)]
+                self._step_t, self._lr_t, self._sched, self._seed, getattr(self, "_ls", None), self._valid_acc]
         own += list(ops._Rng.base.values())
         if self.ema is not None:
             own += self.ema.arenas()
@@ -687,5 +699,141 @@ class TrainStep:
             self.last["loss_scale"] = self._ls[0:1]
         return self.last
 
+    # ------------------------------------------------------------------ validation: forward only, no training state touched
+    def valid_begin(self):
+        """Start a validation pass: zero the accumulator [ntokens, loss_sum, nll_sum, n_correct] (a device tensor the engine owns)."""
+        self._valid_acc.zero_()
 
-Trainer = TrainStep            # the name round-1 code and tests use; `ofasys_amd.Trainer` is the fit() facade (engine.py)
+    @contextlib.contextmanager
+    def _valid_mode(self, model):
+        """`model` as a validation forward runs it: eval mode, no autograd, and the decoder layers' `need_attn` off -- in eval mode a
+        layer otherwise returns its cross-attention weights (the reference's layers do: its generators turn that off with
+        make_generation_fast_), which nobody reads here and which takes attention off the fused kernels (packed batches run on those
+        alone).  On exit the mode and the flags are as they were found, and so is the host side of the Philox position (eval mode
+        draws nothing unless a module says apply_during_inference)."""
+        was_training = model.training
+        flagged = [m for m in model.modules() if getattr(m, "need_attn", None) is True]
+        rng = ops._Rng.offset
+        model.eval()
+        for m in flagged:
+            m.need_attn = False
+        try:
+            with torch.no_grad():
+                yield model
+        finally:
+            for m in flagged:
+                m.need_attn = True
+            ops._Rng.offset = rng
+            model.train(was_training)
+
+    def _valid_forward(self, samples, model):
+        """The micro-batches through `model` (see _valid_mode) and through ops.criterion_eval (the engine's label_smoothing /
+        constraint_range; no drop_worst: the reference's eval call never drops) into the accumulator.  Nothing here reads or writes
+        the gradient arena, the step statistics, the optimizer or EMA state or the device counters."""
+        with self._valid_mode(model):
+            for s in samples:
+                logits, target, cm, nodes, _ = self._criterion_inputs(model, s)
+                ops.criterion_eval(logits, target, self.pad, self.label_smoothing, self.constraint_range, cm, nodes,
+                                   s["constraint_trie"] if nodes is not None else None, acc=self._valid_acc)
+
+    def captured_valid_graphs(self):
+        return sum(1 for e in self._valid_graphs.values() if "graphs" in e)
+
+    def _capture_valid(self, samples, model):
+        import gc
+        gc.collect()
+        if self._pool is None:
+            self._pool = torch.cuda.graph_pool_handle()
+        entry = {"static": samples, "graphs": []}
+        with capture_audit() as audit, _AtenAudit(audit):          # (the pins: see _capture)
+            g = torch.cuda.CUDAGraph()
+            _KEEP_ALIVE.append(g)
+            with torch.cuda.graph(g, pool=self._pool, capture_error_mode=_CAPTURE_MODE):
+                self._valid_forward(samples, model)
+            entry["graphs"] = [g]
+        entry["audit"] = audit
+        entry["pins"] = audit.tensors()
+        return entry
+
+    def _replay_valid(self, entry, samples):
+        if samples is not entry["static"]:
+            K.copy_batched([(dst, src) for (_, dst), (_, src) in zip(entry["static_tensors"], sample_tensors(samples)) if dst is not src])
+        entry["graphs"][0].replay()
+
+    def valid_step(self, samples: List[dict], eager: bool = False, use_ema: bool = False):
+        """One validation batch: the micro-batch dicts `train_step` takes (pack plans, target_packed, constraint_masks,
+        constraint_nodes + constraint_trie [+ constraint_nodes_packed], with the same refusals), forward only, accumulated on the device
+        (engine/trainer.py:982-1030 `valid_step`; the criterion in eval mode, label_smoothed_cross_entropy.py:114-198).  A micro-batch
+        with "reward" (SCST) is refused: the reference validates those by generating.  use_ema: the forward runs on the averaged
+        model (`self.ema.get_model()`).  With use_graph, one forward-only hipGraph per (batch structure, use_ema) is captured after
+        `graph_warmup` eager visits -- its own table and its own cap of `max_graphs`, the engine's memory pool -- and replayed.
+        Nothing is returned and nothing synchronises: `valid_result()` reads the pass."""
+        for s in samples:
+            if s.get("reward") is not None:
+                raise NotImplementedError("an SCST micro-batch (reward) cannot be validated by the criterion: the reference validates "
+                                          "such tasks by generating (engine/criterion/scst_loss.py)")
+        if use_ema:
+            if self.ema is None:
+                raise RuntimeError("valid_step(use_ema=True) needs an EMA of the weights: build the engine with ema={'store_ema': True}")
+            model = self.ema.get_model()
+        else:
+            model = self.model
+        structure = None
+        if self.use_graph and not eager:
+            try:
+                structure = (sample_structure(samples), bool(use_ema))
+            except _Uncapturable:
+                structure = None                    # (train_step warns about such samples; validation just runs them eagerly)
+        if structure is not None:
+            entry = self._valid_graphs.get(structure)
+            if entry is None:
+                if len(self._valid_graphs) >= 64 * max(self.max_graphs, 1):
+                    self._valid_graphs = {k: e for k, e in self._valid_graphs.items() if "graphs" in e}
+                entry = self._valid_graphs[structure] = {"seen": 0}
+            if "graphs" in entry:
+                self._replay_valid(entry, samples)
+                return
+            if entry["seen"] >= self.graph_warmup:
+                if self.captured_valid_graphs() >= self.max_graphs:
+                    if not self._warned_valid_cap:
+                        warnings.warn(f"ofasys_amd.TrainStep: {self.max_graphs} validation batch structures are captured already; "
+                                      "further ones run eagerly (bucket the padded lengths or raise max_graphs)")
+                        self._warned_valid_cap = True
+                else:
+                    try:
+                        torch.cuda.synchronize()
+                        cap = self._capture_valid(samples, model)
+                    except Exception as e:
+                        warnings.warn(f"ofasys_amd.TrainStep: hipGraph capture (validation) failed ({type(e).__name__}: {e}); a failed "
+                                      "capture cannot be retried in this process -- running eagerly")
+                        self.use_graph = False
+                    else:
+                        cap["static_tensors"] = sample_tensors(cap["static"])
+                        entry.update(cap)
+                        self._replay_valid(entry, samples)
+                        return
+            else:
+                entry["seen"] += 1
+        self._valid_forward(samples, model)
+
+    def valid_result(self):
+        """The pass since valid_begin(): ONE synchronisation (and, data parallel, one all-reduce of the accumulator) ->
+        dict(loss, nll_loss, ppl, ntokens, sample_size, n_correct, total, accuracy); see `valid_metrics`."""
+        return valid_metrics(self._valid_acc, self.group if self.world > 1 else None, self.world)
+
+
+def valid_metrics(acc, group=None, world=1):
+    """The accumulator [ntokens, loss_sum, nll_sum, n_correct] (fp64 [4]; summed over the ranks of `group` when world > 1, on a copy)
+    -> the reference's validation log (label_smoothed_cross_entropy.py:200-238 `reduce_metrics`): loss per sample_size and nll_loss
+    per token in base 2, ppl = 2 ** nll_loss, accuracy = 100 n_correct / total.  sample_size = ntokens (sentence_avg is off).
+    An empty pass gives zeros, not NaN."""
+    if world > 1:
+        acc = all_reduce_scalars(acc.clone(), group)
+    ntokens, loss_sum, nll_sum, n_correct = acc.tolist()            # the one synchronisation
+    ln2 = 0.6931471805599453
+    nll = nll_sum / max(ntokens, 1.0) / ln2
+    return {"loss": loss_sum / max(ntokens, 1.0) / ln2, "nll_loss": nll, "ppl": 2.0 ** nll if nll < 1000.0 else float("inf"), "ntokens": ntokens, "sample_size": ntokens,
+            "n_correct": n_correct, "total": ntokens, "accuracy": 100.0 * n_correct / max(ntokens, 1.0)}
+
+
+Trainer = TrainStep           # the name round-1 code and tests use; `ofasys_amd.Trainer` is the fit() facade (engine.py)
