@@ -490,6 +490,37 @@ int ofa_trie_ls_cross_entropy_bwd(const void* logits, const int64_t* target, con
                                   const float* row_w, const float* grad_scale, void* dlogits, int64_t rows, int64_t V,
                                   int64_t ld, int64_t ignore_index, float eps, int64_t cstart, int64_t cend, int dtype,
                                   void* stream);
+/* The trie-edge head (csrc/trie_head.hip): the same criterion computed from FEATURES, the [rows, V] logits and their gradient never
+ * built.  Row r on node n = node[r] has the slots j = 0 .. min(degree(n), Cmax) - 1, slot j being edge node_edge_off[n] + j; feats
+ * [rows, D] (row stride ld_x), W [V, D] (ld_w), bias [V] or NULL, all of `dtype`, D a whole number of 16-byte vectors, rows 16-byte aligned.
+ * fwd, one launch: z[r, j] = feats[r] . W[edge_token[e]] (+ bias) with fp32 accumulation into z fp32 [rows, Cmax]; over the allowed
+ * slots ofa_trie_ls_cross_entropy_fwd's lse, row_loss, row_nll, row_cnt (same formulas, same refusals, +inf for a dead row) and the
+ * UNSCALED compact gradient g fp32 [rows, Cmax]: g[r, j] = w_nll (p_j - [tok_j == target]) + eps_i (C p_j - 1), exactly 0 in a disallowed
+ * slot and in every slot of an ignored, filler (node -1) or dead row.  Slots past a row's degree are not written.  row_hit != NULL
+ * (validation): also "the target is the arg-max of the allowed children" with ofa_criterion_eval's tie rule (value, then lowest token);
+ * g may then be NULL.
+ * bwd_dx: dfeats[r, :] = grad_scale[0] row_w[r] sum_j g[r, j] W[tok_j, :] in `dtype` (row stride ld_dx), every row written in full.
+ * bwd_dw: dW[u, :] += grad_scale[0] sum_{(r, j): tok_j = u} row_w[r] g[r, j] feats[r, :] (and dbias[u] += the same sum of coefficients,
+ * dbias optional), no float atomics: one wave per distinct token u = head_tokens[.] walks tok_edge[tok_edge_off[.] ..) in order (the
+ * plan's inverse CSR by token: head_tokens int32 [U] ascending, tok_edge_off [U + 1], tok_edge [E]), per edge the rows
+ * bucket_rows[bucket_off[n] .. bucket_off[n + 1]) of the edge's node n = edge_node[e] in order (rows ordered by node, int32 [rows] and
+ * [N + 1], built per step), sums in fp32 and does one read-modify-write of dW[u] in `dtype`: the same inputs give the same bits.  A
+ * token without a contributing row is not touched.  grad_scale (device scalar) and row_w are optional (NULL = 1).
+ * Every index read from device memory is clamped or skipped before use; a token outside [0, V) is never dereferenced. */
+int ofa_trie_head_fwd(const void* feats, int64_t ld_x, const void* W, int64_t ld_w, const void* bias, int64_t D, int64_t V,
+                      const int64_t* target, const int32_t* node, const int32_t* node_edge_off, const int32_t* edge_token, int64_t N,
+                      int64_t E, int64_t Cmax, float* z, float* lse, float* row_loss, float* row_nll, float* row_cnt, float* g,
+                      int32_t* row_hit, int64_t rows, int64_t ignore_index, float eps, int64_t cstart, int64_t cend, int dtype,
+                      void* stream);
+int ofa_trie_head_bwd_dx(const float* g, const void* W, int64_t ld_w, int64_t D, int64_t V, const int64_t* target, const int32_t* node,
+                         const int32_t* node_edge_off, const int32_t* edge_token, int64_t N, int64_t E, int64_t Cmax,
+                         const float* row_w, const float* grad_scale, void* dfeats, int64_t ld_dx, int64_t rows, int64_t ignore_index,
+                         int64_t cstart, int64_t cend, int dtype, void* stream);
+int ofa_trie_head_bwd_dw(const float* g, const void* feats, int64_t ld_x, int64_t D, int64_t V, const int32_t* node_edge_off,
+                         const int32_t* edge_node, int64_t N, int64_t E, int64_t Cmax, const int32_t* head_tokens,
+                         const int32_t* tok_edge_off, const int32_t* tok_edge, int64_t U, const int32_t* bucket_rows,
+                         const int32_t* bucket_off, const float* row_w, const float* grad_scale, void* dW, int64_t ld_dw, void* dbias,
+                         int64_t rows, int64_t cstart, int64_t cend, int dtype, void* stream);
 /* self-critical sequence training (engine/criterion/scst_loss.py:24-36, 214-233): reward-weighted NLL of the generated tokens, forward
  * AND gradient in one call.  Row r belongs to sentence s = row_seq ? row_seq[r] : r / rows_per_seq and carries the weight
  * w = reward[s] (fp32 [nseq]; an s outside [0, nseq) reads nothing and weighs 0).  Over the allowed vocabulary A -- all of it

@@ -52,6 +52,8 @@ class CommonConfig:
     validate_interval_updates: int = 0 # fit() validates every N completed updates and once at the end (0: never; the reference's name)
     max_valid_steps: Optional[int] = None      # at most this many batches per task and validation pass (None: the whole split)
     validate_with_ema: bool = False    # fit()'s validation passes run on the EMA weights (needs store_ema)
+    closed_set_edge_head: bool = False # closed-set micro-batches (cfg.text.closed_set_nodes) train and validate through the trie-edge
+                                       # head: no [rows, V] vocabulary projection (TrainStep(closed_set_edge_head=True)); opt-in
 
 
 @dataclass
@@ -199,7 +201,8 @@ class Trainer:
         self.step_engine = TrainStep(model, lr=cfg.optimization.lr[0], betas=tuple(cfg.optimizer.adam_betas), eps=cfg.optimizer.adam_eps,
                                      weight_decay=cfg.optimizer.weight_decay, clip_norm=cfg.optimization.clip_norm,
                                      use_graph=cfg.common.use_graph, label_smoothing=crit.label_smoothing,
-                                     drop_worst_ratio=crit.drop_worst_ratio, loss_scale=self._loss_scale_cfg(world), ema=cfg.ema)
+                                     drop_worst_ratio=crit.drop_worst_ratio, loss_scale=self._loss_scale_cfg(world), ema=cfg.ema,
+                                     closed_set_edge_head=cfg.common.closed_set_edge_head)
         for task in tasks:
             task.init_data_iterator("train", rank, world)
         self._device, self._rank, self._world = device, rank, world

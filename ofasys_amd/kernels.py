@@ -1071,6 +1071,105 @@ def trie_ls_cross_entropy_bwd(logits2d, target, nodes, trie, lse, row_cnt, row_w
     return dlogits
 
 
+# ------------------------------------------------------------------ trie-edge head (csrc/trie_head.hip)
+HEAD_TRIE_KEYS = ("node_edge_off", "edge_token", "edge_node", "head_tokens", "tok_edge_off", "tok_edge")
+
+
+def _trie_head_proj(who, feats, weight, bias):
+    if feats.dim() != 2 or weight.dim() != 2 or feats.stride(1) != 1 or weight.stride(1) != 1:
+        raise OfaError(f"{who}: features [rows, D] and projection rows [V, D] must have a contiguous last dimension")
+    if weight.dtype != feats.dtype or (bias is not None and bias.dtype != feats.dtype):
+        raise OfaError(f"{who}: features ({feats.dtype}), projection ({weight.dtype}) and bias must share one dtype")
+    if weight.shape[1] != feats.shape[1] or (bias is not None and (bias.numel() != weight.shape[0] or not bias.is_contiguous())):
+        raise OfaError(f"{who}: projection [V, D] / bias [V] do not match the features' width")
+
+
+def _ld(x):
+    return x.stride(0) if x.shape[0] > 1 else max(x.stride(0), x.shape[1])
+
+
+def trie_head_cmax(trie):
+    """The slots per row of the trie-edge head's compact buffers: the plan's max_degree, which the trie dict must carry."""
+    if trie.get("max_degree") is None:
+        raise ValueError("trie_head: the trie's device arrays carry no \"max_degree\" (TraversePlan.head_arrays / to_device do)")
+    return int(trie["max_degree"])
+
+
+def trie_head_fwd(feats, weight, bias, target, nodes, trie, ignore_index, eps, cstart=-1, cend=-1, want_grad=True, want_hit=False):
+    """The trie-edge head's forward launch (ofa_trie_head_fwd): feats [rows, D], weight [V, D], bias [V] or None of one dtype; target
+    int64 [rows], nodes int32 [rows]; trie: the device arrays of TraversePlan.head_arrays.  -> dict(z, g fp32 [rows, Cmax] (g None
+    without want_grad), lse, row_loss, row_nll, row_cnt fp32 [rows], row_hit int32 [rows] or None).  Slots past a row's degree are
+    not written."""
+    _trie_head_proj("trie_head_fwd", feats, weight, bias)
+    rows, D = feats.shape
+    V = weight.shape[0]
+    targs = _trie_args(feats, target, nodes, trie)
+    Cmax = trie_head_cmax(trie)
+    dev = feats.device
+    z = torch.empty(rows, Cmax, dtype=torch.float32, device=dev)
+    g = torch.empty(rows, Cmax, dtype=torch.float32, device=dev) if want_grad else None
+    out = [torch.empty(rows, dtype=torch.float32, device=dev) for _ in range(4)]
+    hit = torch.empty(rows, dtype=torch.int32, device=dev) if want_hit else None
+    lib().call("ofa_trie_head_fwd", ptr(feats), _ld(feats), ptr(weight), _ld(weight), ptr(bias), D, V, ptr(target), *targs, Cmax, ptr(z),
+               *[ptr(o) for o in out], ptr(g), ptr(hit), rows, int(ignore_index), float(eps), int(cstart), int(cend), dtype_code(feats),
+               stream())
+    return dict(z=z, g=g, lse=out[0], row_loss=out[1], row_nll=out[2], row_cnt=out[3], row_hit=hit)
+
+
+def trie_head_bwd_dx(g, weight, target, nodes, trie, row_w, grad_scale, ignore_index, cstart=-1, cend=-1, out=None):
+    """dfeats [rows, D] of weight's dtype = grad_scale[0] * row_w[r] * sum_j g[r, j] W[tok_j] (ofa_trie_head_bwd_dx); every row is
+    written.  row_w fp32 [rows] and grad_scale (fp32 device scalar) are optional."""
+    rows, D = g.shape[0], weight.shape[1]
+    targs = _trie_args(g, target, nodes, trie)
+    Cmax = trie_head_cmax(trie)
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.shape == (rows, Cmax), (g.dtype, g.shape, Cmax)
+    if out is None:
+        out = torch.empty(rows, D, dtype=weight.dtype, device=weight.device)
+    lib().call("ofa_trie_head_bwd_dx", ptr(g), ptr(weight), _ld(weight), D, weight.shape[0], ptr(target), *targs, Cmax, ptr(row_w),
+               ptr(grad_scale), ptr(out), _ld(out), rows, int(ignore_index), int(cstart), int(cend), dtype_code(weight), stream())
+    return out
+
+
+def trie_head_buckets(nodes, trie):
+    """The step's row buckets, on the device without a host synchronisation: (bucket_rows int32 [rows]: the row indices ordered by node,
+    ascending within a node; bucket_off int32 [N + 1]).  Rows on a node outside [0, N) sort past every bucket."""
+    N = int(trie["N"])
+    nd = nodes.reshape(-1)
+    key = torch.where((nd >= 0) & (nd < N), nd, torch.full_like(nd, N))
+    skey, order = torch.sort(key, stable=True)
+    ids = trie.get("node_ids")
+    if ids is None:
+        ids = torch.arange(N + 1, dtype=torch.int32, device=nd.device)
+    off = torch.searchsorted(skey, ids, out_int32=True)
+    return order.to(torch.int32), off
+
+
+def trie_head_bwd_dw(g, feats, trie, buckets, row_w, grad_scale, dweight, dbias=None, cstart=-1, cend=-1):
+    """dweight[u] += grad_scale[0] * sum over (row, slot) pairs whose token is u of row_w[r] g[r, slot] feats[r] (ofa_trie_head_bwd_dw),
+    dbias[u] likewise: a PARTIAL writer of dweight -- it touches the rows of the tokens that have contributing rows and nothing
+    else -- in a fixed order, without float atomics.  buckets: trie_head_buckets(nodes, trie) of this step."""
+    rows, D = feats.shape
+    Cmax = trie_head_cmax(trie)
+    N, E, U = int(trie["N"]), int(trie["E"]), int(trie["U"])
+    for k in HEAD_TRIE_KEYS:
+        assert trie[k].dtype == torch.int32 and trie[k].is_contiguous(), k
+    assert trie["head_tokens"].numel() == U and trie["tok_edge_off"].numel() == U + 1 and trie["tok_edge"].numel() == E
+    assert trie["edge_node"].numel() == E and trie["node_edge_off"].numel() == N + 1
+    brows, boff = buckets
+    assert brows.dtype == boff.dtype == torch.int32 and brows.numel() == rows and boff.numel() == N + 1
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.shape == (rows, Cmax), (g.dtype, g.shape, Cmax)
+    assert dweight.dtype == feats.dtype and dweight.stride(1) == 1 and dweight.shape[1] == D and feats.stride(1) == 1
+    assert dbias is None or (dbias.dtype == feats.dtype and dbias.is_contiguous() and dbias.numel() == dweight.shape[0])
+    _accum(dweight, True, full=False)                # the rows of the batch's tokens only: a partial writer always adds
+    if dbias is not None:
+        _accum(dbias, True, full=False)
+    lib().call("ofa_trie_head_bwd_dw", ptr(g), ptr(feats), _ld(feats), D, dweight.shape[0], ptr(trie["node_edge_off"]),
+               ptr(trie["edge_node"]), N, E, Cmax, ptr(trie["head_tokens"]), ptr(trie["tok_edge_off"]), ptr(trie["tok_edge"]), U,
+               ptr(brows), ptr(boff), ptr(row_w), ptr(grad_scale), ptr(dweight), _ld(dweight), ptr(dbias), rows, int(cstart), int(cend),
+               dtype_code(feats), stream())
+    return dweight
+
+
 def criterion_eval(logits2d, target, V, ignore_index, eps, cstart=-1, cend=-1, cmask=None, nodes=None, trie=None):
     """Validation's criterion rows in one read of the logits (ofa_criterion_eval): returns row_loss, row_nll (fp32 [rows]) and row_hit
     (int32 [rows]: the target is the arg-max over the allowed set).  The allowed set: the whole vocabulary, the range, a byte mask

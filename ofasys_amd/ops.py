@@ -2109,6 +2109,117 @@ def trie_label_smoothed_cross_entropy(logits, target, nodes, trie, ignore_index,
                                                  seed)
 
 
+def _drop_worst(row_loss, row_nll, valid, drop_worst_ratio):
+    """The drop-worst ranking of (Trie)LabelSmoothedCrossEntropyFn on row_loss, on the device: -> (row_w, row_loss, row_nll, ntokens)."""
+    n = valid.sum()
+    k = (n.double() * (1 - drop_worst_ratio)).floor().long()                        # int(n * (1 - ratio)), on the device
+    key = torch.where(valid, row_loss, torch.full_like(row_loss, float("inf")))
+    order = torch.argsort(key, stable=True)
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(order.numel(), device=order.device)
+    keep = rank < k
+    zero = torch.zeros_like(row_loss)
+    return keep.float(), torch.where(keep, row_loss, zero), torch.where(keep, row_nll, zero), k   # (a dropped +inf row: 0, not NaN)
+
+
+def _head_inputs(who, feats, weight, bias, target, nodes):
+    D = feats.shape[-1]
+    f2d = feats.reshape(-1, D)
+    if f2d.stride(1) != 1 or f2d.stride(0) % (4 if f2d.dtype == torch.float32 else 8) != 0 or f2d.data_ptr() % 16 != 0:
+        f2d = f2d.contiguous()
+    if f2d.dtype != weight.dtype:
+        raise ValueError(f"{who}: features are {f2d.dtype}, the projection is {weight.dtype}")
+    t = target.reshape(-1).contiguous()
+    nd = nodes.reshape(-1).to(device=f2d.device, dtype=torch.int32).contiguous()
+    if nd.numel() != f2d.shape[0] or t.numel() != f2d.shape[0]:
+        raise ValueError(f"{who}: {nd.numel()} nodes and {t.numel()} targets for {f2d.shape[0]} feature rows")
+    return f2d, t, nd
+
+
+class TrieHeadCrossEntropyFn(torch.autograd.Function):
+    """TrieLabelSmoothedCrossEntropyFn without the vocabulary projection (csrc/trie_head.hip): the decoder's FEATURES [..., D] go in,
+    the logits of each row's node's children, the loss and the compact gradient g [rows, max_degree] come out of one launch, and the
+    backward runs the two gradient kernels on g -- dfeats (every row written) and the projection's rows of the batch's tokens.  The
+    weight gradient is a PARTIAL writer of `weight._ofa_grad` (kernels._accum(full=False)), so on a tied embedding it composes with the
+    dense head of another micro-batch and the embedding's own rows in either order; without a sink it is a zero [V, D] tensor with
+    the rows added.  Loss scaling and drop-worst enter in the backward: there is no seeded form."""
+
+    @staticmethod
+    def forward(ctx, feats, weight, bias, target, nodes, trie, ignore_index, eps, constraint_range, drop_worst_ratio):
+        f2d, t, nd = _head_inputs("trie_head_cross_entropy", feats, weight, bias, target, nodes)
+        cs, ce = constraint_range if constraint_range is not None else (-1, -1)
+        out = K.trie_head_fwd(f2d, weight, bias, t, nd, trie, ignore_index, eps, cs, ce, want_grad=True)
+        row_loss, row_nll = out["row_loss"], out["row_nll"]
+        valid = t.ne(ignore_index)
+        row_w = None
+        if drop_worst_ratio > 0:
+            row_w, row_loss, row_nll, ntok = _drop_worst(row_loss, row_nll, valid, drop_worst_ratio)
+        else:
+            ntok = valid.sum()
+        ctx.buckets = K.trie_head_buckets(nd, trie) if ctx.needs_input_grad[1] else None      # (this step's rows by node, for dW)
+        ctx.save_for_backward(f2d, weight, t, nd, out["g"], row_w)
+        ctx.bias_ref, ctx.trie = bias, trie
+        ctx.cfg = (ignore_index, cs, ce, feats.shape)
+        ctx.mark_non_differentiable(ntok)
+        return K.sum_f32(row_loss), K.sum_f32(row_nll).detach(), ntok
+
+    @staticmethod
+    def backward(ctx, dloss, dnll, dntok):
+        f2d, weight, t, nd, g, row_w = ctx.saved_tensors
+        ignore_index, cs, ce, shape = ctx.cfg
+        trie, bias = ctx.trie, ctx.bias_ref
+        gs = dloss.reshape(1).float().contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = K.trie_head_bwd_dx(g, weight, t, nd, trie, row_w, gs, ignore_index, cs, ce).view(shape)
+        if ctx.needs_input_grad[1]:
+            gw = _sink(weight)
+            gb = _sink(bias) if bias is not None and ctx.needs_input_grad[2] else None
+            want_b = bias is not None and ctx.needs_input_grad[2]
+            if gw is None:
+                dw = torch.zeros_like(weight, memory_format=torch.contiguous_format)
+            if want_b and gb is None:
+                db = torch.zeros_like(bias)
+            K.trie_head_bwd_dw(g, f2d, trie, ctx.buckets, row_w, gs, gw if gw is not None else dw,
+                               (gb if gb is not None else db) if want_b else None, cs, ce)
+            if gw is not None:
+                _sink_done(weight)
+            if gb is not None:
+                _sink_done(bias)
+        return dx, dw, db, None, None, None, None, None, None, None
+
+
+def trie_head_cross_entropy(feats, weight, bias, target, nodes, trie, ignore_index, eps, constraint_range=None, drop_worst_ratio=0.0):
+    """-> (loss_sum, nll_sum, ntokens): trie_label_smoothed_cross_entropy(linear(feats, weight, bias), ...) computed over the children
+    of each row's trie node alone -- no [rows, V] logits, no dense dX / dW products.  feats [..., D] (the decoder with
+    features_only=True), weight [V, D] / bias [V] or None: the output projection (a tied embedding included); nodes: int32, one trie
+    node per feature row (-1: no closed set at that position); trie: Task.constraint_trie_on(device) / TraversePlan.head_arrays."""
+    for k in K.HEAD_TRIE_KEYS + ("N", "E", "U", "max_degree"):
+        if trie.get(k) is None:
+            raise ValueError(f"trie_head_cross_entropy: the trie's device arrays carry no {k!r} (Task.constraint_trie_on / "
+                             f"TraversePlan.head_arrays hand out all of them)")
+    if not 0 <= drop_worst_ratio < 1:
+        raise ValueError(f"trie_head_cross_entropy: drop_worst_ratio must be in [0, 1), got {drop_worst_ratio}")
+    return TrieHeadCrossEntropyFn.apply(feats, weight, bias, target, nodes, trie, ignore_index, eps, constraint_range, drop_worst_ratio)
+
+
+def trie_head_eval(feats, weight, bias, target, nodes, trie, pad, eps, constraint_range=None, acc=None):
+    """criterion_eval(nodes=...) from features (validation with the trie-edge head): the forward launch of trie_head_cross_entropy
+    with its arg-max output, then eval_stats_add.  Returns (acc, row_loss, row_nll, row_hit); nothing is synchronised."""
+    for k in ("node_edge_off", "edge_token", "N", "E", "max_degree"):
+        if trie.get(k) is None:
+            raise ValueError(f"trie_head_eval: the trie's device arrays carry no {k!r}")
+    with torch.no_grad():
+        f2d, t, nd = _head_inputs("trie_head_eval", feats.detach(), weight, bias, target, nodes)
+        cs, ce = constraint_range if constraint_range is not None else (-1, -1)
+        out = K.trie_head_fwd(f2d, weight.detach(), None if bias is None else bias.detach(), t, nd, trie, pad, eps, cs, ce,
+                              want_grad=False, want_hit=True)
+        if acc is None:
+            acc = torch.zeros(4, dtype=torch.float64, device=f2d.device)
+        K.eval_stats_add(acc, out["row_loss"], out["row_nll"], out["row_hit"], t, pad)
+    return acc, out["row_loss"], out["row_nll"], out["row_hit"]
+
+
 class ScstLossFn(torch.autograd.Function):
     """Self-critical sequence training loss (engine/criterion/scst_loss.py:24-36, 214-233): sum over rows of
     reward[sentence] * NLL(log_softmax_fp32(logits over the allowed vocabulary), target), ignore_index rows contributing 0; returns

@@ -221,8 +221,8 @@ class Task:
             raise ValueError(f"task {self.name}: no answer trie -- set cfg.text.closed_set_nodes and prepare a closed set")
         cache, key = self._trie_dev, torch.device(device)
         if key not in cache or cache[key][0] is not plan:      # (a closed set prepared again: a new plan, new arrays)
-            cache[key] = (plan, {"node_edge_off": torch.from_numpy(plan.node_edge_off).to(key),
-                                 "edge_token": torch.from_numpy(plan.edge_token).to(key), "N": plan.N, "E": plan.E})
+            # (with the inverse CSR by token, edge_node, node_ids, U and max_degree: what the trie-edge head reads as well)
+            cache[key] = (plan, plan.head_arrays(key))
         return cache[key][1]
 
     # ------------------------------------------------------------------ iteration (task/base.py:396-449, in process)

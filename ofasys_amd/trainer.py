@@ -261,8 +261,13 @@ class TrainStep:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_norm=1.0, process_group=None,
                  bucket_bytes: int = 64 << 20, use_graph: bool = False, graph_warmup: int = 2,
                  label_smoothing: float = 0.0, constraint_range=None, drop_worst_ratio: float = 0.0, dp_graph: str = None,
-                 loss_scale=None, max_graphs: int = 16, shard_optimizer: bool = False, ema=None):
-        """ema: an ema.EMAConfig (or a dict of its fields) with store_ema set keeps an exponential moving average of the weights
+                 loss_scale=None, max_graphs: int = 16, shard_optimizer: bool = False, ema=None,
+                 closed_set_edge_head: bool = False):
+        """closed_set_edge_head (opt-in): a micro-batch that carries "constraint_nodes" runs the decoder for FEATURES and
+        ops.trie_head_cross_entropy (csrc/trie_head.hip) -- the logits of each row's trie node's children, the loss and both gradients
+        without the [rows, V] vocabulary projection -- and, in valid_step, ops.trie_head_eval.  Every other micro-batch takes the dense
+        head in the same step.  Off (the default): every launch is what it was.
+        ema: an ema.EMAConfig (or a dict of its fields) with store_ema set keeps an exponential moving average of the weights
         (engine/ema/ema.py), updated on the device as the last launches of every update; `self.ema` is the ema.EMA object.  Fixed at
         construction: a captured step holds exactly the launches `_update` made when it was recorded.
         shard_optimizer (data parallel, opt-in): gradients are reduce-SCATTERED, every rank clips and updates only the 1 / world of
@@ -287,6 +292,7 @@ class TrainStep:
         # criterion: plain cross entropy (engine/criterion/cross_entropy.py) or, with any of these set, the label-smoothed
         # one (label_smoothed_cross_entropy.py); a sample may carry its own "constraint_masks" [B, Tt, V]
         self.label_smoothing, self.constraint_range, self.drop_worst_ratio = label_smoothing, constraint_range, drop_worst_ratio
+        self.closed_set_edge_head = bool(closed_set_edge_head)
         self._stats = torch.zeros(3, dtype=torch.float64, device=dev)      # [sample_size, loss_sum, ntokens]
         self._gsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self._gnorm_t = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -410,15 +416,33 @@ class TrainStep:
     def _fused_norm(self):
         return self.world == 1 and not K.tail_old(K.TAIL_NORM_SCHEDULE)
 
-    def _criterion_inputs(self, model, s):
+    def _edge_head(self, s):
+        """Does this micro-batch take the trie-edge head (closed_set_edge_head and a well-formed node micro-batch; a malformed one goes
+        the dense way and meets its refusal there)?"""
+        return (self.closed_set_edge_head and s.get("constraint_nodes") is not None and s.get("constraint_masks") is None
+                and s.get("reward") is None and s.get("constraint_trie") is not None)
+
+    @staticmethod
+    def output_projection(model):
+        """(weight [V, D], bias or None) of the decoder's text output projection: the tied token embedding, or the adaptor's own Linear."""
+        ga = model.decoder.adaptor
+        text = ga.name2adaptor["text"]
+        if text.share_input_output_embed:
+            return ga.embed_tokens.weight, None
+        proj = text.output_projection
+        return proj.weight, getattr(proj, "bias", None)
+
+    def _criterion_inputs(self, model, s, features=False):
         """One micro-batch through `model` -> (logits, target, constraint masks, constraint nodes, pack plan) as the criterion takes
-        them: by padded position, or (pack plan) by packed decoder row.  The train step and the validation step share it."""
+        them: by padded position, or (pack plan) by packed decoder row.  The train step and the validation step share it.
+        features: the decoder's features [.., D] stand where the logits would (the trie-edge head projects them itself)."""
         plan = s.get("pack")
         target = s["target"]
+        fo = {"features_only": True} if features else {}
         if plan is None:
-            logits = model(s["slots"])[0]
+            logits = model(s["slots"], **fo)[0]
         else:                                    # ragged batch (packing.py): logits and targets by packed decoder row
-            logits = model(s["slots"], pack=plan)[0]
+            logits = model(s["slots"], pack=plan, **fo)[0]
             target = s.get("target_packed")
             if target is None:
                 idx = plan.dec_index
@@ -449,10 +473,16 @@ class TrainStep:
     def _micro_batches(self, samples):
         model = self.model
         for s in samples:
-            logits, target, cm, nodes, plan = self._criterion_inputs(model, s)
+            head = self._edge_head(s)
+            logits, target, cm, nodes, plan = self._criterion_inputs(model, s, features=head)
             counted = False
             size = None
-            if nodes is not None:
+            if head:
+                # (the features stand in `logits`; loss scaling reaches the gradient kernels through backward's seed)
+                weight, bias = self.output_projection(model)
+                loss, _, n = ops.trie_head_cross_entropy(logits, weight, bias, target, nodes, s["constraint_trie"], self.pad,
+                                                         self.label_smoothing, self.constraint_range, self.drop_worst_ratio)
+            elif nodes is not None:
                 if self.loss_scale_cfg is None and (self._seed is None or self._seed.device != logits.device):
                     self._seed = torch.ones((), dtype=torch.float32, device=logits.device)
                 loss, _, n = ops.trie_label_smoothed_cross_entropy(logits, target, nodes, s["constraint_trie"], self.pad,
@@ -732,6 +762,12 @@ class TrainStep:
         the gradient arena, the step statistics, the optimizer or EMA state or the device counters."""
         with self._valid_mode(model):
             for s in samples:
+                if self._edge_head(s):
+                    feats, target, _, nodes, _ = self._criterion_inputs(model, s, features=True)
+                    weight, bias = self.output_projection(model)
+                    ops.trie_head_eval(feats, weight, bias, target, nodes, s["constraint_trie"], self.pad, self.label_smoothing,
+                                       self.constraint_range, acc=self._valid_acc)
+                    continue
                 logits, target, cm, nodes, _ = self._criterion_inputs(model, s)
                 ops.criterion_eval(logits, target, self.pad, self.label_smoothing, self.constraint_range, cm, nodes,
                                    s["constraint_trie"] if nodes is not None else None, acc=self._valid_acc)

@@ -85,8 +85,22 @@ class TraversePlan:
             lo, hi = int(self.node_edge_off[n]), int(self.node_edge_off[n + 1])
             items.extend((n, e, min(e + self.ITEM_EDGES, hi)) for e in range(lo, hi, self.ITEM_EDGES))
         self.items = np.array(items, np.int32).reshape(-1, 3)
-        self._child_of = None                                # walk()'s (node, token) -> child map, built on first use
+        self.head_tokens, self.tok_edge_off, self.tok_edge = self.invert_edges(self.edge_token)
+        self.U = len(self.head_tokens)
+        self._child_of = None                               # walk()'s (node, token) -> child map, built on first use
         assert E == len(self.edge_token) == len(self.edge_node) and int(self.path_off[-1]) == self.P
+
+    @staticmethod
+    def invert_edges(edge_token):
+        """The inverse CSR by token of an edge list: (head_tokens [U] the distinct tokens, ascending; tok_edge_off [U + 1]; tok_edge [E]
+        the edge indices, ascending within a token), int32.  One token can hang under many nodes; the trie-edge head's weight
+        gradient (csrc/trie_head.hip) gives each distinct token to one wave, which walks that token's edges in this order."""
+        edge_token = np.asarray(edge_token, np.int32)
+        order = np.argsort(edge_token, kind="stable").astype(np.int32)              # by token, then by edge index
+        tokens, counts = np.unique(edge_token, return_counts=True)
+        off = np.zeros(len(tokens) + 1, np.int32)
+        off[1:] = np.cumsum(counts)
+        return tokens.astype(np.int32), off, order
 
     def allowed(self, c: int, t: int) -> List[int]:
         """The tokens position t of answer c may take: Trie.get_next_layer(prev_output_tokens[c, :t + 1])."""
@@ -129,8 +143,18 @@ class TraversePlan:
         """The arrays the kernels read (kernels.closed_set_*), on `device`, plus the padded decoder inputs."""
         d = {k: torch.from_numpy(getattr(self, k)).to(device) for k in
              ("node_edge_off", "edge_token", "edge_node", "rep_ans", "rep_pos", "path_off", "path_edge", "items",
-              "prev_output_tokens", "edge_child")}
-        d.update(C=self.C, N=self.N, E=self.E, P=self.P, Tmax=self.Tmax, max_degree=self.max_degree)
+              "prev_output_tokens", "edge_child", "head_tokens", "tok_edge_off", "tok_edge")}
+        d.update(C=self.C, N=self.N, E=self.E, P=self.P, Tmax=self.Tmax, max_degree=self.max_degree, U=self.U)
+        return d
+
+    def head_arrays(self, device) -> Dict[str, object]:
+        """What the node criterion and the trie-edge head read, on `device`: the CSR by node (node_edge_off, edge_token, edge_node), the
+        inverse CSR by token (head_tokens, tok_edge_off, tok_edge), node_ids = arange(N + 1) (the per-step row buckets search it) and
+        the ints N, E, U, max_degree."""
+        d = {k: torch.from_numpy(getattr(self, k)).to(device) for k in
+             ("node_edge_off", "edge_token", "edge_node", "head_tokens", "tok_edge_off", "tok_edge")}
+        d["node_ids"] = torch.arange(self.N + 1, dtype=torch.int32, device=device)
+        d.update(N=self.N, E=self.E, U=self.U, max_degree=self.max_degree)
         return d
 
 
