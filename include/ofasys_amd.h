@@ -910,6 +910,38 @@ int ofa_diverse_group_select(const void* ws, const ofa_gen_state* st, int bsz, i
 int ofa_diverse_sibling_select(const void* ws, const ofa_gen_state* st, int bsz, int K, int V, int step, int max_len, int eos, int unk,
                                float unk_penalty, int normalize, float len_penalty, float rate, void* stream);
 
+/* ---- CTC loss on the encoder output (csrc/ctc.hip; engine/criterion/speech_to_text_loss.py:217-225, 326-362): F.ctc_loss(log_softmax_fp32
+ * (logits), blank = 0, reduction = "sum", zero_infinity), forward and gradient, in four launches that read lengths and targets from
+ * device memory (nothing synchronises; grids come from B, Tmax and Lmax) and use no float atomics: equal inputs give equal bits.
+ * logits [rows, C] of `dtype`, row stride ld.  Sentence b is the rows seg[b * seg_ld] + t * row_stride, t < seg[b * seg_ld + 1] <= Tmax
+ * (seg int32; padded T x B x C: offset b, stride B; packed: a segment table's q_off / q_len, stride 1); a description that leaves
+ * [0, rows) or exceeds Tmax reads as an empty sentence.  Labels: target[b, p] - ds (int64 [B, Lmax]) at the positions that are neither
+ * pad nor eos, compacted in order by the kernel; a label outside [1, C) makes the sentence infeasible.
+ * Sums along the time axis (row_lse, alpha, beta, nll_raw, nll64) are fp64; exp / log run in fp32 on differences of size O(1).
+ * A segment out of range trains on as an empty sentence; a row of all -inf logits gives NaN downstream.
+ * ofa_ctc_rows: row_lse[r] = log sum_c exp logits[r, c] (fp64) and, if asked for, row_argmax[r] (int32, the lowest class among equals).
+ * ofa_ctc_alpha_beta: the two recursions in fp32 log space on logits - row_lse; alpha, beta: fp64 [B, Tmax, 2 Lmax + 1] slabs, ws_meta
+ * int32 [B, 3, Lmax] and ws_L int32 [B] for ofa_ctc_grad; nll_raw[b] = -log p(labels | rows) (+inf: infeasible), nll64[b] the same with
+ * +inf replaced by 0 under zero_infinity and nll[b] its fp32 rounding.  2 Lmax + 1 <= 2304 and 2 <= C <= 8192 (ofa_ctc_max_target / ofa_ctc_max_classes), else
+ * OFA_ERR_UNSUPPORTED.
+ * ofa_ctc_grad: dlogits [rows, C] of `dtype` (row stride ld_d) = seed[0] (1 if NULL) * d nll_sum / d logits: every row outside a
+ * sentence's length exactly 0, the rows of an infeasible sentence 0 under zero_infinity and NaN without it (torch's values).
+ * ofa_ctc_greedy_decode: out[b, :out_len[b]] (int32 [B, Tmax], -1 behind) = the row arg-max of sentence b with consecutive duplicates
+ * collapsed, then blanks dropped. */
+int64_t ofa_ctc_max_classes(void);
+int64_t ofa_ctc_max_target(void);
+int ofa_ctc_rows(const void* logits, int64_t ld, int64_t rows, int64_t C, double* row_lse, int32_t* row_argmax, int dtype, void* stream);
+int ofa_ctc_alpha_beta(const void* logits, int64_t ld, int64_t rows, int64_t C, const double* row_lse, const int32_t* seg,
+                       int64_t seg_ld, int64_t row_stride, int64_t B, int64_t Tmax, const int64_t* target, int64_t Lmax, int64_t ds,
+                       int64_t pad, int64_t eos, double* alpha, double* beta, int32_t* ws_meta, int32_t* ws_L, double* nll_raw, float* nll,
+                       double* nll64, int zero_infinity, int dtype, void* stream);
+int ofa_ctc_grad(const void* logits, int64_t ld, int64_t rows, int64_t C, const double* row_lse, const int32_t* seg, int64_t seg_ld,
+                 int64_t row_stride, int64_t B, int64_t Tmax, int64_t Lmax, const double* alpha, const double* beta,
+                 const int32_t* ws_meta, const int32_t* ws_L, const double* nll_raw, const float* seed, void* dlogits, int64_t ld_d,
+                 int zero_infinity, int dtype, void* stream);
+int ofa_ctc_greedy_decode(const int32_t* row_argmax, int64_t rows, const int32_t* seg, int64_t seg_ld, int64_t row_stride, int64_t B,
+                          int64_t Tmax, int32_t* out, int32_t* out_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

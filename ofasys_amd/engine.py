@@ -253,6 +253,17 @@ class Trainer:
         if s.get("constraint_nodes") is not None:         # cfg.text.closed_set_nodes: one trie node per target position
             mb["constraint_nodes"] = s["constraint_nodes"]
             mb["constraint_trie"] = task.constraint_trie_on(self._device)
+        c = task.cfg.criterion
+        if c.name == "speech_to_text_loss":               # (only such tasks: every other micro-batch is what it was)
+            d = task.global_dict
+            if "<phone>_dict_begin" not in d or "<phone>_dict_end" not in d:
+                raise ValueError(f"task {task.name}: criterion speech_to_text_loss needs the '<phone>_dict_begin' .. '<phone>_dict_end' rows "
+                                 "of the dictionary (cfg.text.phone_dict registers them)")
+            # a sample's own "encoder_target" is passed through unchanged; collate's is the target (no text-to-phone)
+            mb["encoder_target"] = s["encoder_target"] if s.get("encoder_target") is not None else s["target"]
+            mb["ctc_range"] = f'{d.index("<phone>_dict_begin")},{d.index("<phone>_dict_end")}'
+            mb["ce_weight"], mb["ctc_weight"] = float(c.ce_weight), float(c.ctc_weight)
+            mb["zero_infinity"], mb["sentence_avg"] = bool(c.zero_infinity), bool(c.sentence_avg)
         return mb
 
     # ------------------------------------------------------------------ validation
@@ -273,7 +284,10 @@ class Trainer:
     def validate(self, tasks=None, split="valid", use_ema=False, max_steps=None):
         """One pass over `split` of every task that has it (default: the tasks of setup() / fit()) -> {task name: result dict}:
         loss, nll_loss (base 2 per token), ppl, ntokens, sample_size and -- for tasks with cfg.criterion.report_accuracy --
-        n_correct, total, accuracy (TrainStep.valid_result).  use_ema: with the averaged weights.  max_steps: at most that many
+        n_correct, total, accuracy (TrainStep.valid_result).  A task with the speech_to_text_loss criterion and ctc_weight > 0 also gets
+        ctc_loss (the summed CTC loss of the pass, natural log), c_errors and c_total: the unit-level edit distance of the greedy CTC
+        decode against the labels and the label count (speech_to_text_loss.py:294-300; a device decode, a plain Python Levenshtein
+        on the host once per pass; this rank's figures).  Out of scope: word-level WER, post_process and the KenLM decoder.  use_ema: with the averaged weights.  max_steps: at most that many
         batches per task.  Appends {"update", "ema", **results} to `valid_history`; one synchronisation per task."""
         if self.step_engine is None:
             raise RuntimeError("Trainer.validate needs setup() or fit() first: the step engine owns the model")

@@ -1852,3 +1852,85 @@ def trie_beam_advance(plan, node, st, K, step):
     state, bsz = _gen_state(st)
     lib().call("ofa_trie_beam_advance", ptr(node), ptr(plan["node_edge_off"]), ptr(plan["edge_token"]), ptr(plan["edge_child"]),
                plan["N"], plan["E"], state, bsz, int(K), int(step), stream())
+
+
+# ------------------------------------------------------------------ CTC loss on the encoder output (csrc/ctc.hip)
+def ctc_limits():
+    """(most classes, longest padded target row) the CTC kernels take."""
+    c = lib().cdll
+    return int(c.ofa_ctc_max_classes()), int(c.ofa_ctc_max_target())
+
+
+def _ctc_rows2d(who, logits2d):
+    if logits2d.dim() != 2 or logits2d.stride(1) != 1:
+        raise OfaError(f"{who}: logits must be [rows, C] rows with a contiguous last dimension")
+    C = logits2d.shape[1]
+    if not 2 <= C <= ctc_limits()[0]:
+        raise ValueError(f"{who}: C={C} classes; the CTC kernels take 2 .. {ctc_limits()[0]} (one float per class in LDS)")
+    return logits2d.shape[0], C
+
+
+def _ctc_seg(who, seg, row_stride, tmax):
+    if seg.dtype != torch.int32 or seg.dim() != 2 or seg.shape[1] < 2 or seg.stride(1) != 1:
+        raise OfaError(f"{who}: seg must be int32 [B, >= 2] = (row offset, length, ...) per sentence")
+    if row_stride < 1 or not 0 <= tmax < 65536:
+        raise ValueError(f"{who}: row_stride={row_stride}, tmax={tmax}")
+    return seg.shape[0], (seg.stride(0) if seg.shape[0] > 1 else max(seg.stride(0), seg.shape[1]))
+
+
+def ctc_rows(logits2d, want_argmax=False):
+    """The row pass (ofa_ctc_rows): -> (row_lse fp64 [rows], row_argmax int32 [rows] or None; ties take the lowest class)."""
+    rows, C = _ctc_rows2d("ctc_rows", logits2d)
+    lse = torch.empty(rows, dtype=torch.float64, device=logits2d.device)
+    am = torch.empty(rows, dtype=torch.int32, device=logits2d.device) if want_argmax else None
+    lib().call("ofa_ctc_rows", ptr(logits2d), _ld(logits2d), rows, C, ptr(lse), ptr(am), dtype_code(logits2d), stream())
+    return lse, am
+
+
+def ctc_alpha_beta(logits2d, row_lse, seg, row_stride, tmax, target, ds, pad, eos, zero_infinity):
+    """The two recursions (ofa_ctc_alpha_beta).  seg int32 [B, >= 2]: (row offset, length) of every sentence, rows off + t * row_stride,
+    length <= tmax; target int64 [B, Lmax].  -> dict(alpha, beta fp64 [B, tmax, 2 Lmax + 1], meta, L: the labels as the gradient
+    kernel reads them, nll_raw, nll64 fp64 [B], nll fp32 [B]: nll64 / nll have +inf replaced by 0 under zero_infinity)."""
+    rows, C = _ctc_rows2d("ctc_alpha_beta", logits2d)
+    B, seg_ld = _ctc_seg("ctc_alpha_beta", seg, row_stride, tmax)
+    if target.dtype != torch.int64 or target.dim() != 2 or target.shape[0] != B or not target.is_contiguous() or target.shape[1] < 1:
+        raise OfaError(f"ctc_alpha_beta: encoder_target must be a contiguous int64 [B={B}, Lmax >= 1], got {tuple(target.shape)}")
+    Lmax = target.shape[1]
+    if Lmax > ctc_limits()[1]:
+        raise ValueError(f"ctc_alpha_beta: a target row of {Lmax} positions has {2 * Lmax + 1} states; the looped recursion takes "
+                         f"{2 * ctc_limits()[1] + 1} (targets of up to {ctc_limits()[1]} positions)")
+    dev = logits2d.device
+    S = 2 * Lmax + 1
+    st = dict(alpha=torch.empty(B, tmax, S, dtype=torch.float64, device=dev), beta=torch.empty(B, tmax, S, dtype=torch.float64, device=dev),
+              meta=torch.empty(B, 3, Lmax, dtype=torch.int32, device=dev), L=torch.empty(B, dtype=torch.int32, device=dev),
+              nll_raw=torch.empty(B, dtype=torch.float64, device=dev), nll=torch.empty(B, dtype=torch.float32, device=dev),
+              nll64=torch.empty(B, dtype=torch.float64, device=dev), Lmax=Lmax)
+    lib().call("ofa_ctc_alpha_beta", ptr(logits2d), _ld(logits2d), rows, C, ptr(row_lse), ptr(seg), seg_ld, int(row_stride), B, int(tmax),
+               ptr(target), Lmax, int(ds), int(pad), int(eos), ptr(st["alpha"]), ptr(st["beta"]), ptr(st["meta"]), ptr(st["L"]),
+               ptr(st["nll_raw"]), ptr(st["nll"]), ptr(st["nll64"]), int(bool(zero_infinity)), dtype_code(logits2d), stream())
+    return st
+
+
+def ctc_grad(logits2d, row_lse, seg, row_stride, tmax, st, seed, zero_infinity, out=None):
+    """dlogits [rows, C] of the logits' dtype = seed[0] * d sum(nll) / d logits (ofa_ctc_grad); st: ctc_alpha_beta's result; seed: fp32
+    device scalar or None (1).  Every row is written: exact zeros outside the sentences' lengths."""
+    rows, C = _ctc_rows2d("ctc_grad", logits2d)
+    B, seg_ld = _ctc_seg("ctc_grad", seg, row_stride, tmax)
+    if out is None:
+        out = torch.empty(rows, C, dtype=logits2d.dtype, device=logits2d.device)
+    lib().call("ofa_ctc_grad", ptr(logits2d), _ld(logits2d), rows, C, ptr(row_lse), ptr(seg), seg_ld, int(row_stride), B, int(tmax),
+               st["Lmax"], ptr(st["alpha"]), ptr(st["beta"]), ptr(st["meta"]), ptr(st["L"]), ptr(st["nll_raw"]), ptr(seed), ptr(out),
+               out.stride(0) if rows > 1 else C, int(bool(zero_infinity)), dtype_code(logits2d), stream())
+    return out
+
+
+def ctc_greedy_decode(row_argmax, seg, row_stride, tmax):
+    """-> (tokens int32 [B, tmax] with -1 behind each sentence's tokens, lengths int32 [B]) from the row pass's arg-max (ofa_ctc_greedy_decode)."""
+    B, seg_ld = _ctc_seg("ctc_greedy_decode", seg, row_stride, tmax)
+    if row_argmax.dtype != torch.int32 or not row_argmax.is_contiguous():
+        raise OfaError("ctc_greedy_decode: row_argmax must be a contiguous int32 [rows]")
+    out = torch.empty(B, tmax, dtype=torch.int32, device=row_argmax.device)
+    n = torch.empty(B, dtype=torch.int32, device=row_argmax.device)
+    lib().call("ofa_ctc_greedy_decode", ptr(row_argmax), row_argmax.numel(), ptr(seg), seg_ld, int(row_stride), B, int(tmax), ptr(out), ptr(n),
+               stream())
+    return out, n

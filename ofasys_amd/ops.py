@@ -2220,6 +2220,160 @@ def trie_head_eval(feats, weight, bias, target, nodes, trie, pad, eps, constrain
     return acc, out["row_loss"], out["row_nll"], out["row_hit"]
 
 
+class CtcLayout:
+    """Where the sentences of a CTC batch lie in the logits' rows: sentence b is the rows seg[b, 0] + t * row_stride, t < seg[b, 1]
+    <= tmax (seg: int32 device tensor [B, >= 2]).  Lengths are device data; tmax is a launch bound taken from shapes."""
+
+    def __init__(self, seg, row_stride, tmax, batch_major=False):
+        self.seg, self.row_stride, self.tmax, self.batch_major = seg, int(row_stride), int(tmax), bool(batch_major)
+
+    @classmethod
+    def padded(cls, lengths, T, batch_major=False):
+        """The T x B x C encoder output: sentence b is rows b, b + B, ...; lengths: device integer tensor [B] (non-pad positions).
+        batch_major: the logits are a [T, B, C] VIEW of [B, T, C] storage (what the layer stack hands out); the rows are then read
+        in storage order -- sentence b is rows b T, b T + 1, ... -- and no transposed copy is made."""
+        B = lengths.numel()
+        first = torch.arange(B, dtype=torch.int32, device=lengths.device)
+        seg = torch.stack([first * T if batch_major else first, lengths.reshape(-1).to(torch.int32)], 1)
+        return cls(seg.contiguous(), 1 if batch_major else B, T, batch_major)
+
+    @classmethod
+    def packed(cls, segments):
+        """Packed rows: a packing.Segments table on the logits' device (PackPlan.enc_self: q_off, q_len), a sentence's rows contiguous."""
+        return cls(segments.table, 1, segments.max_q)
+
+
+def _ctc_inputs(who, logits, layout, encoder_target):
+    """-> (logits as [rows, C] in the row order the layout describes, restore: a [rows, C] gradient -> the logits' shape and layout,
+    encoder_target as a contiguous int64 tensor on the logits' device)."""
+    C = logits.shape[-1]
+    t = encoder_target
+    if t.dim() != 2 or t.shape[0] != layout.seg.shape[0]:
+        raise ValueError(f"{who}: encoder_target must be [B={layout.seg.shape[0]}, Lmax], got {tuple(t.shape)}")
+    t = t.to(device=logits.device, dtype=torch.int64).contiguous()
+    shape = logits.shape
+    if layout.batch_major:
+        if logits.dim() != 3 or not logits.transpose(0, 1).is_contiguous():
+            raise ValueError(f"{who}: a batch-major layout needs logits that are a [T, B, C] view of contiguous [B, T, C] storage")
+        return logits.transpose(0, 1).reshape(-1, C), lambda d: d.view(shape[1], shape[0], C).transpose(0, 1), t
+    l2d = logits.reshape(-1, C) if logits.is_contiguous() else logits.contiguous().view(-1, C)
+    return l2d, lambda d: d.view(shape), t
+
+
+class CtcLossFn(torch.autograd.Function):
+    """F.ctc_loss(log_softmax_fp32(logits), labels, blank=0, reduction="sum", zero_infinity) over the sentences of a CtcLayout
+    (csrc/ctc.hip; engine/criterion/speech_to_text_loss.py:326-362) -> (loss_sum, per-sentence nll).  The labels are encoder_target -
+    ds at the positions that are neither pad nor eos, derived by the kernel.  With a usable seed (see _SeededGrad) the forward's
+    launch sequence ends with the gradient launch and the backward hands its result out; otherwise the backward runs that launch
+    on the saved alpha / beta slabs at the scale it is given.  A gradient on the per-sentence nll is not supported."""
+
+    @staticmethod
+    def forward(ctx, logits, layout, encoder_target, ds, pad, eos, zero_infinity, seed=None, stat=None):
+        l2d, ctx.restore, t = _ctc_inputs("ctc_loss", logits, layout, encoder_target)
+        lse, _ = K.ctc_rows(l2d)
+        st = K.ctc_alpha_beta(l2d, lse, layout.seg, layout.row_stride, layout.tmax, t, ds, pad, eos, zero_infinity)
+        ctx.layout, ctx.zero_infinity = layout, bool(zero_infinity)
+        ctx.seeded = _SeededGrad()
+        if ctx.needs_input_grad[0]:
+            if _SeededGrad.usable(seed, l2d.device):
+                d = K.ctc_grad(l2d, lse, layout.seg, layout.row_stride, layout.tmax, st, seed, zero_infinity)
+                ctx.seeded = _SeededGrad(seed, d)
+            ctx.save_for_backward(l2d, lse, st["alpha"], st["beta"], st["meta"], st["L"], st["nll_raw"])
+            ctx.Lmax = st["Lmax"]
+        nll = st["nll"]
+        ctx.mark_non_differentiable(nll)
+        # (the sentences' fp64 values are summed and the sum rounded once: an fp32 sum would round at the size of the loss per addend)
+        total = st["nll64"].sum()
+        if stat is not None:
+            stat += total
+        return total.float(), nll
+
+    @staticmethod
+    def backward(ctx, dloss, dnll):
+        l2d, lse, alpha, beta, meta, L, nll_raw = ctx.saved_tensors
+        d = ctx.seeded.take(dloss)
+        if d is None:
+            lay = ctx.layout
+            st = dict(alpha=alpha, beta=beta, meta=meta, L=L, nll_raw=nll_raw, Lmax=ctx.Lmax)
+            d = K.ctc_grad(l2d, lse, lay.seg, lay.row_stride, lay.tmax, st, dloss.reshape(1).float().contiguous(), ctx.zero_infinity,
+                           out=ctx.seeded.spare())
+        return ctx.restore(d), None, None, None, None, None, None, None, None
+
+
+def ctc_loss(logits, layout, encoder_target, ds, pad, eos, zero_infinity, seed=None, stat=None):
+    """-> (loss_sum fp32 scalar, per_sentence_nll fp32 [B]).  stat: an fp64 device accumulator [1] the summed loss is added to BEFORE its
+    rounding to fp32 (the step's and the validation pass's ctc_loss statistics), on the device, nothing synchronised.  logits [..., C] in fp32 / bf16 / fp16 (the padded T x B x C encoder
+    projection, or packed rows), layout: a CtcLayout, encoder_target [B, Lmax] integer.  Blank is class 0 (the `ds` row itself).
+    Infeasible sentences (target longer than the input, repeats without room for the blank, a label outside [1, C)): nll 0 and a zero
+    gradient with zero_infinity, +inf and NaN gradient rows without.  Refuses C and Lmax above kernels.ctc_limits() with a ValueError."""
+    return CtcLossFn.apply(logits, layout, encoder_target, int(ds), int(pad), int(eos), bool(zero_infinity), seed, stat)
+
+
+def ctc_greedy_decode(logits, layout):
+    """Greedy CTC decode on the device: per sentence the row arg-max (ties: the lowest class), consecutive duplicates collapsed, blanks
+    (class 0) dropped.  -> (tokens int32 [B, tmax], -1 behind each sentence's tokens; lengths int32 [B]); nothing is synchronised."""
+    with torch.no_grad():
+        if layout.batch_major:
+            l2d = logits.detach().transpose(0, 1).reshape(-1, logits.shape[-1])
+        else:
+            l2d = logits.detach().reshape(-1, logits.shape[-1])
+        _, am = K.ctc_rows(l2d, want_argmax=True)
+        return K.ctc_greedy_decode(am, layout.seg, layout.row_stride, layout.tmax)
+
+
+def edit_distance(a, b):
+    """Levenshtein distance of two sequences, on the host in plain Python: the unit-level error count of a greedy CTC decode against
+    its labels (speech_to_text_loss.py:294-300 uses the `editdistance` package for it).  Word-level WER, post_process and the KenLM
+    decoder are out of scope."""
+    a, b = list(a), list(b)
+    prev = list(range(len(b) + 1))
+    for i, x in enumerate(a, 1):
+        cur = [i]
+        for j, y in enumerate(b, 1):
+            cur.append(min(prev[j] + 1, cur[j - 1] + 1, prev[j - 1] + (x != y)))
+        prev = cur
+    return prev[-1]
+
+
+class EncoderCtcLogitsFn(torch.autograd.Function):
+    """enc . weight[ds:de]^T (speech_to_text_loss.py:217-225).  The weight gradient belongs to rows ds:de of the (tied) embedding: with a
+    gradient sink it is accumulated into that row range of the arena view through kernels._accum, like every other writer of the
+    parameter in the step; without one it is a zero [V, D] tensor with the rows stored."""
+
+    @staticmethod
+    def forward(ctx, x2d, weight, ds, de):
+        ctx.save_for_backward(x2d, weight)
+        ctx.range = (ds, de)
+        return K.gemm(x2d, weight[ds:de], False, True)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2d, weight = ctx.saved_tensors
+        ds, de = ctx.range
+        dy = dy if dy.stride(-1) == 1 else dy.contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = K.gemm(dy, weight[ds:de], False, False)
+        if ctx.needs_input_grad[1]:
+            gw = _sink(weight)
+            if gw is not None:
+                K.gemm(dy, x2d, True, False, out=gw[ds:de], accumulate=True)
+                _sink_done(weight)
+            else:
+                dw = torch.zeros_like(weight, memory_format=torch.contiguous_format)
+                K.gemm(dy, x2d, True, False, out=dw[ds:de])
+        return dx, dw, None, None
+
+
+def encoder_ctc_logits(enc, weight, ds, de):
+    """The CTC logits [..., de - ds] of the encoder output enc [..., D]: its projection onto rows ds:de of the token embedding."""
+    ds, de = int(ds), int(de)
+    if not 0 <= ds < de <= weight.shape[0]:
+        raise ValueError(f"encoder_ctc_logits: rows [{ds}, {de}) of a [{weight.shape[0]}, {weight.shape[1]}] embedding")
+    x2d, restore = rows_view(enc)
+    return restore(EncoderCtcLogitsFn.apply(x2d, weight, ds, de))
+
+
 class ScstLossFn(torch.autograd.Function):
     """Self-critical sequence training loss (engine/criterion/scst_loss.py:24-36, 214-233): sum over rows of
     reward[sentence] * NLL(log_softmax_fp32(logits over the allowed vocabulary), target), ignore_index rows contributing 0; returns

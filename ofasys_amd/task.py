@@ -52,7 +52,13 @@ class CriterionConfig:                                # engine/criterion/label_s
     drop_worst_ratio: float = 0.0
     report_accuracy: bool = False                     # validation also reports n_correct / total / accuracy (:49-52, :180-198)
     # "scst_reward_criterion" (engine/criterion/scst_loss.py:39-56; used by a task with cfg.scst): the fields below are its own
+    # "speech_to_text_loss" (engine/criterion/speech_to_text_loss.py:24-95): ce_weight * the label-smoothed loss on the decoder +
+    # ctc_weight * CTC on the encoder output projected onto the '<phone>_dict_begin' .. '<phone>_dict_end' rows of the token embedding
+    # (cfg.text.phone_dict registers them); ce_weight, ctc_weight, zero_infinity (and sentence_avg) are its own, the reference's defaults
     name: str = "label_smoothed_cross_entropy"
+    ce_weight: float = 1.0
+    ctc_weight: float = 0.0
+    zero_infinity: bool = False
     scst_cider_cached_tokens: Any = "corpus"          # a pickle path (ref_len, document_frequency), such a dict, or "corpus"
     sentence_avg: bool = False
     ignore_prefix_size: int = 0

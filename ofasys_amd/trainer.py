@@ -294,6 +294,7 @@ class TrainStep:
         self.label_smoothing, self.constraint_range, self.drop_worst_ratio = label_smoothing, constraint_range, drop_worst_ratio
         self.closed_set_edge_head = bool(closed_set_edge_head)
         self._stats = torch.zeros(3, dtype=torch.float64, device=dev)      # [sample_size, loss_sum, ntokens]
+        self._ctc_stat = torch.zeros(1, dtype=torch.float64, device=dev)   # sum of the step's CTC losses (speech-to-text micro-batches)
         self._gsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self._gnorm_t = torch.zeros(1, dtype=torch.float32, device=dev)
         # device-resident schedule: _step_t = number of updates done; _lr_t = learning rate; _sched = [grad multiplier,
@@ -357,6 +358,8 @@ class TrainStep:
         # validation (valid_begin / valid_step / valid_result): its accumulator [ntokens, loss_sum, nll_sum, n_correct] and its own
         # table of forward-only graphs; nothing of the training state above is written by it
         self._valid_acc = torch.zeros(4, dtype=torch.float64, device=dev)
+        self._valid_ctc = torch.zeros(1, dtype=torch.float64, device=dev)      # summed CTC loss of the pass (speech-to-text micro-batches)
+        self._valid_decodes = []                    # per such micro-batch (greedy tokens, their lengths, encoder_target, ds), on the device
         self._valid_graphs = {}                     # (batch structure, use_ema) -> dict(graphs, static samples, seen count)
         self._warned_valid_cap = False
         ema_cfg = as_config(ema)
@@ -388,12 +391,16 @@ class TrainStep:
         if first_touch:
             self.fp.repoint()
             # (structure None: eager steps share one list.  The step's statistics and the sum of squares are cleared by the same launch.)
-            ops.grad_begin(self.fp.grad, self._prezero.get(structure, ()), also=(self._stats, self._gsq))
+            # (a step without a speech-to-text micro-batch launches exactly what it launched before: its CTC statistic is not touched)
+            stt = (self._ctc_stat,) if any(self._speech_to_text(s) for s in samples) else ()
+            ops.grad_begin(self.fp.grad, self._prezero.get(structure, ()), also=(self._stats, self._gsq) + stt)
             self._gsq_cleared = True
         else:
             ops.grad_abort()
             self.fp.zero_grad()
             self._stats.zero_()
+            if any(self._speech_to_text(s) for s in samples):
+                self._ctc_stat.zero_()
         self.reducer.overlap = overlap_reduce
         # gradients are only read after backward unless buckets are all-reduced from inside it: fold lazily, in batches
         ops.defer_reductions(self.world == 1 or not overlap_reduce)
@@ -423,6 +430,55 @@ class TrainStep:
                 and s.get("reward") is None and s.get("constraint_trie") is not None)
 
     @staticmethod
+    def _speech_to_text(s):
+        """Does this micro-batch take the speech-to-text criterion (engine/criterion/speech_to_text_loss.py): "encoder_target" and
+        "ctc_range" in the dict?"""
+        return s.get("encoder_target") is not None and s.get("ctc_range") is not None
+
+    def _speech_to_text_loss(self, model, s, logits, target, cm, plan, encoder_out):
+        """ce_weight * (today's label-smoothed loss on the decoder) + ctc_weight * CTC(encoder output . embed_tokens[ds:de]^T) ->
+        (loss, ntokens).  A weight of 0 launches nothing of its side's criterion.  The CE side is ops.label_smoothed_cross_entropy
+        whatever the engine's label_smoothing (0 included: not the fused cross_entropy_sum path a plain micro-batch of such an
+        engine takes), so "ctc_weight = 0 is today's step bit for bit" means the label-smoothed op's step.  The CTC loss is added
+        to `self._ctc_stat`, this rank's sum: data parallel, it is not all-reduced with the step statistics."""
+        ds, de = (int(v) for v in s["ctc_range"].split(","))
+        ce_w, ctc_w = float(s.get("ce_weight", 1.0)), float(s.get("ctc_weight", 0.0))
+        if ce_w < 0 or ctc_w < 0 or ce_w + ctc_w == 0:
+            raise ValueError(f"speech_to_text_loss: ce_weight={ce_w}, ctc_weight={ctc_w}: one of them must be positive, none negative")
+        if s.get("reward") is not None or s.get("constraint_nodes") is not None:
+            raise NotImplementedError("a speech-to-text micro-batch (encoder_target) carries neither a reward nor constraint_nodes")
+        loss, n = None, None
+        if ce_w > 0:
+            loss, _, n = ops.label_smoothed_cross_entropy(logits, target, self.pad, self.label_smoothing, self.constraint_range, cm,
+                                                          self.drop_worst_ratio)
+            if ce_w != 1.0:
+                loss = loss * ce_w
+        if ctc_w > 0:
+            x, lay = self._ctc_logits(model, ds, de, plan, encoder_out)
+            lc, _ = ops.ctc_loss(x, lay, s["encoder_target"], ds, self.pad, model.global_dict.eos(), bool(s.get("zero_infinity", False)),
+                                 stat=self._ctc_stat)              # (the statistic takes the fp64 sum, before its rounding to fp32)
+            lc = lc if ctc_w == 1.0 else lc * ctc_w
+            loss = lc if loss is None else loss + lc
+        if n is None:
+            n = target.ne(self.pad).sum()
+        return loss, n
+
+    @staticmethod
+    def _ctc_logits(model, ds, de, plan, encoder_out):
+        """-> (the CTC logits of the encoder output: its projection onto rows ds:de of the token embedding, their ops.CtcLayout)."""
+        enc = encoder_out["encoder_out"][0]                  # T x B x C, or packed rows [rows, 1, C]
+        weight = model.decoder.adaptor.embed_tokens.weight   # (:218: rows ds:de of the decoder's token embedding)
+        x = ops.encoder_ctc_logits(enc, weight, ds, de)
+        if plan is not None:
+            return x, ops.CtcLayout.packed(plan.enc_self)
+        # input lengths: the non-pad encoder positions of a sentence, counted over the whole source (:347-350); like the
+        # reference, the first `length` time steps are the ones read
+        masks = encoder_out["encoder_padding_mask"][0]
+        lengths = masks.shape[1] - masks.sum(1) if masks is not None else torch.full((enc.shape[1],), enc.shape[0], device=enc.device)
+        bm = not x.is_contiguous() and x.transpose(0, 1).is_contiguous()
+        return x, ops.CtcLayout.padded(lengths, x.shape[0], batch_major=bm)
+
+    @staticmethod
     def output_projection(model):
         """(weight [V, D], bias or None) of the decoder's text output projection: the tied token embedding, or the adaptor's own Linear."""
         ga = model.decoder.adaptor
@@ -432,17 +488,22 @@ class TrainStep:
         proj = text.output_projection
         return proj.weight, getattr(proj, "bias", None)
 
-    def _criterion_inputs(self, model, s, features=False):
+    def _criterion_inputs(self, model, s, features=False, encoder_out=False):
         """One micro-batch through `model` -> (logits, target, constraint masks, constraint nodes, pack plan) as the criterion takes
         them: by padded position, or (pack plan) by packed decoder row.  The train step and the validation step share it.
-        features: the decoder's features [.., D] stand where the logits would (the trie-edge head projects them itself)."""
+        features: the decoder's features [.., D] stand where the logits would (the trie-edge head projects them itself).
+        encoder_out: a sixth element, the encoder's output dict (the speech-to-text criterion reads it)."""
         plan = s.get("pack")
         target = s["target"]
         fo = {"features_only": True} if features else {}
+        if encoder_out:
+            fo["return_encoder_out"] = True
         if plan is None:
-            logits = model(s["slots"], **fo)[0]
+            out = model(s["slots"], **fo)
         else:                                    # ragged batch (packing.py): logits and targets by packed decoder row
-            logits = model(s["slots"], pack=plan, **fo)[0]
+            out = model(s["slots"], pack=plan, **fo)
+        logits = out[0]
+        if plan is not None:
             target = s.get("target_packed")
             if target is None:
                 idx = plan.dec_index
@@ -468,16 +529,24 @@ class TrainStep:
                     idx = plan.dec_index
                     packed = nodes.reshape(-1)[idx.clamp_min(0)].masked_fill(idx < 0, -1)
                 nodes = packed.view(1, -1)
+        if encoder_out:
+            return logits, target, cm, nodes, plan, out[2]
         return logits, target, cm, nodes, plan
 
     def _micro_batches(self, samples):
         model = self.model
         for s in samples:
             head = self._edge_head(s)
-            logits, target, cm, nodes, plan = self._criterion_inputs(model, s, features=head)
+            stt = self._speech_to_text(s)
+            logits, target, cm, nodes, plan, *enc = self._criterion_inputs(model, s, features=head, encoder_out=stt)
             counted = False
             size = None
-            if head:
+            if stt:
+                # speech-to-text: label-smoothed CE on the decoder plus CTC on the encoder output, one backward on the weighted sum
+                loss, n = self._speech_to_text_loss(model, s, logits, target, cm, plan, enc[0])
+                if s.get("sentence_avg"):            # sample_size = nsentences (speech_to_text_loss.py:241)
+                    size = s["target"].shape[0]
+            elif head:
                 # (the features stand in `logits`; loss scaling reaches the gradient kernels through backward's seed)
                 weight, bias = self.output_projection(model)
                 loss, _, n = ops.trie_head_cross_entropy(logits, weight, bias, target, nodes, s["constraint_trie"], self.pad,
@@ -645,7 +714,8 @@ class TrainStep:
         """Tensors whose lifetime is the step engine's / the model's own (what a capture may address without a pin)."""
         own = list(self.model.parameters()) + list(self.model.buffers())
         own += [self.fp.flat, self.fp.grad, self.master, self.exp_avg, self.exp_avg_sq, self._stats, self._gsq, self._gnorm_t,
-                self._step_t, self._lr_t, self._sched, self._seed, getattr(self, "_ls", None), self._valid_acc]
+                self._step_t, self._lr_t, self._sched, self._seed, getattr(self, "_ls", None), self._valid_acc, self._ctc_stat,
+                self._valid_ctc]
         own += list(ops._Rng.base.values())
         if self.ema is not None:
             own += self.ema.arenas()
@@ -725,6 +795,8 @@ class TrainStep:
             self._update()
         self.num_updates += 1
         self.last = {"stats": self._stats, "gnorm": self._gnorm, "skipped": self._sched[3:5]}
+        if any(self._speech_to_text(s) for s in samples):
+            self.last["ctc_loss"] = self._ctc_stat          # (the step's summed CTC term; other steps report what they always did)
         if self.loss_scale_cfg is not None:
             self.last["loss_scale"] = self._ls[0:1]
         return self.last
@@ -733,6 +805,8 @@ class TrainStep:
     def valid_begin(self):
         """Start a validation pass: zero the accumulator [ntokens, loss_sum, nll_sum, n_correct] (a device tensor the engine owns)."""
         self._valid_acc.zero_()
+        self._valid_ctc.zero_()
+        self._valid_decodes = []
 
     @contextlib.contextmanager
     def _valid_mode(self, model):
@@ -759,9 +833,26 @@ class TrainStep:
     def _valid_forward(self, samples, model):
         """The micro-batches through `model` (see _valid_mode) and through ops.criterion_eval (the engine's label_smoothing /
         constraint_range; no drop_worst: the reference's eval call never drops) into the accumulator.  Nothing here reads or writes
-        the gradient arena, the step statistics, the optimizer or EMA state or the device counters."""
+        the gradient arena, the step statistics, the optimizer or EMA state or the device counters.
+        A speech-to-text micro-batch (speech_to_text_loss.py:259-322) evaluates the decoder side if ce_weight > 0 and, if ctc_weight
+        > 0, adds its CTC loss to `_valid_ctc` and decodes greedily on the device.  -> [(tokens, lengths, encoder_target, ds)] of
+        those micro-batches: the caller keeps copies until the pass ends."""
+        outs = []
         with self._valid_mode(model):
             for s in samples:
+                if self._speech_to_text(s):
+                    ds, de = (int(v) for v in s["ctc_range"].split(","))
+                    logits, target, cm, _, plan, enc = self._criterion_inputs(model, s, encoder_out=True)
+                    if float(s.get("ce_weight", 1.0)) > 0:
+                        ops.criterion_eval(logits, target, self.pad, self.label_smoothing, self.constraint_range, cm, None, None,
+                                           acc=self._valid_acc)
+                    if float(s.get("ctc_weight", 0.0)) > 0:
+                        x, lay = self._ctc_logits(model, ds, de, plan, enc)
+                        ops.ctc_loss(x, lay, s["encoder_target"], ds, self.pad, model.global_dict.eos(),
+                                     bool(s.get("zero_infinity", False)), stat=self._valid_ctc)
+                        toks, n = ops.ctc_greedy_decode(x, lay)
+                        outs.append((toks, n, s["encoder_target"], ds))
+                    continue
                 if self._edge_head(s):
                     feats, target, _, nodes, _ = self._criterion_inputs(model, s, features=True)
                     weight, bias = self.output_projection(model)
@@ -771,6 +862,11 @@ class TrainStep:
                 logits, target, cm, nodes, _ = self._criterion_inputs(model, s)
                 ops.criterion_eval(logits, target, self.pad, self.label_smoothing, self.constraint_range, cm, nodes,
                                    s["constraint_trie"] if nodes is not None else None, acc=self._valid_acc)
+        return outs
+
+    def _keep_decodes(self, outs):
+        """Copies of a batch's greedy decodes (a replayed graph writes the same buffers again) wait on the device for valid_result."""
+        self._valid_decodes += [(t.clone(), n.clone(), et.clone(), ds) for t, n, et, ds in outs]
 
     def captured_valid_graphs(self):
         return sum(1 for e in self._valid_graphs.values() if "graphs" in e)
@@ -785,7 +881,7 @@ class TrainStep:
             g = torch.cuda.CUDAGraph()
             _KEEP_ALIVE.append(g)
             with torch.cuda.graph(g, pool=self._pool, capture_error_mode=_CAPTURE_MODE):
-                self._valid_forward(samples, model)
+                entry["decodes"] = self._valid_forward(samples, model)
             entry["graphs"] = [g]
         entry["audit"] = audit
         entry["pins"] = audit.tensors()
@@ -795,6 +891,7 @@ class TrainStep:
         if samples is not entry["static"]:
             K.copy_batched([(dst, src) for (_, dst), (_, src) in zip(entry["static_tensors"], sample_tensors(samples)) if dst is not src])
         entry["graphs"][0].replay()
+        self._keep_decodes(entry["decodes"])
 
     def valid_step(self, samples: List[dict], eager: bool = False, use_ema: bool = False):
         """One validation batch: the micro-batch dicts `train_step` takes (pack plans, target_packed, constraint_masks,
@@ -850,12 +947,28 @@ class TrainStep:
                         return
             else:
                 entry["seen"] += 1
-        self._valid_forward(samples, model)
+        self._keep_decodes(self._valid_forward(samples, model))
 
     def valid_result(self):
         """The pass since valid_begin(): ONE synchronisation (and, data parallel, one all-reduce of the accumulator) ->
-        dict(loss, nll_loss, ppl, ntokens, sample_size, n_correct, total, accuracy); see `valid_metrics`."""
-        return valid_metrics(self._valid_acc, self.group if self.world > 1 else None, self.world)
+        dict(loss, nll_loss, ppl, ntokens, sample_size, n_correct, total, accuracy); see `valid_metrics`.  A pass that held
+        speech-to-text micro-batches with ctc_weight > 0 also reports ctc_loss (the summed CTC loss, natural log), c_errors and
+        c_total: the unit-level edit distance of the greedy CTC decode against the labels and the label count
+        (speech_to_text_loss.py:294-300), computed here on the host with ops.edit_distance -- this rank's figures.  Word-level WER,
+        post_process and the KenLM decoder are out of scope."""
+        res = valid_metrics(self._valid_acc, self.group if self.world > 1 else None, self.world)
+        if self._valid_decodes:
+            res["ctc_loss"] = float(self._valid_ctc)
+            pad, eos = self.pad, self.model.global_dict.eos()
+            errs = total = 0
+            for toks, n, et, ds in self._valid_decodes:
+                toks, n, et = toks.tolist(), n.tolist(), et.tolist()
+                for b in range(len(n)):
+                    ref = [v - ds for v in et[b] if v != pad and v != eos]
+                    errs += ops.edit_distance(toks[b][:n[b]], ref)
+                    total += len(ref)
+            res["c_errors"], res["c_total"] = errs, total
+        return res
 
 
 def valid_metrics(acc, group=None, world=1):
