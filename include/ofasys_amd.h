@@ -355,6 +355,13 @@ int ofa_step_tail_old(int item);
 /* ---- elementwise pieces of the layer (transformer_layer.py:167-208): */
 int ofa_gelu_fwd(const void* x, void* y, int64_t n, int dtype, void* stream);                  /* module/gelu.py:18-19 */
 int ofa_gelu_bwd(const void* dy, const void* x, void* dx, int64_t n, int dtype, void* stream);
+/* QuickGELU of the ViT blocks (module/vit.py: x * sigmoid(1.702 x)); h, a, dy, dh: dense [rows, cols], fp32 math, one rounding.
+ * bwd: dh = dy * s * (1 + 1.702 h (1 - s)), s = sigmoid(1.702 h); ws != NULL: also the column sums of dh (the bias gradient of the
+ * Linear in front) as fp32 partial rows [ofa_quick_gelu_bwd_slots()][cols], every one written on every call, for ofa_fold_batched.
+ * cols must be a whole number of 16-byte vectors and the buffers 16-byte aligned (else OFA_ERR_UNSUPPORTED); rows == 0: nothing. */
+int ofa_quick_gelu_fwd(const void* h, void* a, int64_t rows, int cols, int dtype, void* stream);
+int ofa_quick_gelu_bwd(const void* dy, const void* h, void* dh, float* ws, int64_t rows, int cols, int dtype, void* stream);
+int ofa_quick_gelu_bwd_slots(int64_t rows, int cols, int dtype);        /* host only */
 /* y = residual + dropout_p(x); mask is regenerated from (seed, offset) with Philox4x32-10, nothing is stored.
  * offset_base (optional, device int64[1]) is added to `offset` on the device: the stream position of a captured
  * (hipGraph) train step lives there and is advanced by the step itself, so replays draw fresh masks. */

@@ -50,39 +50,26 @@ def _sync_batch_norm_2d(out_chan, momentum=0.1, eps=1e-3):
     return bn
 
 
-@register_config("ofasys.adaptor", "image_resnet", ImageResnetAdaptorConfig)
-class ImageResnetAdaptor(BaseAdaptor):
+class ImageGridAdaptor(BaseAdaptor):
+    """What the image adaptors with a backbone share (image_resnet, image_vit): a backbone `embed_images` that turns [B, 3, H, W] into
+    batch-major feature rows of an h x w grid, `image_proj` onto the model width, 2-D position ids, their embedding and the 2-D
+    relative-position bias."""
     pos_batch_invariant = True          # positions are arange- / grid-derived: identical for every batch row
 
-    def __init__(self, embed_tokens: Embedding, dictionary: Dictionary, is_src: bool, general_adaptor,
-                 cfg: ImageResnetAdaptorConfig):
-        super().__init__(embed_tokens, dictionary, is_src, general_adaptor, cfg)
+    def _build_grid(self, cfg, backbone, width):
+        """Members in the reference's order (state-dict order and the initial RNG stream): embed_image_positions, embed_images
+        (`backbone()` builds it), image_proj, image_rel_pos_table_list, image_rp_bucket."""
         if cfg.pretrained_ckpt_path:
             raise NotImplementedError("pretrained_ckpt_path: load the state dict through model.load_state_dict instead")
         self.embed_image_positions = Embedding(cfg.image_bucket_size ** 2 + 1, cfg.embed_dim)
-        backbone = {"resnet50": resnet50_backbone, "resnet101": resnet101_backbone, "resnet152": resnet152_backbone}[cfg.resnet_type]
-        # image_resnet.py:87-90: norm_layer = SynBatchNorm2d when cfg.sync_bn (module/layer.py:26-27: nn.SyncBatchNorm converted from
-        # nn.BatchNorm2d(momentum=0.1, eps=1e-3) -- note the eps, 100x the plain layer's -- same parameters, buffers and state-dict
-        # keys).  Here the modules stay nn.BatchNorm2d holders carrying a flag: in training ops.batch_norm all-reduces each layer's
-        # per-channel sums over the default process group (ops.SyncBatchNormFn)
-        self.embed_images = backbone(norm_layer=_sync_batch_norm_2d if cfg.sync_bn else None, drop_path_rate=cfg.resnet_drop_path_rate)
-        self.image_proj = Linear(1024, cfg.embed_dim)
+        self.embed_images = backbone()
+        self.image_proj = Linear(width if width is not None else self.embed_images.width, cfg.embed_dim)
         image_num_rel_dis = (2 * cfg.image_bucket_size - 1) * (2 * cfg.image_bucket_size - 1) + 3
         image_rp_bucket = make_image_bucket_position(cfg.image_bucket_size, image_num_rel_dis)
         num_rel_pos_tables = 1 if self.cfg.share_attn_bias else self.num_layers
         self.image_rel_pos_table_list = nn.ModuleList(
             [Embedding(image_num_rel_dis, cfg.num_attention_heads, zero_init=True) for _ in range(num_rel_pos_tables)])
         self.register_buffer("image_rp_bucket", image_rp_bucket)
-
-    def train(self, mode=True):                                               # image_resnet.py:107-114
-        super().train(mode)
-        if self.cfg.freeze_resnet:
-            for m in self.embed_images.modules():
-                if isinstance(m, nn.BatchNorm2d):
-                    m.eval()
-                    m.weight.requires_grad = False
-                    m.bias.requires_grad = False
-        return self
 
     def get_rel_pos_bias(self, batch_size, seq_length, idx, **kwargs):
         """[T,T,A] values = table_idx[ bucket[ids][:, ids] ]  (image_resnet.py:116-128).  The reference gathers per batch
@@ -121,3 +108,27 @@ class ImageResnetAdaptor(BaseAdaptor):
                 values = self.get_rel_pos_bias(batch_size, seq_length, idx, image_position_ids=position_ids)
                 self_attn_bias.append(self.expand_rel_pos_bias(values, batch_size))
         return AdaptorOutput(image_embed, mask, pos_embed, self_attn_bias)
+
+
+@register_config("ofasys.adaptor", "image_resnet", ImageResnetAdaptorConfig)
+class ImageResnetAdaptor(ImageGridAdaptor):
+    def __init__(self, embed_tokens: Embedding, dictionary: Dictionary, is_src: bool, general_adaptor,
+                 cfg: ImageResnetAdaptorConfig):
+        super().__init__(embed_tokens, dictionary, is_src, general_adaptor, cfg)
+        backbone = {"resnet50": resnet50_backbone, "resnet101": resnet101_backbone, "resnet152": resnet152_backbone}[cfg.resnet_type]
+        # image_resnet.py:87-90: norm_layer = SynBatchNorm2d when cfg.sync_bn (module/layer.py:26-27: nn.SyncBatchNorm converted from
+        # nn.BatchNorm2d(momentum=0.1, eps=1e-3) -- note the eps, 100x the plain layer's -- same parameters, buffers and state-dict
+        # keys).  Here the modules stay nn.BatchNorm2d holders carrying a flag: in training ops.batch_norm all-reduces each layer's
+        # per-channel sums over the default process group (ops.SyncBatchNormFn)
+        self._build_grid(cfg, lambda: backbone(norm_layer=_sync_batch_norm_2d if cfg.sync_bn else None,
+                                               drop_path_rate=cfg.resnet_drop_path_rate), 1024)
+
+    def train(self, mode=True):                                               # image_resnet.py:107-114
+        super().train(mode)
+        if self.cfg.freeze_resnet:
+            for m in self.embed_images.modules():
+                if isinstance(m, nn.BatchNorm2d):
+                    m.eval()
+                    m.weight.requires_grad = False
+                    m.bias.requires_grad = False
+        return self

@@ -785,6 +785,38 @@ def gelu_bwd(dy, x):
     return dx
 
 
+def quick_gelu_fwd(h):
+    """a = h * sigmoid(1.702 h) on [rows, cols] (module/vit.py QuickGELU)."""
+    h = h.contiguous()
+    rows, cols = _rows_cols(h)
+    a = torch.empty_like(h)
+    lib().call("ofa_quick_gelu_fwd", ptr(h), ptr(a), rows, cols, dtype_code(h), stream())
+    return a
+
+
+def quick_gelu_bwd_slots(rows, cols, dtype_code_):
+    return lib().cdll.ofa_quick_gelu_bwd_slots(int(rows), int(cols), int(dtype_code_))
+
+
+def quick_gelu_bwd(dy, h, dbias=None, fold=None, want_partials=False):
+    """dh of QuickGELU.  dbias (with fold): the column sums of dh -- the bias gradient of the Linear in front -- are ADDED to it: the
+    kernel leaves fp32 partial rows and `fold` (a FoldQueue / ImmediateFold) finishes them.  want_partials: -> (dh, partial rows
+    [slots, cols]) with nothing folded."""
+    dy, h = dy.contiguous(), h.contiguous()
+    rows, cols = _rows_cols(h)
+    dh = torch.empty_like(h)
+    ws = None
+    if (dbias is not None or want_partials) and rows > 0:
+        ns = quick_gelu_bwd_slots(rows, cols, dtype_code(h))
+        ws = torch.empty(ns, cols, dtype=torch.float32, device=h.device)
+    lib().call("ofa_quick_gelu_bwd", ptr(dy), ptr(h), ptr(dh), ptr(ws), rows, cols, dtype_code(h), stream())
+    if dbias is not None and ws is not None:
+        # registered AFTER the launch that writes the partial rows: an ImmediateFold folds at once, a FoldQueue at its flush
+        fold.add(ws, 0, dbias, cols, cols, ns)
+        fold.flush_if_large()
+    return (dh, ws) if want_partials else dh
+
+
 def dropout_add(x, residual, p, seed, offset, offset_base=None):
     """offset_base: optional device int64[1] added to `offset` on the device (graph-safe Philox stream position)."""
     x = x.contiguous()

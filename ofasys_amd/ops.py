@@ -693,6 +693,38 @@ def gelu(x):
     return restore(GeluFn.apply(x2d))
 
 
+class QuickGeluFn(torch.autograd.Function):
+    """a = h * sigmoid(1.702 h) (module/vit.py QuickGELU); saves only h.  bias_param: the bias of the Linear that produced h, called with
+    skip_bias_grad=True -- its gradient (the column sums of dh) leaves the backward kernel as partial rows for the fold when the
+    parameter has an arena sink, and is a separate column sum handed to autograd when it has none."""
+
+    @staticmethod
+    def forward(ctx, h, bias_param):
+        ctx.save_for_backward(h)
+        ctx.bias_ref = bias_param
+        return K.quick_gelu_fwd(h)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (h,) = ctx.saved_tensors
+        bias = ctx.bias_ref
+        if bias is None or not ctx.needs_input_grad[1]:
+            return K.quick_gelu_bwd(dy, h), None
+        gb = _sink(bias)
+        if gb is not None and gb.is_contiguous():
+            dh = K.quick_gelu_bwd(dy, h, dbias=gb, fold=_fold() or K.ImmediateFold())
+            _sink_done(bias)
+            return dh, None
+        dh = K.quick_gelu_bwd(dy, h)
+        return dh, K.colsum(dh, out_dtype=bias.dtype)
+
+
+def quick_gelu(h, bias_param=None):
+    """QuickGELU over the last dim's rows.  bias_param: see QuickGeluFn (the caller's Linear skipped its own bias gradient)."""
+    h2d, restore = rows_view(h)
+    return restore(QuickGeluFn.apply(h2d, bias_param))
+
+
 class DropoutAddFn(torch.autograd.Function):
     """y = residual + dropout_p(x)  (residual may be None)."""
 
@@ -1194,7 +1226,7 @@ class _AttnCs:
     __slots__ = ("bufs", "bias_ws", "c_ws", "ns")
 
 
-def _attn_cs_begin(gb, c_ref, B, T, S, seg, heads, dev, packed_kvq=False, want_q=True):
+def _attn_cs_begin(gb, c_ref, B, T, S, seg, heads, dev, packed_kvq=False, want_q=True, order="kvq"):
     """-> (_AttnCs or None, FoldQueue or ImmediateFold).  gb: the arena gradient of the call's packed bias ([3D] k|v|q for packed_kvq, else
     [D] of the q projection) or None; c_ref: the c_attn Parameter whose gradient is wanted (or None).  Only for gradients that live
     contiguously in the arena -- with or without a FoldQueue, so that a step computes the same bits whichever way its reductions run."""
@@ -1212,8 +1244,8 @@ def _attn_cs_begin(gb, c_ref, B, T, S, seg, heads, dev, packed_kvq=False, want_q
     cs.ns, cs.bufs, cs.bias_ws, cs.c_ws = ns, {}, None, None
     if use_b:
         cs.bias_ws = torch.empty(ns, 3 * D if packed_kvq else D, dtype=torch.float32, device=dev)
-        if packed_kvq:
-            cs.bufs.update(k=cs.bias_ws[:, 0:D], v=cs.bias_ws[:, D:2 * D], q=cs.bias_ws[:, 2 * D:3 * D])
+        if packed_kvq:                                   # order: the packed bias' column blocks ("qkv": nn.MultiheadAttention's in_proj)
+            cs.bufs.update({n: cs.bias_ws[:, i * D:(i + 1) * D] for i, n in enumerate(order)})
         else:
             cs.bufs["q"] = cs.bias_ws
     if use_c:
@@ -1283,6 +1315,75 @@ class PackedSelfAttentionFn(torch.autograd.Function):
         if cs:
             fq.flush_if_large()
         return (dx, *gws, *gbs, dbias, None, dc, None, None, None, None, None)
+
+
+class InProjSelfAttentionFn(torch.autograd.Function):
+    """Self-attention core over nn.MultiheadAttention's single packed parameter pair in_proj_weight [3D, D] / in_proj_bias [3D] (q|k|v
+    row blocks, read in place: no reorder, no copy) in front of the fused attention kernels: one N = 3D GEMM, attention on the column
+    slices (no bias, no mask, no c_attn); the backward writes dq|dk|dv as column slices of one [B,T,3D] buffer, then one dgrad GEMM
+    (K = 3D), one weight-gradient product and one bias column sum (the attention backward's epilogues where _attn_cs_begin offers
+    them).  16-bit operands, head_dim 64 (module/vit.py keeps everything else on ops.linear + ops.attention)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, heads, scale):
+        B, T, D = x.shape
+        x2d = x.view(B * T, D)
+        qkv = K.gemm(x2d, w, False, True, bias=b).view(B, T, 3 * D)
+        out, lse = K.attn_fwd(qkv[:, :, 0:D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:3 * D], heads, scale)
+        ctx.save_for_backward(x2d, qkv, out, lse, w)
+        ctx.bias_ref = b
+        ctx.cfg = (heads, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2d, qkv, out, lse, w = ctx.saved_tensors
+        heads, scale = ctx.cfg
+        b = ctx.bias_ref
+        B, T, D3 = qkv.shape
+        D = D3 // 3
+        gw, gb = _sink(w), _sink(b)
+        dqkv = torch.empty_like(qkv)
+        cs, fq = _attn_cs_begin(gb if ctx.needs_input_grad[2] else None, None, B, T, T, None, heads, qkv.device, packed_kvq=True,
+                                order="qkv")
+        K.attn_bwd(qkv[:, :, 0:D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:3 * D], out, dout, lse, heads, scale,
+                   outs=(dqkv[:, :, 0:D], dqkv[:, :, D:2 * D], dqkv[:, :, 2 * D:3 * D]), cs=cs.bufs if cs else None)
+        d2 = dqkv.view(B * T, D3)
+        dx = K.gemm(d2, w, False, False).view(B, T, D) if ctx.needs_input_grad[0] else None
+        dw = db = None
+        if ctx.needs_input_grad[1]:
+            if gw is not None:
+                _wgrad(d2, x2d, gw, 1.0, w)
+            else:
+                dw = K.gemm(d2, x2d, True, False)
+        if ctx.needs_input_grad[2]:
+            if cs and cs.bias_ws is not None:
+                fq.add(cs.bias_ws, 0, gb, D3, D3, cs.ns, 1.0, True)
+                _sink_done(b)
+                fq.flush_if_large()
+            elif gb is not None:
+                K.colsum(d2, out=gb, accumulate=True, fold=_fold())
+                _sink_done(b)
+            else:
+                db = K.colsum(d2, out_dtype=b.dtype)
+        return dx, dw, db, None, None
+
+
+def in_proj_self_attention_ok(x, heads):
+    """Does InProjSelfAttentionFn take this input (16-bit operands, head_dim 64)?"""
+    return x.dtype in (torch.bfloat16, torch.float16) and x.shape[-1] == heads * 64
+
+
+def in_proj_self_attention(x, in_proj_weight, in_proj_bias, heads):
+    """Self-attention core of nn.MultiheadAttention(D, heads) on batch-major rows x [B,T,D], up to (not including) out_proj.  The
+    fused path where in_proj_self_attention_ok; otherwise the unfused tier: three ops.linear over the parameter's row blocks (views)
+    and ops.attention."""
+    B, T, D = x.shape
+    scale = (D // heads) ** -0.5
+    if in_proj_self_attention_ok(x, heads):
+        return InProjSelfAttentionFn.apply(x.contiguous(), in_proj_weight, in_proj_bias, heads, scale)
+    q, k, v = (linear(x, in_proj_weight[i * D:(i + 1) * D], in_proj_bias[i * D:(i + 1) * D]) for i in range(3))
+    return attention(q, k, v, heads, scale)[0]
 
 
 class CrossKVShared:
