@@ -1,0 +1,216 @@
+"""Which criterion a micro-batch takes, and the host code that applies it (the kernels and autograd Functions are ops.py's).
+
+A micro-batch is the dict `TrainStep.train_step` / `valid_step` take.  `route` reads its keys and scalars -- no tensor data, no model,
+no device -- and names the criterion or refuses the dict; `forward` runs the model and lays the criterion's inputs out; `train_loss`
+and `evaluate` apply the routed criterion in the two directions.  The engine computes the routes of a step's micro-batches once, up
+front, so a refusal fires BEFORE the model forward of the step (it used to fire after the refused micro-batch's own forward); types,
+messages and precedence are what they were.
+
+    route            keys of the micro-batch                                 training                       validation
+    speech_to_text   encoder_target + ctc_range                              label-smoothed CE + CTC        criterion_eval, CTC loss + greedy decode
+    trie_head        constraint_nodes (+ constraint_trie), edge_head set     trie_head_cross_entropy        trie_head_eval
+    trie_nodes       constraint_nodes (+ constraint_trie)                    trie_label_smoothed_c._e.      criterion_eval(nodes)
+    scst             reward                                                  scst_loss                      refused
+    label_smoothed   constraint_masks, or any of label_smoothing /           label_smoothed_cross_entropy   criterion_eval
+                     constraint_range / drop_worst_ratio set
+    plain            none of these                                           cross_entropy_sum              criterion_eval
+"""
+from typing import NamedTuple, Optional, Tuple
+
+import torch
+
+from . import ops
+
+ROUTES = ("speech_to_text", "trie_head", "trie_nodes", "scst", "label_smoothed", "plain")
+
+
+class Settings(NamedTuple):
+    """The criterion's settings, handed to every function here per call (the engine builds one from its constructor arguments)."""
+    pad: int
+    eos: int
+    label_smoothing: float = 0.0
+    constraint_range: Optional[Tuple[int, int]] = None
+    drop_worst_ratio: float = 0.0
+    edge_head: bool = False             # a well-formed node micro-batch takes the trie-edge head (TrainStep(closed_set_edge_head=True))
+
+
+class Inputs(NamedTuple):
+    """What `forward` hands a criterion: by padded position, or (pack plan) by packed decoder row."""
+    logits: torch.Tensor                # (trie_head: the decoder's features [.., D] stand here; the head projects them itself)
+    target: torch.Tensor
+    masks: Optional[torch.Tensor]
+    nodes: Optional[torch.Tensor]
+    plan: object
+    encoder_out: Optional[dict]         # (speech_to_text alone)
+
+
+def output_projection(model):
+    """(weight [V, D], bias or None) of the decoder's text output projection: the tied token embedding, or the adaptor's own
+    Linear (adaptor/text.py:72)."""
+    ga = model.decoder.adaptor
+    text = ga.name2adaptor["text"]
+    if text.share_input_output_embed:
+        return ga.embed_tokens.weight, None
+    proj = text.output_projection
+    return proj.weight, getattr(proj, "bias", None)
+
+
+def route(s, settings, training=True):
+    """Micro-batch dict -> one of ROUTES, or the refusal of a malformed one.  An absent key and a key set to None are the same.
+    A malformed node micro-batch under `edge_head` is no head batch: it meets the dense path's refusal."""
+    def has(k):
+        return s.get(k) is not None
+    if not training and has("reward"):
+        raise NotImplementedError("an SCST micro-batch (reward) cannot be validated by the criterion: the reference validates "
+                                  "such tasks by generating (engine/criterion/scst_loss.py)")
+    if has("pack") and has("constraint_masks"):
+        raise NotImplementedError("constraint masks are laid out by padded position: run such samples without a pack plan")
+    if has("constraint_nodes"):
+        if has("constraint_masks"):
+            raise ValueError("a micro-batch carries its closed set as constraint_masks or as constraint_nodes, not both")
+        if has("reward"):
+            raise NotImplementedError("an SCST micro-batch (reward) cannot carry constraint_nodes: its criterion takes a "
+                                      "constraint range only (engine/criterion/scst_loss.py:214-217)")
+        if not has("constraint_trie"):
+            raise ValueError("constraint_nodes need \"constraint_trie\": the device arrays of the answer trie "
+                             "(Task.constraint_trie_on(device))")
+    if has("encoder_target") and has("ctc_range"):
+        if training:                    # (validation reads the weights' signs alone and ignores the nodes: as it always did)
+            ce_w, ctc_w = float(s.get("ce_weight", 1.0)), float(s.get("ctc_weight", 0.0))
+            if ce_w < 0 or ctc_w < 0 or ce_w + ctc_w == 0:
+                raise ValueError(f"speech_to_text_loss: ce_weight={ce_w}, ctc_weight={ctc_w}: one of them must be positive, none negative")
+            if has("reward") or has("constraint_nodes"):
+                raise NotImplementedError("a speech-to-text micro-batch (encoder_target) carries neither a reward nor constraint_nodes")
+        return "speech_to_text"
+    if has("constraint_nodes"):
+        return "trie_head" if settings.edge_head else "trie_nodes"
+    if has("reward"):
+        if has("constraint_masks"):
+            raise NotImplementedError("an SCST micro-batch (reward) cannot carry constraint_masks: its criterion takes a "
+                                      "constraint range only (engine/criterion/scst_loss.py:214-217)")
+        return "scst"
+    if settings.label_smoothing > 0 or settings.constraint_range is not None or settings.drop_worst_ratio > 0 or has("constraint_masks"):
+        return "label_smoothed"
+    return "plain"
+
+
+def forward(model, s, kind, settings):
+    """One micro-batch through `model` -> Inputs.  The train step and the validation step share it."""
+    plan = s.get("pack")
+    kw = {"features_only": True} if kind == "trie_head" else {"return_encoder_out": True} if kind == "speech_to_text" else {}
+    if plan is not None:                         # ragged batch (packing.py): logits and targets by packed decoder row
+        kw["pack"] = plan
+    out = model(s["slots"], **kw)
+    target = s["target"]
+    if plan is not None:
+        target = s.get("target_packed")
+        if target is None:
+            idx = plan.dec_index
+            target = s["target"].reshape(-1)[idx.clamp_min(0)].masked_fill(idx < 0, settings.pad).view(1, -1)
+    # closed-set targets by trie node (collate's closed_set_nodes): one int32 per target position instead of a mask row, and
+    # "constraint_trie", the task's device arrays of the answer trie; the nodes follow the targets into a packed layout
+    nodes = s.get("constraint_nodes")
+    if nodes is not None and plan is not None:
+        packed = s.get("constraint_nodes_packed")
+        if packed is None:
+            idx = plan.dec_index
+            packed = nodes.reshape(-1)[idx.clamp_min(0)].masked_fill(idx < 0, -1)
+        nodes = packed.view(1, -1)
+    return Inputs(out[0], target, s.get("constraint_masks"), nodes, plan, out[2] if kind == "speech_to_text" else None)
+
+
+def _ctc(model, s, x, settings, stat):
+    """The CTC side of a speech-to-text micro-batch -> (loss, the CTC logits: the encoder output's projection onto rows ds:de of the
+    token embedding, their ops.CtcLayout, ds); the summed loss is added to `stat` on the device."""
+    ds, de = (int(v) for v in s["ctc_range"].split(","))
+    enc = x.encoder_out["encoder_out"][0]                # T x B x C, or packed rows [rows, 1, C]
+    weight = model.decoder.adaptor.embed_tokens.weight   # (:218: rows ds:de of the decoder's token embedding)
+    y = ops.encoder_ctc_logits(enc, weight, ds, de)
+    if x.plan is not None:
+        lay = ops.CtcLayout.packed(x.plan.enc_self)
+    else:
+        # input lengths: the non-pad encoder positions of a sentence, counted over the whole source (:347-350); like the
+        # reference, the first `length` time steps are the ones read
+        masks = x.encoder_out["encoder_padding_mask"][0]
+        lengths = masks.shape[1] - masks.sum(1) if masks is not None else torch.full((enc.shape[1],), enc.shape[0], device=enc.device)
+        bm = not y.is_contiguous() and y.transpose(0, 1).is_contiguous()
+        lay = ops.CtcLayout.padded(lengths, y.shape[0], batch_major=bm)
+    loss, _ = ops.ctc_loss(y, lay, s["encoder_target"], ds, settings.pad, settings.eos, bool(s.get("zero_infinity", False)),
+                           stat=stat)                    # (the statistic takes the fp64 sum, before its rounding to fp32)
+    return loss, y, lay, ds
+
+
+def train_loss(model, s, kind, x, cfg, seed=None, stats=None, ctc_stat=None):
+    """The routed criterion on x = forward(...) -> (loss, ntokens, sample_size or None: ntokens).  ntokens is None on the plain route:
+    its statistics are the caller's (with `stats`, an ops.StepStats, the criterion kernel may have added them: stats.done).
+    seed: the tensor the caller will hand to loss.backward (ops._SeededGrad), None when it is not known yet (loss scaling); the routes
+    whose forward can write the logits' gradient take it."""
+    size = None
+    if kind == "speech_to_text":
+        # ce_weight * (the label-smoothed loss on the decoder) + ctc_weight * CTC(encoder output . embed_tokens[ds:de]^T), one backward on
+        # the weighted sum (engine/criterion/speech_to_text_loss.py).  A weight of 0 launches nothing of its side's criterion.  The CE
+        # side is ops.label_smoothed_cross_entropy whatever label_smoothing is (0 included: not the fused cross_entropy_sum a plain
+        # micro-batch takes).  The CTC loss is added to `ctc_stat`, this rank's sum: it is not all-reduced with the step statistics.
+        ce_w, ctc_w = float(s.get("ce_weight", 1.0)), float(s.get("ctc_weight", 0.0))
+        loss, n = None, None
+        if ce_w > 0:
+            loss, _, n = ops.label_smoothed_cross_entropy(x.logits, x.target, cfg.pad, cfg.label_smoothing, cfg.constraint_range, x.masks,
+                                                          cfg.drop_worst_ratio)
+            if ce_w != 1.0:
+                loss = loss * ce_w
+        if ctc_w > 0:
+            lc = _ctc(model, s, x, cfg, ctc_stat)[0]
+            lc = lc if ctc_w == 1.0 else lc * ctc_w
+            loss = lc if loss is None else loss + lc
+        if n is None:
+            n = x.target.ne(cfg.pad).sum()
+        if s.get("sentence_avg"):                # sample_size = nsentences (speech_to_text_loss.py:241)
+            size = s["target"].shape[0]
+    elif kind == "trie_head":
+        # (the features stand in x.logits; loss scaling reaches the gradient kernels through backward's seed)
+        weight, bias = output_projection(model)
+        loss, _, n = ops.trie_head_cross_entropy(x.logits, weight, bias, x.target, x.nodes, s["constraint_trie"], cfg.pad,
+                                                 cfg.label_smoothing, cfg.constraint_range, cfg.drop_worst_ratio)
+    elif kind == "trie_nodes":
+        loss, _, n = ops.trie_label_smoothed_cross_entropy(x.logits, x.target, x.nodes, s["constraint_trie"], cfg.pad, cfg.label_smoothing,
+                                                           cfg.constraint_range, cfg.drop_worst_ratio, seed=seed)
+    elif kind == "scst":
+        # self-critical sequence training (scst.ScstRewardCriterion builds such a micro-batch): the generated tokens' NLL weighted
+        # by the sentence's reward, loss and logits gradient in one pass (engine/criterion/scst_loss.py:24-36)
+        row_seq = None
+        if x.plan is not None:                   # packed decoder rows: the sentence of padded row i is i // Tt (filler rows: -1)
+            row_seq = torch.div(x.plan.dec_index, s["target"].shape[1], rounding_mode="floor").to(torch.int32)
+        cr = s.get("constraint_range")
+        cr = tuple(int(v) for v in cr.split(",")) if cr is not None else cfg.constraint_range
+        loss, n = ops.scst_loss(x.logits, x.target, s["reward"], cfg.pad, cr, row_seq, seed=seed)
+        if s.get("sentence_avg"):                # sample_size = nsentences (scst_loss.py:93)
+            size = s["reward"].numel()
+    elif kind == "label_smoothed":
+        loss, _, n = ops.label_smoothed_cross_entropy(x.logits, x.target, cfg.pad, cfg.label_smoothing, cfg.constraint_range, x.masks,
+                                                      cfg.drop_worst_ratio)
+    else:
+        # (the backward seed is known here: the criterion kernel writes the logits' gradient in its one pass over them)
+        loss, n = ops.cross_entropy_sum(x.logits, x.target, cfg.pad, seed=seed, stats=stats), None
+    return loss, n, size
+
+
+def evaluate(model, s, kind, x, cfg, acc, ctc_stat=None):
+    """The routed criterion in eval mode on x = forward(...): adds [ntokens, loss_sum, nll_sum, n_correct] to `acc` (label_smoothing /
+    constraint_range; no drop_worst: the reference's eval call never drops).  A speech-to-text micro-batch
+    (speech_to_text_loss.py:259-322) evaluates the decoder side if ce_weight > 0 and, if ctc_weight > 0, adds its CTC loss to
+    `ctc_stat` and decodes greedily on the device -> (tokens, lengths, encoder_target, ds); every other call returns None."""
+    if kind == "speech_to_text":
+        decode = None
+        if float(s.get("ce_weight", 1.0)) > 0:
+            ops.criterion_eval(x.logits, x.target, cfg.pad, cfg.label_smoothing, cfg.constraint_range, x.masks, None, None, acc=acc)
+        if float(s.get("ctc_weight", 0.0)) > 0:
+            _, y, lay, ds = _ctc(model, s, x, cfg, ctc_stat)
+            decode = (*ops.ctc_greedy_decode(y, lay), s["encoder_target"], ds)
+        return decode
+    if kind == "trie_head":
+        weight, bias = output_projection(model)
+        ops.trie_head_eval(x.logits, weight, bias, x.target, x.nodes, s["constraint_trie"], cfg.pad, cfg.label_smoothing,
+                           cfg.constraint_range, acc=acc)
+        return
+    ops.criterion_eval(x.logits, x.target, cfg.pad, cfg.label_smoothing, cfg.constraint_range, x.masks, x.nodes,
+                       s["constraint_trie"] if x.nodes is not None else None, acc=acc)

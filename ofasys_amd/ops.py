@@ -2015,6 +2015,36 @@ def _ce_rows(logits):
     return l2d
 
 
+def _range(constraint_range):
+    return constraint_range if constraint_range is not None else (-1, -1)
+
+
+def _criterion_rows(who, logits, target, constraint_range=None, constraint_masks=None, nodes=None):
+    """What every criterion over [..., V] logits starts with -> (the [rows, V] view, the flat target, cs, ce, the [rows, V] masks or
+    None, the nodes as int32 [rows] on the logits' device or None)."""
+    V = logits.shape[-1]
+    l2d = _ce_rows(logits)
+    t = target.reshape(-1).contiguous()
+    cm = constraint_masks.reshape(-1, V).contiguous() if constraint_masks is not None else None
+    nd = None
+    if nodes is not None:
+        nd = nodes.reshape(-1).to(device=l2d.device, dtype=torch.int32).contiguous()
+        if nd.numel() != l2d.shape[0]:
+            raise ValueError(f"{who}: {nd.numel()} nodes for {l2d.shape[0]} rows")
+    return (l2d, t, *_range(constraint_range), cm, nd)
+
+
+def _drop_rank(row_loss, valid, drop_worst_ratio):
+    """The drop-worst ranking on row_loss, on the device (a stable sort, no host sync) -> (keep: the rows that stay, their number k)."""
+    n = valid.sum()
+    k = (n.double() * (1 - drop_worst_ratio)).floor().long()                        # int(n * (1 - ratio)), on the device
+    key = torch.where(valid, row_loss, torch.full_like(row_loss, float("inf")))
+    order = torch.argsort(key, stable=True)
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(order.numel(), device=order.device)
+    return rank < k, k
+
+
 class _SeededGrad:
     """The logits' gradient a criterion's forward wrote at the scale of `seed`: the fp32 device scalar the caller says it WILL hand to
     `loss.backward(seed)` (trainer.TrainStep: its constant ones tensor).  It is handed out once, and only to a backward that receives
@@ -2106,23 +2136,14 @@ class LabelSmoothedCrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, ignore_index, eps, constraint_range, constraint_masks, drop_worst_ratio):
         V = logits.shape[-1]
-        l2d = _ce_rows(logits)
-        t = target.reshape(-1).contiguous()
-        cs, ce = constraint_range if constraint_range is not None else (-1, -1)
-        cm = constraint_masks.reshape(-1, V).contiguous() if constraint_masks is not None else None
+        l2d, t, cs, ce, cm, _ = _criterion_rows("label_smoothed_cross_entropy", logits, target, constraint_range, constraint_masks)
         lse, row_loss, row_nll, row_cnt = K.ls_cross_entropy_fwd(l2d, t, V, ignore_index, eps, cs, ce, cm)
         valid = t.ne(ignore_index)
         row_w = None
         if drop_worst_ratio > 0:
-            n = valid.sum()
-            k = (n.double() * (1 - drop_worst_ratio)).floor().long()                # int(n * (1 - ratio)), on the device
-            key = torch.where(valid, row_loss, torch.full_like(row_loss, float("inf")))
-            order = torch.argsort(key, stable=True)
-            rank = torch.empty_like(order)
-            rank[order] = torch.arange(order.numel(), device=order.device)
-            row_w = (rank < k).float()
-            row_loss, row_nll = row_loss * row_w, row_nll * row_w
-            ntok = k
+            keep, ntok = _drop_rank(row_loss, valid, drop_worst_ratio)
+            row_w = keep.float()
+            row_loss, row_nll = row_loss * row_w, row_nll * row_w     # (a dropped +inf row: NaN here, 0 in the trie forms' torch.where)
         else:
             ntok = valid.sum()
         ctx.save_for_backward(l2d, t, lse, row_cnt, row_w, cm)
@@ -2157,12 +2178,7 @@ class TrieLabelSmoothedCrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, nodes, trie, ignore_index, eps, constraint_range, drop_worst_ratio, seed):
         V = logits.shape[-1]
-        l2d = _ce_rows(logits)
-        t = target.reshape(-1).contiguous()
-        nd = nodes.reshape(-1).to(device=l2d.device, dtype=torch.int32).contiguous()
-        if nd.numel() != l2d.shape[0]:
-            raise ValueError(f"trie_label_smoothed_cross_entropy: {nd.numel()} nodes for {l2d.shape[0]} rows")
-        cs, ce = constraint_range if constraint_range is not None else (-1, -1)
+        l2d, t, cs, ce, _, nd = _criterion_rows("trie_label_smoothed_cross_entropy", logits, target, constraint_range, nodes=nodes)
         seeded = drop_worst_ratio <= 0 and ctx.needs_input_grad[0] and _SeededGrad.usable(seed, l2d.device)
         lse, row_loss, row_nll, row_cnt, d = K.trie_ls_cross_entropy_fwd(l2d, t, nd, trie, V, ignore_index, eps, cs, ce,
                                                                          grad_scale=seed if seeded else None, want_grad=seeded)
@@ -2170,17 +2186,7 @@ class TrieLabelSmoothedCrossEntropyFn(torch.autograd.Function):
         valid = t.ne(ignore_index)
         row_w = None
         if drop_worst_ratio > 0:
-            n = valid.sum()
-            k = (n.double() * (1 - drop_worst_ratio)).floor().long()                # int(n * (1 - ratio)), on the device
-            key = torch.where(valid, row_loss, torch.full_like(row_loss, float("inf")))
-            order = torch.argsort(key, stable=True)
-            rank = torch.empty_like(order)
-            rank[order] = torch.arange(order.numel(), device=order.device)
-            keep = rank < k
-            row_w = keep.float()
-            zero = torch.zeros_like(row_loss)
-            row_loss, row_nll = torch.where(keep, row_loss, zero), torch.where(keep, row_nll, zero)   # (a dropped +inf row: 0, not NaN)
-            ntok = k
+            row_w, row_loss, row_nll, ntok = _drop_worst(row_loss, row_nll, valid, drop_worst_ratio)
         else:
             ntok = valid.sum()
         ctx.save_for_backward(l2d, t, nd, lse, row_cnt, row_w, trie["node_edge_off"], trie["edge_token"])
@@ -2211,16 +2217,11 @@ def trie_label_smoothed_cross_entropy(logits, target, nodes, trie, ignore_index,
 
 
 def _drop_worst(row_loss, row_nll, valid, drop_worst_ratio):
-    """The drop-worst ranking of (Trie)LabelSmoothedCrossEntropyFn on row_loss, on the device: -> (row_w, row_loss, row_nll, ntokens)."""
-    n = valid.sum()
-    k = (n.double() * (1 - drop_worst_ratio)).floor().long()                        # int(n * (1 - ratio)), on the device
-    key = torch.where(valid, row_loss, torch.full_like(row_loss, float("inf")))
-    order = torch.argsort(key, stable=True)
-    rank = torch.empty_like(order)
-    rank[order] = torch.arange(order.numel(), device=order.device)
-    keep = rank < k
+    """Drop-worst of the trie forms: the rows _drop_rank drops are set to 0 -> (row_w, row_loss, row_nll, ntokens)."""
+    keep, k = _drop_rank(row_loss, valid, drop_worst_ratio)
+    row_w = keep.float()
     zero = torch.zeros_like(row_loss)
-    return keep.float(), torch.where(keep, row_loss, zero), torch.where(keep, row_nll, zero), k   # (a dropped +inf row: 0, not NaN)
+    return row_w, torch.where(keep, row_loss, zero), torch.where(keep, row_nll, zero), k   # (a dropped +inf row: 0, not NaN)
 
 
 def _head_inputs(who, feats, weight, bias, target, nodes):
@@ -2248,7 +2249,7 @@ class TrieHeadCrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feats, weight, bias, target, nodes, trie, ignore_index, eps, constraint_range, drop_worst_ratio):
         f2d, t, nd = _head_inputs("trie_head_cross_entropy", feats, weight, bias, target, nodes)
-        cs, ce = constraint_range if constraint_range is not None else (-1, -1)
+        cs, ce = _range(constraint_range)
         out = K.trie_head_fwd(f2d, weight, bias, t, nd, trie, ignore_index, eps, cs, ce, want_grad=True)
         row_loss, row_nll = out["row_loss"], out["row_nll"]
         valid = t.ne(ignore_index)
@@ -2312,7 +2313,7 @@ def trie_head_eval(feats, weight, bias, target, nodes, trie, pad, eps, constrain
             raise ValueError(f"trie_head_eval: the trie's device arrays carry no {k!r}")
     with torch.no_grad():
         f2d, t, nd = _head_inputs("trie_head_eval", feats.detach(), weight, bias, target, nodes)
-        cs, ce = constraint_range if constraint_range is not None else (-1, -1)
+        cs, ce = _range(constraint_range)
         out = K.trie_head_fwd(f2d, weight.detach(), None if bias is None else bias.detach(), t, nd, trie, pad, eps, cs, ce,
                               want_grad=False, want_hit=True)
         if acc is None:
@@ -2483,8 +2484,7 @@ class ScstLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, reward, ignore_index, constraint_range, row_seq, seed):
         V = logits.shape[-1]
-        l2d = _ce_rows(logits)
-        t = target.reshape(-1).contiguous()
+        l2d, t, cs, ce, _, _ = _criterion_rows("scst_loss", logits, target, constraint_range)
         w = reward.reshape(-1).to(device=l2d.device, dtype=torch.float32).contiguous()
         rows = l2d.shape[0]
         if row_seq is not None:
@@ -2496,7 +2496,6 @@ class ScstLossFn(torch.autograd.Function):
             if w.numel() == 0 or rows % w.numel() != 0:
                 raise ValueError(f"scst_loss: {rows} rows do not divide into {w.numel()} sentences (pass row_seq)")
             rps = rows // w.numel()
-        cs, ce = constraint_range if constraint_range is not None else (-1, -1)
         seeded = ctx.needs_input_grad[0] and _SeededGrad.usable(seed, l2d.device)
         lse, row_loss, d = K.scst_loss_fwd_grad(l2d, t, w, seed if seeded else None, V, ignore_index, rps, row_seq, cs, ce)
         ctx.seeded = _SeededGrad(seed, d) if seeded else _SeededGrad()      # (a backward that cannot take it runs the same entry again)
@@ -2531,18 +2530,10 @@ def criterion_eval(logits, target, pad, eps, constraint_range=None, constraint_m
     None: a fresh zero accumulator) in a fixed order.  The allowed set as in label_smoothed_cross_entropy (range, byte masks) or
     trie_label_smoothed_cross_entropy (nodes + trie).  Returns (acc, row_loss, row_nll, row_hit); nothing is synchronised."""
     V = logits.shape[-1]
+    if nodes is not None and constraint_masks is not None:
+        raise ValueError("criterion_eval: a closed set comes as constraint_masks or as nodes, not both")
     with torch.no_grad():
-        l2d = _ce_rows(logits.detach())
-        t = target.reshape(-1).contiguous()
-        cs, ce = constraint_range if constraint_range is not None else (-1, -1)
-        cm = constraint_masks.reshape(-1, V).contiguous() if constraint_masks is not None else None
-        nd = None
-        if nodes is not None:
-            if cm is not None:
-                raise ValueError("criterion_eval: a closed set comes as constraint_masks or as nodes, not both")
-            nd = nodes.reshape(-1).to(device=l2d.device, dtype=torch.int32).contiguous()
-            if nd.numel() != l2d.shape[0]:
-                raise ValueError(f"criterion_eval: {nd.numel()} nodes for {l2d.shape[0]} rows")
+        l2d, t, cs, ce, cm, nd = _criterion_rows("criterion_eval", logits.detach(), target, constraint_range, constraint_masks, nodes)
         row_loss, row_nll, row_hit = K.criterion_eval(l2d, t, V, pad, eps, cs, ce, cm, nd, trie)
         if acc is None:
             acc = torch.zeros(4, dtype=torch.float64, device=l2d.device)

@@ -20,6 +20,7 @@ from typing import List
 import torch
 import torch.utils._python_dispatch          # noqa: F401  (TorchDispatchMode: the capture audit's view of torch-native ops)
 
+from . import criterion
 from . import kernels as K
 from . import ops
 from .distributed import GradBucketReducer, all_reduce_scalars
@@ -293,6 +294,9 @@ class TrainStep:
         # one (label_smoothed_cross_entropy.py); a sample may carry its own "constraint_masks" [B, Tt, V]
         self.label_smoothing, self.constraint_range, self.drop_worst_ratio = label_smoothing, constraint_range, drop_worst_ratio
         self.closed_set_edge_head = bool(closed_set_edge_head)
+        # ... gathered in the record every route of criterion.py reads its settings from, handed in per call
+        self.criterion = criterion.Settings(self.pad, model.global_dict.eos(), label_smoothing, constraint_range, drop_worst_ratio,
+                                            self.closed_set_edge_head)
         self._stats = torch.zeros(3, dtype=torch.float64, device=dev)      # [sample_size, loss_sum, ntokens]
         self._ctc_stat = torch.zeros(1, dtype=torch.float64, device=dev)   # sum of the step's CTC losses (speech-to-text micro-batches)
         self._gsq = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -376,7 +380,7 @@ class TrainStep:
         self._lr_t.fill_(self._lr)                  # outside any captured region: replays read the new value
 
     # ------------------------------------------------------------------ the three phases of a step
-    def _fwd_bwd(self, samples, overlap_reduce, structure=None):
+    def _fwd_bwd(self, samples, routes, overlap_reduce, structure=None):
         model = self.model
         model.train()
         ops.drop_pending()
@@ -392,21 +396,21 @@ class TrainStep:
             self.fp.repoint()
             # (structure None: eager steps share one list.  The step's statistics and the sum of squares are cleared by the same launch.)
             # (a step without a speech-to-text micro-batch launches exactly what it launched before: its CTC statistic is not touched)
-            stt = (self._ctc_stat,) if any(self._speech_to_text(s) for s in samples) else ()
+            stt = (self._ctc_stat,) if "speech_to_text" in routes else ()
             ops.grad_begin(self.fp.grad, self._prezero.get(structure, ()), also=(self._stats, self._gsq) + stt)
             self._gsq_cleared = True
         else:
             ops.grad_abort()
             self.fp.zero_grad()
             self._stats.zero_()
-            if any(self._speech_to_text(s) for s in samples):
+            if "speech_to_text" in routes:
                 self._ctc_stat.zero_()
         self.reducer.overlap = overlap_reduce
         # gradients are only read after backward unless buckets are all-reduced from inside it: fold lazily, in batches
         ops.defer_reductions(self.world == 1 or not overlap_reduce)
         self.reducer.begin_step(structure, dynamic=self.dynamic_autograd or self.sync_collectives)
         try:
-            self._micro_batches(samples)
+            self._micro_batches(samples, routes)
             ops.flush_folds()
         except BaseException:
             ops.grad_abort()                         # (every sink adds again: nothing of this step's touched set outlives it)
@@ -423,182 +427,45 @@ class TrainStep:
     def _fused_norm(self):
         return self.world == 1 and not K.tail_old(K.TAIL_NORM_SCHEDULE)
 
-    def _edge_head(self, s):
-        """Does this micro-batch take the trie-edge head (closed_set_edge_head and a well-formed node micro-batch; a malformed one goes
-        the dense way and meets its refusal there)?"""
-        return (self.closed_set_edge_head and s.get("constraint_nodes") is not None and s.get("constraint_masks") is None
-                and s.get("reward") is None and s.get("constraint_trie") is not None)
-
-    @staticmethod
-    def _speech_to_text(s):
-        """Does this micro-batch take the speech-to-text criterion (engine/criterion/speech_to_text_loss.py): "encoder_target" and
-        "ctc_range" in the dict?"""
-        return s.get("encoder_target") is not None and s.get("ctc_range") is not None
-
-    def _speech_to_text_loss(self, model, s, logits, target, cm, plan, encoder_out):
-        """ce_weight * (today's label-smoothed loss on the decoder) + ctc_weight * CTC(encoder output . embed_tokens[ds:de]^T) ->
-        (loss, ntokens).  A weight of 0 launches nothing of its side's criterion.  The CE side is ops.label_smoothed_cross_entropy
-        whatever the engine's label_smoothing (0 included: not the fused cross_entropy_sum path a plain micro-batch of such an
-        engine takes), so "ctc_weight = 0 is today's step bit for bit" means the label-smoothed op's step.  The CTC loss is added
-        to `self._ctc_stat`, this rank's sum: data parallel, it is not all-reduced with the step statistics."""
-        ds, de = (int(v) for v in s["ctc_range"].split(","))
-        ce_w, ctc_w = float(s.get("ce_weight", 1.0)), float(s.get("ctc_weight", 0.0))
-        if ce_w < 0 or ctc_w < 0 or ce_w + ctc_w == 0:
-            raise ValueError(f"speech_to_text_loss: ce_weight={ce_w}, ctc_weight={ctc_w}: one of them must be positive, none negative")
-        if s.get("reward") is not None or s.get("constraint_nodes") is not None:
-            raise NotImplementedError("a speech-to-text micro-batch (encoder_target) carries neither a reward nor constraint_nodes")
-        loss, n = None, None
-        if ce_w > 0:
-            loss, _, n = ops.label_smoothed_cross_entropy(logits, target, self.pad, self.label_smoothing, self.constraint_range, cm,
-                                                          self.drop_worst_ratio)
-            if ce_w != 1.0:
-                loss = loss * ce_w
-        if ctc_w > 0:
-            x, lay = self._ctc_logits(model, ds, de, plan, encoder_out)
-            lc, _ = ops.ctc_loss(x, lay, s["encoder_target"], ds, self.pad, model.global_dict.eos(), bool(s.get("zero_infinity", False)),
-                                 stat=self._ctc_stat)              # (the statistic takes the fp64 sum, before its rounding to fp32)
-            lc = lc if ctc_w == 1.0 else lc * ctc_w
-            loss = lc if loss is None else loss + lc
-        if n is None:
-            n = target.ne(self.pad).sum()
-        return loss, n
-
-    @staticmethod
-    def _ctc_logits(model, ds, de, plan, encoder_out):
-        """-> (the CTC logits of the encoder output: its projection onto rows ds:de of the token embedding, their ops.CtcLayout)."""
-        enc = encoder_out["encoder_out"][0]                  # T x B x C, or packed rows [rows, 1, C]
-        weight = model.decoder.adaptor.embed_tokens.weight   # (:218: rows ds:de of the decoder's token embedding)
-        x = ops.encoder_ctc_logits(enc, weight, ds, de)
-        if plan is not None:
-            return x, ops.CtcLayout.packed(plan.enc_self)
-        # input lengths: the non-pad encoder positions of a sentence, counted over the whole source (:347-350); like the
-        # reference, the first `length` time steps are the ones read
-        masks = encoder_out["encoder_padding_mask"][0]
-        lengths = masks.shape[1] - masks.sum(1) if masks is not None else torch.full((enc.shape[1],), enc.shape[0], device=enc.device)
-        bm = not x.is_contiguous() and x.transpose(0, 1).is_contiguous()
-        return x, ops.CtcLayout.padded(lengths, x.shape[0], batch_major=bm)
-
-    @staticmethod
-    def output_projection(model):
-        """(weight [V, D], bias or None) of the decoder's text output projection: the tied token embedding, or the adaptor's own Linear."""
-        ga = model.decoder.adaptor
-        text = ga.name2adaptor["text"]
-        if text.share_input_output_embed:
-            return ga.embed_tokens.weight, None
-        proj = text.output_projection
-        return proj.weight, getattr(proj, "bias", None)
+    output_projection = staticmethod(criterion.output_projection)
 
     def _criterion_inputs(self, model, s, features=False, encoder_out=False):
-        """One micro-batch through `model` -> (logits, target, constraint masks, constraint nodes, pack plan) as the criterion takes
-        them: by padded position, or (pack plan) by packed decoder row.  The train step and the validation step share it.
-        features: the decoder's features [.., D] stand where the logits would (the trie-edge head projects them itself).
-        encoder_out: a sixth element, the encoder's output dict (the speech-to-text criterion reads it)."""
-        plan = s.get("pack")
-        target = s["target"]
-        fo = {"features_only": True} if features else {}
-        if encoder_out:
-            fo["return_encoder_out"] = True
-        if plan is None:
-            out = model(s["slots"], **fo)
-        else:                                    # ragged batch (packing.py): logits and targets by packed decoder row
-            out = model(s["slots"], pack=plan, **fo)
-        logits = out[0]
-        if plan is not None:
-            target = s.get("target_packed")
-            if target is None:
-                idx = plan.dec_index
-                target = s["target"].reshape(-1)[idx.clamp_min(0)].masked_fill(idx < 0, self.pad).view(1, -1)
-        cm = s.get("constraint_masks")
-        if plan is not None and cm is not None:
-            raise NotImplementedError("constraint masks are laid out by padded position: run such samples without a pack plan")
-        # closed-set targets by trie node (collate's closed_set_nodes): one int32 per target position instead of a mask row, and
-        # "constraint_trie", the task's device arrays of the answer trie; the nodes follow the targets into a packed layout
-        nodes = s.get("constraint_nodes")
-        if nodes is not None:
-            if cm is not None:
-                raise ValueError("a micro-batch carries its closed set as constraint_masks or as constraint_nodes, not both")
-            if s.get("reward") is not None:
-                raise NotImplementedError("an SCST micro-batch (reward) cannot carry constraint_nodes: its criterion takes a "
-                                          "constraint range only (engine/criterion/scst_loss.py:214-217)")
-            if s.get("constraint_trie") is None:
-                raise ValueError("constraint_nodes need \"constraint_trie\": the device arrays of the answer trie "
-                                 "(Task.constraint_trie_on(device))")
-            if plan is not None:
-                packed = s.get("constraint_nodes_packed")
-                if packed is None:
-                    idx = plan.dec_index
-                    packed = nodes.reshape(-1)[idx.clamp_min(0)].masked_fill(idx < 0, -1)
-                nodes = packed.view(1, -1)
-        if encoder_out:
-            return logits, target, cm, nodes, plan, out[2]
-        return logits, target, cm, nodes, plan
+        """criterion.forward with the engine's settings, under the name and with the tuple the tests' oracles take:
+        (logits or features, target, masks, nodes, pack plan[, the encoder's output dict])."""
+        kind = "trie_head" if features else "speech_to_text" if encoder_out else "plain"
+        x = criterion.forward(model, s, kind, self.criterion)
+        return x[:5] + ((x.encoder_out,) if encoder_out else ())
 
-    def _micro_batches(self, samples):
-        model = self.model
-        for s in samples:
-            head = self._edge_head(s)
-            stt = self._speech_to_text(s)
-            logits, target, cm, nodes, plan, *enc = self._criterion_inputs(model, s, features=head, encoder_out=stt)
+    def _loss_seed(self, loss=None):
+        """The backward seed of a micro-batch's loss: the engine's constant ones tensor (autograd's default is one fill per call), which
+        the criteria that write the logits' gradient in their forward are told in advance (ops._SeededGrad).  None under loss scaling:
+        the seed is then the scale (FP16Optimizer.backward: loss * loss_scale, fp16_optimizer.py:92-102), a device value.
+        loss: the loss about to be seeded -- one of another shape, dtype or device gets a new constant."""
+        if self.loss_scale_cfg is not None:
+            return None
+        if loss is not None and (self._seed.shape != loss.shape or self._seed.dtype != loss.dtype or self._seed.device != loss.device):
+            self._seed = torch.ones_like(loss)
+        return self._seed
+
+    def _micro_batches(self, samples, routes):
+        """Forward, the routed criterion (criterion.py), backward and the step statistics of every micro-batch."""
+        cfg = self.criterion
+        fused = self._ce_stats if (self.fp.flat.is_cuda and not K.tail_old(K.TAIL_CRITERION_STATS)) else None
+        for s, kind in zip(samples, routes):
+            x = criterion.forward(self.model, s, kind, cfg)
+            loss, n, size = criterion.train_loss(self.model, s, kind, x, cfg, seed=self._loss_seed(), stats=fused, ctc_stat=self._ctc_stat)
             counted = False
-            size = None
-            if stt:
-                # speech-to-text: label-smoothed CE on the decoder plus CTC on the encoder output, one backward on the weighted sum
-                loss, n = self._speech_to_text_loss(model, s, logits, target, cm, plan, enc[0])
-                if s.get("sentence_avg"):            # sample_size = nsentences (speech_to_text_loss.py:241)
-                    size = s["target"].shape[0]
-            elif head:
-                # (the features stand in `logits`; loss scaling reaches the gradient kernels through backward's seed)
-                weight, bias = self.output_projection(model)
-                loss, _, n = ops.trie_head_cross_entropy(logits, weight, bias, target, nodes, s["constraint_trie"], self.pad,
-                                                         self.label_smoothing, self.constraint_range, self.drop_worst_ratio)
-            elif nodes is not None:
-                if self.loss_scale_cfg is None and (self._seed is None or self._seed.device != logits.device):
-                    self._seed = torch.ones((), dtype=torch.float32, device=logits.device)
-                loss, _, n = ops.trie_label_smoothed_cross_entropy(logits, target, nodes, s["constraint_trie"], self.pad,
-                                                                   self.label_smoothing, self.constraint_range, self.drop_worst_ratio,
-                                                                   seed=self._seed if self.loss_scale_cfg is None else None)
-            elif s.get("reward") is not None:
-                # self-critical sequence training (scst.ScstRewardCriterion builds such a micro-batch): the generated tokens' NLL
-                # weighted by the sentence's reward, loss and logits gradient in one pass (engine/criterion/scst_loss.py:24-36)
-                if cm is not None:
-                    raise NotImplementedError("an SCST micro-batch (reward) cannot carry constraint_masks: its criterion takes a "
-                                              "constraint range only (engine/criterion/scst_loss.py:214-217)")
-                row_seq = None
-                if plan is not None:                 # packed decoder rows: the sentence of padded row i is i // Tt (filler rows: -1)
-                    row_seq = torch.div(plan.dec_index, s["target"].shape[1], rounding_mode="floor").to(torch.int32)
-                cr = s.get("constraint_range")
-                cr = tuple(int(v) for v in cr.split(",")) if cr is not None else self.constraint_range
-                if self.loss_scale_cfg is None and (self._seed is None or self._seed.device != logits.device):
-                    self._seed = torch.ones((), dtype=torch.float32, device=logits.device)
-                loss, n = ops.scst_loss(logits, target, s["reward"], self.pad, cr, row_seq,
-                                        seed=self._seed if self.loss_scale_cfg is None else None)
-                if s.get("sentence_avg"):            # sample_size = nsentences (scst_loss.py:93)
-                    size = s["reward"].numel()
-            elif self.label_smoothing > 0 or self.constraint_range is not None or self.drop_worst_ratio > 0 or cm is not None:
-                loss, _, n = ops.label_smoothed_cross_entropy(logits, target, self.pad, self.label_smoothing,
-                                                              self.constraint_range, cm, self.drop_worst_ratio)
-            else:
-                # (the backward seed is known here: the criterion kernel writes the logits' gradient in its one pass over them)
-                if self.loss_scale_cfg is None and (self._seed is None or self._seed.device != logits.device):
-                    self._seed = torch.ones((), dtype=torch.float32, device=logits.device)
-                fused = self._ce_stats if (logits.is_cuda and not K.tail_old(K.TAIL_CRITERION_STATS)) else None
-                loss = ops.cross_entropy_sum(logits, target, self.pad, seed=self._seed if self.loss_scale_cfg is None else None,
-                                             stats=fused)
-                n = None
-                if fused is not None and fused.done:     # (the criterion kernel's last block added the statistics)
+            if n is None:                            # the plain route: its statistics are added before the backward
+                if fused is not None and fused.done:     # (the criterion kernel's last block added them)
                     counted = True
-                elif loss.is_cuda and loss.dtype == torch.float32 and target.is_contiguous() and target.dtype == torch.int64:
+                elif loss.is_cuda and loss.dtype == torch.float32 and x.target.is_contiguous() and x.target.dtype == torch.int64:
                     # [sample_size, loss_sum, ntokens] += (non-pad targets, loss, non-pad targets) in one launch
-                    K.step_stats_add(self._stats, loss.detach(), target, self.pad)
+                    K.step_stats_add(self._stats, loss.detach(), x.target, self.pad)
                     counted = True
                 else:
-                    n = target.ne(self.pad).sum()
-            if self.loss_scale_cfg is None:
-                if self._seed is None or self._seed.shape != loss.shape or self._seed.dtype != loss.dtype or self._seed.device != loss.device:
-                    self._seed = torch.ones_like(loss)
-                loss.backward(self._seed)
-            else:                                    # FP16Optimizer.backward: loss * loss_scale (fp16_optimizer.py:92-102)
-                loss.backward(self._ls[0].to(loss.dtype))
+                    n = x.target.ne(self.pad).sum()
+            seed = self._loss_seed(loss)
+            loss.backward(seed if seed is not None else self._ls[0].to(loss.dtype))
             if not counted:
                 self._stats[0] += n if size is None else size
                 self._stats[1] += loss.detach().double()
@@ -675,7 +542,7 @@ class TrainStep:
     def captured_graphs(self):
         return sum(1 for e in self._graphs.values() if "graphs" in e)
 
-    def _capture(self, samples, structure, mode):
+    def _capture(self, samples, routes, structure, mode):
         import gc
         gc.collect()                      # drop unreachable autograd graphs (see the class docstring) before recording
         if self._pool is None:
@@ -692,7 +559,7 @@ class TrainStep:
                 g = torch.cuda.CUDAGraph()
                 _KEEP_ALIVE.append(g)
                 with torch.cuda.graph(g, pool=pool, capture_error_mode=_CAPTURE_MODE):
-                    self._fwd_bwd(samples, overlap_reduce=self.world > 1, structure=structure)
+                    self._fwd_bwd(samples, routes, overlap_reduce=self.world > 1, structure=structure)
                     if self.world > 1:
                         self._reduce()
                     self._update()
@@ -701,7 +568,7 @@ class TrainStep:
                 ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
                 _KEEP_ALIVE.extend((ga, gb))
                 with torch.cuda.graph(ga, pool=pool, capture_error_mode=_CAPTURE_MODE):
-                    self._fwd_bwd(samples, overlap_reduce=False)
+                    self._fwd_bwd(samples, routes, overlap_reduce=False)
                 with torch.cuda.graph(gb, pool=pool, capture_error_mode=_CAPTURE_MODE):
                     self._update()
                 entry["graphs"] = [ga, gb]
@@ -739,12 +606,12 @@ class TrainStep:
             entry["graphs"][1].replay()
 
     def train_step(self, samples: List[dict], eager: bool = False):
-        """samples: one dict per (task, micro-batch): {"slots": [...], "target": LongTensor[B,Tt], optional
-        "constraint_masks", "task"}.  With "reward" (fp32, one value per row of `target`) the micro-batch takes the SCST criterion
-        (ops.scst_loss; optional "constraint_range": "start,end" and "sentence_avg": True).  With "constraint_nodes" (int32 [B, Tt],
-        -1 where no closed set applies) and "constraint_trie" (the answer trie's device arrays: Task.constraint_trie_on) it takes the
-        node form of the label-smoothed criterion (ops.trie_label_smoothed_cross_entropy), with or without a pack plan; optional
-        "constraint_nodes_packed" as "target_packed"."""
+        """samples: one dict per (task, micro-batch): {"slots": [...], "target": LongTensor[B,Tt], optional "task", "pack"} and the keys
+        that choose its criterion (criterion.py has the table): "constraint_masks"; "reward" (fp32, one value per row of `target`: SCST,
+        optional "constraint_range": "start,end" and "sentence_avg": True); "constraint_nodes" (int32 [B, Tt], -1 where no closed set
+        applies) with "constraint_trie" (Task.constraint_trie_on; optional "constraint_nodes_packed" as "target_packed"); "encoder_target"
+        with "ctc_range".  criterion.route names each micro-batch's criterion, or refuses the dict, before anything runs."""
+        routes = [criterion.route(s, self.criterion) for s in samples]
         done = False
         structure = None
         if (self.use_graph and not eager) or self.world > 1:
@@ -775,7 +642,7 @@ class TrainStep:
                 rng_state = ops._Rng.offset
                 try:
                     torch.cuda.synchronize()
-                    cap = self._capture(samples, structure, mode)
+                    cap = self._capture(samples, routes, structure, mode)
                 except Exception as e:              # anything uncapturable (a custom adaptor, a collective): eager from now on
                     warnings.warn(f"ofasys_amd.TrainStep: hipGraph capture ({mode}) failed ({type(e).__name__}: {e}); a failed "
                                   "capture cannot be retried in this process -- running eagerly")
@@ -790,12 +657,12 @@ class TrainStep:
             else:
                 entry["seen"] += 1
         if not done:
-            self._fwd_bwd(samples, overlap_reduce=True, structure=structure)
+            self._fwd_bwd(samples, routes, overlap_reduce=True, structure=structure)
             self._reduce()
             self._update()
         self.num_updates += 1
         self.last = {"stats": self._stats, "gnorm": self._gnorm, "skipped": self._sched[3:5]}
-        if any(self._speech_to_text(s) for s in samples):
+        if "speech_to_text" in routes:
             self.last["ctc_loss"] = self._ctc_stat          # (the step's summed CTC term; other steps report what they always did)
         if self.loss_scale_cfg is not None:
             self.last["loss_scale"] = self._ls[0:1]
@@ -830,38 +697,18 @@ class TrainStep:
             ops._Rng.offset = rng
             model.train(was_training)
 
-    def _valid_forward(self, samples, model):
-        """The micro-batches through `model` (see _valid_mode) and through ops.criterion_eval (the engine's label_smoothing /
-        constraint_range; no drop_worst: the reference's eval call never drops) into the accumulator.  Nothing here reads or writes
-        the gradient arena, the step statistics, the optimizer or EMA state or the device counters.
-        A speech-to-text micro-batch (speech_to_text_loss.py:259-322) evaluates the decoder side if ce_weight > 0 and, if ctc_weight
-        > 0, adds its CTC loss to `_valid_ctc` and decodes greedily on the device.  -> [(tokens, lengths, encoder_target, ds)] of
-        those micro-batches: the caller keeps copies until the pass ends."""
+    def _valid_forward(self, samples, routes, model):
+        """The micro-batches through `model` (see _valid_mode) and through criterion.evaluate into the accumulator (and `_valid_ctc`).
+        Nothing here reads or writes the gradient arena, the step statistics, the optimizer or EMA state or the device counters.
+        -> [(tokens, lengths, encoder_target, ds)], the greedy CTC decodes of the speech-to-text micro-batches: the caller keeps
+        copies until the pass ends."""
         outs = []
         with self._valid_mode(model):
-            for s in samples:
-                if self._speech_to_text(s):
-                    ds, de = (int(v) for v in s["ctc_range"].split(","))
-                    logits, target, cm, _, plan, enc = self._criterion_inputs(model, s, encoder_out=True)
-                    if float(s.get("ce_weight", 1.0)) > 0:
-                        ops.criterion_eval(logits, target, self.pad, self.label_smoothing, self.constraint_range, cm, None, None,
-                                           acc=self._valid_acc)
-                    if float(s.get("ctc_weight", 0.0)) > 0:
-                        x, lay = self._ctc_logits(model, ds, de, plan, enc)
-                        ops.ctc_loss(x, lay, s["encoder_target"], ds, self.pad, model.global_dict.eos(),
-                                     bool(s.get("zero_infinity", False)), stat=self._valid_ctc)
-                        toks, n = ops.ctc_greedy_decode(x, lay)
-                        outs.append((toks, n, s["encoder_target"], ds))
-                    continue
-                if self._edge_head(s):
-                    feats, target, _, nodes, _ = self._criterion_inputs(model, s, features=True)
-                    weight, bias = self.output_projection(model)
-                    ops.trie_head_eval(feats, weight, bias, target, nodes, s["constraint_trie"], self.pad, self.label_smoothing,
-                                       self.constraint_range, acc=self._valid_acc)
-                    continue
-                logits, target, cm, nodes, _ = self._criterion_inputs(model, s)
-                ops.criterion_eval(logits, target, self.pad, self.label_smoothing, self.constraint_range, cm, nodes,
-                                   s["constraint_trie"] if nodes is not None else None, acc=self._valid_acc)
+            for s, kind in zip(samples, routes):
+                x = criterion.forward(model, s, kind, self.criterion)
+                decode = criterion.evaluate(model, s, kind, x, self.criterion, self._valid_acc, self._valid_ctc)
+                if decode is not None:
+                    outs.append(decode)
         return outs
 
     def _keep_decodes(self, outs):
@@ -871,7 +718,7 @@ class TrainStep:
     def captured_valid_graphs(self):
         return sum(1 for e in self._valid_graphs.values() if "graphs" in e)
 
-    def _capture_valid(self, samples, model):
+    def _capture_valid(self, samples, routes, model):
         import gc
         gc.collect()
         if self._pool is None:
@@ -881,7 +728,7 @@ class TrainStep:
             g = torch.cuda.CUDAGraph()
             _KEEP_ALIVE.append(g)
             with torch.cuda.graph(g, pool=self._pool, capture_error_mode=_CAPTURE_MODE):
-                entry["decodes"] = self._valid_forward(samples, model)
+                entry["decodes"] = self._valid_forward(samples, routes, model)
             entry["graphs"] = [g]
         entry["audit"] = audit
         entry["pins"] = audit.tensors()
@@ -901,10 +748,7 @@ class TrainStep:
         model (`self.ema.get_model()`).  With use_graph, one forward-only hipGraph per (batch structure, use_ema) is captured after
         `graph_warmup` eager visits -- its own table and its own cap of `max_graphs`, the engine's memory pool -- and replayed.
         Nothing is returned and nothing synchronises: `valid_result()` reads the pass."""
-        for s in samples:
-            if s.get("reward") is not None:
-                raise NotImplementedError("an SCST micro-batch (reward) cannot be validated by the criterion: the reference validates "
-                                          "such tasks by generating (engine/criterion/scst_loss.py)")
+        routes = [criterion.route(s, self.criterion, training=False) for s in samples]
         if use_ema:
             if self.ema is None:
                 raise RuntimeError("valid_step(use_ema=True) needs an EMA of the weights: build the engine with ema={'store_ema': True}")
@@ -935,7 +779,7 @@ class TrainStep:
                 else:
                     try:
                         torch.cuda.synchronize()
-                        cap = self._capture_valid(samples, model)
+                        cap = self._capture_valid(samples, routes, model)
                     except Exception as e:
                         warnings.warn(f"ofasys_amd.TrainStep: hipGraph capture (validation) failed ({type(e).__name__}: {e}); a failed "
                                       "capture cannot be retried in this process -- running eagerly")
@@ -947,7 +791,7 @@ class TrainStep:
                         return
             else:
                 entry["seen"] += 1
-        self._keep_decodes(self._valid_forward(samples, model))
+        self._keep_decodes(self._valid_forward(samples, routes, model))
 
     def valid_result(self):
         """The pass since valid_begin(): ONE synchronisation (and, data parallel, one all-reduce of the accumulator) ->

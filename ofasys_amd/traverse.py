@@ -15,6 +15,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
+from . import criterion
 from . import kernels as K
 from .preprocessor import ModalityType, Slot
 from .task import Task
@@ -229,16 +230,7 @@ class TraverseTask(Task):
                               "scores": torch.empty(bsz, self.plan.C, dtype=torch.float32, device=device)}
         return self._buf[key]
 
-    @staticmethod
-    def output_projection(model):
-        """(weight [V, D], bias or None) of the decoder's text output projection: the tied token embedding, or the adaptor's own
-        Linear (adaptor/text.py:72)."""
-        ga = model.decoder.adaptor
-        text = ga.name2adaptor["text"]
-        if text.share_input_output_embed:
-            return ga.embed_tokens.weight, None
-        proj = text.output_projection
-        return proj.weight, getattr(proj, "bias", None)
+    output_projection = staticmethod(criterion.output_projection)
 
     # ------------------------------------------------------------------ scoring (traverse_task.py:63-110)
     @torch.no_grad()
