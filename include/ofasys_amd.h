@@ -949,6 +949,35 @@ int ofa_ctc_grad(const void* logits, int64_t ld, int64_t rows, int64_t C, const 
 int ofa_ctc_greedy_decode(const int32_t* row_argmax, int64_t rows, const int32_t* seg, int64_t seg_ld, int64_t row_stride, int64_t B,
                           int64_t Tmax, int32_t* out, int32_t* out_len, void* stream);
 
+/* ---- text-to-speech (adaptor/audio.py:327-336, 468-477, 721-763; engine/criterion/tacotron2_loss.py:169-198), csrc/conv1d.hip and
+ * csrc/tacotron_loss.hip.
+ * Conv1d over time on batch-major channels-last rows: x [B*T, C] -> col [B*T, Kpad], taps ordered (k, c), odd k, padding (k-1)/2,
+ * Kpad a multiple of 8 and >= k*C (like ofa_im2col).  A tap outside its own sample's T rows is zero (never the neighbouring sample's
+ * row); the columns k*C .. Kpad-1 are zero.  ofa_fold1d is the adjoint as a gather: every dx element is the fp32 sum of its <= k taps
+ * in ascending tap order, rounded once.  16-byte accesses when C is a whole number of vectors and the buffers are aligned, else one
+ * element per access.  An even k: OFA_ERR_UNSUPPORTED.  B == 0: nothing. */
+int ofa_unfold1d(const void* x, void* col, int64_t B, int T, int C, int k, int Kpad, int dtype, void* stream);
+int ofa_fold1d(const void* dcol, void* dx, int64_t B, int T, int C, int k, int Kpad, int dtype, void* stream);
+/* y = dropout_p(tanh(x)), tanh in fp32; the mask is ofa_dropout_add_fwd's (Philox position offset + *offset_base, element e: halfword
+ * e % 8 of counter e / 8).  Backward reads dy and y alone: dx = dy * keep / (1-p) * (1 - t^2), t = y (1-p).  p == 0: exact tanh. */
+int ofa_tanh_dropout_fwd(const void* x, void* y, int64_t n, float p, uint64_t seed, uint64_t offset, const int64_t* offset_base,
+                         int dtype, void* stream);
+int ofa_tanh_dropout_bwd(const void* dy, const void* y, void* dx, int64_t n, float p, uint64_t seed, uint64_t offset,
+                         const int64_t* offset_base, int dtype, void* stream);
+/* The Tacotron2 criterion over feat_out, post, target [B, T, F] and eos_out [B, T] (contiguous, one dtype); frame (b, t) is valid iff
+ * t < lengths[b] (int64, device), N = the number of valid frames:
+ *   l1 = sum |feat - tgt| + sum |post - tgt|, mse = the same with squares, eos = sum bce_with_logits(eos_t, [t == len - 1], pos_weight);
+ *   OFA_REDUCE_MEAN divides l1 and mse by N F and eos by N, OFA_REDUCE_SUM does not;  out (fp32 [4]) = (l1 + mse + eos, l1, mse, eos).
+ * grad != 0: dfeat, dpost [B, T, F] and deos [B, T] of `dtype` = seed[0] (a device scalar; NULL: 1) times the gradient of out[0];
+ * padded frames exactly 0, d|d| at d == 0 is 0.  grad == 0 writes the scalars alone (validation).
+ * partial: fp64 [3 * ofa_tacotron2_loss_blocks(B*T, F)], folded in a fixed order by a second one-workgroup launch: equal inputs give
+ * equal bits.  Refused before any launch: F <= 0 and an unknown reduction (OFA_ERR_INVALID), target_dtype != dtype (OFA_ERR_UNSUPPORTED). */
+enum { OFA_REDUCE_MEAN = 0, OFA_REDUCE_SUM = 1 };
+int64_t ofa_tacotron2_loss_blocks(int64_t rows, int F);                  /* host only */
+int ofa_tacotron2_loss(const void* feat_out, const void* post, const void* target, const void* eos_out, const int64_t* lengths,
+                       int B, int T, int F, float bce_pos_weight, int reduction, const float* seed, double* partial,
+                       float* out, void* dfeat, void* dpost, void* deos, int grad, int dtype, int target_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

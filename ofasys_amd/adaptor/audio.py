@@ -2,9 +2,13 @@
 fbank [B,T,80] -> Conv2d(1,D,3,2)+ReLU -> Conv2d(D,D,3,2)+ReLU -> Linear(D*19, D); learned positions; padding mask from
 the subsampled lengths; 1-D log-bucket relative-position bias (bucket table [4096,4096], 2*max_position-1 rows).
 
+The target branch (text-to-speech training, :327-336, 468-477, 721-763): fbank frames -> prenet (Linear + ReLU + dropout that draws in
+eval mode too) -> Linear(embed_dim) on the way in; on the way out feat_proj / eos_proj and post = feat_out + postnet(feat_out), the
+postnet (Conv1d + BatchNorm1d + tanh + dropout) on channels-last rows over the padded layout (ops.conv1d_bn, ops.tanh_dropout).
+
 The whole parameter set of the reference adaptor is mirrored (decoder prenet / postnet / feat_proj / eos_proj / mask_emb)
-so checkpoints interchange; the target-side branch (fbank generation, TTS) is outside the train-step hot path and raises
-NotImplementedError, as does is_transformer_layers (a branch the reference itself cannot construct).  The time / channel mask
+so checkpoints interchange; is_transformer_layers (a branch the reference itself cannot construct) raises NotImplementedError; the
+autoregressive speech generator is out of scope.  The time / channel mask
 DRAWS (get_mask_indices, :401-450) belong to the speech-pretraining criterion, which hands them over in the slot value."""
 from dataclasses import dataclass, field
 
@@ -82,6 +86,13 @@ class Prenet(nn.Module):                                                       #
             nn.Sequential(nn.Linear(in_dim if i == 0 else n_units, n_units), nn.ReLU()) for i in range(n_layers))
         self.dropout = dropout
 
+    def forward(self, x):
+        for layer in self.layers:
+            lin = layer[0]
+            # F.dropout(layer(x), p=self.dropout) with the default training=True (:731, "always applies dropout"): eval mode draws too
+            x = ops.dropout_add(ops.relu(ops.linear(x, lin.weight, lin.bias)), None, self.dropout, True)
+        return x
+
 
 class Postnet(nn.Module):                                                      # adaptor/audio.py:735-763 (decoder side)
     def __init__(self, in_dim, n_channels, kernel_size, n_layers, dropout):
@@ -95,6 +106,21 @@ class Postnet(nn.Module):                                                      #
                           + ([nn.Tanh()] if i < n_layers - 1 else []) + [nn.Dropout(dropout)])
             nn.init.xavier_uniform_(cur_layers[0].weight, torch.nn.init.calculate_gain("tanh" if i < n_layers - 1 else "linear"))
             self.convolutions.append(nn.Sequential(*cur_layers))
+
+    def forward(self, x, residual=None):
+        """x [B, T, C] -> [B, T, C] (+ residual, added in the last layer's dropout kernel).  The layers run on batch-major channels-last
+        rows [B*T, C] over the PADDED layout: like the reference, padded frames are convolved and counted in the batch statistics
+        (they reach valid frames through the window and through the statistics).  Per layer: ops.conv1d_bn (time-unfold, MFMA GEMM
+        with the column-statistics epilogue, BatchNorm), then tanh + dropout in one row kernel, or the last layer's dropout."""
+        B, T, C = x.shape
+        h = x.contiguous().view(B * T, C)
+        last = len(self.convolutions) - 1
+        for i, seq in enumerate(self.convolutions):
+            h = ops.conv1d_bn(h, seq[0], seq[1], B, T)
+            if i < last:
+                h = ops.tanh_dropout(h, seq[-1].p, self.training)
+        p = self.convolutions[last][-1].p if last >= 0 else 0.0
+        return ops.dropout_add(h.view(B, T, -1), residual, p, self.training)
 
 
 @register_config("ofasys.adaptor", "audio_fbank", AudioFbankAdaptorConfig)
@@ -141,10 +167,21 @@ class AudioFbankAdaptor(BaseAdaptor):
 
     def forward(self, slot: Slot, **kwargs) -> AdaptorOutput:
         assert slot.modality == ModalityType.AUDIO
-        if not slot.is_src:
-            raise NotImplementedError("target-side fbank slots (speech generation) are outside the train-step hot path")
         fbank = slot.value["fbank"]
         fbank_lengths = slot.value["fbank_lengths"]
+        if not slot.is_src:                                                    # adaptor/audio.py:327-336: the decoder's input frames
+            if fbank.dim() != 3 or fbank.shape[-1] != self.out_dim:
+                raise ValueError(f"audio_fbank: target frames {tuple(fbank.shape)} are not [B, T, {self.out_dim}] "
+                                 "(output_frame_dim * n_frames_per_step)")
+            pre, proj = self.prenet[0], self.prenet[1]
+            feature = ops.linear(pre(fbank), proj.weight, proj.bias)
+            T = feature.shape[1]
+            if T > self.embed_audio_positions.weight.shape[0]:
+                raise ValueError(f"audio_fbank: {T} target frames exceed the {self.embed_audio_positions.weight.shape[0]} audio positions")
+            pos = torch.arange(T, device=feature.device)[None, :]
+            padding_mask = pos >= fbank_lengths.to(feature.device)[:, None]    # lengths_to_padding_mask, on the device, no sync
+            pos_embed = self.embed_audio_positions(pos).expand(feature.shape[0], -1, -1)
+            return AdaptorOutput(feature, padding_mask, pos_embed, [])
         mask_indices = slot.value.get("mask_indices", None)
         feature, feature_length = self.subsample(fbank, fbank_lengths)
         T2 = feature.shape[1]
@@ -170,4 +207,26 @@ class AudioFbankAdaptor(BaseAdaptor):
         return AdaptorOutput(feature, padding_mask, pos_embed, [])
 
     def forward_output(self, x, extra, slot, **kwargs):
-        raise NotImplementedError("fbank output head (feat_proj / eos_proj / postnet) is outside the train-step hot path")
+        """adaptor/audio.py:468-477 -> (post, extra) with extra["eos_out"] [B, T, 1] and extra["feature_out"] (before the postnet).
+        extra["attn"] stays what the decoder gives: the reference transposes the attention map, the fused attention forms none
+        ([None]).  x must be the padded [B, T, D] decoder output: the postnet's window and batch statistics run over padded frames too,
+        so packed rows would change the numbers."""
+        fbank = slot.value["fbank"]
+        if x.dim() != 3 or x.shape[:2] != fbank.shape[:2]:
+            raise NotImplementedError(f"audio_fbank output head: decoder rows {tuple(x.shape)} are not the padded [B, T] = "
+                                      f"{tuple(fbank.shape[:2])} layout of the target frames (a pack plan with an fbank target slot "
+                                      "is not supported: the postnet convolves and normalises padded frames too)")
+        attn = extra.get("attn")
+        if attn and attn[0] is not None:
+            extra["attn"] = [attn[0].transpose(2, 1)]
+        x = x.contiguous()                                                     # batch-major rows: the postnet's time axis is T
+        feat_out = ops.linear(x, self.feat_proj.weight, self.feat_proj.bias)
+        # eos_proj has ONE output row: the projection runs 8 wide on zero-padded copies of its weight and bias (8 * D + 8 elements per
+        # step), so that the output rows, the bias gradient's column sum and the weight-gradient GEMM keep whole 16-byte vectors
+        w8 = torch.nn.functional.pad(self.eos_proj.weight, (0, 0, 0, 7))
+        b8 = torch.nn.functional.pad(self.eos_proj.bias, (0, 7))
+        eos_out = ops.linear(x, w8, b8)[..., :1]
+        post = self.postnet(feat_out, residual=feat_out)
+        extra["eos_out"] = eos_out
+        extra["feature_out"] = feat_out
+        return post, extra

@@ -14,6 +14,12 @@ messages and precedence are what they were.
     label_smoothed   constraint_masks, or any of label_smoothing /           label_smoothed_cross_entropy   criterion_eval
                      constraint_range / drop_worst_ratio set
     plain            none of these                                           cross_entropy_sum              criterion_eval
+
+A text-to-speech micro-batch -- "target_lengths" next to a floating-point "target" [B, T, F] of fbank frames -- takes the one route outside
+that table, "tacotron2" (EXTRA_ROUTES): the model returns (post, extra) and ops.tacotron2_loss applies the reference's ofa_tacotron2
+criterion (engine/criterion/tacotron2_loss.py) with reduction "mean"; validation is the same kernel without the gradient.  It carries
+none of the token criteria's keys and no pack plan (the postnet runs over the padded layout), and the reference criterion's guided
+attention loss and its own CTC term are refused.
 """
 from typing import NamedTuple, Optional, Tuple
 
@@ -22,6 +28,7 @@ import torch
 from . import ops
 
 ROUTES = ("speech_to_text", "trie_head", "trie_nodes", "scst", "label_smoothed", "plain")
+EXTRA_ROUTES = ("tacotron2",)           # routes whose target is not a token sequence: keyed by "target_lengths", never reached without it
 
 
 class Settings(NamedTuple):
@@ -42,6 +49,7 @@ class Inputs(NamedTuple):
     nodes: Optional[torch.Tensor]
     plan: object
     encoder_out: Optional[dict]         # (speech_to_text alone)
+    extra: Optional[dict] = None        # (tacotron2 alone: the output head's eos_out / feature_out; `logits` holds the postnet's frames)
 
 
 def output_projection(model):
@@ -60,6 +68,21 @@ def route(s, settings, training=True):
     A malformed node micro-batch under `edge_head` is no head batch: it meets the dense path's refusal."""
     def has(k):
         return s.get(k) is not None
+    if has("target_lengths"):
+        for k in ("reward", "constraint_nodes", "constraint_masks", "encoder_target"):
+            if has(k):
+                raise NotImplementedError(f"a text-to-speech micro-batch (target_lengths) cannot carry {k}: its criterion is "
+                                          "ofa_tacotron2 on fbank frames (engine/criterion/tacotron2_loss.py), not a token criterion")
+        if has("pack"):
+            raise NotImplementedError("a text-to-speech micro-batch (target_lengths) cannot carry a pack plan: the postnet convolves and "
+                                      "normalises padded frames too, a packed layout would change the numbers")
+        if s.get("use_guided_attention_loss"):
+            raise NotImplementedError("use_guided_attention_loss is not supported: the fused attention forms no [B, A, Tt, Ts] weights "
+                                      "for the guided attention loss to read")
+        if float(s.get("ctc_weight", 0.0) or 0.0) > 0:
+            raise NotImplementedError("ofa_tacotron2 with its own ctc_weight > 0 is not supported (tacotron2_loss.py:135-152); "
+                                      "CTC training is the speech_to_text_loss criterion's")
+        return "tacotron2"
     if not training and has("reward"):
         raise NotImplementedError("an SCST micro-batch (reward) cannot be validated by the criterion: the reference validates "
                                   "such tasks by generating (engine/criterion/scst_loss.py)")
@@ -96,6 +119,9 @@ def route(s, settings, training=True):
 
 def forward(model, s, kind, settings):
     """One micro-batch through `model` -> Inputs.  The train step and the validation step share it."""
+    if kind == "tacotron2":                      # (no pack plan: route refused one) -> the frames after the postnet, and the head's extras
+        post, extra = model(s["slots"])
+        return Inputs(post, s["target"], None, None, None, None, extra)
     plan = s.get("pack")
     kw = {"features_only": True} if kind == "trie_head" else {"return_encoder_out": True} if kind == "speech_to_text" else {}
     if plan is not None:                         # ragged batch (packing.py): logits and targets by packed decoder row
@@ -140,12 +166,28 @@ def _ctc(model, s, x, settings, stat):
     return loss, y, lay, ds
 
 
-def train_loss(model, s, kind, x, cfg, seed=None, stats=None, ctc_stat=None):
+def _tacotron_size(s):
+    """sample_size of a text-to-speech micro-batch on the device (tacotron2_loss.py:155): nsentences under sentence_avg, else ntokens =
+    the sum of the target lengths -> (ntokens, sample_size or None: ntokens)."""
+    n = s["target_lengths"].sum()
+    return n, (s["target"].shape[0] if s.get("sentence_avg") else None)
+
+
+def train_loss(model, s, kind, x, cfg, seed=None, stats=None, ctc_stat=None, tts_stat=None):
     """The routed criterion on x = forward(...) -> (loss, ntokens, sample_size or None: ntokens).  ntokens is None on the plain route:
     its statistics are the caller's (with `stats`, an ops.StepStats, the criterion kernel may have added them: stats.done).
     seed: the tensor the caller will hand to loss.backward (ops._SeededGrad), None when it is not known yet (loss scaling); the routes
     whose forward can write the logits' gradient take it."""
     size = None
+    if kind == "tacotron2":
+        # l1 + mse + eos under reduction "mean" (what task.train_step -> criterion(model, sample, update_num=) uses), loss and the three
+        # gradients in one launch; the terms are added to `tts_stat` (fp64 [3]: l1, mse, eos) on the device
+        loss, terms = ops.tacotron2_loss(x.extra["feature_out"], x.logits, x.extra["eos_out"], x.target, s["target_lengths"],
+                                         float(s.get("bce_pos_weight", 1.0)), "mean", seed=seed)
+        if tts_stat is not None:
+            tts_stat += terms
+        n, size = _tacotron_size(s)
+        return loss, n, size
     if kind == "speech_to_text":
         # ce_weight * (the label-smoothed loss on the decoder) + ctc_weight * CTC(encoder output . embed_tokens[ds:de]^T), one backward on
         # the weighted sum (engine/criterion/speech_to_text_loss.py).  A weight of 0 launches nothing of its side's criterion.  The CE
@@ -194,11 +236,22 @@ def train_loss(model, s, kind, x, cfg, seed=None, stats=None, ctc_stat=None):
     return loss, n, size
 
 
-def evaluate(model, s, kind, x, cfg, acc, ctc_stat=None):
+def evaluate(model, s, kind, x, cfg, acc, ctc_stat=None, tts_acc=None):
     """The routed criterion in eval mode on x = forward(...): adds [ntokens, loss_sum, nll_sum, n_correct] to `acc` (label_smoothing /
     constraint_range; no drop_worst: the reference's eval call never drops).  A speech-to-text micro-batch
     (speech_to_text_loss.py:259-322) evaluates the decoder side if ce_weight > 0 and, if ctc_weight > 0, adds its CTC loss to
-    `ctc_stat` and decodes greedily on the device -> (tokens, lengths, encoder_target, ds); every other call returns None."""
+    `ctc_stat` and decodes greedily on the device -> (tokens, lengths, encoder_target, ds); every other call returns None.
+    A text-to-speech micro-batch adds [sample_size, sample_size * (loss, l1, mse, eos), ntokens] to `tts_acc` (fp64 [6]): the
+    reference's reduce_metrics weighs a batch's values by its sample_size (tacotron2_loss.py:201-214)."""
+    if kind == "tacotron2":
+        out = ops.tacotron2_eval(x.extra["feature_out"], x.logits, x.extra["eos_out"], x.target, s["target_lengths"],
+                                 float(s.get("bce_pos_weight", 1.0)), "mean")
+        n, size = _tacotron_size(s)
+        w = n.double() if size is None else torch.full((), float(size), dtype=torch.float64, device=out.device)
+        tts_acc[0:1] += w
+        tts_acc[1:5] += out.double() * w
+        tts_acc[5:6] += n
+        return
     if kind == "speech_to_text":
         decode = None
         if float(s.get("ce_weight", 1.0)) > 0:

@@ -264,6 +264,14 @@ class Trainer:
             mb["ctc_range"] = f'{d.index("<phone>_dict_begin")},{d.index("<phone>_dict_end")}'
             mb["ce_weight"], mb["ctc_weight"] = float(c.ce_weight), float(c.ctc_weight)
             mb["zero_infinity"], mb["sentence_avg"] = bool(c.zero_infinity), bool(c.sentence_avg)
+        elif c.name == "ofa_tacotron2":                   # text-to-speech: fbank frames as the target (criterion.py, route "tacotron2")
+            if s.get("target_lengths") is None:
+                raise ValueError(f"task {task.name}: criterion ofa_tacotron2 needs an [AUDIO:fbank] target slot (the collated sample "
+                                 "carries no target_lengths)")
+            mb["target_lengths"] = s["target_lengths"]
+            mb["bce_pos_weight"], mb["sentence_avg"] = float(c.bce_pos_weight), bool(c.sentence_avg)
+            # (refused by criterion.route before the model runs: the guided attention loss and the criterion's own CTC term)
+            mb["use_guided_attention_loss"], mb["ctc_weight"] = bool(c.use_guided_attention_loss), float(c.ctc_weight)
         return mb
 
     # ------------------------------------------------------------------ validation

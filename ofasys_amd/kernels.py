@@ -1966,3 +1966,75 @@ def ctc_greedy_decode(row_argmax, seg, row_stride, tmax):
     lib().call("ofa_ctc_greedy_decode", ptr(row_argmax), row_argmax.numel(), ptr(seg), seg_ld, int(row_stride), B, int(tmax), ptr(out), ptr(n),
                stream())
     return out, n
+
+
+# ------------------------------------------------------------------ text-to-speech: csrc/conv1d.hip, csrc/tacotron_loss.hip
+def unfold1d(x, B, T, C, k):
+    """x: batch-major channels-last rows [B*T, C] -> col [B*T, Kpad], taps ordered (k, c), padding (k-1)/2 inside every sample."""
+    x = x.contiguous()
+    if x.numel() != B * T * C:
+        raise OfaError(f"unfold1d: {tuple(x.shape)} is not [B*T, C] = [{B}*{T}, {C}]")
+    Kpad = (k * C + 7) // 8 * 8
+    col = torch.empty(B * T, Kpad, dtype=x.dtype, device=x.device)
+    lib().call("ofa_unfold1d", ptr(x), ptr(col), B, T, C, k, Kpad, dtype_code(x), stream())
+    return col
+
+
+def fold1d(dcol, B, T, C, k):
+    """The adjoint of unfold1d: dcol [B*T, Kpad] -> dx [B*T, C], every element the fp32 sum of its <= k taps in tap order."""
+    dcol = dcol.contiguous()
+    if dcol.dim() != 2 or dcol.shape[0] != B * T or dcol.shape[1] < k * C or dcol.shape[1] % 8:
+        raise OfaError(f"fold1d: {tuple(dcol.shape)} is not [B*T, Kpad] for B={B} T={T} C={C} k={k}")
+    dx = torch.empty(B * T, C, dtype=dcol.dtype, device=dcol.device)
+    lib().call("ofa_fold1d", ptr(dcol), ptr(dx), B, T, C, k, dcol.shape[1], dtype_code(dcol), stream())
+    return dx
+
+
+def tanh_dropout_fwd(x, p, seed, offset, offset_base=None):
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    lib().call("ofa_tanh_dropout_fwd", ptr(x), ptr(y), x.numel(), float(p), seed, offset, ptr(offset_base), dtype_code(x), stream())
+    return y
+
+
+def tanh_dropout_bwd(dy, y, p, seed, offset, offset_base=None):
+    dy, y = dy.contiguous(), y.contiguous()
+    if dy.shape != y.shape or dy.dtype != y.dtype:
+        raise OfaError("tanh_dropout_bwd: dy and y differ in shape or dtype")
+    dx = torch.empty_like(y)
+    lib().call("ofa_tanh_dropout_bwd", ptr(dy), ptr(y), ptr(dx), y.numel(), float(p), seed, offset, ptr(offset_base), dtype_code(y),
+               stream())
+    return dx
+
+
+TACOTRON_REDUCTIONS = {"mean": 0, "sum": 1}
+
+
+def tacotron2_loss(feat_out, post, target, eos_out, lengths, bce_pos_weight, reduction, seed=None, grad=False, grads=None):
+    """-> (out fp32 [4] = (loss, l1, mse, eos), (dfeat, dpost, deos) or None).  feat_out, post, target [B, T, F] and eos_out [B, T] (or
+    [B, T, 1]) of one dtype, lengths int64 [B] on the device; seed: fp32 device scalar or None (1); grads: buffers to write into."""
+    if reduction not in TACOTRON_REDUCTIONS:
+        raise OfaError(f"tacotron2_loss: unknown reduction {reduction!r} (mean | sum)")
+    if feat_out.dim() != 3 or post.shape != feat_out.shape or target.shape != feat_out.shape:
+        raise OfaError(f"tacotron2_loss: feat_out {tuple(feat_out.shape)}, post {tuple(post.shape)} and target {tuple(target.shape)} "
+                       "must be one [B, T, F]")
+    B, T, F = feat_out.shape
+    if eos_out.numel() != B * T:
+        raise OfaError(f"tacotron2_loss: eos_out {tuple(eos_out.shape)} is not [B, T] = [{B}, {T}]")
+    if post.dtype != feat_out.dtype or eos_out.dtype != feat_out.dtype:
+        raise OfaError("tacotron2_loss: feat_out, post and eos_out must share one dtype")
+    if lengths.dtype != torch.int64 or lengths.numel() != B:
+        raise OfaError("tacotron2_loss: lengths must be int64 [B]")
+    feat_out, post, target, eos_out, lengths = (t.contiguous() for t in (feat_out, post, target, eos_out, lengths))
+    dev = feat_out.device
+    nblocks = lib().cdll.ofa_tacotron2_loss_blocks(B * T, F)
+    partial = torch.empty(max(nblocks, 1) * 3, dtype=torch.float64, device=dev)
+    out = torch.empty(4, dtype=torch.float32, device=dev)
+    d = None
+    if grad:
+        d = grads if grads is not None else (torch.empty_like(feat_out), torch.empty_like(post), torch.empty_like(eos_out))
+    lib().call("ofa_tacotron2_loss", ptr(feat_out), ptr(post), ptr(target), ptr(eos_out), ptr(lengths), B, T, F, float(bce_pos_weight),
+               TACOTRON_REDUCTIONS[reduction], ptr(seed), ptr(partial), ptr(out), ptr(d[0]) if grad else None,
+               ptr(d[1]) if grad else None, ptr(d[2]) if grad else None, int(bool(grad)), dtype_code(feat_out), dtype_code(target),
+               stream())
+    return out, d

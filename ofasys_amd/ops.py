@@ -2882,3 +2882,141 @@ class ReluFn(torch.autograd.Function):
 def relu(x):
     x2d, restore = rows_view(x)
     return restore(ReluFn.apply(x2d))
+
+
+# ---------------------------------------------------------------------------------------------- text-to-speech (csrc/conv1d.hip, tacotron_loss.hip)
+class Conv1dFn(torch.autograd.Function):
+    """nn.Conv1d(odd k, padding (k-1)/2) over time on batch-major channels-last rows [B*T, Cin]: time-unfold + MFMA GEMM
+    (adaptor/audio.py:743-748).  weight keeps torch's [Cout, Cin, k] layout (state dict); the GEMM reads a (k, c)-ordered copy made
+    here per call (Cout * k * Cin elements read and written: 0.4 M for the widest postnet layer, against rows * k * Cin of the unfold)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, geom, want_stats=False):
+        """-> (y [B*T, Cout], stats): as Conv2dFn.forward."""
+        B, T = geom
+        Cout, Cin, k = weight.shape
+        if k % 2 == 0:
+            raise OfaError(f"conv1d: kernel size {k} is even (the length-keeping padding (k-1)/2 needs an odd one)")
+        if x.dim() != 2 or x.shape[0] != B * T or x.shape[1] != Cin:
+            raise OfaError(f"conv1d: rows {tuple(x.shape)} are not [B*T, Cin] = [{B}*{T}, {Cin}]")
+        col = K.unfold1d(x, B, T, Cin, k)
+        w2 = weight.permute(0, 2, 1).reshape(Cout, k * Cin)
+        if col.shape[1] != w2.shape[1]:
+            w2 = torch.nn.functional.pad(w2, (0, col.shape[1] - w2.shape[1]))
+        w2 = w2.contiguous()
+        stats = None
+        if want_stats:
+            y, stats = K.gemm_colstat(col, w2, bias=bias)
+        else:
+            y = K.gemm(col, w2, False, True, bias=bias)
+        if stats is None:
+            stats = torch.empty(0, dtype=torch.float64, device=y.device)
+        ctx.mark_non_differentiable(stats)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(col, w2)
+        ctx.geom = (B, T, Cin, k)
+        ctx.has_bias, ctx.wdtype = bias is not None, weight.dtype
+        return y, stats
+
+    @staticmethod
+    def backward(ctx, dy, _dstats=None):
+        if dy is None:
+            return None, None, None, None, None
+        col, w2 = ctx.saved_tensors
+        B, T, Cin, k = ctx.geom
+        Cout = w2.shape[0]
+        dy = dy.contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = K.fold1d(K.gemm(dy, w2, False, False), B, T, Cin, k)
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dw2 = K.gemm(dy, col, True, False)                                    # [Cout, Kpad]
+            dw = dw2[:, :k * Cin].reshape(Cout, k, Cin).permute(0, 2, 1)
+        db = K.colsum(dy, out_dtype=ctx.wdtype) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        return dx, dw, db, None, None
+
+
+def conv1d_bn(x, conv, bn, B, T):
+    """BatchNorm1d(Conv1d(x)) on batch-major channels-last rows [B*T, Cin] -> [B*T, Cout]: a layer of the Tacotron postnet up to its
+    tail (adaptor/audio.py:743-749), over the PADDED layout -- the reference convolves and normalises padded frames too.  In training
+    the GEMM's epilogue leaves the column statistics (conv_bn); eval mode uses the running statistics."""
+    weight = conv.weight
+    if conv.stride[0] != 1 or conv.dilation[0] != 1 or conv.groups != 1 or conv.padding[0] != (weight.shape[2] - 1) // 2:
+        raise OfaError("conv1d_bn: only stride 1, dilation 1, groups 1 and padding (k-1)/2")
+    training = bn.training or bn.running_mean is None
+    want = (_ConvBn.epilogue_stats and training and x.is_cuda and weight.dtype in (torch.bfloat16, torch.float16)
+            and _bn_sync_group(bn) is None)
+    y, stats = Conv1dFn.apply(x, weight, conv.bias, (B, T), want)
+    return batch_norm(y, bn, stats=stats if stats.numel() else None)
+
+
+class TanhDropoutFn(torch.autograd.Function):
+    """y = dropout_p(tanh(x)) in one pass; the backward reads dy and y and regenerates the mask (nothing but y is kept)."""
+
+    @staticmethod
+    def forward(ctx, x, p):
+        seed, off, base = _Rng.reserve(x.numel(), x.device) if p > 0 else (0, 0, None)
+        ctx.p, ctx.seed, ctx.off, ctx.base = p, seed, off, base
+        y = K.tanh_dropout_fwd(x, p, seed, off, base)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        return K.tanh_dropout_bwd(dy, y, ctx.p, ctx.seed, ctx.off, ctx.base), None
+
+
+def tanh_dropout(x, p, training):
+    """dropout(tanh(x)) (the tail of the postnet's inner layers, adaptor/audio.py:751-752); plain tanh when not training / p == 0."""
+    x2d, restore = rows_view(x)
+    return restore(TanhDropoutFn.apply(x2d, float(p) if training else 0.0))
+
+
+class Tacotron2LossFn(torch.autograd.Function):
+    """engine/criterion/tacotron2_loss.py:169-198 in one launch (csrc/tacotron_loss.hip) -> (loss, terms = [l1, mse, eos]).  With a
+    usable seed (see _SeededGrad) the forward's one pass writes the three gradients and the backward hands them out; otherwise the
+    backward runs the kernel again at the scale it is given.  A gradient on the terms is not supported."""
+
+    @staticmethod
+    def forward(ctx, feat_out, post, eos_out, target, lengths, pos_weight, reduction, seed=None):
+        need = any(ctx.needs_input_grad[:3])
+        ctx.seeded = _SeededGrad()
+        ctx.cfg = (float(pos_weight), reduction, feat_out.shape, post.shape, eos_out.shape)
+        pre = need and _SeededGrad.usable(seed, feat_out.device)
+        out, d = K.tacotron2_loss(feat_out, post, target, eos_out, lengths, pos_weight, reduction, seed=seed if pre else None, grad=pre)
+        if pre:
+            ctx.seeded = _SeededGrad(seed, d)
+        if need:
+            ctx.save_for_backward(feat_out, post, eos_out, target, lengths)
+        terms = out[1:4]
+        ctx.mark_non_differentiable(terms)
+        return out[0], terms
+
+    @staticmethod
+    def backward(ctx, dloss, _dterms=None):
+        feat_out, post, eos_out, target, lengths = ctx.saved_tensors
+        pos_weight, reduction, s_feat, s_post, s_eos = ctx.cfg
+        d = ctx.seeded.take(dloss)
+        if d is None:
+            _, d = K.tacotron2_loss(feat_out, post, target, eos_out, lengths, pos_weight, reduction,
+                                    seed=dloss.reshape(1).float().contiguous(), grad=True, grads=ctx.seeded.spare())
+        return d[0].view(s_feat), d[1].view(s_post), d[2].view(s_eos), None, None, None, None, None
+
+
+def tacotron2_loss(feat_out, post, eos_out, target, lengths, bce_pos_weight=1.0, reduction="mean", seed=None):
+    """-> (loss fp32 scalar, terms fp32 [3] = (l1_loss, mse_loss, eos_loss)), `compute_loss` of the reference's ofa_tacotron2 criterion:
+    feat_out (before the postnet), post (after), target [B, T, F], eos_out [B, T, 1] or [B, T], lengths int64 [B] on the device."""
+    if reduction not in K.TACOTRON_REDUCTIONS:
+        raise ValueError(f"tacotron2_loss: unknown reduction {reduction!r} (mean | sum)")
+    if target.dtype != feat_out.dtype:
+        target = target.to(feat_out.dtype)
+    return Tacotron2LossFn.apply(feat_out, post, eos_out, target, lengths, float(bce_pos_weight), reduction, seed)
+
+
+def tacotron2_eval(feat_out, post, eos_out, target, lengths, bce_pos_weight=1.0, reduction="mean"):
+    """The validation form: the four scalars (loss, l1, mse, eos) fp32 [4], no gradient and no extra pass."""
+    if target.dtype != feat_out.dtype:
+        target = target.to(feat_out.dtype)
+    return K.tacotron2_loss(feat_out, post, target, eos_out, lengths, bce_pos_weight, reduction)[0]

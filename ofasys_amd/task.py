@@ -22,6 +22,7 @@ import torch
 
 from .preprocessor.collate import (BoxPreprocessConfig, DefaultBoxPreprocess, DefaultTextPreprocess, GeneralPreprocess,
                                    PreprocessConfig, TensorPreprocess, TextPreprocessConfig, default_preprocess)
+from .preprocessor.audio import FbankPreprocess
 from .preprocessor.instruction import Instruction, ModalityType, Slot
 
 # adaptor/general.py:36-46
@@ -55,7 +56,11 @@ class CriterionConfig:                                # engine/criterion/label_s
     # "speech_to_text_loss" (engine/criterion/speech_to_text_loss.py:24-95): ce_weight * the label-smoothed loss on the decoder +
     # ctc_weight * CTC on the encoder output projected onto the '<phone>_dict_begin' .. '<phone>_dict_end' rows of the token embedding
     # (cfg.text.phone_dict registers them); ce_weight, ctc_weight, zero_infinity (and sentence_avg) are its own, the reference's defaults
+    # "ofa_tacotron2" (engine/criterion/tacotron2_loss.py:24-45; a task whose target slot is [AUDIO:fbank]): bce_pos_weight and
+    # sentence_avg are honoured; use_guided_attention_loss = True and its own ctc_weight > 0 are refused before the model runs
     name: str = "label_smoothed_cross_entropy"
+    bce_pos_weight: float = 1.0
+    use_guided_attention_loss: bool = False
     ce_weight: float = 1.0
     ctc_weight: float = 0.0
     zero_infinity: bool = False
@@ -189,7 +194,8 @@ class Task:
         name2pre = {"text": DefaultTextPreprocess(global_dict, self.cfg.text), "box": DefaultBoxPreprocess(global_dict, self.cfg.box)}
         for name, mod in (("image", ModalityType.IMAGE), ("video", ModalityType.VIDEO)):
             name2pre[name] = ImageTensorPreprocess(global_dict, self.cfg.image, mod)
-        name2pre["audio"] = TensorPreprocess(global_dict, PreprocessConfig(), ModalityType.AUDIO)
+        # (source-side and plain tensor values as TensorPreprocess; a target-side fbank slot collates as a text-to-speech target)
+        name2pre["audio"] = FbankPreprocess(global_dict, PreprocessConfig(), ModalityType.AUDIO)
         name2pre["table"] = name2pre["phone"] = name2pre["text"]     # STRUCT / PHONE columns arrive as token ids (text adaptor)
         self.general_preprocess = GeneralPreprocess(global_dict, name2pre)
 

@@ -299,6 +299,7 @@ class TrainStep:
                                             self.closed_set_edge_head)
         self._stats = torch.zeros(3, dtype=torch.float64, device=dev)      # [sample_size, loss_sum, ntokens]
         self._ctc_stat = torch.zeros(1, dtype=torch.float64, device=dev)   # sum of the step's CTC losses (speech-to-text micro-batches)
+        self._tts_stat = torch.zeros(3, dtype=torch.float64, device=dev)   # the step's [l1, mse, eos] terms (text-to-speech micro-batches)
         self._gsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self._gnorm_t = torch.zeros(1, dtype=torch.float32, device=dev)
         # device-resident schedule: _step_t = number of updates done; _lr_t = learning rate; _sched = [grad multiplier,
@@ -363,6 +364,9 @@ class TrainStep:
         # table of forward-only graphs; nothing of the training state above is written by it
         self._valid_acc = torch.zeros(4, dtype=torch.float64, device=dev)
         self._valid_ctc = torch.zeros(1, dtype=torch.float64, device=dev)      # summed CTC loss of the pass (speech-to-text micro-batches)
+        # text-to-speech micro-batches: [sample_size, sample_size * (loss, l1, mse, eos), ntokens] of the pass, and whether it held any
+        self._valid_tts = torch.zeros(6, dtype=torch.float64, device=dev)
+        self._valid_has_tts = False
         self._valid_decodes = []                    # per such micro-batch (greedy tokens, their lengths, encoder_target, ds), on the device
         self._valid_graphs = {}                     # (batch structure, use_ema) -> dict(graphs, static samples, seen count)
         self._warned_valid_cap = False
@@ -397,6 +401,8 @@ class TrainStep:
             # (structure None: eager steps share one list.  The step's statistics and the sum of squares are cleared by the same launch.)
             # (a step without a speech-to-text micro-batch launches exactly what it launched before: its CTC statistic is not touched)
             stt = (self._ctc_stat,) if "speech_to_text" in routes else ()
+            if "tacotron2" in routes:                # (likewise: the text-to-speech terms are cleared only by a step that adds to them)
+                stt += (self._tts_stat,)
             ops.grad_begin(self.fp.grad, self._prezero.get(structure, ()), also=(self._stats, self._gsq) + stt)
             self._gsq_cleared = True
         else:
@@ -405,6 +411,8 @@ class TrainStep:
             self._stats.zero_()
             if "speech_to_text" in routes:
                 self._ctc_stat.zero_()
+            if "tacotron2" in routes:
+                self._tts_stat.zero_()
         self.reducer.overlap = overlap_reduce
         # gradients are only read after backward unless buckets are all-reduced from inside it: fold lazily, in batches
         ops.defer_reductions(self.world == 1 or not overlap_reduce)
@@ -453,7 +461,8 @@ class TrainStep:
         fused = self._ce_stats if (self.fp.flat.is_cuda and not K.tail_old(K.TAIL_CRITERION_STATS)) else None
         for s, kind in zip(samples, routes):
             x = criterion.forward(self.model, s, kind, cfg)
-            loss, n, size = criterion.train_loss(self.model, s, kind, x, cfg, seed=self._loss_seed(), stats=fused, ctc_stat=self._ctc_stat)
+            loss, n, size = criterion.train_loss(self.model, s, kind, x, cfg, seed=self._loss_seed(), stats=fused, ctc_stat=self._ctc_stat,
+                                                      tts_stat=self._tts_stat)
             counted = False
             if n is None:                            # the plain route: its statistics are added before the backward
                 if fused is not None and fused.done:     # (the criterion kernel's last block added them)
@@ -582,7 +591,7 @@ class TrainStep:
         own = list(self.model.parameters()) + list(self.model.buffers())
         own += [self.fp.flat, self.fp.grad, self.master, self.exp_avg, self.exp_avg_sq, self._stats, self._gsq, self._gnorm_t,
                 self._step_t, self._lr_t, self._sched, self._seed, getattr(self, "_ls", None), self._valid_acc, self._ctc_stat,
-                self._valid_ctc]
+                self._valid_ctc, self._tts_stat, self._valid_tts]
         own += list(ops._Rng.base.values())
         if self.ema is not None:
             own += self.ema.arenas()
@@ -610,7 +619,9 @@ class TrainStep:
         that choose its criterion (criterion.py has the table): "constraint_masks"; "reward" (fp32, one value per row of `target`: SCST,
         optional "constraint_range": "start,end" and "sentence_avg": True); "constraint_nodes" (int32 [B, Tt], -1 where no closed set
         applies) with "constraint_trie" (Task.constraint_trie_on; optional "constraint_nodes_packed" as "target_packed"); "encoder_target"
-        with "ctc_range".  criterion.route names each micro-batch's criterion, or refuses the dict, before anything runs."""
+        with "ctc_range"; "target_lengths" (int64 [B]) with a floating-point "target" [B, T, F] of fbank frames: text-to-speech, the
+        ofa_tacotron2 criterion (optional "bce_pos_weight", "sentence_avg"), whose step reports l1_loss / mse_loss / eos_loss in `last`.
+        criterion.route names each micro-batch's criterion, or refuses the dict, before anything runs."""
         routes = [criterion.route(s, self.criterion) for s in samples]
         done = False
         structure = None
@@ -664,6 +675,8 @@ class TrainStep:
         self.last = {"stats": self._stats, "gnorm": self._gnorm, "skipped": self._sched[3:5]}
         if "speech_to_text" in routes:
             self.last["ctc_loss"] = self._ctc_stat          # (the step's summed CTC term; other steps report what they always did)
+        if "tacotron2" in routes:                           # (the terms of the step's text-to-speech micro-batches, summed over them)
+            self.last["l1_loss"], self.last["mse_loss"], self.last["eos_loss"] = self._tts_stat[0:1], self._tts_stat[1:2], self._tts_stat[2:3]
         if self.loss_scale_cfg is not None:
             self.last["loss_scale"] = self._ls[0:1]
         return self.last
@@ -673,6 +686,8 @@ class TrainStep:
         """Start a validation pass: zero the accumulator [ntokens, loss_sum, nll_sum, n_correct] (a device tensor the engine owns)."""
         self._valid_acc.zero_()
         self._valid_ctc.zero_()
+        self._valid_tts.zero_()
+        self._valid_has_tts = False
         self._valid_decodes = []
 
     @contextlib.contextmanager
@@ -706,7 +721,7 @@ class TrainStep:
         with self._valid_mode(model):
             for s, kind in zip(samples, routes):
                 x = criterion.forward(model, s, kind, self.criterion)
-                decode = criterion.evaluate(model, s, kind, x, self.criterion, self._valid_acc, self._valid_ctc)
+                decode = criterion.evaluate(model, s, kind, x, self.criterion, self._valid_acc, self._valid_ctc, self._valid_tts)
                 if decode is not None:
                     outs.append(decode)
         return outs
@@ -749,6 +764,7 @@ class TrainStep:
         `graph_warmup` eager visits -- its own table and its own cap of `max_graphs`, the engine's memory pool -- and replayed.
         Nothing is returned and nothing synchronises: `valid_result()` reads the pass."""
         routes = [criterion.route(s, self.criterion, training=False) for s in samples]
+        self._valid_has_tts = self._valid_has_tts or "tacotron2" in routes
         if use_ema:
             if self.ema is None:
                 raise RuntimeError("valid_step(use_ema=True) needs an EMA of the weights: build the engine with ema={'store_ema': True}")
@@ -812,6 +828,19 @@ class TrainStep:
                     errs += ops.edit_distance(toks[b][:n[b]], ref)
                     total += len(ref)
             res["c_errors"], res["c_total"] = errs, total
+        if self._valid_has_tts:
+            # text-to-speech batches (tacotron2_loss.py:201-214 `reduce_metrics`): every value is the batches' mean weighted by their
+            # sample_size, natural units (no base-2 conversion there); a pass of such batches alone reports these as its loss
+            acc = self._valid_tts
+            if self.world > 1:
+                acc = all_reduce_scalars(acc.clone(), self.group)
+            ss, loss, l1, mse, eos, ntok = acc.tolist()
+            d = ss + 1e-8
+            res.update({"l1_loss": l1 / d, "mse_loss": mse / d, "eos_loss": eos / d})
+            if res["ntokens"] == 0:
+                res.update({"loss": loss / d, "ntokens": ntok, "sample_size": ss})
+            else:
+                res["tts_loss"] = loss / d
         return res
 
 
