@@ -1163,6 +1163,116 @@ def _shared_dbias(dbias, bias, shared):
     return dbias.to(bias.dtype).view(bias.shape)
 
 
+class _AttnCs:
+    """Partial-row buffers of one attention backward call (kernels.attn_bwd cs=): bufs = the dict handed to the kernels, bias_ws /
+    c_ws = the fp32 buffers to register with the queue fq (None: that gradient takes the separate-pass route), ns = partial rows.
+    As constructed: empty -- both gradients take the separate pass."""
+    __slots__ = ("bufs", "bias_ws", "c_ws", "ns", "fq")
+
+    def __init__(self):
+        self.bufs, self.bias_ws, self.c_ws, self.ns, self.fq = {}, None, None, 0, None
+
+
+def _attn_cs_begin(gb, c_ref, B, T, S, seg, heads, dev, order=None):
+    """-> _AttnCs.  gb: the arena gradient of the call's packed bias ([3D], column blocks in `order` -- "kvq", or "qkv" for
+    nn.MultiheadAttention's in_proj -- or, with order None, [D] of the q projection) or None; c_ref: the c_attn Parameter whose gradient
+    is wanted (or None).  Only for gradients that live contiguously in the arena -- with or without a FoldQueue, so that a step computes
+    the same bits whichever way its reductions run."""
+    cs = _AttnCs()
+    cs.fq = _fold() or K.ImmediateFold()                 # (no queue: gradients are consumed inside backward -- fold right behind the kernels)
+    D = heads * 64
+    gc = _sink(c_ref) if c_ref is not None else None
+    use_b = gb is not None and gb.is_contiguous()
+    cs.ns = K.attn_cs_slots(B, T, seg)
+    if order and K.attn_cs_slots(B, S, seg, k_side=True) != cs.ns:
+        use_b = False                                    # (self-attention: the same tiles on both sides -- anything else keeps the pass)
+    if use_b:
+        cs.bias_ws = torch.empty(cs.ns, len(order or "q") * D, dtype=torch.float32, device=dev)
+        cs.bufs.update({n: cs.bias_ws[:, i * D:(i + 1) * D] for i, n in enumerate(order or "q")})
+    if gc is not None and gc.is_contiguous():
+        cs.c_ws = torch.empty(cs.ns, heads, dtype=torch.float32, device=dev)
+        cs.bufs["c"] = cs.c_ws
+    return cs
+
+
+class _AttnBackward:
+    """The attention backward of one call and what it leaves behind.  Constructing it launches the kernels: saved = (q, k, v, out, lse,
+    bias, kpm, c_attn), cfg = (heads, scale, causal, seg, bias_shared), outs = the caller's (dq, dk, dv) views or None, c_ref = the c_attn
+    Parameter whose gradient is wanted (or None), gb / order = the arena bias gradient the kernels' epilogues may serve (_attn_cs_begin),
+    extra = further cs= buffers (CrossKVShared.dkv_cs' k= / v= slices), epilogue=False: no epilogue buffers at all.
+    -> .grads (dq, dk, dv), .dbias (for autograd), .bias_part = (queue, partial rows, ns) of the bias column sums the epilogues
+    produced (for _proj_backward) or None: the separate pass.  finish() -- AFTER the projections' launches -- completes c_attn."""
+
+    def __init__(self, saved, cfg, dout, outs, need_dbias, c_ref, gb=None, order=None, extra=None, epilogue=True):
+        q, k, v, out, lse, bias, kpm, c_attn = saved
+        heads, scale, causal, seg, shared = cfg
+        self.c_ref, self.dims = c_ref, (q.shape[0], heads, q.shape[1])
+        # the bias gradients (column sums of dq / dk / dv) and the c_attn gradient come out of the backward kernels' epilogues as partial
+        # rows for the FoldQueue when the gradients live in the arena: no pass over the d buffer, no c_attn_grad launch
+        cs = self.cs = _attn_cs_begin(gb, c_ref, q.shape[0], q.shape[1], k.shape[1], seg, heads, q.device, order) if epilogue else _AttnCs()
+        *self.grads, dbias, self.delta = K.attn_bwd(q, k, v, out, dout, lse, heads, scale, bias=bias, kpm=kpm, c_attn=c_attn, causal=causal,
+                                                    need_dbias=need_dbias, seg=seg, bias_shared=shared,
+                                                    dbias_dtype=_dbias_dtype(bias, shared), outs=outs, cs={**cs.bufs, **(extra or {})} or None)
+        self.dbias = _shared_dbias(dbias, bias, shared)
+        self.bias_part = (cs.fq, cs.bias_ws, cs.ns) if cs.bias_ws is not None else None
+
+    def finish(self):
+        """-> the c_attn gradient for autograd (None: not wanted, or it went to the arena)."""
+        cs, dc = self.cs, None
+        if cs.c_ws is not None:
+            cs.fq.add(cs.c_ws, 0, _sink(self.c_ref), cs.c_ws.shape[1], cs.c_ws.shape[1], cs.ns, 1.0, True)
+            _sink_done(self.c_ref)
+        elif self.c_ref is not None:
+            dc = _c_attn_grad(self.delta, self.c_ref, *self.dims)
+        if cs.bufs:
+            cs.fq.flush_if_large()
+        return dc
+
+
+def _packed(ws, arena_view):
+    """Packed projection weight [sum(N_i), K] (or bias [sum N_i]): the arena view when the parameters are adjacent in
+    the flat arena (zero copy), else a concatenated copy."""
+    return arena_view if arena_view is not None else torch.cat([w.reshape(w.shape[0], -1) if w.dim() > 1 else w for w in ws])
+
+
+def _slices(g, ws):
+    """A fresh packed gradient's per-parameter slices, for autograd."""
+    outs, o = [], 0
+    for w in ws:
+        n = w.shape[0]
+        outs.append(g[o:o + n].view(w.shape))
+        o += n
+    return outs
+
+
+def _proj_backward(d, x2, W, ws, bs, gw, gb, part, need):
+    """Backward of a packed projection y = x2 W^T + b given d = dy [B, T, N] (contiguous): W [N, K] packs the weights `ws` row-wise, the
+    biases `bs` likewise; gw / gb: their packed arena gradients (or None: fresh slices go back to autograd); part: _AttnBackward.bias_part;
+    need = (dx, weights, biases) wanted.  One input-gradient GEMM, one weight-gradient product (through the layer's grouped launch when
+    it goes to the arena) and the bias column sums: the registered partial rows, else one colsum.  Tells the sinks.
+    -> dx [B, T, K] or None, [weight gradients], [bias gradients]."""
+    d2 = d.view(-1, d.shape[-1])
+    dx = K.gemm(d2, W, False, False).view(*d.shape[:-1], W.shape[1]) if need[0] else None
+    gws, gbs = [None] * len(ws), [None] * len(bs)
+    if need[1]:
+        if gw is not None:
+            _wgrad(d2, x2, gw, 1.0, *ws)
+        else:
+            gws = _slices(K.gemm(d2, x2, True, False), ws)
+    if need[2]:
+        if part is not None:
+            fq, rows, ns = part
+            fq.add(rows, 0, gb, rows.shape[1], rows.shape[1], ns, 1.0, True)
+        elif gb is not None:
+            K.colsum(d2, out=gb, accumulate=True, fold=_fold())
+        else:
+            gbs = _slices(K.colsum(d2, out_dtype=d2.dtype), bs)
+        if gb is not None:
+            for b in bs:
+                _sink_done(b)
+    return dx, gws, gbs
+
+
 class FusedAttentionFn(torch.autograd.Function):
     """bf16 fused attention on [B,T,D] rows (csrc/attention.hip)."""
 
@@ -1172,92 +1282,22 @@ class FusedAttentionFn(torch.autograd.Function):
         out, lse = K.attn_fwd(q, k, v, heads, scale, bias=bias, kpm=kpm, c_attn=c_attn, causal=causal, seg=seg, bias_shared=bias_shared)
         ctx.save_for_backward(q, k, v, out, lse, bias, kpm, c_attn)
         ctx.c_ref = c_attn                                  # the Parameter object (carries the gradient sink)
-        ctx.heads, ctx.scale, ctx.causal, ctx.seg, ctx.bias_shared = heads, scale, causal, seg, bias_shared
+        ctx.cfg = (heads, scale, causal, seg, bias_shared)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        q, k, v, out, lse, bias, kpm, c_attn = ctx.saved_tensors
-        need_dbias = bias is not None and ctx.needs_input_grad[3]
-        dq, dk, dv, dbias, delta = K.attn_bwd(q, k, v, out, dout, lse, ctx.heads, ctx.scale, bias=bias, kpm=kpm,
-                                              c_attn=c_attn, causal=ctx.causal, need_dbias=need_dbias, seg=ctx.seg,
-                                              bias_shared=ctx.bias_shared, dbias_dtype=_dbias_dtype(bias, ctx.bias_shared))
-        dbias = _shared_dbias(dbias, bias, ctx.bias_shared)
-        dc = None
-        if c_attn is not None and ctx.needs_input_grad[5]:
-            dc = _c_attn_grad(delta, ctx.c_ref, q.shape[0], ctx.heads, q.shape[1])
-        return dq, dk, dv, dbias, None, dc, None, None, None, None
-
-
-def _packed(ws, arena_view):
-    """Packed projection weight [sum(N_i), K] (or bias [sum N_i]): the arena view when the parameters are adjacent in
-    the flat arena (zero copy), else a concatenated copy."""
-    return arena_view if arena_view is not None else torch.cat([w.reshape(w.shape[0], -1) if w.dim() > 1 else w for w in ws])
-
-
-def _packed_wgrads(ws, gview, dy2, x2):
-    """Weight gradients dy2^T x2 of row-wise packed weights `ws`: into their packed arena view (through the layer's grouped
-    launch) when there is one, else fresh slices for autograd."""
-    if gview is not None:
-        _wgrad(dy2, x2, gview, 1.0, *ws)
-        return [None] * len(ws)
-    return _packed_grads(ws, None, lambda o, acc, f: K.gemm(dy2, x2, True, False, out=o, accumulate=acc, fold=f))
-
-
-def _packed_grads(ws, gview, grad_packed_fn, inputs=()):
-    """Run `grad_packed_fn(out, accumulate)` into the packed arena gradient when there is one (and notify the sinks); otherwise compute a fresh packed gradient and return its per-parameter slices for autograd."""
-    if gview is not None:
-        grad_packed_fn(gview, True, _fold())
-        for w in ws:
-            _sink_done(w)
-        return [None] * len(ws)
-    g = grad_packed_fn(None, False, None)
-    outs, o = [], 0
-    for w in ws:
-        n = w.shape[0]
-        outs.append(g[o:o + n].view(w.shape))
-        o += n
-    return outs
-
-
-class _AttnCs:
-    """Partial-row buffers of one attention backward call (kernels.attn_bwd cs=): bufs = the dict handed to the kernels, bias_ws /
-    c_ws = the fp32 buffers to register with the FoldQueue (None: that gradient takes the separate-pass route), ns = partial rows."""
-    __slots__ = ("bufs", "bias_ws", "c_ws", "ns")
-
-
-def _attn_cs_begin(gb, c_ref, B, T, S, seg, heads, dev, packed_kvq=False, want_q=True, order="kvq"):
-    """-> (_AttnCs or None, FoldQueue or ImmediateFold).  gb: the arena gradient of the call's packed bias ([3D] k|v|q for packed_kvq, else
-    [D] of the q projection) or None; c_ref: the c_attn Parameter whose gradient is wanted (or None).  Only for gradients that live
-    contiguously in the arena -- with or without a FoldQueue, so that a step computes the same bits whichever way its reductions run."""
-    fq = _fold() or K.ImmediateFold()                    # (no queue: gradients are consumed inside backward -- fold right behind the kernels)
-    D = heads * 64
-    gc = _sink(c_ref) if c_ref is not None else None
-    use_b = gb is not None and gb.is_contiguous() and want_q
-    use_c = gc is not None and gc.is_contiguous()
-    ns = K.attn_cs_slots(B, T, seg)
-    if packed_kvq and K.attn_cs_slots(B, S, seg, k_side=True) != ns:
-        use_b = False                                    # (self-attention: the same tiles on both sides -- anything else keeps the pass)
-    if not (use_b or use_c):
-        return None, None
-    cs = _AttnCs()
-    cs.ns, cs.bufs, cs.bias_ws, cs.c_ws = ns, {}, None, None
-    if use_b:
-        cs.bias_ws = torch.empty(ns, 3 * D if packed_kvq else D, dtype=torch.float32, device=dev)
-        if packed_kvq:                                   # order: the packed bias' column blocks ("qkv": nn.MultiheadAttention's in_proj)
-            cs.bufs.update({n: cs.bias_ws[:, i * D:(i + 1) * D] for i, n in enumerate(order)})
-        else:
-            cs.bufs["q"] = cs.bias_ws
-    if use_c:
-        cs.c_ws = torch.empty(ns, heads, dtype=torch.float32, device=dev)
-        cs.bufs["c"] = cs.c_ws
-    return cs, fq
+        bias, c_attn = ctx.saved_tensors[5], ctx.saved_tensors[7]
+        ab = _AttnBackward(ctx.saved_tensors, ctx.cfg, dout, None, bias is not None and ctx.needs_input_grad[3],
+                           ctx.c_ref if (c_attn is not None and ctx.needs_input_grad[5]) else None, epilogue=False)
+        return (*ab.grads, ab.dbias, None, ab.finish(), None, None, None, None)
 
 
 class PackedSelfAttentionFn(torch.autograd.Function):
     """Self-attention core with ONE packed k|v|q projection (N = 3D) in front of the fused attention kernels
     (multihead_attention.py:199-346 up to, not including, out_proj).  The attention backward writes dk|dv|dq as column
-    slices of one [B,T,3D] buffer, which then feeds one dgrad GEMM (K = 3D), one wgrad GEMM and one bias reduce."""
+    slices of one [B,T,3D] buffer (_AttnBackward), which then feeds one dgrad GEMM (K = 3D), one wgrad GEMM and one bias reduce
+    (_proj_backward)."""
 
     @staticmethod
     def forward(ctx, x, wk, wv, wq, bk, bv, bq, bias, kpm, c_attn, heads, scale, causal, pack, bias_shared=False):
@@ -1272,57 +1312,29 @@ class PackedSelfAttentionFn(torch.autograd.Function):
         ctx.save_for_backward(x2d, kvq, out, lse, bias, kpm, c_attn, W)
         ctx.c_ref = c_attn
         ctx.params = (wk, wv, wq, bk, bv, bq)
-        ctx.cfg = (heads, scale, causal, pack)
-        ctx.seg, ctx.bias_shared = seg, bias_shared
+        ctx.cfg = (heads, scale, causal, seg, bias_shared)
+        ctx.pack = pack
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x2d, kvq, out, lse, bias, kpm, c_attn, W = ctx.saved_tensors
-        heads, scale, causal, pack = ctx.cfg
-        wk, wv, wq, bk, bv, bq = ctx.params
-        B, T, D3 = kvq.shape
-        D = D3 // 3
+        pack, D = ctx.pack, kvq.shape[2] // 3
         k, v, q = kvq[:, :, 0:D], kvq[:, :, D:2 * D], kvq[:, :, 2 * D:3 * D]
         dkvq = torch.empty_like(kvq)                                   # (ragged mode: the kernels zero the filler rows)
-        need_dbias = bias is not None and ctx.needs_input_grad[7]
-        # the bias gradients (column sums of dk | dv | dq) and the c_attn gradient come out of the backward kernels' epilogues as partial
-        # rows for the FoldQueue when the gradients live in the arena: no pass over dkvq, no c_attn_grad launch
-        want_c = c_attn is not None and ctx.needs_input_grad[9]
-        cs, fq = _attn_cs_begin(pack.get("gb"), ctx.c_ref if want_c else None, B, T, T, ctx.seg, heads, kvq.device, packed_kvq=True)
-        _, _, _, dbias, delta = K.attn_bwd(q, k, v, out, dout, lse, heads, scale, bias=bias, kpm=kpm, c_attn=c_attn,
-                                           causal=causal, need_dbias=need_dbias, seg=ctx.seg, bias_shared=ctx.bias_shared,
-                                           dbias_dtype=_dbias_dtype(bias, ctx.bias_shared), outs=(dkvq[:, :, 2 * D:3 * D], dkvq[:, :, 0:D], dkvq[:, :, D:2 * D]),
-                                           cs=cs.bufs if cs else None)
-        dbias = _shared_dbias(dbias, bias, ctx.bias_shared)
-        d2 = dkvq.view(B * T, D3)
-        dx = K.gemm(d2, W, False, False).view(B, T, D) if ctx.needs_input_grad[0] else None
-        gws = _packed_wgrads((wk, wv, wq), pack.get("gw"), d2, x2d)
-        dc = None
-        if cs and cs.bias_ws is not None:
-            fq.add(cs.bias_ws, 0, pack.get("gb"), D3, D3, cs.ns, 1.0, True)
-            for w in (bk, bv, bq):
-                _sink_done(w)
-            gbs = [None] * 3
-        else:
-            gbs = _packed_grads((bk, bv, bq), pack.get("gb"),
-                                lambda o, acc, f: K.colsum(d2, out=o, accumulate=acc, out_dtype=d2.dtype, fold=f), (d2,))
-        if cs and cs.c_ws is not None:
-            fq.add(cs.c_ws, 0, _sink(ctx.c_ref), heads, heads, cs.ns, 1.0, True)
-            _sink_done(ctx.c_ref)
-        elif want_c:
-            dc = _c_attn_grad(delta, ctx.c_ref, B, heads, T)
-        if cs:
-            fq.flush_if_large()
-        return (dx, *gws, *gbs, dbias, None, dc, None, None, None, None, None)
+        ab = _AttnBackward((q, k, v, out, lse, bias, kpm, c_attn), ctx.cfg, dout, (dkvq[:, :, 2 * D:3 * D], dkvq[:, :, 0:D], dkvq[:, :, D:2 * D]),
+                           bias is not None and ctx.needs_input_grad[7], ctx.c_ref if (c_attn is not None and ctx.needs_input_grad[9]) else None,
+                           gb=pack.get("gb"), order="kvq")
+        dx, gws, gbs = _proj_backward(dkvq, x2d, W, ctx.params[:3], ctx.params[3:], pack.get("gw"), pack.get("gb"), ab.bias_part,
+                                      (ctx.needs_input_grad[0], True, True))
+        return (dx, *gws, *gbs, ab.dbias, None, ab.finish(), None, None, None, None, None)
 
 
 class InProjSelfAttentionFn(torch.autograd.Function):
     """Self-attention core over nn.MultiheadAttention's single packed parameter pair in_proj_weight [3D, D] / in_proj_bias [3D] (q|k|v
     row blocks, read in place: no reorder, no copy) in front of the fused attention kernels: one N = 3D GEMM, attention on the column
-    slices (no bias, no mask, no c_attn); the backward writes dq|dk|dv as column slices of one [B,T,3D] buffer, then one dgrad GEMM
-    (K = 3D), one weight-gradient product and one bias column sum (the attention backward's epilogues where _attn_cs_begin offers
-    them).  16-bit operands, head_dim 64 (module/vit.py keeps everything else on ops.linear + ops.attention)."""
+    slices (no bias, no mask, no c_attn).  The backward is PackedSelfAttentionFn's, the "pack" being the parameter pair itself in
+    column order "qkv".  16-bit operands, head_dim 64 (module/vit.py keeps everything else on ops.linear + ops.attention)."""
 
     @staticmethod
     def forward(ctx, x, w, b, heads, scale):
@@ -1332,40 +1344,19 @@ class InProjSelfAttentionFn(torch.autograd.Function):
         out, lse = K.attn_fwd(qkv[:, :, 0:D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:3 * D], heads, scale)
         ctx.save_for_backward(x2d, qkv, out, lse, w)
         ctx.bias_ref = b
-        ctx.cfg = (heads, scale)
+        ctx.cfg = (heads, scale, False, None, False)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x2d, qkv, out, lse, w = ctx.saved_tensors
-        heads, scale = ctx.cfg
-        b = ctx.bias_ref
-        B, T, D3 = qkv.shape
-        D = D3 // 3
-        gw, gb = _sink(w), _sink(b)
+        b, D = ctx.bias_ref, qkv.shape[2] // 3
+        gb = _sink(b) if ctx.needs_input_grad[2] else None
         dqkv = torch.empty_like(qkv)
-        cs, fq = _attn_cs_begin(gb if ctx.needs_input_grad[2] else None, None, B, T, T, None, heads, qkv.device, packed_kvq=True,
-                                order="qkv")
-        K.attn_bwd(qkv[:, :, 0:D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:3 * D], out, dout, lse, heads, scale,
-                   outs=(dqkv[:, :, 0:D], dqkv[:, :, D:2 * D], dqkv[:, :, 2 * D:3 * D]), cs=cs.bufs if cs else None)
-        d2 = dqkv.view(B * T, D3)
-        dx = K.gemm(d2, w, False, False).view(B, T, D) if ctx.needs_input_grad[0] else None
-        dw = db = None
-        if ctx.needs_input_grad[1]:
-            if gw is not None:
-                _wgrad(d2, x2d, gw, 1.0, w)
-            else:
-                dw = K.gemm(d2, x2d, True, False)
-        if ctx.needs_input_grad[2]:
-            if cs and cs.bias_ws is not None:
-                fq.add(cs.bias_ws, 0, gb, D3, D3, cs.ns, 1.0, True)
-                _sink_done(b)
-                fq.flush_if_large()
-            elif gb is not None:
-                K.colsum(d2, out=gb, accumulate=True, fold=_fold())
-                _sink_done(b)
-            else:
-                db = K.colsum(d2, out_dtype=b.dtype)
+        ab = _AttnBackward((qkv[:, :, 0:D], qkv[:, :, D:2 * D], qkv[:, :, 2 * D:3 * D], out, lse, None, None, None), ctx.cfg, dout,
+                           (dqkv[:, :, 0:D], dqkv[:, :, D:2 * D], dqkv[:, :, 2 * D:3 * D]), False, None, gb=gb, order="qkv")
+        dx, (dw,), (db,) = _proj_backward(dqkv, x2d, w, (w,), (b,), _sink(w), gb, ab.bias_part, ctx.needs_input_grad)
+        ab.finish()
         return dx, dw, db, None, None
 
 
@@ -1417,7 +1408,7 @@ class CrossKVShared:
         return self.dkv_all[:, lo:lo + 2 * self.D].view(B, S, 2 * self.D)
 
     def dkv_cs(self, layer, ns):
-        """Layer `layer`'s (k, v) column slices of the stack-wide partial rows of colsum(dkv_all) [ns, L * 2D] (fp32) -- every layer's
+        """Layer `layer`'s k= / v= column slices (kernels.attn_bwd cs=) of the stack-wide partial rows of colsum(dkv_all) [ns, L * 2D] (fp32) -- every layer's
         dK/dV kernel writes its own slice, finish() registers ONE fold -- or None when the bias gradient takes the separate pass."""
         gb = self.pack.get("gb")
         if len(self.users) != self.L or gb is None or not gb.is_contiguous():
@@ -1426,7 +1417,7 @@ class CrossKVShared:
             self.cs_all = torch.empty(ns, self.L * 2 * self.D, dtype=torch.float32, device=self.kv_all.device)
         assert self.cs_all.shape[0] == ns
         lo = layer * 2 * self.D
-        return self.cs_all[:, lo:lo + self.D], self.cs_all[:, lo + self.D:lo + 2 * self.D]
+        return {"k": self.cs_all[:, lo:lo + self.D], "v": self.cs_all[:, lo + self.D:lo + 2 * self.D]}
 
     def finish(self, need_dx):
         """After the last participating layer's slice has been written: d enc, d W_all, d b_all.  A layer that did not take part
@@ -1490,75 +1481,41 @@ class PackedCrossAttentionFn(torch.autograd.Function):
         ctx.save_for_backward(xq2, xkv2, q, (kv if kv_all is None else None), out, lse, bias, kpm, c_attn, W)
         ctx.c_ref = c_attn
         ctx.params = (wk, wv, wq, bk, bv, bq)
-        ctx.cfg = (heads, scale, pack)
-        ctx.seg, ctx.bias_shared = seg, bias_shared
+        ctx.cfg = (heads, scale, False, seg, bias_shared)
+        ctx.pack = pack
         return out
 
     @staticmethod
     def backward(ctx, dout):
         xq2, xkv2, q, kv, out, lse, bias, kpm, c_attn, W = ctx.saved_tensors
-        heads, scale, pack = ctx.cfg
         wk, wv, wq, bk, bv, bq = ctx.params
         B, T, D = q.shape
-        shared_kv = ctx.kv_all
+        shared_kv, kv_cs = ctx.kv_all, None
         if shared_kv is not None:
+            # the k | v side of a stack-wide projection: the layer's slice of the ONE d buffer, its bias column sums into CrossKVShared's
+            # partial rows, folded once by finish()
             S = shared_kv.kv_all.shape[0] // B
-            kv = shared_kv.kv(ctx.layer, B, S)
-            dkv = shared_kv.dkv(ctx.layer, B, S)
+            kv, dkv = shared_kv.kv(ctx.layer, B, S), shared_kv.dkv(ctx.layer, B, S)
+            kv_cs = shared_kv.dkv_cs(ctx.layer, K.attn_cs_slots(B, S, ctx.cfg[3], k_side=True))
         else:
-            S = kv.shape[1]
             dkv = torch.empty_like(kv)
-        k, v = kv[:, :, 0:D], kv[:, :, D:2 * D]
         dq = torch.empty_like(q)                                       # (ragged mode: the kernels zero the filler rows)
-        need_dbias = bias is not None and ctx.needs_input_grad[8]
-        # bias gradients / c_attn gradient from the backward kernels' epilogues (see PackedSelfAttentionFn.backward); the k | v side of a
-        # stack-wide projection goes into CrossKVShared's partial rows, folded once by finish()
-        want_c = c_attn is not None and ctx.needs_input_grad[10]
-        cs, fq = _attn_cs_begin(_sink(bq), ctx.c_ref if want_c else None, B, T, S, ctx.seg, heads, q.device)
-        kv_cs = None
-        if shared_kv is not None:
-            kv_cs = shared_kv.dkv_cs(ctx.layer, K.attn_cs_slots(B, S, ctx.seg, k_side=True))
-        bufs = dict(cs.bufs) if cs else {}
-        if kv_cs is not None:
-            bufs.update(k=kv_cs[0], v=kv_cs[1])
-        _, _, _, dbias, delta = K.attn_bwd(q, k, v, out, dout, lse, heads, scale, bias=bias, kpm=kpm, c_attn=c_attn,
-                                           causal=False, need_dbias=need_dbias, seg=ctx.seg, bias_shared=ctx.bias_shared,
-                                           dbias_dtype=_dbias_dtype(bias, ctx.bias_shared), outs=(dq, dkv[:, :, 0:D], dkv[:, :, D:2 * D]),
-                                           cs=bufs or None)
-        dbias = _shared_dbias(dbias, bias, ctx.bias_shared)
-        dq2 = dq.view(B * T, D)
-        dxq = K.gemm(dq2, wq, False, False).view(B, T, D) if ctx.needs_input_grad[0] else None
-        gq = _packed_wgrads((wq,), _sink(wq), dq2, xq2)
-        if cs and cs.bias_ws is not None:
-            fq.add(cs.bias_ws, 0, _sink(bq), D, D, cs.ns, 1.0, True)
-            _sink_done(bq)
-            gbq = [None]
-        else:
-            gbq = _packed_grads((bq,), _sink(bq), lambda o, acc, f: K.colsum(dq2, out=o, accumulate=acc, out_dtype=dq2.dtype, fold=f),
-                                (dq2,))
+        ab = _AttnBackward((q, kv[:, :, 0:D], kv[:, :, D:2 * D], out, lse, bias, kpm, c_attn), ctx.cfg, dout,
+                           (dq, dkv[:, :, 0:D], dkv[:, :, D:2 * D]), bias is not None and ctx.needs_input_grad[8],
+                           ctx.c_ref if (c_attn is not None and ctx.needs_input_grad[10]) else None, gb=_sink(bq), extra=kv_cs)
+        dxq, (gq,), (gbq,) = _proj_backward(dq, xq2, wq, (wq,), (bq,), _sink(wq), _sink(bq), ab.bias_part,
+                                            (ctx.needs_input_grad[0], True, True))
         if shared_kv is not None:
             # the slice is written; layer 0 -- the last cross-attention backward of the stack -- closes the shared projection
             shared_kv.done += 1
-            dxkv = None
+            dxkv, gws, gbs = None, [None, None], [None, None]
             if ctx.layer == min(shared_kv.users):
                 dx2 = shared_kv.finish(ctx.needs_input_grad[1])
                 dxkv = dx2.view(B, S, D) if dx2 is not None else None
-            gws, gbs = [None, None], [None, None]
         else:
-            dkv2 = dkv.view(B * S, 2 * D)
-            dxkv = K.gemm(dkv2, W, False, False).view(B, S, D) if ctx.needs_input_grad[1] else None
-            gws = _packed_wgrads((wk, wv), pack.get("gw"), dkv2, xkv2)
-            gbs = _packed_grads((bk, bv), pack.get("gb"),
-                                lambda o, acc, f: K.colsum(dkv2, out=o, accumulate=acc, out_dtype=dkv2.dtype, fold=f), (dkv2,))
-        dc = None
-        if cs and cs.c_ws is not None:
-            fq.add(cs.c_ws, 0, _sink(ctx.c_ref), heads, heads, cs.ns, 1.0, True)
-            _sink_done(ctx.c_ref)
-        elif want_c:
-            dc = _c_attn_grad(delta, ctx.c_ref, B, heads, T)
-        if cs:
-            fq.flush_if_large()
-        return (dxq, dxkv, gws[0], gws[1], gq[0], gbs[0], gbs[1], gbq[0], dbias, None, dc, None, None, None, None, None, None)
+            dxkv, gws, gbs = _proj_backward(dkv, xkv2, W, (wk, wv), (bk, bv), ctx.pack.get("gw"), ctx.pack.get("gb"), None,
+                                            (ctx.needs_input_grad[1], True, True))
+        return (dxq, dxkv, *gws, gq, *gbs, gbq, ab.dbias, None, ab.finish(), None, None, None, None, None, None)
 
 
 class UnfusedAttentionFn(torch.autograd.Function):
