@@ -641,6 +641,12 @@ int ofa_im2col(const void* x, void* col, int B, int H, int W, int C, int KH, int
                int x_nchw, int dtype, void* stream);
 int ofa_col2im(const void* dcol, void* dx, int B, int H, int W, int C, int KH, int KW, int stride, int pad, int Kpad,
                int dtype, void* stream);
+/* Host only: the kernel ofa_im2col launches for these sizes -- 0 one element per access, 1 16-byte vectors (NHWC, C and Kpad whole
+ * vectors), 2 the LDS tile kernel of an NCHW source (64 * Kpad elements within 48 KB); -1 for a bad argument. */
+int ofa_im2col_route(int B, int Ho, int Wo, int C, int Kpad, int x_nchw, int dtype);
+/* Host only: the launch shapes of the BatchNorm kernels over [rows, C] -- out[0] the row groups of the statistics kernels (= the fp64
+ * partial rows they leave), out[1] log2 of the column vectors per statistics block, out[2] the blocks of the apply / dx kernels. */
+int ofa_batchnorm_route(int64_t rows, int C, int dtype, int* out);
 /* torch.nn.BatchNorm2d over the rows of [rows, C] (module/resnet.py:105-128): y = [relu]((x-mean)*rstd*gamma + beta
  * [+ residual]).  use_running == 0: batch statistics (biased variance), running buffers (fp32, optional) updated with
  * `momentum` and the unbiased variance; use_running != 0: eval mode.  mean/rstd: fp32 [C] outputs kept for backward.

@@ -17,6 +17,9 @@ static inline int grid_1d(int64_t work) {
   return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
 
+// im2col_kernel's own choice between 16-byte vectors and single elements (n: elements of a 16-byte vector); ofa_im2col_route reports it
+__host__ __device__ inline bool im2col_vector(bool nchw, int C, int Kpad, int n) { return !nchw && (C % n) == 0 && (Kpad % n) == 0; }
+
 // col[(b, oh, ow)][(kh*KW + kw)*C + c] = x[b, oh*s - p + kh, ow*s - p + kw, c]  (0 outside), columns K..Kpad-1 zero.
 // NCHW: x is [B, C, H, W] (the image itself, first convolution); else [B, H, W, C].
 template <typename T, bool NCHW>
@@ -24,7 +27,7 @@ __global__ __launch_bounds__(256) void im2col_kernel(const T* __restrict__ x, T*
                                                      int KH, int KW, int stride, int pad, int Ho, int Wo, int Kpad) {
   constexpr int N = Vec<T>::N;
   const int K = KH * KW * C;
-  if (!NCHW && (C % N) == 0 && (Kpad % N) == 0) {
+  if (im2col_vector(NCHW, C, Kpad, N)) {
     const int vpr = Kpad / N;
     const int64_t total = (int64_t)B * Ho * Wo * vpr;
     for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < total; v += (int64_t)gridDim.x * 256) {
@@ -330,7 +333,9 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const double* __re
   }
 }
 
-// y = [relu]( (x - mean)*rstd*gamma + beta [+ residual] )
+// y = [relu]( (x - mean)*rstd*gamma + beta [+ residual] ); a NaN goes through the ReLU as it does through torch's, so that the fp16
+// loss scaler sees it.  The backward gates (y > 0, and the recomputed one) stay as they are: false for a NaN, whose gradient is gated
+// away -- the overflow check trips on the forward value.
 template <typename T>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ x, const T* __restrict__ gamma,
                                                        const T* __restrict__ beta, const float* __restrict__ mean,
@@ -350,7 +355,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ x, 
     for (int j = 0; j < N; ++j) {
       float t = (a[j] - mean[c + j]) * rstd[c + j] * g[j] + b[j];
       if (residual) t += r[j];
-      a[j] = relu ? fmaxf(t, 0.f) : t;
+      a[j] = relu ? (t > 0.f ? t : (t != t ? t : 0.f)) : t;      // NaN propagates (torch.relu; fmaxf would return 0)
     }
     store_vec<T>(y + v * N, a);
   }
@@ -489,13 +494,14 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* __restrict__ 
   }
 }
 
-// y = max(x, 0) [* mask of y for backward]
+// y = max(x, 0), NaN propagating as in torch.relu (fmaxf returns 0 for NaN) [or y = x * [gate > 0] for backward: that gate stays as
+// it is, false for a NaN gate]
 template <typename T>
 __global__ __launch_bounds__(256) void relu_kernel(const T* __restrict__ x, const T* __restrict__ gate, T* __restrict__ y,
                                                    int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float v = ld1<T>(x + i);
-    st1<T>(y + i, gate ? (ld1<T>(gate + i) > 0.f ? v : 0.f) : fmaxf(v, 0.f));
+    st1<T>(y + i, gate ? (ld1<T>(gate + i) > 0.f ? v : 0.f) : (v > 0.f ? v : (v != v ? v : 0.f)));
   }
 }
 
@@ -503,7 +509,18 @@ __global__ __launch_bounds__(256) void relu_kernel(const T* __restrict__ x, cons
 using namespace ofa;
 
 #define OFA_DT(name) OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, name ": bad dtype %d", dtype)
-extern "C" int ofa_conv_out_size(int in, int k, int stride, int pad) { return (in + 2 * pad - k) / stride + 1; }
+// floor((in + 2 pad - k) / stride) + 1, and 0 when the kernel does not fit at all (C's division would round -1 / 2 up to 0 and call
+// that one output position, which the callers' buffers -- sized with floor division -- do not hold)
+extern "C" int ofa_conv_out_size(int in, int k, int stride, int pad) { return in + 2 * pad < k ? 0 : (in + 2 * pad - k) / stride + 1; }
+
+// which kernel ofa_im2col launches: 0 im2col_kernel by elements, 1 im2col_kernel by 16-byte vectors, 2 im2col_nchw_lds_kernel; -1: bad
+// argument.  Host only.
+extern "C" int ofa_im2col_route(int B, int Ho, int Wo, int C, int Kpad, int x_nchw, int dtype) {
+  if (!OFA_DT_OK(dtype) || B <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || Kpad <= 0) return -1;
+  const int es = dt_size(dtype);
+  if (x_nchw && (Kpad * es) % 16 == 0 && (size_t)64 * Kpad * es <= 48 * 1024 && (int64_t)B * Ho * Wo <= ((int64_t)1 << 36)) return 2;
+  return im2col_vector(x_nchw != 0, C, Kpad, dt_vecn(dtype)) ? 1 : 0;
+}
 
 extern "C" int ofa_im2col(const void* x, void* col, int B, int H, int W, int C, int KH, int KW, int stride, int pad, int Kpad,
                           int x_nchw, int dtype, void* stream) {
@@ -515,7 +532,7 @@ extern "C" int ofa_im2col(const void* x, void* col, int B, int H, int W, int C, 
   hipStream_t st = (hipStream_t)stream;
   const int64_t total = (int64_t)B * Ho * Wo * Kpad;
   const int es = dt_size(dtype);
-  if (x_nchw && (Kpad * es) % 16 == 0 && (size_t)64 * Kpad * es <= 48 * 1024 && (int64_t)B * Ho * Wo <= ((int64_t)1 << 36)) {
+  if (ofa_im2col_route(B, Ho, Wo, C, Kpad, x_nchw, dtype) == 2) {
     const int64_t rows = (int64_t)B * Ho * Wo;
     const dim3 g((unsigned)((rows + 63) / 64)), blk(256);
     const size_t lds = (size_t)64 * Kpad * es;
@@ -540,7 +557,9 @@ extern "C" int ofa_col2im(const void* dcol, void* dx, int B, int H, int W, int C
   OFA_REQUIRE(dcol && dx && B > 0 && H > 0 && W > 0 && C > 0 && Kpad >= KH * KW * C, OFA_ERR_INVALID, "col2im: bad argument");
   const int n = dt_vecn(dtype);
   OFA_REQUIRE(C % n == 0 && Kpad % n == 0, OFA_ERR_UNSUPPORTED, "col2im: C=%d / Kpad=%d must be multiples of %d", C, Kpad, n);
+  OFA_REQUIRE(KH > 0 && KW > 0 && stride > 0 && pad >= 0, OFA_ERR_INVALID, "col2im: bad argument");
   const int Ho = ofa_conv_out_size(H, KH, stride, pad), Wo = ofa_conv_out_size(W, KW, stride, pad);
+  OFA_REQUIRE(Ho > 0 && Wo > 0, OFA_ERR_INVALID, "col2im: empty output (H=%d W=%d k=%dx%d s=%d p=%d)", H, W, KH, KW, stride, pad);
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(grid_1d((int64_t)B * H * W * (C / n))), block(256);
   dispatch_dtype(dtype, [&](auto tag) {
@@ -561,13 +580,26 @@ static int bn_groups(int64_t rows) {
   int64_t g = (rows + 127) / 128;
   return (int)(g < 1 ? 1 : (g > 256 ? 256 : g));
 }
+// the launch shapes of the BatchNorm kernels over [rows, C]: out[0] = row groups of the statistics kernels (gridDim.y, = partial rows),
+// out[1] = log2 of the column vectors per statistics block, out[2] = blocks of the apply / input-gradient kernels.  Host only.
+extern "C" int ofa_batchnorm_route(int64_t rows, int C, int dtype, int* out) {
+  OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "batchnorm_route: bad dtype %d", dtype);
+  OFA_REQUIRE(out && rows > 0 && C > 0, OFA_ERR_INVALID, "batchnorm_route: bad argument");
+  const int n = dt_vecn(dtype);
+  OFA_REQUIRE(C % n == 0, OFA_ERR_UNSUPPORTED, "batchnorm: C=%d must be a multiple of %d", C, n);
+  out[0] = bn_groups(rows);
+  out[1] = bn_cw_log2(C / n);
+  out[2] = grid_1d(rows * (C / n));
+  return 0;
+}
 extern "C" int ofa_batchnorm_ws_floats(int C) { return 4 * 256 * C + 2 * C; }   // fp64 partials [256][2][C] + fp32 sums [2][C]
 
 // column statistics of x into ws (fp64 partials [groups][2][C]); returns the group count
 static int bn_fwd_colstat(const void* x, float* ws, int64_t rows, int C, int dtype, hipStream_t st) {
   const int n = dt_vecn(dtype);
-  const int groups = bn_groups(rows);
-  const int cwl = bn_cw_log2(C / n);
+  int route[3];
+  if (ofa_batchnorm_route(rows, C, dtype, route)) return 0;      // (unreachable: every caller has checked these arguments)
+  const int groups = route[0], cwl = route[1];
   dim3 grid(cdiv(C / n, 1 << cwl), groups), block(256);
   dispatch_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
@@ -578,8 +610,9 @@ static int bn_fwd_colstat(const void* x, float* ws, int64_t rows, int C, int dty
 
 static int bn_apply_launch(const void* x, const void* gamma, const void* beta, const void* residual, void* y, const float* mean,
                            const float* rstd, int64_t rows, int C, int relu, int dtype, hipStream_t st) {
-  const int n = dt_vecn(dtype);
-  dim3 grid(grid_1d(rows * (C / n))), block(256);
+  int route[3];
+  if (int rc = ofa_batchnorm_route(rows, C, dtype, route)) return rc;
+  dim3 grid(route[2]), block(256);
   dispatch_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     hipLaunchKernelGGL((bn_apply_kernel<T>), grid, block, 0, st, (const T*)x, (const T*)gamma, (const T*)beta, (const float*)mean, (const float*)rstd, (const T*)residual, (T*)y, rows, C, relu);
@@ -645,8 +678,9 @@ static int bn_bwd_stats_launch(const void* dy, const void* y, const void* x, con
                                float* sums, void* dgamma, void* dbeta, float* ws, int64_t rows, int C, int relu, int accumulate,
                                const void* beta, int dtype, hipStream_t st) {
   const int n = dt_vecn(dtype);
-  const int groups = bn_groups(rows);
-  const int cwl = bn_cw_log2(C / n);
+  int route[3];
+  if (int rc = ofa_batchnorm_route(rows, C, dtype, route)) return rc;
+  const int groups = route[0], cwl = route[1];
   dim3 grid(cdiv(C / n, 1 << cwl), groups), block(256);
   dispatch_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
@@ -660,8 +694,9 @@ static int bn_bwd_stats_launch(const void* dy, const void* y, const void* x, con
 static int bn_bwd_dx_launch(const void* dy, const void* y, const void* x, const void* gamma, const float* mean, const float* rstd,
                             const float* sums, void* dx, void* dres, int64_t rows, const double* stat_rows, int C, int batch_stats,
                             int relu, const void* beta, int dtype, hipStream_t st) {
-  const int n = dt_vecn(dtype);
-  dim3 g2(grid_1d(rows * (C / n))), block(256);
+  int route[3];
+  if (int rc = ofa_batchnorm_route(rows, C, dtype, route)) return rc;
+  dim3 g2(route[2]), block(256);
   dispatch_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     hipLaunchKernelGGL((bn_bwd_dx_kernel<T>), g2, block, 0, st, (const T*)dy, (const T*)y, (const T*)x, (const T*)gamma, mean, rstd, (const float*)sums, (T*)dx, (T*)dres, rows, C, relu, batch_stats, (const T*)beta, stat_rows);
@@ -716,6 +751,7 @@ extern "C" int ofa_maxpool_fwd(const void* x, void* y, uint8_t* arg, int B, int 
   OFA_DT("maxpool_fwd");
   OFA_REQUIRE(x && y && arg && B > 0 && H > 0 && W > 0 && C > 0 && K > 0 && K * K <= 255 && stride > 0 && pad >= 0, OFA_ERR_INVALID, "maxpool_fwd: bad argument");
   const int Ho = ofa_conv_out_size(H, K, stride, pad), Wo = ofa_conv_out_size(W, K, stride, pad);
+  OFA_REQUIRE(Ho > 0 && Wo > 0, OFA_ERR_INVALID, "maxpool_fwd: empty output (H=%d W=%d k=%d s=%d p=%d)", H, W, K, stride, pad);
   hipStream_t st = (hipStream_t)stream;
   const int nvec = dt_vecn(dtype);
   OFA_REQUIRE(C % nvec == 0, OFA_ERR_UNSUPPORTED, "maxpool_fwd: C=%d must be a multiple of %d", C, nvec);
@@ -730,8 +766,9 @@ extern "C" int ofa_maxpool_fwd(const void* x, void* y, uint8_t* arg, int B, int 
 extern "C" int ofa_maxpool_bwd(const void* dy, const uint8_t* arg, void* dx, int B, int H, int W, int C, int K, int stride, int pad,
                                int dtype, void* stream) {
   OFA_DT("maxpool_bwd");
-  OFA_REQUIRE(dy && dx && arg && B > 0 && H > 0 && W > 0 && C > 0 && K > 0, OFA_ERR_INVALID, "maxpool_bwd: bad argument");
+  OFA_REQUIRE(dy && dx && arg && B > 0 && H > 0 && W > 0 && C > 0 && K > 0 && stride > 0 && pad >= 0, OFA_ERR_INVALID, "maxpool_bwd: bad argument");
   const int Ho = ofa_conv_out_size(H, K, stride, pad), Wo = ofa_conv_out_size(W, K, stride, pad);
+  OFA_REQUIRE(Ho > 0 && Wo > 0, OFA_ERR_INVALID, "maxpool_bwd: empty output (H=%d W=%d k=%d s=%d p=%d)", H, W, K, stride, pad);
   hipStream_t st = (hipStream_t)stream;
   const int nvec = dt_vecn(dtype);
   OFA_REQUIRE(C % nvec == 0, OFA_ERR_UNSUPPORTED, "maxpool_bwd: C=%d must be a multiple of %d", C, nvec);

@@ -15,7 +15,7 @@ def test_header_parses_and_library_exports_every_symbol():
                  "ofa_scaled_softmax_fwd", "ofa_scaled_masked_softmax_fwd", "ofa_scaled_upper_triang_masked_softmax_fwd",
                  "ofa_scaled_softmax_bwd", "ofa_scaled_masked_softmax_bwd", "ofa_scaled_upper_triang_masked_softmax_bwd",
                  "ofa_get_batch_per_block", "ofa_embedding_bwd", "ofa_cross_entropy_fwd", "ofa_adam_step", "ofa_version",
-                 "ofa_last_error", "ofa_im2col_patch", "ofa_bias_block_add"):
+                 "ofa_last_error", "ofa_im2col_patch", "ofa_bias_block_add", "ofa_batchnorm_route", "ofa_im2col_route"):
         assert must in protos
     assert os.path.exists(L.LIB_PATH), "build with `python __graft_entry__.py` first"
     cdll = ctypes.CDLL(L.LIB_PATH)
@@ -31,6 +31,17 @@ def test_host_only_entry_points():
     for a in [(128, 128, 2, 4), (64, 448, 2, 4), (4, 16, 1, 1), (8, 4096, 1, 1), (16, 100, 3, 3)]:
         assert h.cdll.ofa_get_batch_per_block(*a) == restate.get_batch_per_block(*a)
     assert h.cdll.ofa_layernorm_bwd_ws_rows() > 0
+    # the convolution stack's launch shapes (csrc/conv.hip; tests/test_conv_oracle_cpu.py checks them against every table entry)
+    out = (ctypes.c_int * 3)()
+    for rows, C, dt, want in [(25088, 512, L.BF16, (196, 5, 4096)), (32, 64, L.BF16, (1, 3, 1)), (32768 + 1, 64, L.F32, (256, 4, 2049)),
+                              (1, 8, L.F16, (1, 0, 1))]:
+        assert h.cdll.ofa_batchnorm_route(rows, C, dt, ctypes.addressof(out)) == 0 and tuple(out) == want, (rows, C, dt, tuple(out))
+    assert h.cdll.ofa_batchnorm_route(4, 12, L.BF16, ctypes.addressof(out)) == 2 and h.cdll.ofa_batchnorm_route(4, 8, 7, ctypes.addressof(out)) == 1
+    assert h.cdll.ofa_im2col_route(32, 192, 192, 3, 152, 1, L.BF16) == 2           # the image stem: 64 x 152 elements in LDS
+    assert h.cdll.ofa_im2col_route(1, 5, 5, 8, 392, 1, L.BF16) == 0 and h.cdll.ofa_im2col_route(1, 5, 5, 6, 384, 1, L.F16) == 2    # 48 KB
+    assert h.cdll.ofa_im2col_route(2, 7, 7, 64, 576, 0, L.BF16) == 1 and h.cdll.ofa_im2col_route(2, 7, 7, 3, 32, 0, L.BF16) == 0
+    assert h.cdll.ofa_im2col_route(2, 7, 7, 4, 40, 0, L.F32) == 1 and h.cdll.ofa_im2col_route(2, 7, 7, 4, 40, 0, 9) == -1
+    assert h.cdll.ofa_conv_out_size(384, 7, 2, 3) == 192 and h.cdll.ofa_conv_out_size(1, 2, 2, 0) == 0
 
 
 def test_gemm_group_plan_is_host_only():
