@@ -984,6 +984,46 @@ int ofa_tacotron2_loss(const void* feat_out, const void* post, const void* targe
                        int B, int T, int F, float bce_pos_weight, int reduction, const float* seed, double* partial,
                        float* out, void* dfeat, void* dpost, void* deos, int grad, int dtype, int target_dtype, void* stream);
 
+/* ---- autoregressive speech generation (generator/speech_generator.py:143-166 with adaptor/audio.py:327-336, 468-477, 721-732),
+ * csrc/speech_step.hip: everything a decoding step does after the decoder, in ONE launch recorded into the step's hipGraph.  The
+ * descriptor is copied by value into the kernel arguments before the entry point returns.  Per row b of x [B, D] (row stride ldx; the
+ * decoder's output at the new position; every tensor of the model dtype unless said otherwise, weights row-major [out, in] as nn.Linear
+ * holds them, read in place):
+ *   feat = feat_w x + feat_b, rounded to the model dtype  -> feats[b, step, :]  (feats [B, T_cap, out_dim])
+ *   p = sigmoid(round(eos_w x + eos_b)) in fp32           -> eos_prob[b, step]  (fp32 [B, T_cap])
+ *   a row not yet finished with p > *threshold (strict; a device fp32, so one captured step serves every threshold) finishes: out_lens[b] = step + 1, finished[b] = 1 (both int32 [B]), *nfin += 1
+ *   (an integer atomic add per workgroup that has newly finished rows: order-independent, so equal inputs give equal state);
+ *   pad_next[b] (uint8 [B]) = finished[b] AFTER the update: the key-padding flag of position step + 1;
+ *   embed[b, :] ([B, E]) = proj(prenet(feat)): `layers` x (Linear + ReLU + dropout p_drop), every layer's output rounded to the model
+ *   dtype before and after the dropout, then the projection.  Dropout layer l draws ofa_dropout_add_fwd's mask of a [B, P] tensor at
+ *   Philox position offset + l * offset_stride + *offset_base (element e = b * P + column: halfword e % 8 of counter e / 8); p_drop == 0
+ *   draws nothing and is exact.  Dot products accumulate in fp32.
+ * A workgroup owns ofa_speech_step_rows() rows from the head to the embedding: no workgroup waits for another.
+ * ofa_speech_step_route (host only): 1 when the shape is served -- D, out_dim, P, E multiples of 8, 1 <= layers <= 4, the rows of a
+ * workgroup fit the LDS -- else 0 (-1: unknown dtype); ofa_speech_step refuses the others with OFA_ERR_UNSUPPORTED and weights or
+ * buffers that are not 16-byte aligned with OFA_ERR_INVALID. */
+typedef struct ofa_speech_step_args {
+  const void* x;
+  int64_t ldx;
+  const void *feat_w, *feat_b, *eos_w, *eos_b;
+  const void* pre_w[4];
+  const void* pre_b[4];
+  const void *proj_w, *proj_b;
+  void* feats;
+  float* eos_prob;
+  int32_t *finished, *out_lens, *nfin;
+  uint8_t* pad_next;
+  void* embed;
+  const int64_t* offset_base;
+  const float* threshold;
+  uint64_t seed, offset, offset_stride;
+  int32_t B, D, out_dim, P, E, layers, step, T_cap;
+  float p_drop;
+} ofa_speech_step_args;
+int ofa_speech_step_rows(void);                                          /* host only */
+int ofa_speech_step_route(int D, int out_dim, int P, int E, int layers, int dtype);   /* host only */
+int ofa_speech_step(const ofa_speech_step_args* a, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

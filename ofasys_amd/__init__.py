@@ -13,11 +13,13 @@ from .model import GeneralistModel, GeneralistModelConfig  # noqa: E402,F401
 
 from .task import Task, TaskConfig  # noqa: E402,F401
 from .traverse import TraversePlan, TraverseTask  # noqa: E402,F401
-from .generator import DiverseBeamSearch, DiverseSiblingsSearch, Sampling  # noqa: E402,F401
+from .generator import (AutoRegressiveSpeechGenerator, DiverseBeamSearch, DiverseSiblingsSearch, Sampling,  # noqa: E402,F401
+                        SpeechGenerator, SpeechGeneratorOutput)
 from .scst import CiderD, ScstRewardCriterion  # noqa: E402,F401
 from .engine import Trainer, TrainerConfig  # noqa: E402,F401
 
 __all__ = ["Task", "TaskConfig", "TraverseTask", "TraversePlan", "Trainer", "TrainerConfig", "Instruction",
            "GeneralistModel", "GeneralistModelConfig", "Slot", "ModalityType", "Dictionary", "register_config",
            "ConfigStore", "AdaptorOutput", "BaseAdaptor", "BaseAdaptorConfig", "OFAGeneralAdaptor", "Sampling", "CiderD",
-           "ScstRewardCriterion", "DiverseBeamSearch", "DiverseSiblingsSearch"]
+           "ScstRewardCriterion", "DiverseBeamSearch", "DiverseSiblingsSearch", "SpeechGenerator", "AutoRegressiveSpeechGenerator",
+           "SpeechGeneratorOutput"]

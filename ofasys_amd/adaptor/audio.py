@@ -7,8 +7,10 @@ eval mode too) -> Linear(embed_dim) on the way in; on the way out feat_proj / eo
 postnet (Conv1d + BatchNorm1d + tanh + dropout) on channels-last rows over the padded layout (ops.conv1d_bn, ops.tanh_dropout).
 
 The whole parameter set of the reference adaptor is mirrored (decoder prenet / postnet / feat_proj / eos_proj / mask_emb)
-so checkpoints interchange; is_transformer_layers (a branch the reference itself cannot construct) raises NotImplementedError; the
-autoregressive speech generator is out of scope.  The time / channel mask
+so checkpoints interchange; is_transformer_layers (a branch the reference itself cannot construct) raises NotImplementedError.
+Generation (generator.AutoRegressiveSpeechGenerator) feeds the target branch one position per step through `forward_step`: the prenet
+is position-wise and its dropout draws are i.i.d., so only the new frame goes through it (the reference re-runs it over the whole frame
+history every step and keeps the last row, model/transformer.py:447-450).  The time / channel mask
 DRAWS (get_mask_indices, :401-450) belong to the speech-pretraining criterion, which hands them over in the slot value."""
 from dataclasses import dataclass, field
 
@@ -205,6 +207,54 @@ class AudioFbankAdaptor(BaseAdaptor):
             if mch is not None and not self.mask_channel_before:
                 feature = feature.masked_fill(mch, 0.0)
         return AdaptorOutput(feature, padding_mask, pos_embed, [])
+
+    def step_weights(self):
+        """(head, prenet, proj) as ops.speech_step takes them: the Linear parameters of the output head and of the input prenet."""
+        pre, proj = self.prenet[0], self.prenet[1]
+        return ((self.feat_proj.weight, self.feat_proj.bias, self.eos_proj.weight, self.eos_proj.bias),
+                [(layer[0].weight, layer[0].bias) for layer in pre.layers], (proj.weight, proj.bias))
+
+    def embed_frame(self, frame):
+        """frame [B, out_dim] -> [B, embed_dim]: the prenet (its dropout draws, as always) and the projection on ONE frame."""
+        pre, proj = self.prenet[0], self.prenet[1]
+        return ops.linear(pre(frame), proj.weight, proj.bias)
+
+    def forward_step(self, slot: Slot):
+        """The step form of the target branch (generation): slot.value = {"frame_embed": [B, 1, embed_dim], the prenet + projection of the
+        frame that enters at position t (`embed_frame`, or the step kernel's output); "step": t (host int); "padded": bool [B, 1], is
+        position t a padded key of its row}.  -> what the general adaptor returns for a [B, t + 1] target, reduced to what the decoder's
+        incremental path keeps of it: the embedding of position t after the post-forward hook's scale / LayerNorm / dropout, the mask
+        column of position t, the (normalised) position embedding of position t, and per bias table the ROW of position t of the
+        self-attention bias over the t + 1 keys, [B, A, 1, t + 1] (absolute-position term + the relative-position table row).  The
+        decoder builds the cross-attention position bias row from the position embedding.  Inference only."""
+        general = self.general_adaptor
+        embed, t, padded = slot.value["frame_embed"], int(slot.value["step"]), slot.value["padded"]
+        B, n = embed.shape[0], t + 1
+        if n > self.embed_audio_positions.weight.shape[0]:
+            raise ValueError(f"audio_fbank: {n} target frames exceed the {self.embed_audio_positions.weight.shape[0]} audio positions")
+        if self.cfg.entangle_position_embedding or general.cfg.entangle_position_embedding or getattr(general.cfg, "modal_ffn", False):
+            raise NotImplementedError("audio_fbank.forward_step: entangle_position_embedding / modal_ffn are not implemented for generation")
+        embed = ops.scale(embed, self.embed_scale)
+        if self.layernorm_embedding is not None:
+            embed = self.layernorm_embedding(embed)
+        embed = self.dropout_module(embed)                                     # (eval mode: the identity)
+        pos = self.embed_audio_positions(torch.arange(n, device=embed.device)[None, :])          # [1, n, D]
+        if self.layernorm_position is not None:
+            pos = self.layernorm_position(pos)
+        biases = []
+        if self.cfg.use_self_attn_bias:
+            # the row of position t: pos_q(pos_t) * scaling . pos_k(pos_0..t) per head, + rel_pos_table[bucket[t, 0..t]]
+            pos_q = general.pos_q_linear(pos[:, t:], alpha=general.pos_scaling)
+            pos_k = general.pos_k_linear(pos)
+            abs_row = ops.heads_matmul_nt(pos_q, pos_k, general.num_attention_heads)              # [1, A, 1, n]
+            if n > self.audio_rp_bucket.size(0):
+                raise ValueError(f"sequence length {n} exceeds the {self.audio_rp_bucket.size(0)} positions of audio_rp_bucket")
+            bucket = self.audio_rp_bucket[t, :n]                                                  # (a contiguous view: row t)
+            for idx in range(1 if self.cfg.share_attn_bias else self.num_layers):
+                rel = ops.embedding(bucket, self.audio_rel_pos_table_list[idx].weight)            # [n, A]
+                biases.append((abs_row + rel.t().reshape(1, -1, 1, n)).expand(B, -1, -1, -1).contiguous())
+        general.last_pos_shared = True
+        return embed, padded, pos[:, t:].expand(B, -1, -1), biases, None
 
     def forward_output(self, x, extra, slot, **kwargs):
         """adaptor/audio.py:468-477 -> (post, extra) with extra["eos_out"] [B, T, 1] and extra["feature_out"] (before the postnet).

@@ -68,6 +68,8 @@ class OFAGeneralAdaptor(torch.nn.Module):
         return self.name2adaptor[default_adaptor[slot.modality]]
 
     def forward(self, slots: List[Slot], **kwargs):
+        if len(slots) == 1 and isinstance(slots[0].value, dict) and "frame_embed" in slots[0].value:
+            return self.get_adaptor(slots[0]).forward_step(slots[0])        # one generated position (adaptor/audio.py forward_step)
         modality_outputs = [None for _ in range(len(slots))]
         cnt = 0
         for mod in ModalityType:                                        # general.py:137-149 (RNG/dropout order)

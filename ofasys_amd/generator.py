@@ -33,6 +33,11 @@ filled once per generate, outside the step graphs, from a seeded torch.Generator
 `SequenceGenerator(search_strategy=DiverseBeamSearch(...) | DiverseSiblingsSearch(...))` decodes diversely (utils/search.py:532-593,
 718-787): the row pass, the decoder step and the cache reorder are the plain ones, and the sentence pass is csrc/diverse_beam.hip's,
 which works on the candidates the row pass already lists.
+
+`AutoRegressiveSpeechGenerator` is the reference's generator of fbank frames (generator/speech_generator.py:84-200) on
+`SpeechStepDecoder`, a `StepDecoder` that feeds the decoder one embedded frame per step: the step's policy -- fbank head, sigmoid,
+finish rule, next padding flag, finished count, prenet of the new frame -- is one HIP launch (csrc/speech_step.hip) recorded with the
+decoder into the step's graph.
 """
 import math
 from dataclasses import dataclass
@@ -617,3 +622,212 @@ class TrieBeamGenerator(SequenceGenerator):
                                  f"(beam {self.beam_size}, min_len {self.min_len}, max_len {self.max_len}: no answer of the closed "
                                  "set survives the length limits and the beam)")
         return super()._collect(st, bsz)
+
+
+# ---------------------------------------------------------------------------------------------------------------- speech generation
+def _to_numpy(x):
+    return x.detach().cpu().float().numpy() if torch.is_tensor(x) else x
+
+
+@dataclass
+class SpeechGeneratorOutput:
+    """One generated utterance (generator/speech_generator.py:25-54): the denormalised frames [out_len, raw_dim], the end-of-sequence
+    probability of every frame, the head-averaged cross-attention of the alignment layer [S, out_len] with its arg-max per frame, and
+    with `has_targ` the target's frames.  `waveform` / `text` stay None: the vocoder is out of scope."""
+    feature: Any
+    eos_prob: torch.Tensor
+    attn: torch.Tensor
+    alignment: torch.Tensor
+    text: Optional[str] = None
+    waveform: Any = None
+    targ_feature: Any = None
+    targ_waveform: Any = None
+
+    def save_audio(self, audio_name: str, sample_rate: int = 22050, target: bool = False):
+        import soundfile as sf                                  # (only needed here; absent: ImportError)
+        waveform = _to_numpy(self.targ_waveform if target else self.waveform)
+        assert waveform is not None
+        if not audio_name.endswith(".wav"):
+            audio_name = audio_name + ".wav"
+        sf.write(audio_name, waveform, sample_rate)
+
+    def save_fbank(self, fbank_name: str, target: bool = False):
+        import numpy as np
+        feature = _to_numpy(self.targ_feature if target else self.feature)
+        assert feature is not None
+        if not fbank_name.endswith(".npy"):
+            fbank_name = fbank_name + ".npy"
+        np.save(fbank_name, feature)
+
+
+class SpeechGenerator:
+    """Base generator of the AUDIO modality (generator/speech_generator.py:57-81).  stats_npz_path: a LOCAL .npz holding the global
+    cepstral mean / variance statistics `mean` and `std` [raw_dim] (the reference also takes URLs; nothing here fetches one)."""
+
+    def __init__(self, src_dict, stats_npz_path: Optional[str] = None):
+        self.pad, self.unk, self.bos, self.eos = src_dict.pad(), src_dict.unk(), src_dict.bos(), src_dict.eos()
+        self.gcmvn_stats = None
+        if stats_npz_path is not None:
+            import numpy as np
+            with np.load(stats_npz_path) as f:
+                self.gcmvn_stats = {"mean": f["mean"], "std": f["std"]}
+
+    def gcmvn_denormalize(self, x):
+        """x [B, T, C] -> x * std + mean (the identity without statistics)."""
+        if self.gcmvn_stats is None:
+            return x
+        mean = torch.from_numpy(self.gcmvn_stats["mean"]).to(x)
+        std = torch.from_numpy(self.gcmvn_stats["std"]).to(x)
+        assert len(x.shape) == 3 and mean.shape[0] == std.shape[0] == x.shape[2]
+        x = x * std.view(1, 1, -1).expand_as(x)
+        return x + mean.view(1, 1, -1).expand_as(x)
+
+
+class SpeechStepDecoder(StepDecoder):
+    """StepDecoder for an [AUDIO:fbank] target: a step feeds the decoder ONE embedded frame through the audio adaptor's step form
+    (adaptor/audio.py forward_step) instead of a token prefix, returns the new position's features [B, D] and keeps the head-averaged
+    cross-attention row of the alignment layer in `state["attn"][:, t]`.  The buffers a step reads and writes (`state`, see
+    kernels.speech_step) sit at fixed addresses for the step graphs; steps from `graph_cap` on run eagerly (a captured
+    step costs device memory, and max_iter is in the thousands)."""
+
+    def __init__(self, model, max_len: int, target_slot: Slot, use_graph: bool = True, graph_cap: Optional[int] = None):
+        super().__init__(model, max_len, use_graph=use_graph, features_only=True)
+        self.graph_cap = self.max_len if graph_cap is None else int(graph_cap)
+        self.adaptor = model.decoder.adaptor.get_adaptor(target_slot)
+        self.attributes = target_slot.attributes
+        self.state: Optional[Dict[str, torch.Tensor]] = None
+        self._state_inc = None
+
+    def begin(self, src_slots: List[Slot], beam_order: Optional[torch.Tensor] = None):
+        super().begin(src_slots, beam_order)
+        rows, dtype, dev = self._shape[0], self._shape[2], self.tokens.device
+        ad = self.adaptor
+        if self._state_inc is not self.inc:                 # another batch shape (or other parameters): new buffers
+            i32 = dict(dtype=torch.int32, device=dev)
+            self.state = {
+                "feats": torch.zeros(rows, self.max_len, ad.out_dim, dtype=dtype, device=dev),
+                "eos_prob": torch.zeros(rows, self.max_len, dtype=torch.float32, device=dev),
+                "attn": torch.zeros(rows, self.max_len, self._shape[1], dtype=torch.float32, device=dev),
+                "finished": torch.zeros(rows, **i32), "out_lens": torch.zeros(rows, **i32), "nfin": torch.zeros(1, **i32),
+                "pad_next": torch.zeros(rows, 1, dtype=torch.bool, device=dev),
+                "embed": torch.zeros(rows, ad.cfg.embed_dim, dtype=dtype, device=dev),
+                "threshold": torch.zeros(1, dtype=torch.float32, device=dev),
+                "host": torch.zeros(2, dtype=torch.int32, pin_memory=True),
+            }
+            self._state_inc = self.inc
+        st = self.state
+        for name in ("finished", "nfin", "pad_next"):
+            st[name].zero_()
+        st["out_lens"].fill_(self.max_len)
+        with torch.no_grad():                               # position 0 is fed a zero frame (generator/speech_generator.py:142)
+            st["embed"].copy_(ad.embed_frame(torch.zeros(rows, ad.out_dim, dtype=dtype, device=dev)))
+        from . import ops
+        ops.rng_advance()
+        return self
+
+    def step(self, next_tokens=None, post=None, variant=None):
+        if self.use_graph and self.t >= self.graph_cap:     # beyond the cap: eagerly (the host-side cache lengths follow either way)
+            self.use_graph = False
+            try:
+                return super().step(next_tokens, post=post, variant=variant)
+            finally:
+                self.use_graph = True
+        return super().step(next_tokens, post=post, variant=variant)
+
+    def _run(self, t):
+        st = self.state
+        rows = st["embed"].shape[0]
+        slot = Slot(ModalityType.AUDIO, False, {"frame_embed": st["embed"].view(rows, 1, -1), "step": t, "padded": st["pad_next"]},
+                    attributes=self.attributes)
+        out, extra = self.model.decoder([slot], encoder_out=self.enc, incremental_state=self.inc, features_only=True)
+        st["attn"][:, t].copy_(extra["attn"][0][:, 0])      # [B, 1, S]: the new position's row
+        return out[:, -1]
+
+
+class AutoRegressiveSpeechGenerator(SpeechGenerator):
+    """The reference's autoregressive generator of fbank frames (generator/speech_generator.py:84-200) on `SpeechStepDecoder`: a step
+    is the decoder on ONE new position plus one launch (csrc/speech_step.hip: head, sigmoid, finish rule, next padding flag, finished
+    count, prenet of the new frame), recorded into the step's hipGraph -- no host synchronisation inside a step; the all-finished
+    count reaches the host one step late (`SequenceGenerator._loop`) and the step that may have run in excess is cut off before the
+    postnet.  Semantics are the reference's: the finish test is strict, finished rows keep decoding (their later positions are padded
+    keys of their own cache, their later frames are fed back and reach their kept frames through the postnet's window), rows that
+    never finish keep max_iter.  Differences ("Speech generation"): `attn` holds every step's map, results are on
+    the CPU, no waveform, a local statistics file.  fused_step=False (or a shape the kernel does not serve) runs the step's policy as
+    the unfused composition of the existing kernels; `fused` reports which ran."""
+
+    def __init__(self, src_dict, stats_npz_path: Optional[str] = None, max_iter: int = 6000, eos_prob_threshold: float = 0.5,
+                 use_graph: bool = True, fused_step: bool = True, graph_cap: Optional[int] = 512, **unused_kwargs):
+        super().__init__(src_dict, stats_npz_path)
+        self.max_iter, self.eos_prob_threshold = int(max_iter), float(eos_prob_threshold)
+        self.use_graph, self.fused_step, self.graph_cap = use_graph, bool(fused_step), graph_cap
+        self.fused: Optional[bool] = None                   # which step path the last generate() ran
+        self.steps_run = 0
+        self._dec: Optional[SpeechStepDecoder] = None
+
+    def check_limits(self, model, audio_adaptor):
+        """max_iter against what the model can address, before anything runs."""
+        for limit, what in ((audio_adaptor.embed_audio_positions.weight.shape[0], "embed_audio_positions"),
+                            (audio_adaptor.audio_rp_bucket.size(0), "audio_rp_bucket"),
+                            (model.decoder.max_positions(), "the decoder's max_target_positions")):
+            if self.max_iter > int(limit):
+                raise ValueError(f"AutoRegressiveSpeechGenerator: max_iter={self.max_iter} exceeds {what} ({int(limit)})")
+
+    @torch.no_grad()
+    def generate(self, model, sample, has_targ: bool = False, **kwargs):
+        from . import ops
+        model.eval()
+        net_input = sample["net_input"]
+        source_slots = [s for s in net_input["slots"] if s.is_src]
+        target_slot = Slot.get_target_slot_from_slots(net_input["slots"])
+        assert target_slot.modality == ModalityType.AUDIO, (
+            f"the target slot does not match the generator,"
+            f" target_slot: {target_slot.modality}, generator: AutoRegressiveSpeechGenerator")
+        ad = model.decoder.adaptor.get_adaptor(target_slot)
+        self.check_limits(model, ad)
+        first = source_slots[0].value
+        src = first["fbank"] if isinstance(first, dict) else first
+        bsz = src.shape[0]
+        n, out_dim = ad.n_frames_per_step, ad.out_dim
+        raw_dim = out_dim // n
+
+        if self._dec is None or self._dec.model is not model or self._dec.adaptor is not ad or self._dec.max_len != self.max_iter:
+            self._dec = SpeechStepDecoder(model, self.max_iter, target_slot, use_graph=self.use_graph, graph_cap=self.graph_cap)
+        dec = self._dec
+        dec.begin(source_slots)
+        st = dec.state
+        head, prenet, proj = ad.step_weights()
+        p_drop = float(ad.prenet[0].dropout)
+        self.fused = self.fused_step and ops.speech_step_fusable(st["embed"].dtype, head, prenet, proj)
+
+        def post(out, t):
+            ops.speech_step(out, head, prenet, proj, st, t, p_drop, fused=self.fused)
+            if p_drop > 0:
+                ops.rng_advance()                           # (captured: a replayed step moves the Philox position on the device)
+
+        st["threshold"].fill_(self.eos_prob_threshold)      # read on the device: a captured step serves every threshold
+        variant = ("fused" if self.fused else "unfused", p_drop)
+        SequenceGenerator._loop(self, dec, st, bsz, self.max_iter, post, None, lambda step: variant)
+
+        out_lens = st["out_lens"].cpu().long()
+        T_run = int(out_lens.max())                         # the steps the reference runs; one more may have run here: cut it off
+        assert T_run <= self.steps_run
+        feat = st["feats"][:, :T_run].contiguous()
+        feat = ad.postnet(feat, residual=feat)              # eval mode: running statistics, no dropout; over the padded [B, T_run]
+        eos_prob = st["eos_prob"][:, :T_run]
+        attn = st["attn"][:, :T_run].transpose(1, 2)        # [B, S, T_run]
+        alignment = attn.max(dim=1)[1]
+        feat = self.gcmvn_denormalize(feat.reshape(bsz, -1, raw_dim))
+        eos_prob = eos_prob.repeat_interleave(n, dim=1).cpu()
+        attn = attn.repeat_interleave(n, dim=2).cpu()
+        alignment = alignment.repeat_interleave(n, dim=1).cpu()
+        out_lens = out_lens * n
+        feat = feat.cpu()
+        finalized = [SpeechGeneratorOutput(feature=feat[b, :l].clone(), eos_prob=eos_prob[b, :l].clone(), attn=attn[b, :, :l].clone(),
+                                           alignment=alignment[b, :l].clone()) for b, l in enumerate(out_lens.tolist())]
+        if has_targ:
+            assert sample["target"].size(-1) == out_dim
+            tgt_feats = self.gcmvn_denormalize(sample["target"].view(bsz, -1, raw_dim))
+            tgt_lens = (sample["target_lengths"] * n).tolist()
+            for b, (f, l) in enumerate(zip(tgt_feats, tgt_lens)):
+                finalized[b].targ_feature = f[:l].cpu()
+        return finalized

@@ -8,7 +8,7 @@ import ctypes
 
 import torch
 
-from .lib import (BF16, F32, GEMM_ACCUM, GEMM_BIAS_COL, GEMM_BIAS_ROW, GEMM_FORCE_SIMPLE, GEMM_OUT_F32, OfaError,
+from .lib import (BF16, F16, F32, GEMM_ACCUM, GEMM_BIAS_COL, GEMM_BIAS_ROW, GEMM_FORCE_SIMPLE, GEMM_OUT_F32, OfaError,
                   dptr, dtype_code, lib, ptr, stream)
 
 _ws_cache = {}
@@ -2038,3 +2038,63 @@ def tacotron2_loss(feat_out, post, target, eos_out, lengths, bce_pos_weight, red
                ptr(d[1]) if grad else None, ptr(d[2]) if grad else None, int(bool(grad)), dtype_code(feat_out), dtype_code(target),
                stream())
     return out, d
+
+
+# ------------------------------------------------------------------ autoregressive speech generation (csrc/speech_step.hip)
+class _SpeechStepArgs(ctypes.Structure):      # ofa_speech_step_args
+    _fields_ = [("x", ctypes.c_void_p), ("ldx", ctypes.c_int64), ("feat_w", ctypes.c_void_p), ("feat_b", ctypes.c_void_p),
+                ("eos_w", ctypes.c_void_p), ("eos_b", ctypes.c_void_p), ("pre_w", ctypes.c_void_p * 4), ("pre_b", ctypes.c_void_p * 4),
+                ("proj_w", ctypes.c_void_p), ("proj_b", ctypes.c_void_p), ("feats", ctypes.c_void_p), ("eos_prob", ctypes.c_void_p),
+                ("finished", ctypes.c_void_p), ("out_lens", ctypes.c_void_p), ("nfin", ctypes.c_void_p), ("pad_next", ctypes.c_void_p),
+                ("embed", ctypes.c_void_p), ("offset_base", ctypes.c_void_p), ("threshold", ctypes.c_void_p), ("seed", ctypes.c_uint64), ("offset", ctypes.c_uint64),
+                ("offset_stride", ctypes.c_uint64), ("B", ctypes.c_int32), ("D", ctypes.c_int32), ("out_dim", ctypes.c_int32),
+                ("P", ctypes.c_int32), ("E", ctypes.c_int32), ("layers", ctypes.c_int32), ("step", ctypes.c_int32),
+                ("T_cap", ctypes.c_int32), ("p_drop", ctypes.c_float)]
+
+
+def speech_step_rows():
+    """Rows a workgroup of the step kernel owns (host only)."""
+    return int(lib().cdll.ofa_speech_step_rows())
+
+
+def speech_step_ok(D, out_dim, P, E, layers, dtype):
+    """Does the fused step kernel serve this shape (host only)?  dtype: a torch dtype."""
+    code = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}.get(dtype)
+    return code is not None and int(lib().cdll.ofa_speech_step_route(int(D), int(out_dim), int(P), int(E), int(layers), code)) == 1
+
+
+def speech_step(x, head, prenet, proj, state, step, p_drop, seed=0, offset=0, offset_stride=0, offset_base=None):
+    """One launch of ofa_speech_step.  x [B, D] (rows may be strided); head = (feat_w, feat_b, eos_w, eos_b); prenet = [(w, b), ...];
+    proj = (w, b); state: the generator's fixed-address buffers -- "feats" [B, T_cap, out_dim] and "embed" [B, E] of x's dtype,
+    "eos_prob" fp32 [B, T_cap], "finished" / "out_lens" int32 [B], "nfin" int32 [1], "pad_next" bool / uint8 [B], "threshold" fp32 [1] (the finish test p > threshold)."""
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise OfaError("speech_step: x must be [B, D] rows")
+    B, D = x.shape
+    feat_w, feat_b, eos_w, eos_b = head
+    feats, embed = state["feats"], state["embed"]
+    tensors = [feat_w, feat_b, eos_w, eos_b, proj[0], proj[1], feats, embed] + [t for wb in prenet for t in wb]
+    if any(t.dtype != x.dtype or not t.is_contiguous() for t in tensors):
+        raise OfaError("speech_step: the weights, feats and embed must be contiguous tensors of x's dtype")
+    out_dim, P, E = feat_w.shape[0], proj[0].shape[1], proj[0].shape[0]
+    if (feat_w.shape[1] != D or eos_w.numel() != D or eos_b.numel() != 1 or feats.shape[0] != B or feats.shape[2] != out_dim
+            or tuple(embed.shape) != (B, E) or tuple(state["eos_prob"].shape) != (B, feats.shape[1])
+            or state["eos_prob"].dtype != torch.float32 or len(prenet) > 4
+            or any(tuple(w.shape) != (P, out_dim if i == 0 else P) or b.numel() != P for i, (w, b) in enumerate(prenet))):
+        raise OfaError("speech_step: shape mismatch between x, the weights and the state buffers")
+    for name in ("finished", "out_lens", "nfin"):
+        if state[name].dtype != torch.int32 or state[name].numel() != (1 if name == "nfin" else B):
+            raise OfaError(f"speech_step: state['{name}'] must be int32 [{'1' if name == 'nfin' else 'B'}]")
+    if state["threshold"].dtype != torch.float32 or state["threshold"].numel() != 1:
+        raise OfaError("speech_step: state['threshold'] must be fp32 [1]")
+    pad = state["pad_next"]
+    if pad.numel() != B or pad.element_size() != 1 or not pad.is_contiguous():
+        raise OfaError("speech_step: state['pad_next'] must be a contiguous bool / uint8 [B]")
+    a = _SpeechStepArgs(x=ptr(x), ldx=x.stride(0), feat_w=ptr(feat_w), feat_b=ptr(feat_b), eos_w=ptr(eos_w), eos_b=ptr(eos_b),
+                        proj_w=ptr(proj[0]), proj_b=ptr(proj[1]), feats=ptr(feats), eos_prob=ptr(state["eos_prob"]),
+                        finished=ptr(state["finished"]), out_lens=ptr(state["out_lens"]), nfin=ptr(state["nfin"]), pad_next=ptr(pad),
+                        embed=ptr(embed), offset_base=ptr(offset_base), threshold=ptr(state["threshold"]), seed=int(seed), offset=int(offset),
+                        offset_stride=int(offset_stride), B=B, D=D, out_dim=out_dim, P=P, E=E, layers=len(prenet), step=int(step),
+                        T_cap=feats.shape[1], p_drop=float(p_drop))
+    for i, (w, b) in enumerate(prenet):
+        a.pre_w[i], a.pre_b[i] = ptr(w), ptr(b)
+    lib().call("ofa_speech_step", ctypes.addressof(a), dtype_code(x), stream())

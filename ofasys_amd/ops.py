@@ -2977,3 +2977,56 @@ def tacotron2_eval(feat_out, post, eos_out, target, lengths, bce_pos_weight=1.0,
     if target.dtype != feat_out.dtype:
         target = target.to(feat_out.dtype)
     return K.tacotron2_loss(feat_out, post, target, eos_out, lengths, bce_pos_weight, reduction)[0]
+
+
+# ---------------------------------------------------------------------------------------------- speech generation (csrc/speech_step.hip)
+def speech_step_fusable(x_dtype, head, prenet, proj):
+    """Can ofa_speech_step serve these weights: a served shape (K.speech_step_ok) and contiguous, 16-byte aligned tensors of one dtype?"""
+    feat_w, feat_b, eos_w, eos_b = head
+    tensors = [feat_w, feat_b, eos_w, eos_b, proj[0], proj[1]] + [t for wb in prenet for t in wb]
+    if not prenet or any(t.dtype != x_dtype or not t.is_contiguous() for t in tensors):
+        return False
+    if any(t.data_ptr() % 16 for t in (feat_w, eos_w, proj[0]) + tuple(w for w, _ in prenet)):
+        return False
+    return K.speech_step_ok(feat_w.shape[1], feat_w.shape[0], proj[0].shape[1], proj[0].shape[0], len(prenet), x_dtype)
+
+
+def speech_step(x, head, prenet, proj, state, step, p_drop, fused=True):
+    """Everything an autoregressive speech-generation step does after the decoder (generator/speech_generator.py:155-166 and the next
+    step's adaptor/audio.py:327-336 prenet), on the device, without a host synchronisation; inference only.  x [B, D]: the decoder's
+    output at the new position; head = (feat_w, feat_b, eos_w, eos_b), prenet = [(w, b), ...], proj = (w, b): the adaptor's Linear
+    parameters, read in place; state: kernels.speech_step's buffers.  fused: ONE launch (ofa_speech_step); else the unfused composition
+    of the existing kernels (linear / relu / dropout_add) and small torch ops on the state -- the same roundings and the same dropout
+    masks (both reserve the Philox positions of one [B, prenet_dim] dropout per layer, in layer order), so the two differ in the summation
+    order of the dot products alone."""
+    B = x.shape[0]
+    P = proj[0].shape[1]
+    if fused:
+        seed = off0 = stride = 0
+        base = None
+        if p_drop > 0:
+            offs = [_Rng.reserve(B * P, x.device) for _ in prenet]
+            seed, off0, base = offs[0]
+            stride = offs[1][1] - off0 if len(offs) > 1 else 0
+            assert all(o[1] == off0 + i * stride for i, o in enumerate(offs))
+        K.speech_step(x, head, prenet, proj, state, step, p_drop, seed, off0, stride, base)
+        return
+    feat_w, feat_b, eos_w, eos_b = head
+    feat = linear(x, feat_w, feat_b)
+    # (eos_proj has one output row: the GEMM runs 8 wide on zero-padded copies, as the training head does)
+    eos = linear(x, torch.nn.functional.pad(eos_w, (0, 0, 0, 7)), torch.nn.functional.pad(eos_b, (0, 7)))[:, 0]
+    p = torch.sigmoid(eos.float())
+    state["feats"][:, step].copy_(feat)
+    state["eos_prob"][:, step].copy_(p)
+    was = state["finished"].ne(0)
+    cross = p > state["threshold"]                                        # (fp32 [1] on the device: no threshold in a captured step)
+    newly = cross & ~was
+    state["out_lens"].masked_fill_(newly, step + 1)
+    state["nfin"].add_(newly.sum().to(torch.int32))
+    fin = was | cross
+    state["finished"].copy_(fin)
+    state["pad_next"].view(-1).copy_(fin)
+    h = feat
+    for w, b in prenet:
+        h = dropout_add(relu(linear(h, w, b)), None, p_drop, True)
+    state["embed"].copy_(linear(h, proj[0], proj[1]))

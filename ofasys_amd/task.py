@@ -5,10 +5,11 @@
     task.add_dataset(rows, "train")            # any sequence of dict rows: datasets.Dataset, list of dicts, ...
 
 Generation: `Task.generator` / `Task.inference` run beam search (ofasys_amd/generator.py SequenceGenerator; task/base.py:232-246,
-470-556, 727-793) for TEXT targets.
+470-556, 727-793) for TEXT targets and the autoregressive speech generator (AutoRegressiveSpeechGenerator; task/base.py:555-561) for
+AUDIO targets.
 Validation: `Task.valid_batches` walks a split once, in order; `Trainer.validate` (engine.py) runs it through the step engine's
 forward-only `valid_step` -- loss, NLL and, with `cfg.criterion.report_accuracy`, token accuracy (task/base.py:680-703).
-What stays out: file / OSS readers, multi-worker prefetch, generation metrics, non-text generators, checkpoint state.  The
+What stays out: file / OSS readers, multi-worker prefetch, generation metrics, the image / motion generators and the vocoder, checkpoint state.  The
 batch iterator is a plain in-process loop over the bound dataset: micro-batches of `micro_batch_size` rows, each rank of a
 data-parallel job reading its own contiguous shard (io/reader/dataset.py:49-53), reshuffled per epoch with a seeded permutation.
 """
@@ -304,6 +305,20 @@ class Task:
             raise ValueError(f"task {self.name}: initialize(global_dict) before building a generator")
         return SequenceGenerator(self.global_dict, **self.generator_kwargs(**gen_kwargs))
 
+    def build_speech_generator(self, stats_npz_path: Optional[str] = None, **gen_kwargs):
+        """AutoRegressiveSpeechGenerator from the reference's generator arguments (task/base.py:555-561): `max_iter` (default 1500) and
+        `eos_prob_threshold` (default 0.5) are taken out, the rest (beam-search arguments of the shared default JSON among them) is
+        ignored as there.  stats_npz_path: a local .npz with the `mean` / `std` of the global cepstral normalisation, or None (the
+        reference's default is a URL, which nothing here fetches)."""
+        from .generator import AutoRegressiveSpeechGenerator
+        if self.global_dict is None:
+            raise ValueError(f"task {self.name}: initialize(global_dict) before building a generator")
+        max_iter = gen_kwargs.pop("max_iter", 1500)
+        eos_prob_threshold = gen_kwargs.pop("eos_prob_threshold", 0.5)
+        extra = {k: gen_kwargs.pop(k) for k in ("use_graph", "fused_step", "graph_cap") if k in gen_kwargs}
+        return AutoRegressiveSpeechGenerator(self.global_dict, stats_npz_path=stats_npz_path, max_iter=max_iter,
+                                             eos_prob_threshold=eos_prob_threshold, **extra)
+
     def sampling_generator(self, **gen_kwargs):
         """SequenceGenerator(search_strategy=Sampling(...)) from the reference's generator arguments: `sampling`, `sampling_topk`,
         `sampling_topp` (task/base.py:488-515, with its checks) and `seed` are taken out here, the rest goes through
@@ -358,7 +373,8 @@ class Task:
 
     @property
     def generator(self):
-        """Built on first use from cfg.evaluation.generator_args (JSON) and cfg.constraint_range (text targets)."""
+        """Built on first use from cfg.evaluation.generator_args (JSON) and cfg.constraint_range (text targets); an [AUDIO:...]
+        target gets the autoregressive speech generator (`build_speech_generator`)."""
         if self._generator is None:
             gen_args = json.loads(self.cfg.evaluation.generator_args)
             if self.target_modality == ModalityType.TEXT:
@@ -366,6 +382,9 @@ class Task:
                 # SequenceGenerator refuses a trie rather than generate free text
                 gen_args["constraint_trie"] = self.general_preprocess.name2pre["text"].constraint_trie
                 gen_args["constraint_range"] = self.cfg.constraint_range
+            elif self.target_modality == ModalityType.AUDIO:
+                self._generator = self.build_speech_generator(**gen_args)
+                return self._generator
             elif self.target_modality is not None:
                 raise NotImplementedError(f"task {self.name}: generation for {self.target_modality} targets is not implemented")
             self._generator = self.build_generator(**gen_args)
@@ -396,7 +415,8 @@ class Task:
         """Beam search on `sample` (a collated batch); for TEXT targets every hypothesis gets `.text` through the task's text
         tokenizer (preprocessor/default/text.py:340-371).  As there, a sample with `prefix_tokens` has the sentence's prefix (its
         entries that are neither <pad> nor <eos>) cut from the front of `.tokens` before decoding; scores and positional scores
-        keep the prefix positions.  The model is left in eval mode."""
+        keep the prefix positions.  An AUDIO target: the speech generator's SpeechGeneratorOutput list, untouched.  The model is left
+        in eval mode."""
         model.eval()
         outputs = self.generator.generate(model, sample, **kwargs)
         if self.target_modality == ModalityType.TEXT:
