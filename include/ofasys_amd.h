@@ -1024,6 +1024,45 @@ int ofa_speech_step_rows(void);                                          /* host
 int ofa_speech_step_route(int D, int out_dim, int P, int E, int layers, int dtype);   /* host only */
 int ofa_speech_step(const ofa_speech_step_args* a, int dtype, void* stream);
 
+/* ---- motion diffusion training (adaptor/motion_6d.py:84-107, module/diffusion.py:156-173, engine/criterion/diffusion_loss.py:50-57),
+ * csrc/diffusion.hip: the three row passes around the stack.  x0, noise and the loss target are fp32 [B, T, Dd] (contiguous; Dd is
+ * rarely a multiple of 4: their rows are read with 16-byte loads when Dd % 4 == 0 and the base is aligned, one element per access
+ * otherwise); the model-dtype rows are W = max_data_dim wide and always take 16-byte accesses when W is a whole number of vectors.
+ * Levels t (int64 [B], device) index the fp32 schedule tables [n_levels]; a level outside [0, n_levels) is clamped.
+ *
+ * ofa_diffusion_q_sample: out [B, T, W] of `dtype` <-
+ *     x_t = fma(sqrt_acp[t_b], x0, sqrt_1m_acp[t_b] * noise)                      (fp32)
+ *     v   = known_w ? fma(known_w[b, t], x0, (1 - known_w[b, t]) * x_t) : x_t     (known_w fp32 [B, T] or NULL; 0 gives x_t, 1 gives x0, exactly)
+ *   rounded once to `dtype`; columns >= Dd and the frames with masks[b, t] != 0 (bool [B, T] or NULL) are exact zeros.
+ *
+ * ofa_film_fwd: out = (rows[r, :D] + 1) * h + rows[r, D:] over h [B, T, D], rows [R, 2D] (one dtype, contiguous, D % 8 == 0), r =
+ *   row_of[b, t] (int32 [B, T]) or b when row_of is NULL; fp32 arithmetic (the sum scale + 1 rounded, then one fma), one store rounding.
+ * ofa_film_bwd: dh = (rows[r, :D] + 1) * dout, and drows [R, 2D] of `dtype`: drows[r, :D] = sum of dout * h, drows[r, D:] = sum of dout
+ *   over the positions of row r, fp32 sums in a fixed order without atomics: workgroup (chunk, b) adds its OFA_FILM_CHUNK frames of
+ *   sentence b in ascending t into partial (fp32 [B, chunks, slots, 2D], chunks = ceil(T / OFA_FILM_CHUNK), slots = 1 without row_of,
+ *   else 2), then one pass adds the chunks in ascending order.  With row_of, R must be B + 1 and every row_of[b, t] either b or B: the
+ *   shared row B collects, in sentence order, every position that is not its sentence's own (the level-0 row of in-betweening).
+ *   Without it R >= B.  Every row of drows is written (rows nobody reads: zeros).
+ *
+ * ofa_diffusion_loss: out (fp32 [1]) = scale / B * sum_b( sum_{t unmasked} sum_{d < Dd} |w_b * (pred - target)| / (Dd * count_b) ),
+ *   count_b = the unmasked frames of sentence b (masks NULL: T), w_b = w[t_b] (w NULL, the epsilon objective: 1).  pred [B, T, W] of
+ *   `dtype` is read in place at columns < Dd.  Per-thread fp32 sums of a few elements, then fp64 in a fixed order: workgroup (i, b)
+ *   owns ofa_diffusion_loss_frames(Dd) frames of sentence b -> partial (fp64 [B, blocks]), counts (fp64 [B]); a second one-workgroup
+ *   launch folds them.  grad != 0: dpred [B, T, W] of `dtype` = seed[0] (device scalar; NULL: 1) * scale * w_b * sign(pred - target) /
+ *   (Dd * count_b * B), exact zeros at masked frames, at columns >= Dd and where pred == target.  A sentence without an unmasked
+ *   frame divides by zero like the reference (the host checks where lengths are host-known).  Equal inputs give equal bits. */
+enum { OFA_FILM_CHUNK = 16 };
+int ofa_diffusion_q_sample(const float* x0, const float* noise, const int64_t* t, const float* known_w, const void* masks,
+                           const float* sqrt_acp, const float* sqrt_1m_acp, int n_levels, int B, int T, int Dd, int W, void* out,
+                           int dtype, void* stream);
+int ofa_film_fwd(const void* h, const void* rows, const int32_t* row_of, int B, int T, int D, int R, void* out, int dtype, void* stream);
+int ofa_film_bwd(const void* dout, const void* h, const void* rows, const int32_t* row_of, int B, int T, int D, int R, void* dh,
+                 float* partial, void* drows, int dtype, void* stream);
+int64_t ofa_diffusion_loss_frames(int Dd);                               /* host only */
+int ofa_diffusion_loss(const void* pred, const float* target, const int64_t* t, const void* masks, const float* w, int n_levels,
+                       float scale, const float* seed, int B, int T, int Dd, int W, double* partial, double* counts, float* out,
+                       void* dpred, int grad, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

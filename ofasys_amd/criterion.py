@@ -20,6 +20,14 @@ that table, "tacotron2" (EXTRA_ROUTES): the model returns (post, extra) and ops.
 criterion (engine/criterion/tacotron2_loss.py) with reduction "mean"; validation is the same kernel without the gradient.  It carries
 none of the token criteria's keys and no pack plan (the postnet runs over the padded layout), and the reference criterion's guided
 attention loss and its own CTC term are refused.
+
+A motion-diffusion micro-batch -- "diffusion" (a diffusion.NoiseSchedule) next to ONE target slot whose value is a dict with a
+floating-point "value" [B, T, Dd] (adaptor/motion_6d.py) -- takes the route "diffusion" (DIFFUSION_ROUTES): the reference's diffusion_criterion
+(engine/criterion/diffusion_loss.py, module/diffusion.py `p_losses`).  `forward` draws the noise and one level per sentence on the
+device (or takes "noise" / "noise_level" from the micro-batch: tests and reproduction), noises the frames (ops.diffusion_q_sample) into
+a COPY of the slot value and runs the model with full_context_alignment=True (a denoiser's decoder is not causal); ops.diffusion_loss
+is the weighted L1 loss and the criterion's reduction in one launch, sample_size 1.  The token criteria's keys, a pack plan, a second
+target slot, a slot value that already holds "noise_level" and the two auxiliary losses (they need the BVH forward kinematics) are refused.
 """
 from typing import NamedTuple, Optional, Tuple
 
@@ -29,6 +37,7 @@ from . import ops
 
 ROUTES = ("speech_to_text", "trie_head", "trie_nodes", "scst", "label_smoothed", "plain")
 EXTRA_ROUTES = ("tacotron2",)           # routes whose target is not a token sequence: keyed by "target_lengths", never reached without it
+DIFFUSION_ROUTES = ("diffusion",)       # ... keyed by "diffusion" (kept apart: tests/test_tts_cpu.py pins EXTRA_ROUTES as it stood)
 
 
 class Settings(NamedTuple):
@@ -50,6 +59,8 @@ class Inputs(NamedTuple):
     plan: object
     encoder_out: Optional[dict]         # (speech_to_text alone)
     extra: Optional[dict] = None        # (tacotron2 alone: the output head's eos_out / feature_out; `logits` holds the postnet's frames)
+    # (diffusion: `logits` holds the frame decoder's [B, T, max_data_dim] rows, `target` x0 or the noise (fp32), `masks` the padding
+    #  mask, `extra` {"noise_level": the drawn levels})
 
 
 def output_projection(model):
@@ -68,6 +79,8 @@ def route(s, settings, training=True):
     A malformed node micro-batch under `edge_head` is no head batch: it meets the dense path's refusal."""
     def has(k):
         return s.get(k) is not None
+    if has("diffusion"):
+        return _route_diffusion(s, has)
     if has("target_lengths"):
         for k in ("reward", "constraint_nodes", "constraint_masks", "encoder_target"):
             if has(k):
@@ -117,8 +130,86 @@ def route(s, settings, training=True):
     return "plain"
 
 
+def _diffusion_slot(s):
+    """The one target slot of a motion-diffusion micro-batch (module/diffusion.py:19-33), or its refusal."""
+    targets = [sl for sl in s["slots"] if not sl.is_src]
+    if len(targets) != 1:
+        raise NotImplementedError(f"a diffusion micro-batch has {len(targets)} target slots: the diffusion decoder supports exactly one "
+                                  "(module/diffusion.py:21-24)")
+    v = targets[0].value
+    if not (isinstance(v, dict) and torch.is_tensor(v.get("value")) and v["value"].is_floating_point() and v["value"].dim() == 3):
+        raise ValueError("a diffusion micro-batch needs a target slot whose value is a dict with a floating-point \"value\" [B, T, Dd] "
+                         "(the motion_6d collation: preprocessor/motion.py)")
+    if v.get("masks") is None:
+        raise ValueError("a diffusion micro-batch's slot value needs \"masks\" (bool [B, T], True at padding)")
+    if "noise_level" in v:
+        raise ValueError("the slot value of a diffusion micro-batch already holds \"noise_level\": the criterion corrupts \"value\" and injects "
+                         "the level itself (module/diffusion.py:27-33); supply a level as the micro-batch's own \"noise_level\"")
+    return targets[0]
+
+
+def _route_diffusion(s, has):
+    for k in ("reward", "constraint_nodes", "constraint_masks", "constraint_trie", "encoder_target", "target_lengths"):
+        if has(k):
+            raise NotImplementedError(f"a diffusion micro-batch cannot carry {k}: its criterion is diffusion_criterion on continuous "
+                                      "frames (engine/criterion/diffusion_loss.py), not a token criterion")
+    if has("pack"):
+        raise NotImplementedError("a diffusion micro-batch cannot carry a pack plan: the denoiser's decoder attends without a causal "
+                                  "mask (full_context_alignment), which the packed layout does not serve")
+    for k in ("scale_aux_loss_1", "scale_aux_loss_2"):
+        if float(s.get(k, 0.0) or 0.0) > 0:
+            raise NotImplementedError(f"diffusion_criterion with {k} > 0 is not supported: custom_reg_loss needs the BVH header's forward "
+                                      "kinematics, which is not built")
+    _diffusion_slot(s)
+    return "diffusion"
+
+
+def _forward_diffusion(model, s):
+    import copy
+    sched = s["diffusion"]
+    slot = _diffusion_slot(s)
+    v = slot.value
+    adaptor = model.decoder.adaptor.get_adaptor(slot)
+    width = getattr(adaptor, "max_data_dim", None)
+    if width is None:
+        raise ValueError("a diffusion micro-batch's target slot must select the motion_6d adaptor ([MOTION:...,adaptor=motion_6d])")
+    if adaptor.max_noise_levels < sched.num_train_timesteps + 1:
+        raise ValueError(f"motion_6d: max_noise_levels {adaptor.max_noise_levels} < num_train_timesteps + 1 = {sched.num_train_timesteps + 1}")
+    x0 = v["value_0"] if v.get("value_0") is not None else v["value"]
+    x0 = x0 if x0.dtype == torch.float32 else x0.float()
+    B = x0.shape[0]
+    # the draws of p_losses (module/diffusion.py:158-159), on the device with torch's generator -- capture-aware: a replayed step draws
+    # anew -- unless the micro-batch supplies them
+    noise = s["noise"] if s.get("noise") is not None else torch.randn_like(x0)
+    t = s["noise_level"] if s.get("noise_level") is not None else \
+        torch.randint(0, sched.num_train_timesteps, (B,), device=x0.device, dtype=torch.long)
+    noise = noise if noise.dtype == torch.float32 else noise.float()
+    dtype = adaptor.frame_encoder[0].weight.dtype
+    known_w = v.get("known_w")
+    if known_w is not None and known_w.dtype != torch.float32:
+        known_w = known_w.float()
+    value = ops.diffusion_q_sample(x0, noise, t, sched, width, dtype, known_w=known_w, masks=v["masks"])
+    noised = copy.copy(slot)
+    noised.value = dict(v, value=value, noise_level=t, data_dim=int(x0.shape[-1]))
+    slots = [noised if sl is slot else sl for sl in s["slots"]]
+    pred, _ = model(slots, full_context_alignment=True)[:2]
+    target = x0 if sched.prediction_type == "sample" else noise
+    return Inputs(pred, target, v["masks"], None, None, None, {"noise_level": t})
+
+
+def _diffusion_scale(s):
+    """scale_main_loss times the criterion's weight (diffusion_loss.py:57, :85)."""
+    return float(s.get("scale_main_loss", 1.0)) * float(s.get("criterion_weight", 1.0))
+
+
+def _diffusion_ntokens(x):
+    return x.masks.numel() - x.masks.sum()
+
+
 def forward(model, s, kind, settings):
     """One micro-batch through `model` -> Inputs.  The train step and the validation step share it."""
+    if kind == "diffusion":
+        return _forward_diffusion(model, s)
     if kind == "tacotron2":                      # (no pack plan: route refused one) -> the frames after the postnet, and the head's extras
         post, extra = model(s["slots"])
         return Inputs(post, s["target"], None, None, None, None, extra)
@@ -173,12 +264,20 @@ def _tacotron_size(s):
     return n, (s["target"].shape[0] if s.get("sentence_avg") else None)
 
 
-def train_loss(model, s, kind, x, cfg, seed=None, stats=None, ctc_stat=None, tts_stat=None):
+def train_loss(model, s, kind, x, cfg, seed=None, stats=None, ctc_stat=None, tts_stat=None, diffusion_stat=None):
     """The routed criterion on x = forward(...) -> (loss, ntokens, sample_size or None: ntokens).  ntokens is None on the plain route:
     its statistics are the caller's (with `stats`, an ops.StepStats, the criterion kernel may have added them: stats.done).
     seed: the tensor the caller will hand to loss.backward (ops._SeededGrad), None when it is not known yet (loss scaling); the routes
     whose forward can write the logits' gradient take it."""
     size = None
+    if kind == "diffusion":
+        # the weighted L1 loss, the per-sentence masked mean and the prediction's gradient in one launch; sample_size is 1
+        # (diffusion_loss.py:59); the loss is added to `diffusion_stat` (fp64 [1]) on the device: the step's main_loss
+        loss = ops.diffusion_loss(x.logits, x.target, x.extra["noise_level"], s["diffusion"], masks=x.masks, scale=_diffusion_scale(s),
+                                  seed=seed)
+        if diffusion_stat is not None:
+            diffusion_stat += loss.detach()
+        return loss, _diffusion_ntokens(x), 1
     if kind == "tacotron2":
         # l1 + mse + eos under reduction "mean" (what task.train_step -> criterion(model, sample, update_num=) uses), loss and the three
         # gradients in one launch; the terms are added to `tts_stat` (fp64 [3]: l1, mse, eos) on the device
@@ -236,13 +335,20 @@ def train_loss(model, s, kind, x, cfg, seed=None, stats=None, ctc_stat=None, tts
     return loss, n, size
 
 
-def evaluate(model, s, kind, x, cfg, acc, ctc_stat=None, tts_acc=None):
+def evaluate(model, s, kind, x, cfg, acc, ctc_stat=None, tts_acc=None, diffusion_acc=None):
     """The routed criterion in eval mode on x = forward(...): adds [ntokens, loss_sum, nll_sum, n_correct] to `acc` (label_smoothing /
     constraint_range; no drop_worst: the reference's eval call never drops).  A speech-to-text micro-batch
     (speech_to_text_loss.py:259-322) evaluates the decoder side if ce_weight > 0 and, if ctc_weight > 0, adds its CTC loss to
     `ctc_stat` and decodes greedily on the device -> (tokens, lengths, encoder_target, ds); every other call returns None.
     A text-to-speech micro-batch adds [sample_size, sample_size * (loss, l1, mse, eos), ntokens] to `tts_acc` (fp64 [6]): the
-    reference's reduce_metrics weighs a batch's values by its sample_size (tacotron2_loss.py:201-214)."""
+    reference's reduce_metrics weighs a batch's values by its sample_size (tacotron2_loss.py:201-214).
+    A motion-diffusion micro-batch adds [sample_size = 1, loss, ntokens] to `diffusion_acc` (fp64 [3]; diffusion_loss.py:88-102)."""
+    if kind == "diffusion":
+        out = ops.diffusion_eval(x.logits, x.target, x.extra["noise_level"], s["diffusion"], masks=x.masks, scale=_diffusion_scale(s))
+        diffusion_acc[0:1] += 1.0
+        diffusion_acc[1:2] += out.double()
+        diffusion_acc[2:3] += _diffusion_ntokens(x)
+        return
     if kind == "tacotron2":
         out = ops.tacotron2_eval(x.extra["feature_out"], x.logits, x.extra["eos_out"], x.target, s["target_lengths"],
                                  float(s.get("bce_pos_weight", 1.0)), "mean")

@@ -247,13 +247,20 @@ class Trainer:
 
     def _plain_micro_batch(self, task, s):
         """A collated sample on the device as the micro-batch dict TrainStep.train_step / valid_step take."""
+        c = task.cfg.criterion
+        if c.name == "diffusion_criterion":               # motion diffusion: no token target (criterion.py, route "diffusion")
+            for sl in s["net_input"]["slots"]:            # (the collation's alias, which the device copy split in two)
+                if not sl.is_src and isinstance(sl.value, dict) and "value_0" in sl.value:
+                    sl.value["value_0"] = sl.value["value"]
+            return {"slots": s["net_input"]["slots"], "task": task.name, "diffusion": task.noise_schedule,
+                    "scale_main_loss": float(c.scale_main_loss), "criterion_weight": float(c.weight),
+                    "scale_aux_loss_1": float(c.scale_aux_loss_1), "scale_aux_loss_2": float(c.scale_aux_loss_2)}
         mb = {"slots": s["net_input"]["slots"], "target": s["target"], "task": task.name}
         if s.get("constraint_masks") is not None:
             mb["constraint_masks"] = s["constraint_masks"]
         if s.get("constraint_nodes") is not None:         # cfg.text.closed_set_nodes: one trie node per target position
             mb["constraint_nodes"] = s["constraint_nodes"]
             mb["constraint_trie"] = task.constraint_trie_on(self._device)
-        c = task.cfg.criterion
         if c.name == "speech_to_text_loss":               # (only such tasks: every other micro-batch is what it was)
             d = task.global_dict
             if "<phone>_dict_begin" not in d or "<phone>_dict_end" not in d:

@@ -2040,6 +2040,111 @@ def tacotron2_loss(feat_out, post, target, eos_out, lengths, bce_pos_weight, red
     return out, d
 
 
+# ------------------------------------------------------------------ motion diffusion training: csrc/diffusion.hip
+def _bool_mask(name, masks, B, T):
+    if masks is None:
+        return None
+    if masks.dtype != torch.bool or tuple(masks.shape) != (B, T):
+        raise OfaError(f"{name}: masks must be bool [B, T] = [{B}, {T}], got {masks.dtype} {tuple(masks.shape)}")
+    return masks.contiguous()
+
+
+def _levels(name, t, B):
+    if t.dtype != torch.int64 or t.numel() != B:
+        raise OfaError(f"{name}: the noise levels must be int64 [B] = [{B}], got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def diffusion_q_sample(x0, noise, t, sqrt_acp, sqrt_1m_acp, width, dtype, known_w=None, masks=None):
+    """-> the adaptor's input rows [B, T, width] of `dtype` (ofa_diffusion_q_sample).  x0, noise fp32 [B, T, Dd]; t int64 [B]; the two
+    fp32 schedule tables; known_w fp32 [B, T] or None; masks bool [B, T] or None (masked frames: zeros)."""
+    if x0.dim() != 3 or noise.shape != x0.shape or x0.dtype != torch.float32 or noise.dtype != torch.float32:
+        raise OfaError(f"diffusion_q_sample: x0 {x0.dtype} {tuple(x0.shape)} and noise {noise.dtype} {tuple(noise.shape)} must be one fp32 "
+                       "[B, T, Dd]")
+    B, T, Dd = x0.shape
+    if width < Dd:
+        raise OfaError(f"diffusion_q_sample: data_dim {Dd} exceeds max_data_dim {width}")
+    if sqrt_acp.dtype != torch.float32 or sqrt_1m_acp.dtype != torch.float32 or sqrt_acp.numel() != sqrt_1m_acp.numel():
+        raise OfaError("diffusion_q_sample: the schedule tables must be fp32 of one length")
+    if known_w is not None and (known_w.dtype != torch.float32 or tuple(known_w.shape) != (B, T)):
+        raise OfaError(f"diffusion_q_sample: known_w must be fp32 [B, T] = [{B}, {T}], got {known_w.dtype} {tuple(known_w.shape)}")
+    x0, noise, t, masks = x0.contiguous(), noise.contiguous(), _levels("diffusion_q_sample", t, B), _bool_mask("diffusion_q_sample", masks, B, T)
+    known_w = known_w.contiguous() if known_w is not None else None
+    out = torch.empty(B, T, int(width), dtype=dtype, device=x0.device)
+    lib().call("ofa_diffusion_q_sample", ptr(x0), ptr(noise), ptr(t), ptr(known_w), ptr(masks), ptr(sqrt_acp.contiguous()),
+               ptr(sqrt_1m_acp.contiguous()), sqrt_acp.numel(), B, T, Dd, int(width), ptr(out), dtype_code(out), stream())
+    return out
+
+
+def _film_args(name, h, rows, row_of):
+    if h.dim() != 3 or rows.dim() != 2 or rows.shape[1] != 2 * h.shape[2] or rows.dtype != h.dtype:
+        raise OfaError(f"{name}: h {h.dtype} {tuple(h.shape)} must be [B, T, D] and rows {rows.dtype} {tuple(rows.shape)} [R, 2D] of its dtype")
+    B, T, D = h.shape
+    if row_of is not None and (row_of.dtype != torch.int32 or tuple(row_of.shape) != (B, T)):
+        raise OfaError(f"{name}: row_of must be int32 [B, T] = [{B}, {T}], got {row_of.dtype} {tuple(row_of.shape)}")
+    return B, T, D, rows.shape[0]
+
+
+def film_fwd(h, rows, row_of=None):
+    """(rows[r, :D] + 1) * h + rows[r, D:] with r = row_of[b, t] (int32 [B, T]) or b (ofa_film_fwd)."""
+    B, T, D, R = _film_args("film_fwd", h, rows, row_of)
+    h, rows = h.contiguous(), rows.contiguous()
+    row_of = row_of.contiguous() if row_of is not None else None
+    out = torch.empty_like(h)
+    lib().call("ofa_film_fwd", ptr(h), ptr(rows), ptr(row_of), B, T, D, R, ptr(out), dtype_code(h), stream())
+    return out
+
+
+def film_bwd(dout, h, rows, row_of=None):
+    """-> (dh [B, T, D], drows [R, 2D]) of h's dtype (ofa_film_bwd).  With row_of, R = B + 1 and every entry is its sentence b or B."""
+    B, T, D, R = _film_args("film_bwd", h, rows, row_of)
+    if dout.shape != h.shape or dout.dtype != h.dtype:
+        raise OfaError("film_bwd: dout and h differ in shape or dtype")
+    dout, h, rows = dout.contiguous(), h.contiguous(), rows.contiguous()
+    row_of = row_of.contiguous() if row_of is not None else None
+    nch = (T + FILM_CHUNK - 1) // FILM_CHUNK
+    partial = torch.empty(max(B * nch * (2 if row_of is not None else 1) * 2 * D, 1), dtype=torch.float32, device=h.device)
+    dh, drows = torch.empty_like(h), torch.empty_like(rows)
+    lib().call("ofa_film_bwd", ptr(dout), ptr(h), ptr(rows), ptr(row_of), B, T, D, R, ptr(dh), ptr(partial), ptr(drows), dtype_code(h),
+               stream())
+    return dh, drows
+
+
+FILM_CHUNK = 16         # OFA_FILM_CHUNK of include/ofasys_amd.h: the frames a film_bwd workgroup sums (tests/test_diffusion_cpu.py compares the two)
+
+
+def diffusion_loss(pred, target, t, w, scale, data_dim=None, masks=None, seed=None, grad=False, dpred=None):
+    """-> (loss fp32 [1], dpred [B, T, W] of pred's dtype or None) (ofa_diffusion_loss).  pred [B, T, W] in the model dtype, read in
+    place at columns < Dd; target fp32 [B, T, Dd]; t int64 [B]; w: the fp32 table sqrt(snr + 1), or None (the epsilon objective: weight
+    1); masks bool [B, T] or None; seed: fp32 device scalar or None (1); dpred: a buffer to write into."""
+    if pred.dim() != 3 or target.dim() != 3 or target.dtype != torch.float32 or pred.shape[:2] != target.shape[:2]:
+        raise OfaError(f"diffusion_loss: pred {tuple(pred.shape)} must be [B, T, W] and target {target.dtype} {tuple(target.shape)} fp32 "
+                       "[B, T, Dd]")
+    B, T, W = pred.shape
+    Dd = target.shape[2]
+    if data_dim is not None and int(data_dim) != Dd:
+        raise OfaError(f"diffusion_loss: data_dim {data_dim} is not the target's width {Dd}")
+    if Dd > W:
+        raise OfaError(f"diffusion_loss: the target is {Dd} wide, the prediction rows only {W}")
+    if w is not None and w.dtype != torch.float32:
+        raise OfaError("diffusion_loss: the weight table must be fp32")
+    pred, target, masks = pred.contiguous(), target.contiguous(), _bool_mask("diffusion_loss", masks, B, T)
+    t = _levels("diffusion_loss", t, B) if t is not None else None
+    fpb = lib().cdll.ofa_diffusion_loss_frames(Dd)
+    nblk = (T + fpb - 1) // fpb
+    dev = pred.device
+    partial = torch.empty(B * nblk, dtype=torch.float64, device=dev)
+    counts = torch.empty(B, dtype=torch.float64, device=dev)
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    d = None
+    if grad:
+        d = dpred if dpred is not None else torch.empty_like(pred)
+    lib().call("ofa_diffusion_loss", ptr(pred), ptr(target), ptr(t), ptr(masks), ptr(w.contiguous()) if w is not None else None,
+               w.numel() if w is not None else 0, float(scale), ptr(seed), B, T, Dd, W, ptr(partial), ptr(counts), ptr(out), ptr(d),
+               int(bool(grad)), dtype_code(pred), stream())
+    return out, d
+
+
 # ------------------------------------------------------------------ autoregressive speech generation (csrc/speech_step.hip)
 class _SpeechStepArgs(ctypes.Structure):      # ofa_speech_step_args
     _fields_ = [("x", ctypes.c_void_p), ("ldx", ctypes.c_int64), ("feat_w", ctypes.c_void_p), ("feat_b", ctypes.c_void_p),

@@ -2979,6 +2979,82 @@ def tacotron2_eval(feat_out, post, eos_out, target, lengths, bce_pos_weight=1.0,
     return K.tacotron2_loss(feat_out, post, target, eos_out, lengths, bce_pos_weight, reduction)[0]
 
 
+# ---------------------------------------------------------------------------------------------- motion diffusion training (csrc/diffusion.hip)
+def diffusion_q_sample(x0, noise, t, schedule, width, dtype, known_w=None, masks=None):
+    """q-sample, the in-betweening mix and the zero padding to `width` columns in one pass (module/diffusion.py:160 `add_noise`,
+    adaptor/motion_6d.py:90-97) -> [B, T, width] of `dtype`, the rows the frame encoder's first GEMM reads.  x0, noise fp32 [B, T, Dd];
+    t int64 [B]; schedule: a diffusion.NoiseSchedule.  The inputs are data: no backward."""
+    tab = schedule.on(x0.device)
+    return K.diffusion_q_sample(x0, noise, t, tab.sqrt_acp, tab.sqrt_1m_acp, width, dtype, known_w=known_w, masks=masks)
+
+
+class FilmFn(torch.autograd.Function):
+    """out = (rows[r, :D] + 1) * h + rows[r, D:] (adaptor/motion_6d.py:106-107 on gathered table rows); the backward sums the rows'
+    gradient in fp32 in a fixed order (ofa_film_bwd)."""
+
+    @staticmethod
+    def forward(ctx, h, rows, row_of):
+        ctx.save_for_backward(h, rows, row_of)
+        return K.film_fwd(h, rows, row_of)
+
+    @staticmethod
+    def backward(ctx, dout):
+        h, rows, row_of = ctx.saved_tensors
+        dh, drows = K.film_bwd(dout, h, rows, row_of)
+        return dh, drows, None
+
+
+def film(h, rows, row_of=None):
+    """The noise-level modulation of h [B, T, D] by rows [R, 2D] = (scale | shift): position (b, t) takes row row_of[b, t] (int32
+    [B, T]; R = B + 1 and every entry its sentence b or the shared row B) or, without row_of, row b."""
+    return FilmFn.apply(h, rows, row_of)
+
+
+class DiffusionLossFn(torch.autograd.Function):
+    """module/diffusion.py:156-173 `p_losses` and the criterion's reduction (engine/criterion/diffusion_loss.py:50-57) in one launch.
+    With a usable seed (see _SeededGrad) the forward's one pass writes the prediction's gradient and the backward hands it out;
+    otherwise the backward runs the kernel again at the scale it is given."""
+
+    @staticmethod
+    def forward(ctx, pred, target, t, masks, w, scale, seed=None):
+        need = ctx.needs_input_grad[0]
+        ctx.seeded = _SeededGrad()
+        ctx.scale = float(scale)
+        pre = need and _SeededGrad.usable(seed, pred.device)
+        out, d = K.diffusion_loss(pred, target, t, w, scale, masks=masks, seed=seed if pre else None, grad=pre)
+        if pre:
+            ctx.seeded = _SeededGrad(seed, d)
+        if need:
+            ctx.save_for_backward(pred, target, t, masks, w)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        pred, target, t, masks, w = ctx.saved_tensors
+        d = ctx.seeded.take(dloss)
+        if d is None:
+            _, d = K.diffusion_loss(pred, target, t, w, ctx.scale, masks=masks, seed=dloss.reshape(1).float().contiguous(), grad=True,
+                                    dpred=ctx.seeded.spare())
+        return d, None, None, None, None, None, None
+
+
+def _diffusion_weights(schedule, device):
+    """The fp32 table sqrt(snr + 1) for the `sample` objective, None for `epsilon` (weight 1)."""
+    return schedule.on(device).w if schedule.prediction_type == "sample" else None
+
+
+def diffusion_loss(pred, target, t, schedule, masks=None, scale=1.0, seed=None):
+    """-> the fp32 loss scale * mean_b(sum_t(!mask * mean_d |w_b (pred - target)|) / sum_t(!mask)).  pred [B, T, max_data_dim]: the frame
+    decoder's rows in the model dtype, read in place at the target's columns; target fp32 [B, T, Dd]: x0 for the `sample` objective
+    (w_b = sqrt(snr(t_b) + 1)), the noise for `epsilon` (w_b = 1); t int64 [B]; masks bool [B, T] (True: padding) or None."""
+    return DiffusionLossFn.apply(pred, target, t, masks, _diffusion_weights(schedule, pred.device), float(scale), seed)
+
+
+def diffusion_eval(pred, target, t, schedule, masks=None, scale=1.0):
+    """The validation form: the same launch without the gradient -> fp32 [1]."""
+    return K.diffusion_loss(pred, target, t, _diffusion_weights(schedule, pred.device), scale, masks=masks)[0]
+
+
 # ---------------------------------------------------------------------------------------------- speech generation (csrc/speech_step.hip)
 def speech_step_fusable(x_dtype, head, prenet, proj):
     """Can ofa_speech_step serve these weights: a served shape (K.speech_step_ok) and contiguous, 16-byte aligned tensors of one dtype?"""

@@ -24,6 +24,7 @@ import torch
 from .preprocessor.collate import (BoxPreprocessConfig, DefaultBoxPreprocess, DefaultTextPreprocess, GeneralPreprocess,
                                    PreprocessConfig, TensorPreprocess, TextPreprocessConfig, default_preprocess)
 from .preprocessor.audio import FbankPreprocess
+from .preprocessor.motion import Motion6dPreprocess
 from .preprocessor.instruction import Instruction, ModalityType, Slot
 
 # adaptor/general.py:36-46
@@ -59,7 +60,14 @@ class CriterionConfig:                                # engine/criterion/label_s
     # (cfg.text.phone_dict registers them); ce_weight, ctc_weight, zero_infinity (and sentence_avg) are its own, the reference's defaults
     # "ofa_tacotron2" (engine/criterion/tacotron2_loss.py:24-45; a task whose target slot is [AUDIO:fbank]): bce_pos_weight and
     # sentence_avg are honoured; use_guided_attention_loss = True and its own ctc_weight > 0 are refused before the model runs
+    # "diffusion_criterion" (engine/criterion/diffusion_loss.py:15-31; a task whose target slot is [MOTION:...,adaptor=motion_6d], with
+    # TaskConfig.diffuser_args): scale_main_loss and weight scale the loss; scale_aux_loss_1 / scale_aux_loss_2 > 0 are refused before
+    # the model runs (custom_reg_loss needs the BVH forward kinematics)
     name: str = "label_smoothed_cross_entropy"
+    weight: float = 1.0
+    scale_main_loss: float = 1.0
+    scale_aux_loss_1: float = 0.0
+    scale_aux_loss_2: float = 0.0
     bce_pos_weight: float = 1.0
     use_guided_attention_loss: bool = False
     ce_weight: float = 1.0
@@ -97,6 +105,8 @@ class TaskConfig:                                     # task/base.py:157-189
     constraint_range: Optional[str] = None
     scst: bool = False                                # self-critical sequence training (task/base.py:170-174)
     scst_args: str = "{}"                             # generation arguments of the SCST generator, as JSON
+    # the noise schedule of diffusion training, as JSON (task/base.py:176-179; diffusion.NoiseSchedule lists the keys)
+    diffuser_args: str = '{"scheduler": "DDIMScheduler", "num_inference_steps": 50}'
     _name: Optional[str] = None
 
     def update(self, **kwargs):
@@ -158,6 +168,11 @@ class Task:
         self._sampling_gens: Dict[Any, Any] = {}
         self._diverse_gens: Dict[Any, Any] = {}
         self._trie_dev: Dict[Any, Any] = {}                  # device -> (plan, its device arrays): constraint_trie_on
+        from .diffusion import parse_diffuser_args
+        self.diffuser_args = parse_diffuser_args(self.cfg.diffuser_args)       # (task/base.py:207; an unknown key or value raises here)
+        self._noise_schedule = None
+        if self.cfg.criterion.name == "diffusion_criterion":
+            self._check_diffusion_target()
 
     # ------------------------------------------------------------------ identity / datasets (task/base.py:256-273)
     @property
@@ -176,6 +191,22 @@ class Task:
 
     def add_test_dataset(self, dataset):
         self.add_dataset(dataset, "test")
+
+    def _check_diffusion_target(self):
+        """diffusion_criterion trains continuous motion frames only: every template's target slot must be MOTION with adaptor=motion_6d."""
+        for template in self.templates or []:
+            slot = Slot.get_target_slot_from_slots(Instruction(template).slots)
+            if slot.modality != ModalityType.MOTION or slot.get_attr("adaptor") != "motion_6d":
+                raise ValueError(f"task {self.name}: criterion diffusion_criterion needs a [MOTION:...,adaptor=motion_6d] target slot, "
+                                 f"got [{slot.modality.name}] with adaptor={slot.get_attr('adaptor')!r}")
+
+    @property
+    def noise_schedule(self):
+        """diffusion.NoiseSchedule(**diffuser_args), built once: the step engine's captured graphs address its device tables."""
+        if self._noise_schedule is None:
+            from .diffusion import NoiseSchedule
+            self._noise_schedule = NoiseSchedule(**self.diffuser_args)
+        return self._noise_schedule
 
     def infer_target_modality(self, instruction: Union[str, Instruction]):
         if not isinstance(instruction, Instruction):
@@ -198,6 +229,7 @@ class Task:
         # (source-side and plain tensor values as TensorPreprocess; a target-side fbank slot collates as a text-to-speech target)
         name2pre["audio"] = FbankPreprocess(global_dict, PreprocessConfig(), ModalityType.AUDIO)
         name2pre["table"] = name2pre["phone"] = name2pre["text"]     # STRUCT / PHONE columns arrive as token ids (text adaptor)
+        name2pre["motion_6d"] = Motion6dPreprocess(global_dict)      # rot6d frames: a slot selects it with preprocess=motion_6d
         self.general_preprocess = GeneralPreprocess(global_dict, name2pre)
 
     @classmethod

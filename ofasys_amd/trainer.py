@@ -202,8 +202,8 @@ def _walk(obj, path, out):
     elif hasattr(obj, "tensors") and hasattr(obj, "structure"):         # a packing.PackPlan: index / segment tables
         for i, t in enumerate(obj.tensors()):
             out.append((path + (i,), t))
-    elif obj is None or isinstance(obj, (str, int, float, bool)):
-        pass
+    elif obj is None or isinstance(obj, (str, int, float, bool)) or getattr(obj, "capture_constant", False):
+        pass                                           # (capture_constant: a diffusion.NoiseSchedule -- its device tables never change)
     else:
         raise _Uncapturable(f"{'/'.join(map(str, path))}: {type(obj).__name__}")
 
@@ -228,7 +228,8 @@ def sample_structure(samples):
                       for sl in s["slots"])
         scal = tuple((k, s[k]) for k in sorted(s) if isinstance(s[k], (str, int, float, bool)))
         plan = s["pack"].structure() if s.get("pack") is not None else None          # launch bounds of a ragged batch
-        sig.append((slots, scal, plan))
+        diff = s["diffusion"].structure() if s.get("diffusion") is not None else None    # (the objective chooses the loss kernel's inputs)
+        sig.append((slots, scal, plan) if diff is None else (slots, scal, plan, diff))
     tens = tuple((p, tuple(t.shape), str(t.dtype)) for p, t in sample_tensors(samples))
     return (tuple(sig), tens)
 
@@ -300,6 +301,7 @@ class TrainStep:
         self._stats = torch.zeros(3, dtype=torch.float64, device=dev)      # [sample_size, loss_sum, ntokens]
         self._ctc_stat = torch.zeros(1, dtype=torch.float64, device=dev)   # sum of the step's CTC losses (speech-to-text micro-batches)
         self._tts_stat = torch.zeros(3, dtype=torch.float64, device=dev)   # the step's [l1, mse, eos] terms (text-to-speech micro-batches)
+        self._diffusion_stat = torch.zeros(1, dtype=torch.float64, device=dev)   # the step's summed main_loss (motion-diffusion micro-batches)
         self._gsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self._gnorm_t = torch.zeros(1, dtype=torch.float32, device=dev)
         # device-resident schedule: _step_t = number of updates done; _lr_t = learning rate; _sched = [grad multiplier,
@@ -367,6 +369,9 @@ class TrainStep:
         # text-to-speech micro-batches: [sample_size, sample_size * (loss, l1, mse, eos), ntokens] of the pass, and whether it held any
         self._valid_tts = torch.zeros(6, dtype=torch.float64, device=dev)
         self._valid_has_tts = False
+        # motion-diffusion micro-batches: [sample_size (1 each), loss, ntokens] of the pass
+        self._valid_diffusion = torch.zeros(3, dtype=torch.float64, device=dev)
+        self._valid_has_diffusion = False
         self._valid_decodes = []                    # per such micro-batch (greedy tokens, their lengths, encoder_target, ds), on the device
         self._valid_graphs = {}                     # (batch structure, use_ema) -> dict(graphs, static samples, seen count)
         self._warned_valid_cap = False
@@ -403,6 +408,8 @@ class TrainStep:
             stt = (self._ctc_stat,) if "speech_to_text" in routes else ()
             if "tacotron2" in routes:                # (likewise: the text-to-speech terms are cleared only by a step that adds to them)
                 stt += (self._tts_stat,)
+            if "diffusion" in routes:
+                stt += (self._diffusion_stat,)
             ops.grad_begin(self.fp.grad, self._prezero.get(structure, ()), also=(self._stats, self._gsq) + stt)
             self._gsq_cleared = True
         else:
@@ -413,6 +420,8 @@ class TrainStep:
                 self._ctc_stat.zero_()
             if "tacotron2" in routes:
                 self._tts_stat.zero_()
+            if "diffusion" in routes:
+                self._diffusion_stat.zero_()
         self.reducer.overlap = overlap_reduce
         # gradients are only read after backward unless buckets are all-reduced from inside it: fold lazily, in batches
         ops.defer_reductions(self.world == 1 or not overlap_reduce)
@@ -462,7 +471,7 @@ class TrainStep:
         for s, kind in zip(samples, routes):
             x = criterion.forward(self.model, s, kind, cfg)
             loss, n, size = criterion.train_loss(self.model, s, kind, x, cfg, seed=self._loss_seed(), stats=fused, ctc_stat=self._ctc_stat,
-                                                      tts_stat=self._tts_stat)
+                                                      tts_stat=self._tts_stat, diffusion_stat=self._diffusion_stat)
             counted = False
             if n is None:                            # the plain route: its statistics are added before the backward
                 if fused is not None and fused.done:     # (the criterion kernel's last block added them)
@@ -591,7 +600,7 @@ class TrainStep:
         own = list(self.model.parameters()) + list(self.model.buffers())
         own += [self.fp.flat, self.fp.grad, self.master, self.exp_avg, self.exp_avg_sq, self._stats, self._gsq, self._gnorm_t,
                 self._step_t, self._lr_t, self._sched, self._seed, getattr(self, "_ls", None), self._valid_acc, self._ctc_stat,
-                self._valid_ctc, self._tts_stat, self._valid_tts]
+                self._valid_ctc, self._tts_stat, self._valid_tts, self._diffusion_stat, self._valid_diffusion]
         own += list(ops._Rng.base.values())
         if self.ema is not None:
             own += self.ema.arenas()
@@ -621,6 +630,8 @@ class TrainStep:
         applies) with "constraint_trie" (Task.constraint_trie_on; optional "constraint_nodes_packed" as "target_packed"); "encoder_target"
         with "ctc_range"; "target_lengths" (int64 [B]) with a floating-point "target" [B, T, F] of fbank frames: text-to-speech, the
         ofa_tacotron2 criterion (optional "bce_pos_weight", "sentence_avg"), whose step reports l1_loss / mse_loss / eos_loss in `last`.
+        "diffusion" (a diffusion.NoiseSchedule) with one target slot of continuous motion frames (adaptor/motion_6d.py): diffusion training
+        (optional "noise" / "noise_level": the draws; "scale_main_loss", "criterion_weight"), whose step reports main_loss in `last`.
         criterion.route names each micro-batch's criterion, or refuses the dict, before anything runs."""
         routes = [criterion.route(s, self.criterion) for s in samples]
         done = False
@@ -677,6 +688,8 @@ class TrainStep:
             self.last["ctc_loss"] = self._ctc_stat          # (the step's summed CTC term; other steps report what they always did)
         if "tacotron2" in routes:                           # (the terms of the step's text-to-speech micro-batches, summed over them)
             self.last["l1_loss"], self.last["mse_loss"], self.last["eos_loss"] = self._tts_stat[0:1], self._tts_stat[1:2], self._tts_stat[2:3]
+        if "diffusion" in routes:                           # (the summed loss of the step's motion-diffusion micro-batches: sample_size 1 each)
+            self.last["main_loss"] = self._diffusion_stat
         if self.loss_scale_cfg is not None:
             self.last["loss_scale"] = self._ls[0:1]
         return self.last
@@ -688,6 +701,8 @@ class TrainStep:
         self._valid_ctc.zero_()
         self._valid_tts.zero_()
         self._valid_has_tts = False
+        self._valid_diffusion.zero_()
+        self._valid_has_diffusion = False
         self._valid_decodes = []
 
     @contextlib.contextmanager
@@ -721,7 +736,8 @@ class TrainStep:
         with self._valid_mode(model):
             for s, kind in zip(samples, routes):
                 x = criterion.forward(model, s, kind, self.criterion)
-                decode = criterion.evaluate(model, s, kind, x, self.criterion, self._valid_acc, self._valid_ctc, self._valid_tts)
+                decode = criterion.evaluate(model, s, kind, x, self.criterion, self._valid_acc, self._valid_ctc, self._valid_tts,
+                                            self._valid_diffusion)
                 if decode is not None:
                     outs.append(decode)
         return outs
@@ -765,6 +781,7 @@ class TrainStep:
         Nothing is returned and nothing synchronises: `valid_result()` reads the pass."""
         routes = [criterion.route(s, self.criterion, training=False) for s in samples]
         self._valid_has_tts = self._valid_has_tts or "tacotron2" in routes
+        self._valid_has_diffusion = self._valid_has_diffusion or "diffusion" in routes
         if use_ema:
             if self.ema is None:
                 raise RuntimeError("valid_step(use_ema=True) needs an EMA of the weights: build the engine with ema={'store_ema': True}")
@@ -841,6 +858,16 @@ class TrainStep:
                 res.update({"loss": loss / d, "ntokens": ntok, "sample_size": ss})
             else:
                 res["tts_loss"] = loss / d
+        if self._valid_has_diffusion:
+            # motion-diffusion batches (diffusion_loss.py:88-102 `reduce_metrics`): the losses' sum over sample_size (1 per batch),
+            # natural units; a pass of such batches alone reports it as its loss
+            acc = self._valid_diffusion
+            if self.world > 1:
+                acc = all_reduce_scalars(acc.clone(), self.group)
+            ss, loss, ntok = acc.tolist()
+            res["main_loss"] = loss / max(ss, 1.0)
+            if res["ntokens"] == 0:
+                res.update({"loss": loss / max(ss, 1.0), "ntokens": ntok, "sample_size": ss})
         return res
 
 
