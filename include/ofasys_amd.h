@@ -611,6 +611,13 @@ int ofa_step_schedule_scaled(const float* gsq, const double* sample_size, double
 int ofa_adam_step(float* master, float* exp_avg, float* exp_avg_sq, const void* grad, void* model_param,
                   const float* coef, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                   int step, int dtype, void* stream);
+/* The same with the grid capped at max_blocks blocks of 256 threads: 0 = the kernel's own cap of 65536 (a test reaches the second
+ * quad of a thread and the second grid-stride trip at a small n with it).  ofa_adam_step forwards here with 0.
+ * ofa_adam_step_blocks: host only, the blocks that launch has for n parameters (-1: bad argument). */
+int ofa_adam_step_grid(float* master, float* exp_avg, float* exp_avg_sq, const void* grad, void* model_param,
+                       const float* coef, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                       int step, int dtype, int max_blocks, void* stream);
+int ofa_adam_step_blocks(int64_t n, int max_blocks);
 /* EMA shadow of the weights (engine/ema/ema.py:140-194), decided and applied on the device so that a captured step replays the
  * rule: with t = step[0] (fp64, the number of completed updates) and skip = sched[3] as ofa_step_schedule[_scaled] left them,
  *   apply <=> skip == 0 and t % update_freq == 0;  d = t < start_update ? 0 : decay;  a = fp32(1 - d), rounded once more to a

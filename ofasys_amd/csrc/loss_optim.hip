@@ -1533,11 +1533,20 @@ extern "C" int ofa_sumsq_schedule(const void* x, float* gsq, float* ws, unsigned
   return check_launch("sumsq_schedule");
 }
 
-extern "C" int ofa_adam_step(float* master, float* exp_avg, float* exp_avg_sq, const void* grad, void* model_param,
-                             const float* coef, int64_t n, float lr, float beta1, float beta2, float eps,
-                             float weight_decay, int step, int dtype, void* stream) {
+// Host only: the blocks ofa_adam_step_grid launches for n parameters -- one thread per parameter (a thread owns quads, so three in four
+// idle below the cap), at most max_blocks (0: the kernel's own cap of 65536); -1 for a bad argument.
+extern "C" int ofa_adam_step_blocks(int64_t n, int max_blocks) {
+  if (n < 0 || max_blocks < 0) return -1;
+  const int64_t nbl = (n + 255) / 256;
+  const int64_t cap = max_blocks > 0 ? max_blocks : 65536;      // (small blocks of work: the tail of a 4096-block grid cost 15 %)
+  return (int)(nbl > cap ? cap : nbl);
+}
+
+extern "C" int ofa_adam_step_grid(float* master, float* exp_avg, float* exp_avg_sq, const void* grad, void* model_param,
+                                  const float* coef, int64_t n, float lr, float beta1, float beta2, float eps,
+                                  float weight_decay, int step, int dtype, int max_blocks, void* stream) {
   OFA_REQUIRE(OFA_DT_OK(dtype), OFA_ERR_INVALID, "adam_step: bad dtype %d", dtype);
-  OFA_REQUIRE(n >= 0 && step >= 0 && master && exp_avg && exp_avg_sq && grad && model_param, OFA_ERR_INVALID, "adam_step: bad argument");
+  OFA_REQUIRE(n >= 0 && step >= 0 && max_blocks >= 0 && master && exp_avg && exp_avg_sq && grad && model_param, OFA_ERR_INVALID, "adam_step: bad argument");
   OFA_REQUIRE(step >= 1 || coef, OFA_ERR_INVALID, "adam_step: step == 0 takes the step size and lr from coef[1], coef[2]");
   if (n == 0) return 0;
   // adam.py:205-207
@@ -1547,13 +1556,19 @@ extern "C" int ofa_adam_step(float* master, float* exp_avg, float* exp_avg_sq, c
   hipStream_t st = (hipStream_t)stream;
   OFA_REQUIRE(!(((uintptr_t)master | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) && !(((uintptr_t)grad | (uintptr_t)model_param) & 7),
               OFA_ERR_INVALID, "adam_step: arenas must be 16-byte (fp32 state) / 8-byte (grad, model copy) aligned");
-  int64_t nbl = (n + 255) / 256;
-  const int nb = (int)(nbl > 65536 ? 65536 : nbl);      // (small blocks of work: the tail of a 4096-block grid cost 15 %)
+  const int nb = ofa_adam_step_blocks(n, max_blocks);
   dispatch_dtype(dtype, [&](auto tag) {
     using T = typename decltype(tag)::type;
     hipLaunchKernelGGL((adam_kernel<T>), dim3(nb), dim3(256), 0, st, master, exp_avg, exp_avg_sq, (const T*)grad, (T*)model_param, coef, n, lr, beta1, beta2, eps, weight_decay, step_size, dev_sched);
   });
   return check_launch("adam_step");
+}
+
+extern "C" int ofa_adam_step(float* master, float* exp_avg, float* exp_avg_sq, const void* grad, void* model_param,
+                             const float* coef, int64_t n, float lr, float beta1, float beta2, float eps,
+                             float weight_decay, int step, int dtype, void* stream) {
+  return ofa_adam_step_grid(master, exp_avg, exp_avg_sq, grad, model_param, coef, n, lr, beta1, beta2, eps, weight_decay, step, dtype, 0,
+                            stream);
 }
 
 // the checks the two EMA entry points share; fills the rule the kernels take

@@ -1309,10 +1309,14 @@ def step_schedule_scaled(gsq, sample_size, step, lr, sched, gnorm, loss_scaler, 
                float(threshold or 0.0), float(min_loss_scale), stream())
 
 
-def adam_step(master, exp_avg, exp_avg_sq, grad, model_param, coef, lr, beta1, beta2, eps, weight_decay, step):
-    lib().call("ofa_adam_step", ptr(master), ptr(exp_avg), ptr(exp_avg_sq), ptr(grad), ptr(model_param), ptr(coef),
-               master.numel(), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay), int(step),
-               dtype_code(grad), stream())
+def adam_step(master, exp_avg, exp_avg_sq, grad, model_param, coef, lr, beta1, beta2, eps, weight_decay, step, max_blocks=0):
+    """max_blocks > 0: ofa_adam_step_grid with the grid capped there (a test reaches the second quad and the second trip at a small n)."""
+    args = (ptr(master), ptr(exp_avg), ptr(exp_avg_sq), ptr(grad), ptr(model_param), ptr(coef), master.numel(), float(lr), float(beta1),
+            float(beta2), float(eps), float(weight_decay), int(step), dtype_code(grad))
+    if max_blocks:
+        lib().call("ofa_adam_step_grid", *args, int(max_blocks), stream())
+    else:
+        lib().call("ofa_adam_step", *args, stream())
 
 
 class _EmaSegment(ctypes.Structure):

@@ -264,7 +264,8 @@ def _schedule_state(scaled):
 @pytest.mark.parametrize("n", [1, 255, 256 * 1024 + 3, (1 << 21) + 5])
 def test_fused_norm_and_schedule_equal_the_separate_launches(n, scaled):
     """ofa_sumsq_schedule against ofa_sumsq + ofa_step_schedule[_scaled] + the counter add, bit for bit, on two consecutive calls (the
-    ticket resets itself; gsq needs no clearing): one block (1, 255 elements), 128 blocks, the full 1024-block grid."""
+    ticket resets itself; gsq needs no clearing): one block (1, 255 elements), 128 blocks, the full 1024-block grid on its only
+    trip (tests/test_stream_edges_gpu.py goes past it, against an integer sum)."""
     torch.manual_seed(n % 1000)
     dt = torch.bfloat16
     ticket = torch.zeros(1, dtype=torch.int32, device=DEV)
