@@ -9,13 +9,13 @@ has a scalar fallback.  References are fp32 torch on the same already-rounded in
 same entry point uses for that dtype (fp16 without a precedent: the bf16 one), integer-indexed moves compare bit for bit.
 
 Who launches what (read off the suite; k = tests/test_kernels_gpu.py, h = test_fp16_gpu.py, e = test_step_edges_gpu.py,
-s = test_attn_sbias_gpu.py, m = the model / train-step suites (fp32 and bf16; fp16 through h's two model tests, which are not counted
+s = test_attn_sbias_gpu.py, a = test_attnside_edges_gpu.py, m = the model / train-step suites (fp32 and bf16; fp16 through h's two model tests, which are not counted
 as covering a cell); NEW = a case of this file):
 
   entry point(s)                                    fp32                 bf16                 fp16
   layernorm_fwd/bwd, gelu_layernorm_fwd/bwd         k test_layernorm     k test_layernorm     h test_layernorm_fp16
-  scaled_* softmax fwd/bwd (three families)         k test_softmax_family (all three dtypes)
-  attn_softmax_fwd                                  k test_attn_softmax  k test_attn_softmax  NEW
+  scaled_* softmax fwd/bwd (three families)         k test_softmax_family (all three dtypes); per element: a (all three)
+  attn_softmax_fwd                                  k test_attn_softmax  k test_attn_softmax  NEW; per element: a (all three)
   gemm (simple kernel)                              k test_gemm          k test_gemm          h test_gemm_fp16
   gelu_fwd/bwd, dropout_add_fwd/bwd, add_rowvec_mask  k test_elementwise k test_elementwise   NEW
   embedding_fwd (vector kernel)                     k test_embedding     k test_embedding     h test_embedding_criterion_adam_fp16
@@ -40,16 +40,17 @@ as covering a cell); NEW = a case of this file):
   probs_fwd/bwd                                     NEW                  NEW (fwd: test_model_gpu test_get_normalized_probs_and_train_mode)  NEW
   sumsq                                             k test_adam_and_sumsq  k test_adam_and_sumsq  h test_embedding_criterion_adam_fp16
   adam_step                                         NEW                  k test_adam_and_sumsq  h test_embedding_criterion_adam_fp16
-  bias_block_add/_add_batch/_slice/_grad            NEW                  m                    NEW
-  bias_outer_grad                                   NEW                  s test_bias_build_outer_slot_and_its_gradient  NEW
-  bias_build (16-bit only)                          -                    s test_bias_build_assembles_and_swizzles  NEW
+  bias_block_add/_add_batch/_slice/_grad            NEW                  m                    NEW; per element: a (all three)
+  bias_outer_grad                                   NEW                  s test_bias_build_outer_slot_and_its_gradient  NEW; exact: a (all three)
+  bias_build (16-bit only)                          -                    s test_bias_build_assembles_and_swizzles  NEW; a (both)
   join_fwd                                          k test_residual_join_equals_unfused_chain (fp32, bf16)  h test_residual_join_fp16
   join_bwd                                          k (same)             k (same)             NEW
   beam_topk, beam_prefix_topk, trie_beam_topk, closed_set_edge_logits   test_beam_search_gpu / test_beam_prefix_gpu / test_trie_beam_gpu / test_traverse_gpu (all three)
-  attn_decode                                       k test_attn_decode_matches_reference (fp32, bf16)  NEW
-  attn_bwd_prep (16-bit only)                       -                    k test_fused_attention  h test_fused_attention_fp16
-  mean_heads                                        NEW                  m                    NEW
-  c_attn_grad                                       k test_c_attn_grad_kernel (fp32, bf16)    NEW"""
+  attn_decode                                       k test_attn_decode_matches_reference (fp32, bf16)  NEW; per element: a (all three)
+  attn_bwd_prep (16-bit only)                       -                    k test_fused_attention  h test_fused_attention_fp16; a (both)
+  mean_heads                                        NEW                  m                    NEW; per element: a (all three)
+  c_attn_grad                                       k test_c_attn_grad_kernel (fp32, bf16)    NEW; exact: a (all three)
+  transpose_heads                                   a test_transpose_heads_bit_for_bit (all three)"""
 import pytest
 import torch
 import torch.nn.functional as F
