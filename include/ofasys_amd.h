@@ -1070,6 +1070,52 @@ int ofa_diffusion_loss(const void* pred, const float* target, const int64_t* t, 
                        float scale, const float* seed, int B, int T, int Dd, int W, double* partial, double* counts, float* out,
                        void* dpred, int grad, int dtype, void* stream);
 
+/* ---- motion diffusion sampling (generator/diffusion_generator.py, module/diffusion.py:130-152, preprocessor/default/motion_6d.py:394-419,
+ * adaptor/motion_6d.py:90-97), csrc/diffusion_step.hip: everything of a sampling step that is not the denoiser, in one launch over the
+ * frames [B, T] of Dd = 6 + 6 * joints columns.  fp32 arithmetic in this order, per element:
+ *     p  = pred[b, t, :Dd]                      ([B, T, W] of `dtype`, W >= Dd, read in place: the frame decoder's rows)
+ *     p  = (1 + g) * p - g * pred[b + 1, t]     guidance g != 0 (B even), rows b = 2k only; rows 2k + 1 keep their own prediction
+ *     x  = p at columns < 6; per joint a1 | a2 -> b1 | b2, b1 = a1 / max(|a1|, 1e-12), b2 = normalize(a2 - (b1 . a2) b1), same floor
+ *     x  = x + sum_k nbw[b, t, k] * (value_0[b, n] - x[b, n]), n = nbr[b, t, k], k < 2      in-betweening only (below)
+ *     x  = known_w[b, t] * value_0 + (1 - known_w[b, t]) * x                                in-betweening only
+ *     x  = clamp(x, -1, 1)                      clip != 0
+ *     img[b, t] = x0_hat = x                    (fp32 [B, T, Dd]; zeros at frames with masks[b, t] != 0, bool [B, T] or NULL)
+ *     x_t[b, t] = c0 * x + c1 * x_t[b, t] + sigma * noise[s][b, t]          (c0, c1, sigma) = coef[s] (fp32 [n_steps, 3]); in place;
+ *                                               zeros at masked frames; noise fp32 [B, T, Dd] at noise + s * noise_stride elements, or
+ *                                               NULL (every sigma is 0)
+ *     xin[b, t, :Dd] = known_w * value_0 + (1 - known_w) * x_t (in-betweening) or x_t, rounded once to `dtype`: the next denoiser input
+ *                                               ([B, T, W]; only columns < Dd of unmasked frames are ever written: the caller zeroes it once)
+ *     level[b] = timesteps[min(s + 1, n_steps - 1)]                         (int64 [B] from int64 [n_steps])
+ *   s = counter[0] (int32 [2] on the device: the step index, clamped into the tables, and a ticket the kernel keeps at 0 between
+ *   launches); the launch leaves counter[0] = s + 1.  Under guidance rows 2k + 1 take row 2k's new x_t (and the xin mixed from it with
+ *   their own known_w / value_0 / masks); their img is their own x0_hat.
+ * In-betweening: value_0 fp32 [B, T, Dd], known_w fp32 [B, T], nbr int32 [B, T, 2] (frames of the same sentence) and nbw fp32 [B, T, 2]
+ *   -- the at most two non-zeros of every row of the collation's interp_w; an entry with weight 0 or a frame outside [0, T) is skipped --
+ *   are given together or not at all.  The rectified prediction of the neighbour frames goes through an LDS tile of
+ *   (ofa_diffusion_step_frames() + 2) * Dd floats: UNSUPPORTED beyond 64 KiB.
+ * first != 0: x_t holds the initial x_T and there is no prediction: the launch writes xin from it, level[b] = timesteps[0] and
+ *   counter[0] = 0 (under guidance also x_t[2k + 1] = x_t[2k]), nothing else.
+ * Equal inputs give equal bits.  INVALID: Dd not 6 + 6 * joints, W < Dd, odd B under guidance, n_steps < 1, a partial in-betweening set. */
+typedef struct ofa_diffusion_step_args {
+  const void* pred;
+  float* x_t;
+  const float *noise, *value_0, *known_w;
+  const int32_t* nbr;
+  const float* nbw;
+  const void* masks;
+  const float* coef;
+  const int64_t* timesteps;
+  int32_t* counter;
+  float* img;
+  void* xin;
+  int64_t* level;
+  int64_t noise_stride;
+  int32_t B, T, Dd, W, n_steps, first, clip;
+  float guidance;
+} ofa_diffusion_step_args;
+int ofa_diffusion_step_frames(void);                                     /* host only */
+int ofa_diffusion_sample_step(const ofa_diffusion_step_args* a, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,8 +11,22 @@ Everything is computed in float64 on the host; three fp32 tables go to the devic
     sqrt_acp[t] = sqrt(acp[t])     sqrt_1m_acp[t] = sqrt(1 - acp[t])     w[t] = sqrt(snr + 1) = 1 / sqrt(1 - acp[t])
 A documented difference: the reference keeps acp in fp32 and forms 1 - acp from that.  At t = 0 of the cosine schedule
 1 - acp is 4.1e-5 and the fp32 spacing of acp is 1.4e-3 of it, so the reference's w[0] carries about 7e-4 relative error; these tables
-do not.  Sampling (the scheduler step, DDIM / DDPM) is not built: `clip_sample`, `num_inference_steps`, `set_alpha_to_one` and
-`steps_offset` are accepted and unused."""
+do not.
+
+Sampling (module/diffusion.py:102-154 `sample`, which calls the scheduler's `set_timesteps` and `step`): `sampling_plan()` restates what
+the loop reads of either scheduler as a list of timesteps and one coefficient row (c0, c1, sigma) per step,
+    x_prev = c0 * x0_hat + c1 * x_t + sigma * noise,
+with N = num_train_timesteps, n = num_inference_steps (default N), r = N // n, a = acp:
+    timesteps  t_i = round(i * r), i = n - 1 .. 0 (+ steps_offset, DDIM only); a t_i >= N raises
+    previous   p = t - r; a_prev = a[p] if p >= 0, else 1 (DDIM with set_alpha_to_one=False: a[0])
+    DDIM       (the reference's call: eta = 0, use_clipped_model_output=True)  eps = (x_t - sqrt(a_t) x0_hat) / sqrt(1 - a_t),
+               x_prev = sqrt(a_prev) x0_hat + sqrt(1 - a_prev) eps, i.e. c1 = sqrt(1 - a_prev) / sqrt(1 - a_t),
+               c0 = sqrt(a_prev) - c1 sqrt(a_t), sigma = 0: no noise is drawn
+    DDPM       (ancestral, fixed_small variance) beta = 1 - a_t / a_prev:  c0 = sqrt(a_prev) beta / (1 - a_t),
+               c1 = sqrt(1 - beta) (1 - a_prev) / (1 - a_t), sigma = sqrt(max((1 - a_prev) / (1 - a_t) beta, 1e-20)) for t > 0, else 0
+`clip_sample` clamps x0_hat to [-1, 1] (after the rectification and the infill: csrc/diffusion_step.hip).  Only prediction_type "sample"
+samples, as in the reference.  The coefficients are float64 here and rounded once to fp32 for the device (`sampling_on`); the
+coefficient form is algebraically the reference's two-stage form."""
 import math
 from typing import NamedTuple
 
@@ -24,7 +38,14 @@ BETA_SCHEDULES = ("squaredcos_cap_v2", "linear", "scaled_linear")
 PREDICTION_TYPES = ("sample", "epsilon")
 _DEFAULTS = {"scheduler": "DDIMScheduler", "num_train_timesteps": 1000, "beta_start": 1e-4, "beta_end": 2e-2,
              "beta_schedule": "squaredcos_cap_v2", "prediction_type": "sample"}
-_UNUSED_IN_TRAINING = ("clip_sample", "num_inference_steps", "set_alpha_to_one", "steps_offset")
+_UNUSED_IN_TRAINING = ("clip_sample", "num_inference_steps", "set_alpha_to_one", "steps_offset")      # the sampling side reads them
+
+
+class SamplingPlan(NamedTuple):
+    """timesteps int64 [n], descending; coef [n, 3] = (c0, c1, sigma) per step: float64 numpy from `sampling_plan`, an int64 and an fp32
+    device tensor from `sampling_on`."""
+    timesteps: object
+    coef: object
 
 
 class Tables(NamedTuple):
@@ -48,7 +69,7 @@ def make_betas(beta_schedule, n, beta_start, beta_end):
 
 
 class NoiseSchedule:
-    """The training side of the reference's DiffusionWrapper: NoiseSchedule(**diffuser_args).  `acp` is the float64 cumulative product;
+    """The reference's DiffusionWrapper, training (`on`) and sampling (`sampling_plan`) side: NoiseSchedule(**diffuser_args).  `acp` is the float64 cumulative product;
     `on(device)` hands out the fp32 tables (built once per device and kept: a captured step addresses them)."""
 
     def __init__(self, **kwargs):
@@ -75,6 +96,52 @@ class NoiseSchedule:
         one_minus = 1.0 - self.acp                       # float64: 1 - acp keeps 11 more digits than the reference's fp32 difference
         self.sqrt_acp, self.sqrt_1m_acp, self.w = np.sqrt(self.acp), np.sqrt(one_minus), 1.0 / np.sqrt(one_minus)
         self._dev = {}
+        infer = kwargs.get("num_inference_steps")
+        self.num_inference_steps = n if infer is None else int(infer)
+        self.clip_sample = bool(kwargs.get("clip_sample", False))
+        self.set_alpha_to_one = bool(kwargs.get("set_alpha_to_one", True))
+        self.steps_offset = int(kwargs.get("steps_offset", 0))
+        self._plan_dev = {}
+
+    def sampling_plan(self) -> SamplingPlan:
+        """The sampling loop's timesteps and coefficient rows in float64 (the module docstring has the formulas)."""
+        if self.prediction_type != "sample":
+            raise NotImplementedError(f"sampling with prediction_type {self.prediction_type!r} is not implemented: the reference asserts "
+                                      "prediction_type == 'sample' whenever there is a post-processing function (module/diffusion.py:"
+                                      "140-143), and motion always has one")
+        N, n = self.num_train_timesteps, self.num_inference_steps
+        if not 1 <= n <= N:
+            raise ValueError(f"diffuser_args: num_inference_steps={n} must be in [1, num_train_timesteps={N}]")
+        ddim = self.scheduler == "DDIMScheduler"
+        r = N // n
+        ts = np.round(np.arange(n, dtype=np.float64) * r)[::-1].astype(np.int64) + (self.steps_offset if ddim else 0)
+        if ts.max() >= N or ts.min() < 0:
+            raise ValueError(f"diffuser_args: timestep {int(ts.max() if ts.max() >= N else ts.min())} (steps_offset={self.steps_offset}) is "
+                             f"outside the {N} training levels")
+        a = self.acp
+        a_t = a[ts]
+        prev = ts - r
+        final = 1.0 if (self.set_alpha_to_one or not ddim) else a[0]
+        a_prev = np.where(prev >= 0, a[np.maximum(prev, 0)], final)
+        if ddim:
+            c1 = np.sqrt(1.0 - a_prev) / np.sqrt(1.0 - a_t)
+            c0 = np.sqrt(a_prev) - c1 * np.sqrt(a_t)
+            sigma = np.zeros(n)
+        else:
+            beta = 1.0 - a_t / a_prev
+            c0 = np.sqrt(a_prev) * beta / (1.0 - a_t)
+            c1 = np.sqrt(1.0 - beta) * (1.0 - a_prev) / (1.0 - a_t)
+            sigma = np.where(ts > 0, np.sqrt(np.maximum((1.0 - a_prev) / (1.0 - a_t) * beta, 1e-20)), 0.0)
+        return SamplingPlan(ts, np.stack((c0, c1, sigma), axis=1))
+
+    def sampling_on(self, device) -> SamplingPlan:
+        """The plan on one device: timesteps int64 [n], coef fp32 [n, 3] (rounded once; built once per device and kept, as `on`)."""
+        key = torch.device(device)
+        if key not in self._plan_dev:
+            plan = self.sampling_plan()
+            self._plan_dev[key] = SamplingPlan(torch.from_numpy(plan.timesteps.copy()).to(key),
+                                               torch.from_numpy(plan.coef.astype(np.float32)).to(key))
+        return self._plan_dev[key]
 
     def on(self, device) -> Tables:
         key = torch.device(device)

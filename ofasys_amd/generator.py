@@ -38,6 +38,10 @@ which works on the candidates the row pass already lists.
 `SpeechStepDecoder`, a `StepDecoder` that feeds the decoder one embedded frame per step: the step's policy -- fbank head, sigmoid,
 finish rule, next padding flag, finished count, prenet of the new frame -- is one HIP launch (csrc/speech_step.hip) recorded with the
 decoder into the step's graph.
+
+`DiffusionGenerator` is the reference's diffusion sampler of motion frames (generator/diffusion_generator.py on module/diffusion.py
+`sample`): the encoder once, then per step the denoiser and one HIP launch (csrc/diffusion_step.hip), captured once per batch structure
+and replayed for every step.
 """
 import math
 from dataclasses import dataclass
@@ -831,3 +835,163 @@ class AutoRegressiveSpeechGenerator(SpeechGenerator):
             for b, (f, l) in enumerate(zip(tgt_feats, tgt_lens)):
                 finalized[b].targ_feature = f[:l].cpu()
         return finalized
+
+
+# ---------------------------------------------------------------------------------------------------------------- motion generation
+@dataclass
+class MotionOutput:
+    """One generated motion (generator/diffusion_generator.py:22-75): `feature` fp32 [T, Dd], the last step's x0_hat as rot6d frames
+    (zeros at the sentence's padded frames).  `bvh_header` / `bvh_motion` stay None: the BVH conversion (`batch_decode`) is not built."""
+    feature: Any
+    target_feature: Any = None
+    prompt: Optional[str] = None
+    bvh_header: Any = None
+    bvh_motion: Any = None
+
+    def save_as_gif(self, gif_name: str):
+        raise NotImplementedError("MotionOutput.save_as_gif is not implemented: it needs the BVH header and its kinematics, which are not built")
+
+    def save_as_bvh(self, bvh_name: str):
+        raise NotImplementedError("MotionOutput.save_as_bvh is not implemented: it needs the BVH header and its kinematics, which are not built")
+
+    def save_features(self, feature_name: str):
+        import numpy as np
+        data = {"feature": _to_numpy(self.feature), "target_feature": _to_numpy(self.target_feature), "prompt": self.prompt}
+        if not feature_name.endswith(".npz"):
+            feature_name = feature_name + ".npz"
+        np.savez(file=feature_name, **data)
+
+
+class DiffusionGenerator:
+    """The reference's diffusion sampler of motion frames (generator/diffusion_generator.py:78-118 on module/diffusion.py:102-154): the
+    encoder once, then n = num_inference_steps times the denoiser -- the motion_6d adaptor, the decoder without a causal mask on the
+    reused encoder output, the frame decoder -- and ONE launch (csrc/diffusion_step.hip: guidance, rectification, infill, clip,
+    scheduler step, the next denoiser input and its level).  With use_graph one step is captured once per batch structure and replayed
+    for every later step and batch; the step index and the level live on the device, so the loop has no host synchronisation.
+
+    The target slot's value carries the shape, as the reference's x_dummy does: "value" / "value_0" [B, T, Dd] (zeros will do) and
+    "masks"; with "known_w" and "interp_w" (in-betweening) "value_0" also holds the known frames.  generate(x_T=, noise=) takes the
+    initial state fp32 [B, T, Dd] and the steps' noise fp32 [n, B, T, Dd]; otherwise torch's device generator draws them (inside the
+    captured step too).  Differences ("Motion generation"): the sampler state is fp32 whatever `dtype` says, the
+    results are on the CPU, padded frames are zeros, DDIM draws no noise, DDPM sampling works."""
+
+    def __init__(self, general_preprocess, diffuser_args=None, dtype=torch.float32, device=None, guidance_weight: float = 0.0,
+                 use_graph: bool = True, **unused_kwargs):
+        from .diffusion import NoiseSchedule
+        self.general_preprocess = general_preprocess
+        self.diffusion = diffuser_args if isinstance(diffuser_args, NoiseSchedule) else NoiseSchedule(**(diffuser_args or {}))
+        self.diffusion.sampling_plan()                          # (an objective or a step count that cannot sample raises here)
+        self.dtype = getattr(torch, dtype) if isinstance(dtype, str) else dtype
+        self.device = device
+        self.guidance_weight, self.use_graph = float(guidance_weight), bool(use_graph)
+        self.captures = 0
+        self._key, self._st, self._graph = None, None, None
+        self._ws: Dict[tuple, torch.Tensor] = {}
+        self._ws_keep: List[torch.Tensor] = []
+
+    def _state(self, model, ad, slot, enc, B, T, Dd, inbetween, noise_mode):
+        """The fixed-address buffers of one batch structure; another structure drops them and the captured step."""
+        dev, mdtype = enc["encoder_out"][0].device, ad.frame_encoder[0].weight.dtype
+        plan = self.diffusion.sampling_on(dev)
+        n = plan.timesteps.numel()
+        key = (B, T, Dd, ad.max_data_dim, mdtype, inbetween, noise_mode, n, tuple(enc["encoder_out"][0].shape),
+               next(model.decoder.parameters()).data_ptr(), id(model))
+        if key != self._key:
+            f32 = dict(dtype=torch.float32, device=dev)
+            st = {"x_t": torch.zeros(B, T, Dd, **f32), "img": torch.zeros(B, T, Dd, **f32),
+                  "xin": torch.zeros(B, T, ad.max_data_dim, dtype=mdtype, device=dev),
+                  "level": torch.zeros(B, dtype=torch.int64, device=dev), "counter": torch.zeros(2, dtype=torch.int32, device=dev),
+                  "masks": torch.zeros(B, T, dtype=torch.bool, device=dev), "coef": plan.coef, "timesteps": plan.timesteps}
+            if noise_mode != "none":
+                st["noise"] = torch.zeros(*((n,) if noise_mode == "supplied" else ()), B, T, Dd, **f32)
+            if inbetween:
+                st.update(value_0=torch.zeros(B, T, Dd, **f32), known_w=torch.zeros(B, T, **f32),
+                          nbr=torch.zeros(B, T, 2, dtype=torch.int32, device=dev), nbw=torch.zeros(B, T, 2, **f32))
+            st["enc"] = {k: [t.clone() if torch.is_tensor(t) else t for t in v] if isinstance(v, list) else v for k, v in enc.items()}
+            value = {"value": st["xin"], "masks": st["masks"], "noise_level": st["level"], "data_dim": Dd}
+            if inbetween:
+                value["known_w"] = st["known_w"]
+            st["slot"] = Slot(slot.modality, False, value, attributes=slot.attributes)
+            self._key, self._st, self._graph, self._ws, self._ws_keep = key, st, None, {}, []
+        else:
+            st = self._st
+            st["xin"].zero_()
+            for k, v in enc.items():
+                if isinstance(v, list):
+                    for dst, src in zip(st["enc"][k], v):
+                        if torch.is_tensor(dst):
+                            dst.copy_(src)
+        return st
+
+    def _step(self, model, st, draw):
+        from . import ops
+        pred, _ = model.decoder([st["slot"]], encoder_out=st["enc"], full_context_alignment=True)
+        if draw:
+            st["noise"].normal_()
+        ops.diffusion_sample_step(pred.contiguous(), st, clip_sample=self.diffusion.clip_sample, guidance_weight=self.guidance_weight)
+
+    @torch.no_grad()
+    def generate(self, model, sample, x_T=None, noise=None, **kwargs):
+        from . import ops
+        from .criterion import _diffusion_slot
+        model.eval()
+        net_input = sample["net_input"]
+        slot = _diffusion_slot(net_input)
+        assert slot.modality == ModalityType.MOTION, "Modality other than MOTION not tested yet."
+        ad = model.decoder.adaptor.get_adaptor(slot)
+        sched = self.diffusion
+        if getattr(ad, "max_data_dim", None) is None:
+            raise ValueError("DiffusionGenerator: the target slot must select the motion_6d adaptor ([MOTION:...,adaptor=motion_6d])")
+        if ad.max_noise_levels < sched.num_train_timesteps + 1:
+            raise ValueError(f"motion_6d: max_noise_levels {ad.max_noise_levels} < num_train_timesteps + 1 = {sched.num_train_timesteps + 1}")
+        v = slot.value
+        template = v["value_0"] if v.get("value_0") is not None else v["value"]
+        B, T, Dd = template.shape
+        g = self.guidance_weight
+        if g != 0.0 and B % 2:
+            raise ValueError(f"DiffusionGenerator: guidance pairs sample[0::2] (the conditions) with sample[1::2] (the null conditions): B={B} is odd")
+        inbetween = v.get("known_w") is not None
+        if inbetween and v.get("interp_w") is None:
+            raise ValueError("DiffusionGenerator: in-betweening (known_w) needs interp_w (the motion_6d collation builds both)")
+        plan = sched.sampling_plan()
+        n = len(plan.timesteps)
+        noise_mode = "none" if not plan.coef[:, 2].any() else ("supplied" if noise is not None else "drawn")
+        for name, t, shape in (("x_T", x_T, (B, T, Dd)), ("noise", noise, (n, B, T, Dd))):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32):
+                raise ValueError(f"DiffusionGenerator: {name} must be fp32 {list(shape)}, got {t.dtype} {list(t.shape)}")
+
+        enc = model.encoder([s for s in net_input["slots"] if s.is_src])
+        st = self._state(model, ad, slot, enc, B, T, Dd, inbetween, noise_mode)
+        dev = st["x_t"].device
+        st["masks"].copy_(v["masks"])
+        if inbetween:
+            st["value_0"].copy_(template)
+            st["known_w"].copy_(v["known_w"])
+            nbr, nbw = ops.diffusion_neighbours(v["interp_w"].to(dev))
+            st["nbr"].copy_(nbr)
+            st["nbw"].copy_(nbw)
+        if noise_mode == "supplied":
+            st["noise"].copy_(noise)
+        st["x_t"].copy_(x_T) if x_T is not None else st["x_t"].normal_()
+        ops.diffusion_sample_step(None, st, first=True, guidance_weight=g)
+
+        draw = noise_mode == "drawn"
+        left = n
+        if self.use_graph and self._graph is None:
+            self._step(model, st, draw)                         # the structure's first step runs eagerly (it builds the cached plans)
+            left -= 1
+            if left:
+                graph = torch.cuda.CUDAGraph()
+                torch.cuda.synchronize()
+                with K.capture_workspaces(self._ws) as added, torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    self._step(model, st, draw)
+                self._ws_keep.extend(added.values())
+                self._graph = graph
+                self.captures += 1
+        for _ in range(left):
+            if self.use_graph:
+                self._graph.replay()
+            else:
+                self._step(model, st, draw)
+        img = st["img"].cpu()
+        return [MotionOutput(feature=img[i].clone()) for i in range(B)]

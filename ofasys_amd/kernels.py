@@ -2207,3 +2207,62 @@ def speech_step(x, head, prenet, proj, state, step, p_drop, seed=0, offset=0, of
     for i, (w, b) in enumerate(prenet):
         a.pre_w[i], a.pre_b[i] = ptr(w), ptr(b)
     lib().call("ofa_speech_step", ctypes.addressof(a), dtype_code(x), stream())
+
+
+# ------------------------------------------------------------------ motion diffusion sampling (csrc/diffusion_step.hip)
+class _DiffusionStepArgs(ctypes.Structure):   # ofa_diffusion_step_args
+    _fields_ = [("pred", ctypes.c_void_p), ("x_t", ctypes.c_void_p), ("noise", ctypes.c_void_p), ("value_0", ctypes.c_void_p),
+                ("known_w", ctypes.c_void_p), ("nbr", ctypes.c_void_p), ("nbw", ctypes.c_void_p), ("masks", ctypes.c_void_p),
+                ("coef", ctypes.c_void_p), ("timesteps", ctypes.c_void_p), ("counter", ctypes.c_void_p), ("img", ctypes.c_void_p),
+                ("xin", ctypes.c_void_p), ("level", ctypes.c_void_p), ("noise_stride", ctypes.c_int64), ("B", ctypes.c_int32),
+                ("T", ctypes.c_int32), ("Dd", ctypes.c_int32), ("W", ctypes.c_int32), ("n_steps", ctypes.c_int32),
+                ("first", ctypes.c_int32), ("clip", ctypes.c_int32), ("guidance", ctypes.c_float)]
+
+
+def diffusion_step_frames():
+    """Frames of a step workgroup's tile (host only)."""
+    return int(lib().cdll.ofa_diffusion_step_frames())
+
+
+def diffusion_sample_step(pred, state, first=False, clip=False, guidance=0.0):
+    """One launch of ofa_diffusion_sample_step.  pred [B, T, W] in the model dtype (None with `first`); state: the sampler's
+    fixed-address buffers -- "x_t", "img" fp32 [B, T, Dd], "xin" [B, T, W] of the model dtype, "level" int64 [B], "counter" int32 [2],
+    "coef" fp32 [n, 3], "timesteps" int64 [n], and optionally "noise" fp32 [B, T, Dd] or [n, B, T, Dd], "masks" bool [B, T] and the
+    in-betweening set "value_0" fp32 [B, T, Dd], "known_w" fp32 [B, T], "nbr" int32 [B, T, 2], "nbw" fp32 [B, T, 2]."""
+    x_t, img, xin = state["x_t"], state["img"], state["xin"]
+    if x_t.dim() != 3 or x_t.dtype != torch.float32 or img.dtype != torch.float32 or img.shape != x_t.shape or xin.dim() != 3:
+        raise OfaError(f"diffusion_sample_step: x_t {x_t.dtype} {tuple(x_t.shape)} and img {img.dtype} {tuple(img.shape)} must be one fp32 "
+                       "[B, T, Dd] and xin [B, T, W]")
+    B, T, Dd = x_t.shape
+    W = xin.shape[2]
+    if tuple(xin.shape[:2]) != (B, T) or (not first and (pred is None or pred.shape != xin.shape or pred.dtype != xin.dtype)):
+        raise OfaError(f"diffusion_sample_step: pred and xin must be [B, T, W] = [{B}, {T}, {W}] of one dtype")
+    coef, ts, level, counter = state["coef"], state["timesteps"], state["level"], state["counter"]
+    n = ts.numel()
+    if coef.dtype != torch.float32 or tuple(coef.shape) != (n, 3) or ts.dtype != torch.int64:
+        raise OfaError("diffusion_sample_step: coef must be fp32 [n, 3] and timesteps int64 [n]")
+    if counter.dtype != torch.int32 or counter.numel() != 2:
+        raise OfaError("diffusion_sample_step: state['counter'] must be int32 [2]")
+    _levels("diffusion_sample_step", level, B)
+    masks = _bool_mask("diffusion_sample_step", state.get("masks"), B, T)
+    noise, stride = state.get("noise"), 0
+    if noise is not None:
+        if noise.dtype != torch.float32 or tuple(noise.shape) not in ((B, T, Dd), (n, B, T, Dd)):
+            raise OfaError(f"diffusion_sample_step: noise must be fp32 [B, T, Dd] or [n, B, T, Dd], got {noise.dtype} {tuple(noise.shape)}")
+        stride = B * T * Dd if noise.dim() == 4 else 0
+    fill = [state.get(k) for k in ("value_0", "known_w", "nbr", "nbw")]
+    if any(t is not None for t in fill):
+        v0, kw, nbr, nbw = fill
+        if any(t is None for t in fill) or v0.dtype != torch.float32 or v0.shape != x_t.shape or kw.dtype != torch.float32 \
+                or tuple(kw.shape) != (B, T) or nbr.dtype != torch.int32 or nbw.dtype != torch.float32 \
+                or tuple(nbr.shape) != (B, T, 2) or tuple(nbw.shape) != (B, T, 2):
+            raise OfaError("diffusion_sample_step: in-betweening takes value_0 fp32 [B, T, Dd], known_w fp32 [B, T], nbr int32 [B, T, 2] "
+                           "and nbw fp32 [B, T, 2] together")
+    tensors = [x_t, img, xin, coef, ts, level, counter, noise, masks] + fill + ([] if first else [pred])
+    if any(t is not None and not t.is_contiguous() for t in tensors):
+        raise OfaError("diffusion_sample_step: every buffer must be contiguous")
+    a = _DiffusionStepArgs(pred=None if first else ptr(pred), x_t=ptr(x_t), noise=ptr(noise), value_0=ptr(fill[0]), known_w=ptr(fill[1]),
+                           nbr=ptr(fill[2]), nbw=ptr(fill[3]), masks=ptr(masks), coef=ptr(coef), timesteps=ptr(ts), counter=ptr(counter),
+                           img=ptr(img), xin=ptr(xin), level=ptr(level), noise_stride=stride, B=B, T=T, Dd=Dd, W=W, n_steps=n,
+                           first=int(bool(first)), clip=int(bool(clip)), guidance=float(guidance))
+    lib().call("ofa_diffusion_sample_step", ctypes.addressof(a), dtype_code(xin), stream())

@@ -3055,6 +3055,35 @@ def diffusion_eval(pred, target, t, schedule, masks=None, scale=1.0):
     return K.diffusion_loss(pred, target, t, _diffusion_weights(schedule, pred.device), scale, masks=masks)[0]
 
 
+# ---------------------------------------------------------------------------------------------- motion diffusion sampling (csrc/diffusion_step.hip)
+def diffusion_neighbours(interp_w):
+    """The collation's dense interp_w [B, T, T] (preprocessor/motion.py `interpolate_weight`: at most two non-zeros per row) as the two
+    tables the step kernel reads: nbr int32 [B, T, 2] -- the frames of a row's non-zeros in ascending order; an unused entry is 0 with
+    weight 0 -- and nbw fp32 [B, T, 2].  A row with more than two non-zeros raises ValueError (one host synchronisation, once per batch)."""
+    if interp_w.dim() != 3 or interp_w.shape[1] != interp_w.shape[2]:
+        raise ValueError(f"interp_w must be [B, T, T], got {tuple(interp_w.shape)}")
+    w = interp_w.float()
+    if w.shape[2] < 2:
+        w = torch.nn.functional.pad(w, (0, 2 - w.shape[2]))
+    nz = w != 0
+    most = int(nz.sum(-1).max()) if nz.numel() else 0
+    if most > 2:
+        raise ValueError(f"interp_w has a row with {most} non-zeros: the step kernel takes at most two neighbour frames per frame "
+                         "(what preprocessor/motion.py interpolate_weight builds)")
+    idx = torch.sort(nz.to(torch.int8), dim=-1, descending=True, stable=True)[1][..., :2]
+    nbw = w.gather(-1, idx)
+    return torch.where(nbw != 0, idx, torch.zeros_like(idx)).to(torch.int32).contiguous(), nbw.contiguous()
+
+
+def diffusion_sample_step(pred, state, first=False, clip_sample=False, guidance_weight=0.0):
+    """Everything of a sampling step but the denoiser, in one launch (module/diffusion.py:133-152 with the motion post-processing,
+    preprocessor/default/motion_6d.py:394-419, and the adaptor's in-betweening mix, adaptor/motion_6d.py:90-97): guidance, the rot6d
+    rectification, the infill, the clip, the scheduler step of row state["counter"][0] of state["coef"], and the next denoiser input
+    state["xin"] with its level state["level"].  pred [B, T, max_data_dim]: the frame decoder's rows, read in place; `state`: see
+    kernels.diffusion_sample_step.  first: state["x_t"] holds x_T and only the denoiser input and the level are written."""
+    return K.diffusion_sample_step(pred, state, first=first, clip=clip_sample, guidance=guidance_weight)
+
+
 # ---------------------------------------------------------------------------------------------- speech generation (csrc/speech_step.hip)
 def speech_step_fusable(x_dtype, head, prenet, proj):
     """Can ofa_speech_step serve these weights: a served shape (K.speech_step_ok) and contiguous, 16-byte aligned tensors of one dtype?"""

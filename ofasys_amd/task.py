@@ -6,10 +6,10 @@
 
 Generation: `Task.generator` / `Task.inference` run beam search (ofasys_amd/generator.py SequenceGenerator; task/base.py:232-246,
 470-556, 727-793) for TEXT targets and the autoregressive speech generator (AutoRegressiveSpeechGenerator; task/base.py:555-561) for
-AUDIO targets.
+AUDIO targets, and the diffusion sampler (DiffusionGenerator) for MOTION targets.
 Validation: `Task.valid_batches` walks a split once, in order; `Trainer.validate` (engine.py) runs it through the step engine's
 forward-only `valid_step` -- loss, NLL and, with `cfg.criterion.report_accuracy`, token accuracy (task/base.py:680-703).
-What stays out: file / OSS readers, multi-worker prefetch, generation metrics, the image / motion generators and the vocoder, checkpoint state.  The
+What stays out: file / OSS readers, multi-worker prefetch, generation metrics, the image generator, the BVH conversion of generated motion and the vocoder, checkpoint state.  The
 batch iterator is a plain in-process loop over the bound dataset: micro-batches of `micro_batch_size` rows, each rank of a
 data-parallel job reading its own contiguous shard (io/reader/dataset.py:49-53), reshuffled per epoch with a seeded permutation.
 """
@@ -351,6 +351,14 @@ class Task:
         return AutoRegressiveSpeechGenerator(self.global_dict, stats_npz_path=stats_npz_path, max_iter=max_iter,
                                              eos_prob_threshold=eos_prob_threshold, **extra)
 
+    def build_diffusion_generator(self, **gen_kwargs):
+        """DiffusionGenerator on the task's noise schedule (`diffuser_args`) from the reference's generator arguments: `guidance_weight`,
+        `dtype`, `device` and `use_graph` are taken, the rest (the beam-search arguments of the shared default JSON among them) is
+        ignored, as the speech generator does."""
+        from .generator import DiffusionGenerator
+        extra = {k: gen_kwargs[k] for k in ("guidance_weight", "dtype", "device", "use_graph") if k in gen_kwargs}
+        return DiffusionGenerator(self.general_preprocess, self.noise_schedule, **extra)
+
     def sampling_generator(self, **gen_kwargs):
         """SequenceGenerator(search_strategy=Sampling(...)) from the reference's generator arguments: `sampling`, `sampling_topk`,
         `sampling_topp` (task/base.py:488-515, with its checks) and `seed` are taken out here, the rest goes through
@@ -406,7 +414,8 @@ class Task:
     @property
     def generator(self):
         """Built on first use from cfg.evaluation.generator_args (JSON) and cfg.constraint_range (text targets); an [AUDIO:...]
-        target gets the autoregressive speech generator (`build_speech_generator`)."""
+        target gets the autoregressive speech generator (`build_speech_generator`), a [MOTION:...] target the diffusion sampler
+        (`build_diffusion_generator`)."""
         if self._generator is None:
             gen_args = json.loads(self.cfg.evaluation.generator_args)
             if self.target_modality == ModalityType.TEXT:
@@ -416,6 +425,9 @@ class Task:
                 gen_args["constraint_range"] = self.cfg.constraint_range
             elif self.target_modality == ModalityType.AUDIO:
                 self._generator = self.build_speech_generator(**gen_args)
+                return self._generator
+            elif self.target_modality == ModalityType.MOTION:
+                self._generator = self.build_diffusion_generator(**gen_args)
                 return self._generator
             elif self.target_modality is not None:
                 raise NotImplementedError(f"task {self.name}: generation for {self.target_modality} targets is not implemented")
@@ -447,8 +459,8 @@ class Task:
         """Beam search on `sample` (a collated batch); for TEXT targets every hypothesis gets `.text` through the task's text
         tokenizer (preprocessor/default/text.py:340-371).  As there, a sample with `prefix_tokens` has the sentence's prefix (its
         entries that are neither <pad> nor <eos>) cut from the front of `.tokens` before decoding; scores and positional scores
-        keep the prefix positions.  An AUDIO target: the speech generator's SpeechGeneratorOutput list, untouched.  The model is left
-        in eval mode."""
+        keep the prefix positions.  An AUDIO target: the speech generator's SpeechGeneratorOutput list, a MOTION target: the diffusion
+        generator's MotionOutput list, both untouched.  The model is left in eval mode."""
         model.eval()
         outputs = self.generator.generate(model, sample, **kwargs)
         if self.target_modality == ModalityType.TEXT:
