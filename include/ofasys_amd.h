@@ -1116,6 +1116,36 @@ typedef struct ofa_diffusion_step_args {
 int ofa_diffusion_step_frames(void);                                     /* host only */
 int ofa_diffusion_sample_step(const ofa_diffusion_step_args* a, int dtype, void* stream);
 
+/* ---- the HiFi-GAN vocoder (module/hifigan.py:24-162, module/vocoder.py:154-178), csrc/vocoder.hip: a generator forward on channels-last
+ * rows [B, L, C] of fp16 / bf16 (fp32: UNSUPPORTED), fp32 accumulation, one rounding per output.  lens (int32 [B] on the device, or NULL:
+ * every sample is full) counts a sample's frames BEFORE any upsampling; len_scale is the stage's cumulative upsampling factor, so sample
+ * b has valid = clamp(lens[b] * len_scale, 0, L) rows at this stage.  In every entry point rows >= valid read as zeros and are written as
+ * zeros, and no sample reads a neighbour's rows: a ragged batch gives the bits of its utterances run one at a time.  No atomics: equal
+ * inputs give equal bits.  Nothing reads a length on the host.
+ *
+ * ofa_vocoder_conv: Conv1d(Cin, Cout, k, dilation d, padding d (k-1)/2) with a leaky-ReLU prologue and the residual-block epilogues:
+ *     y[b, t, :] = (bias + sum_{j < k} W_j . act(x[b, t + (j - (k-1)/2) d, :]) + res[b, t, :] + y[b, t, :]) * out_scale
+ *   act(v) = v > 0 ? v : slope * v, applied to the 16-bit input and rounded to it (slope 1: the identity); res (NULL: none) and the old y
+ *   (accum == 0: not read) are added in fp32.  w is [k][Cout][Cin] (tap-major, Cin contiguous), bias [Cout], both of `dtype`.  y may not
+ *   alias x or res.  UNSUPPORTED: Cin / Cout not multiples of 16 in 16..512 (80 is five K-steps: nothing is padded), even k, a halo
+ *   d (k-1)/2 above 25 rows, operands off 16-byte alignment.  ofa_vocoder_conv_tile (host only): the time rows a workgroup owns for a
+ *   shape, 0 when the shape is not served.
+ * ofa_vocoder_upsample: ConvTranspose1d(Cin, Cout, 2u, stride u, padding u/2) with the same prologue, as the 3-tap convolution of the
+ *   polyphase form: w [3][u * Cout][Cin] holds at [jj][r * Cout + co][ci] the transposed convolution's weight [ci][co][j] for
+ *   (jj, j) = (0, r + 3u/2) when r < u/2, (1, r + u/2), (2, r - u/2) when r >= u/2, and zeros elsewhere; bias [u * Cout] is the bias u
+ *   times.  x [B, L, Cin] -> y [B, L * u, Cout]; len_scale is the INPUT's factor.
+ * ofa_vocoder_post: out[b, t] (fp32 [B, L]) = tanh(bias[0] + sum_{j < k, c < C} w[j][c] * act(x[b, t + j - (k-1)/2, c])), zeros at
+ *   rows >= valid; fp32 fma chain in (j, c) order, tanhf.  C a multiple of 8 up to 32, k odd up to 7.  ofa_vocoder_post_tile (host
+ *   only): outputs per workgroup. */
+int ofa_vocoder_conv_tile(int Cin, int Cout, int k, int d);             /* host only */
+int ofa_vocoder_post_tile(void);                                         /* host only */
+int ofa_vocoder_conv(const void* x, const void* w, const void* bias, const void* res, void* y, const int32_t* lens, int B, int L, int Cin,
+                     int Cout, int k, int d, int len_scale, float slope, int accum, float out_scale, int dtype, void* stream);
+int ofa_vocoder_upsample(const void* x, const void* w, const void* bias, void* y, const int32_t* lens, int B, int L, int Cin, int Cout,
+                         int u, int len_scale, float slope, int dtype, void* stream);
+int ofa_vocoder_post(const void* x, const void* w, const void* bias, float* out, const int32_t* lens, int B, int L, int C, int k,
+                     int len_scale, float slope, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,8 @@ from .task import Task, TaskConfig  # noqa: E402,F401
 from .traverse import TraversePlan, TraverseTask  # noqa: E402,F401
 from .generator import (AutoRegressiveSpeechGenerator, DiffusionGenerator, DiverseBeamSearch, DiverseSiblingsSearch, Sampling,  # noqa: E402,F401
                         MotionOutput, SpeechGenerator, SpeechGeneratorOutput)
+from .module.hifigan import Generator as HiFiGANGenerator  # noqa: E402,F401
+from .module.vocoder import HiFiGANVocoder  # noqa: E402,F401
 from .scst import CiderD, ScstRewardCriterion  # noqa: E402,F401
 from .engine import Trainer, TrainerConfig  # noqa: E402,F401
 
@@ -22,4 +24,4 @@ __all__ = ["Task", "TaskConfig", "TraverseTask", "TraversePlan", "Trainer", "Tra
            "GeneralistModel", "GeneralistModelConfig", "Slot", "ModalityType", "Dictionary", "register_config",
            "ConfigStore", "AdaptorOutput", "BaseAdaptor", "BaseAdaptorConfig", "OFAGeneralAdaptor", "Sampling", "CiderD",
            "ScstRewardCriterion", "DiverseBeamSearch", "DiverseSiblingsSearch", "SpeechGenerator", "AutoRegressiveSpeechGenerator",
-           "SpeechGeneratorOutput", "DiffusionGenerator", "MotionOutput"]
+           "SpeechGeneratorOutput", "DiffusionGenerator", "MotionOutput", "HiFiGANVocoder", "HiFiGANGenerator"]

@@ -637,7 +637,8 @@ def _to_numpy(x):
 class SpeechGeneratorOutput:
     """One generated utterance (generator/speech_generator.py:25-54): the denormalised frames [out_len, raw_dim], the end-of-sequence
     probability of every frame, the head-averaged cross-attention of the alignment layer [S, out_len] with its arg-max per frame, and
-    with `has_targ` the target's frames.  `waveform` / `text` stay None: the vocoder is out of scope."""
+    with `has_targ` the target's frames.  `waveform` / `targ_waveform`: fp32 [hop * out_len] when the generator has a vocoder, else
+    None; `text` stays None."""
     feature: Any
     eos_prob: torch.Tensor
     attn: torch.Tensor
@@ -756,12 +757,15 @@ class AutoRegressiveSpeechGenerator(SpeechGenerator):
     postnet.  Semantics are the reference's: the finish test is strict, finished rows keep decoding (their later positions are padded
     keys of their own cache, their later frames are fed back and reach their kept frames through the postnet's window), rows that
     never finish keep max_iter.  Differences ("Speech generation"): `attn` holds every step's map, results are on
-    the CPU, no waveform, a local statistics file.  fused_step=False (or a shape the kernel does not serve) runs the step's policy as
+    the CPU, a local statistics file.  vocoder (module/vocoder.py HiFiGANVocoder, or None): the batch's denormalised frames are vocoded
+    as ONE ragged batch on the device, its lengths read there, and every output carries its `waveform` (with `has_targ` also
+    `targ_waveform`); without one nothing else runs and `waveform` stays None.  fused_step=False (or a shape the kernel does not serve) runs the step's policy as
     the unfused composition of the existing kernels; `fused` reports which ran."""
 
     def __init__(self, src_dict, stats_npz_path: Optional[str] = None, max_iter: int = 6000, eos_prob_threshold: float = 0.5,
-                 use_graph: bool = True, fused_step: bool = True, graph_cap: Optional[int] = 512, **unused_kwargs):
+                 use_graph: bool = True, fused_step: bool = True, graph_cap: Optional[int] = 512, vocoder=None, **unused_kwargs):
         super().__init__(src_dict, stats_npz_path)
+        self.vocoder = vocoder
         self.max_iter, self.eos_prob_threshold = int(max_iter), float(eos_prob_threshold)
         self.use_graph, self.fused_step, self.graph_cap = use_graph, bool(fused_step), graph_cap
         self.fused: Optional[bool] = None                   # which step path the last generate() ran
@@ -825,16 +829,29 @@ class AutoRegressiveSpeechGenerator(SpeechGenerator):
         attn = attn.repeat_interleave(n, dim=2).cpu()
         alignment = alignment.repeat_interleave(n, dim=1).cpu()
         out_lens = out_lens * n
+        wav = self._vocode(feat, out_lens)
         feat = feat.cpu()
         finalized = [SpeechGeneratorOutput(feature=feat[b, :l].clone(), eos_prob=eos_prob[b, :l].clone(), attn=attn[b, :, :l].clone(),
-                                           alignment=alignment[b, :l].clone()) for b, l in enumerate(out_lens.tolist())]
+                                           alignment=alignment[b, :l].clone(), waveform=None if wav is None else wav[b])
+                     for b, l in enumerate(out_lens.tolist())]
         if has_targ:
             assert sample["target"].size(-1) == out_dim
             tgt_feats = self.gcmvn_denormalize(sample["target"].view(bsz, -1, raw_dim))
             tgt_lens = (sample["target_lengths"] * n).tolist()
+            tgt_wav = self._vocode(tgt_feats.to(st["feats"].device), sample["target_lengths"].cpu().long() * n)
             for b, (f, l) in enumerate(zip(tgt_feats, tgt_lens)):
                 finalized[b].targ_feature = f[:l].cpu()
+                if tgt_wav is not None:
+                    finalized[b].targ_waveform = tgt_wav[b]
         return finalized
+
+    def _vocode(self, feat, lens):
+        """feat [B, T, raw_dim] on the device, lens [B] (host) -> the B waveforms fp32 [hop * lens[b]] on the CPU; None without a vocoder."""
+        if self.vocoder is None:
+            return None
+        voc = self.vocoder.to(feat.device)
+        wav = voc(feat, lengths=lens)[:, 0].cpu()
+        return [wav[b, :voc.hop * l].clone() for b, l in enumerate(lens.tolist())]
 
 
 # ---------------------------------------------------------------------------------------------------------------- motion generation

@@ -2266,3 +2266,69 @@ def diffusion_sample_step(pred, state, first=False, clip=False, guidance=0.0):
                            img=ptr(img), xin=ptr(xin), level=ptr(level), noise_stride=stride, B=B, T=T, Dd=Dd, W=W, n_steps=n,
                            first=int(bool(first)), clip=int(bool(clip)), guidance=float(guidance))
     lib().call("ofa_diffusion_sample_step", ctypes.addressof(a), dtype_code(xin), stream())
+
+
+# ---------------------------------------------------------------------------------------------- the HiFi-GAN vocoder (csrc/vocoder.hip)
+def vocoder_conv_tile(Cin, Cout, k, d):
+    """Time rows a workgroup of the convolution owns for this shape; 0: the shape is not served (host only)."""
+    return int(lib().cdll.ofa_vocoder_conv_tile(int(Cin), int(Cout), int(k), int(d)))
+
+
+def vocoder_post_tile():
+    """Outputs per workgroup of conv_post's row kernel (host only)."""
+    return int(lib().cdll.ofa_vocoder_post_tile())
+
+
+def _voc_rows(who, x, lens):
+    if x.dim() != 3 or not x.is_contiguous():
+        raise OfaError(f"{who}: x must be contiguous channels-last rows [B, L, C], got {tuple(x.shape)}")
+    if lens is not None and (lens.dtype != torch.int32 or lens.numel() != x.shape[0] or not lens.is_contiguous()):
+        raise OfaError(f"{who}: lens must be a contiguous int32 [B] on the device")
+
+
+def vocoder_conv(x, w, bias, d=1, lens=None, len_scale=1, slope=1.0, res=None, out=None, accum=False, out_scale=1.0):
+    """One launch of ofa_vocoder_conv.  x [B, L, Cin]; w [k, Cout, Cin] and bias [Cout] of x's dtype (fp16 / bf16); res [B, L, Cout] or
+    None; out: the buffer to write (with accum: to add into), a new one when None.  -> [B, L, Cout]."""
+    _voc_rows("vocoder_conv", x, lens)
+    B, L, Cin = x.shape
+    if w.dim() != 3 or w.shape[2] != Cin or bias.numel() != w.shape[1] or w.dtype != x.dtype or bias.dtype != x.dtype \
+            or not w.is_contiguous() or not bias.is_contiguous():
+        raise OfaError(f"vocoder_conv: w {tuple(w.shape)} must be a contiguous [k, Cout, Cin={Cin}] and bias [Cout] of x's dtype")
+    k, Cout = w.shape[0], w.shape[1]
+    if out is None:
+        if accum:
+            raise OfaError("vocoder_conv: accum adds into `out`")
+        out = torch.empty(B, L, Cout, dtype=x.dtype, device=x.device)
+    for name, t in (("res", res), ("out", out)):
+        if t is not None and (tuple(t.shape) != (B, L, Cout) or t.dtype != x.dtype or not t.is_contiguous()):
+            raise OfaError(f"vocoder_conv: {name} must be a contiguous [B, L, Cout] = [{B}, {L}, {Cout}] of x's dtype")
+    lib().call("ofa_vocoder_conv", ptr(x), ptr(w), ptr(bias), ptr(res), ptr(out), ptr(lens), B, L, Cin, Cout, k, int(d), int(len_scale),
+               float(slope), int(bool(accum)), float(out_scale), dtype_code(x), stream())
+    return out
+
+
+def vocoder_upsample(x, w, bias, u, lens=None, len_scale=1, slope=1.0):
+    """One launch of ofa_vocoder_upsample.  x [B, L, Cin]; w [3, u * Cout, Cin] (the polyphase arrangement) and bias [u * Cout] of x's
+    dtype; len_scale: x's factor.  -> [B, L * u, Cout]."""
+    _voc_rows("vocoder_upsample", x, lens)
+    B, L, Cin = x.shape
+    if w.dim() != 3 or w.shape[0] != 3 or w.shape[2] != Cin or w.shape[1] % u or bias.numel() != w.shape[1] or w.dtype != x.dtype \
+            or bias.dtype != x.dtype or not w.is_contiguous() or not bias.is_contiguous():
+        raise OfaError(f"vocoder_upsample: w {tuple(w.shape)} must be a contiguous [3, u * Cout, Cin={Cin}] and bias [u * Cout] of x's dtype")
+    Cout = w.shape[1] // u
+    out = torch.empty(B, L * u, Cout, dtype=x.dtype, device=x.device)
+    lib().call("ofa_vocoder_upsample", ptr(x), ptr(w), ptr(bias), ptr(out), ptr(lens), B, L, Cin, Cout, int(u), int(len_scale), float(slope),
+               dtype_code(x), stream())
+    return out
+
+
+def vocoder_post(x, w, bias, lens=None, len_scale=1, slope=0.01):
+    """One launch of ofa_vocoder_post.  x [B, L, C]; w [k, C] and bias [1] of x's dtype.  -> fp32 [B, L]."""
+    _voc_rows("vocoder_post", x, lens)
+    B, L, C = x.shape
+    if w.dim() != 2 or w.shape[1] != C or bias.numel() != 1 or w.dtype != x.dtype or bias.dtype != x.dtype or not w.is_contiguous():
+        raise OfaError(f"vocoder_post: w {tuple(w.shape)} must be a contiguous [k, C={C}] and bias [1] of x's dtype")
+    out = torch.empty(B, L, dtype=torch.float32, device=x.device)
+    lib().call("ofa_vocoder_post", ptr(x), ptr(w), ptr(bias), ptr(out), ptr(lens), B, L, C, w.shape[0], int(len_scale), float(slope),
+               dtype_code(x), stream())
+    return out

@@ -3135,3 +3135,20 @@ def speech_step(x, head, prenet, proj, state, step, p_drop, fused=True):
     for w, b in prenet:
         h = dropout_add(relu(linear(h, w, b)), None, p_drop, True)
     state["embed"].copy_(linear(h, proj[0], proj[1]))
+
+
+# ---------------------------------------------------------------------------------------------- the HiFi-GAN vocoder (inference only)
+def vocoder_conv(x, w, bias, d=1, lens=None, len_scale=1, slope=1.0, res=None, out=None, accum=False, out_scale=1.0):
+    """Dilated Conv1d on channels-last rows with the leaky-ReLU prologue and the residual / accumulate / scale epilogues in one launch
+    (kernels.vocoder_conv; csrc/vocoder.hip).  No autograd: the vocoder is a frozen model."""
+    return K.vocoder_conv(x, w, bias, d, lens, len_scale, slope, res, out, accum, out_scale)
+
+
+def vocoder_upsample(x, w, bias, u, lens=None, len_scale=1, slope=1.0):
+    """ConvTranspose1d(kernel 2u, stride u, padding u/2) in its polyphase form through the same kernel (kernels.vocoder_upsample)."""
+    return K.vocoder_upsample(x, w, bias, u, lens, len_scale, slope)
+
+
+def vocoder_post(x, w, bias, lens=None, len_scale=1, slope=0.01):
+    """conv_post: leaky ReLU, Conv1d(C -> 1), tanh; fp32 [B, L] (kernels.vocoder_post)."""
+    return K.vocoder_post(x, w, bias, lens, len_scale, slope)

@@ -9,7 +9,7 @@ Generation: `Task.generator` / `Task.inference` run beam search (ofasys_amd/gene
 AUDIO targets, and the diffusion sampler (DiffusionGenerator) for MOTION targets.
 Validation: `Task.valid_batches` walks a split once, in order; `Trainer.validate` (engine.py) runs it through the step engine's
 forward-only `valid_step` -- loss, NLL and, with `cfg.criterion.report_accuracy`, token accuracy (task/base.py:680-703).
-What stays out: file / OSS readers, multi-worker prefetch, generation metrics, the image generator, the BVH conversion of generated motion and the vocoder, checkpoint state.  The
+What stays out: file / OSS readers, multi-worker prefetch, generation metrics, the image generator, the BVH conversion of generated motion, the Griffin-Lim vocoder, checkpoint state.  The
 batch iterator is a plain in-process loop over the bound dataset: micro-batches of `micro_batch_size` rows, each rank of a
 data-parallel job reading its own contiguous shard (io/reader/dataset.py:49-53), reshuffled per epoch with a seeded permutation.
 """
@@ -341,13 +341,23 @@ class Task:
         """AutoRegressiveSpeechGenerator from the reference's generator arguments (task/base.py:555-561): `max_iter` (default 1500) and
         `eos_prob_threshold` (default 0.5) are taken out, the rest (beam-search arguments of the shared default JSON among them) is
         ignored as there.  stats_npz_path: a local .npz with the `mean` / `std` of the global cepstral normalisation, or None (the
-        reference's default is a URL, which nothing here fetches)."""
+        reference's default is a URL, which nothing here fetches).  `vocoder_config` (a local HiFi-GAN JSON configuration, or such a
+        dict) with `vocoder_checkpoint` (a local checkpoint holding "generator") and `vocoder_dtype` ("float16", the default, or
+        "bfloat16") -- as arguments or in cfg.evaluation.generator_args -- give the generator a HiFiGANVocoder: every output then
+        carries its `waveform`.  Without them nothing changes."""
         from .generator import AutoRegressiveSpeechGenerator
         if self.global_dict is None:
             raise ValueError(f"task {self.name}: initialize(global_dict) before building a generator")
         max_iter = gen_kwargs.pop("max_iter", 1500)
         eos_prob_threshold = gen_kwargs.pop("eos_prob_threshold", 0.5)
         extra = {k: gen_kwargs.pop(k) for k in ("use_graph", "fused_step", "graph_cap") if k in gen_kwargs}
+        voc_cfg, voc_ckpt = gen_kwargs.pop("vocoder_config", None), gen_kwargs.pop("vocoder_checkpoint", None)
+        voc_dtype = gen_kwargs.pop("vocoder_dtype", "float16")
+        if voc_cfg is not None:
+            from .module.vocoder import HiFiGANVocoder
+            extra["vocoder"] = HiFiGANVocoder(voc_ckpt, voc_cfg, dtype=voc_dtype)
+        elif voc_ckpt is not None:
+            raise ValueError(f"task {self.name}: vocoder_checkpoint without vocoder_config (the HiFi-GAN JSON configuration)")
         return AutoRegressiveSpeechGenerator(self.global_dict, stats_npz_path=stats_npz_path, max_iter=max_iter,
                                              eos_prob_threshold=eos_prob_threshold, **extra)
 
