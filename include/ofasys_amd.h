@@ -1146,6 +1146,34 @@ int ofa_vocoder_upsample(const void* x, const void* w, const void* bias, void* y
 int ofa_vocoder_post(const void* x, const void* w, const void* bias, float* out, const int32_t* lens, int B, int L, int C, int k,
                      int len_scale, float slope, int dtype, void* stream);
 
+/* ---- the VQGAN image decoder (taming's Decoder behind VQGANTokenizer.decode), csrc/vqgan.hip: NHWC rows [B, H, W, C] of fp16 / bf16
+ * (fp32: UNSUPPORTED), fp32 accumulation, one rounding per output.  C (Cin, Cout) is a multiple of 32 in 32..512, H and W are any size
+ * >= 1 (H W <= 2^20).  No atomics and no sum across workgroups that depends on the batch: equal inputs give equal bits, and a sample
+ * gives the bits it gives alone.
+ *
+ * ofa_vqgan_groupnorm_stats: GroupNorm(32 groups, eps 1e-6) statistics per (sample, group), finalised into scale[b, c] = gamma[c] rstd
+ *   and shift[b, c] = beta[c] - mean rstd gamma[c] (fp32 [B, C]); gamma / beta of `dtype`.  Centred partial sums per chunk of pixels
+ *   (never E[x^2] - mean^2) combined pairwise in a fixed order by a second kernel.  ws: fp32 workspace of B * chunks * 64 floats,
+ *   chunks = ofa_vqgan_gn_chunks(H W, C) (host only; 0: the shape is not served).
+ * ofa_vqgan_norm_rows: y = x * scale[b, c] + shift[b, c], rounded to `dtype`.
+ * ofa_vqgan_conv3x3: Conv2d(Cin, Cout, 3, stride 1, padding 1) as a tap-loop implicit GEMM on the 32x32x16 MFMA:
+ *     y[b, h, w, :] = bias + sum_{dy, dx} W[dy][dx] . a(b, h + dy - 1, w + dx - 1) + res[b, h, w, :]
+ *   a = 0 outside the image, else act(x[b, h', w', :]) (upsample != 0: x[b, h' >> 1, w' >> 1, :]; H, W are then the OUTPUT's, even, and x
+ *   is [B, H/2, W/2, Cin]) with act(v) = swish(v * scale[b, c] + shift[b, c]) rounded to `dtype` (scale == shift == NULL: the identity).
+ *   w is [3 * dy + dx][Cout][Cin] (tap-major, Cin contiguous), bias [Cout]; res (NULL: none) is added in fp32.  y may not alias x or
+ *   res.  ofa_vqgan_conv_plan (host only): out4 = {tile side in pixels, Cin slice, output channels per workgroup, LDS bytes}.
+ * ofa_vqgan_conv_out: out (fp32, NCHW [B, out_ch, H, W]) = bias + the same convolution of swish(x * scale + shift) (kept in fp32) to
+ *   out_ch <= 4 channels; w [9][out_ch][C].  fp32 fma chain in (slice of 32 channels, tap, channel) order. */
+int ofa_vqgan_conv_plan(int Cin, int Cout, int upsample, int* out4);    /* host only */
+int ofa_vqgan_gn_chunks(int HW, int C);                                  /* host only */
+int ofa_vqgan_groupnorm_stats(const void* x, const void* gamma, const void* beta, float* scale, float* shift, float* ws, int64_t ws_bytes,
+                              int B, int H, int W, int C, int dtype, void* stream);
+int ofa_vqgan_norm_rows(const void* x, const float* scale, const float* shift, void* y, int B, int H, int W, int C, int dtype, void* stream);
+int ofa_vqgan_conv3x3(const void* x, const void* w, const void* bias, const void* res, const float* scale, const float* shift, void* y, int B,
+                      int H, int W, int Cin, int Cout, int upsample, int dtype, void* stream);
+int ofa_vqgan_conv_out(const void* x, const void* w, const void* bias, const float* scale, const float* shift, float* out, int B, int H, int W,
+                       int C, int out_ch, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

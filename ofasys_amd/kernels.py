@@ -2332,3 +2332,79 @@ def vocoder_post(x, w, bias, lens=None, len_scale=1, slope=0.01):
     lib().call("ofa_vocoder_post", ptr(x), ptr(w), ptr(bias), ptr(out), ptr(lens), B, L, C, w.shape[0], int(len_scale), float(slope),
                dtype_code(x), stream())
     return out
+
+
+# ---------------------------------------------------------------------------------------------- the VQGAN image decoder (csrc/vqgan.hip)
+def vqgan_conv_plan(Cin, Cout, upsample=False):
+    """(tile side in pixels, Cin slice, output channels per workgroup, LDS bytes) of ofa_vqgan_conv3x3 for this shape (host only)."""
+    out = (ctypes.c_int * 4)()
+    lib().call("ofa_vqgan_conv_plan", int(Cin), int(Cout), int(bool(upsample)), ctypes.addressof(out))
+    return tuple(out)
+
+
+def _vq_rows(who, x):
+    if x.dim() != 4 or not x.is_contiguous():
+        raise OfaError(f"{who}: x must be contiguous NHWC rows [B, H, W, C], got {tuple(x.shape)}")
+    return x.shape
+
+
+def _vq_tables(who, x, scale, shift):
+    for t in (scale, shift):
+        if t is None or t.dtype != torch.float32 or tuple(t.shape) != (x.shape[0], x.shape[3]) or not t.is_contiguous():
+            raise OfaError(f"{who}: scale and shift must be contiguous fp32 [B, C] = [{x.shape[0]}, {x.shape[3]}]")
+
+
+def vqgan_groupnorm_stats(x, gamma, beta):
+    """One call of ofa_vqgan_groupnorm_stats.  x [B, H, W, C]; gamma, beta [C] of x's dtype.  -> (scale, shift), fp32 [B, C]."""
+    B, H, W, C = _vq_rows("vqgan_groupnorm_stats", x)
+    if gamma.numel() != C or beta.numel() != C or gamma.dtype != x.dtype or beta.dtype != x.dtype or not gamma.is_contiguous() \
+            or not beta.is_contiguous():
+        raise OfaError(f"vqgan_groupnorm_stats: gamma and beta must be contiguous [C={C}] of x's dtype")
+    chunks = int(lib().cdll.ofa_vqgan_gn_chunks(H * W, C))
+    ws = torch.empty(max(1, B * chunks * 64), dtype=torch.float32, device=x.device)
+    scale = torch.empty(B, C, dtype=torch.float32, device=x.device)
+    shift = torch.empty(B, C, dtype=torch.float32, device=x.device)
+    lib().call("ofa_vqgan_groupnorm_stats", ptr(x), ptr(gamma), ptr(beta), ptr(scale), ptr(shift), ptr(ws), ws.numel() * 4, B, H, W, C,
+               dtype_code(x), stream())
+    return scale, shift
+
+
+def vqgan_norm_rows(x, scale, shift):
+    """One launch of ofa_vqgan_norm_rows: x * scale[b, c] + shift[b, c] in x's dtype."""
+    B, H, W, C = _vq_rows("vqgan_norm_rows", x)
+    _vq_tables("vqgan_norm_rows", x, scale, shift)
+    out = torch.empty_like(x)
+    lib().call("ofa_vqgan_norm_rows", ptr(x), ptr(scale), ptr(shift), ptr(out), B, H, W, C, dtype_code(x), stream())
+    return out
+
+
+def vqgan_conv3x3(x, w, bias, scale=None, shift=None, res=None, upsample=False):
+    """One launch of ofa_vqgan_conv3x3.  x [B, H, W, Cin]; w [9, Cout, Cin] and bias [Cout] of x's dtype; scale / shift fp32 [B, Cin] (the
+    norm + swish prologue) or None; res [B, H', W', Cout] or None.  -> [B, H', W', Cout], H' = 2 H with the upsample."""
+    B, H, W, Cin = _vq_rows("vqgan_conv3x3", x)
+    if w.dim() != 3 or w.shape[0] != 9 or w.shape[2] != Cin or bias.numel() != w.shape[1] or w.dtype != x.dtype or bias.dtype != x.dtype \
+            or not w.is_contiguous() or not bias.is_contiguous():
+        raise OfaError(f"vqgan_conv3x3: w {tuple(w.shape)} must be a contiguous [9, Cout, Cin={Cin}] and bias [Cout] of x's dtype")
+    if (scale is None) != (shift is None):
+        raise OfaError("vqgan_conv3x3: scale and shift come together")
+    if scale is not None:
+        _vq_tables("vqgan_conv3x3", x, scale, shift)
+    Cout, up = w.shape[1], 2 if upsample else 1
+    out = torch.empty(B, H * up, W * up, Cout, dtype=x.dtype, device=x.device)
+    if res is not None and (tuple(res.shape) != tuple(out.shape) or res.dtype != x.dtype or not res.is_contiguous()):
+        raise OfaError(f"vqgan_conv3x3: res must be a contiguous {list(out.shape)} of x's dtype")
+    lib().call("ofa_vqgan_conv3x3", ptr(x), ptr(w), ptr(bias), ptr(res), ptr(scale), ptr(shift), ptr(out), B, H * up, W * up, Cin, Cout,
+               int(bool(upsample)), dtype_code(x), stream())
+    return out
+
+
+def vqgan_conv_out(x, w, bias, scale, shift):
+    """One launch of ofa_vqgan_conv_out.  x [B, H, W, C]; w [9, out_ch, C] and bias [out_ch] of x's dtype.  -> fp32 NCHW [B, out_ch, H, W]."""
+    B, H, W, C = _vq_rows("vqgan_conv_out", x)
+    _vq_tables("vqgan_conv_out", x, scale, shift)
+    if w.dim() != 3 or w.shape[0] != 9 or w.shape[2] != C or bias.numel() != w.shape[1] or w.dtype != x.dtype or bias.dtype != x.dtype \
+            or not w.is_contiguous() or not bias.is_contiguous():
+        raise OfaError(f"vqgan_conv_out: w {tuple(w.shape)} must be a contiguous [9, out_ch, C={C}] and bias [out_ch] of x's dtype")
+    out = torch.empty(B, w.shape[1], H, W, dtype=torch.float32, device=x.device)
+    lib().call("ofa_vqgan_conv_out", ptr(x), ptr(w), ptr(bias), ptr(scale), ptr(shift), ptr(out), B, H, W, C, w.shape[1], dtype_code(x), stream())
+    return out

@@ -3152,3 +3152,26 @@ def vocoder_upsample(x, w, bias, u, lens=None, len_scale=1, slope=1.0):
 def vocoder_post(x, w, bias, lens=None, len_scale=1, slope=0.01):
     """conv_post: leaky ReLU, Conv1d(C -> 1), tanh; fp32 [B, L] (kernels.vocoder_post)."""
     return K.vocoder_post(x, w, bias, lens, len_scale, slope)
+
+
+# ---------------------------------------------------------------------------------------------- the VQGAN image decoder (inference only)
+def vqgan_groupnorm_stats(x, gamma, beta):
+    """GroupNorm(32, eps 1e-6) of NHWC rows as the per-(sample, channel) tables (scale, shift) the next kernel applies while staging
+    (kernels.vqgan_groupnorm_stats; csrc/vqgan.hip).  No autograd: the decoder is a frozen model."""
+    return K.vqgan_groupnorm_stats(x, gamma, beta)
+
+
+def vqgan_norm_rows(x, scale, shift):
+    """x * scale + shift: the normalised map without the swish, for AttnBlock's q / k / v (kernels.vqgan_norm_rows)."""
+    return K.vqgan_norm_rows(x, scale, shift)
+
+
+def vqgan_conv3x3(x, w, bias, scale=None, shift=None, res=None, upsample=False):
+    """3 x 3 convolution of NHWC rows in one launch: norm + swish prologue from the tables, optional nearest x2 upsample of the input,
+    bias and residual add in the epilogue (kernels.vqgan_conv3x3)."""
+    return K.vqgan_conv3x3(x, w, bias, scale, shift, res, upsample)
+
+
+def vqgan_conv_out(x, w, bias, scale, shift):
+    """norm + swish -> 3 x 3 convolution to <= 4 channels -> fp32 NCHW (kernels.vqgan_conv_out)."""
+    return K.vqgan_conv_out(x, w, bias, scale, shift)
