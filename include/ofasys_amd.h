@@ -1174,6 +1174,31 @@ int ofa_vqgan_conv3x3(const void* x, const void* w, const void* bias, const void
 int ofa_vqgan_conv_out(const void* x, const void* w, const void* bias, const float* scale, const float* shift, float* out, int B, int H, int W,
                        int C, int out_ch, int dtype, void* stream);
 
+/* ---- the VQGAN image encoder's own kernels (taming's Encoder + GumbelQuantize behind VQGANTokenizer.encode), csrc/vqgan_encode.hip; the
+ * res blocks, attention blocks and conv_out are the decoder's entry points above.  fp16 / bf16 (fp32: UNSUPPORTED), fp32 accumulation, one
+ * rounding per output, no atomics, no sum across workgroups: a sample gives the bits it gives alone.
+ *
+ * ofa_vqgan_downsample: taming's Downsample -- zero pad on the bottom and right only, then Conv2d(C, C, 3, stride 2, padding 0):
+ *     y[b, h, w, :] = bias + sum_{dy, dx} W[dy][dx] . x(b, 2 h + dy, 2 w + dx),   x = 0 at row H and column W
+ *   x [B, H, W, C] -> y [B, H / 2, W / 2, C] (H, W >= 2, any parity); w [3 * dy + dx][Cout][Cin]; Cin = Cout = a multiple of 32 in 32..512.
+ *   ofa_vqgan_downsample_plan (host only): out5 = {output tile rows, output tile columns, Cin slice, output channels per workgroup, LDS bytes}.
+ * ofa_vqgan_conv_in: Conv2d(3, Cout, 3, stride 1, padding 1) from the fp32 NCHW image [B, 3, H, W] (rounded once to `dtype`) to rows
+ *   [B, H, W, Cout].  w32 is [Cout][32] of `dtype`: w32[n][3 * (3 * dy + dx) + c] = weight[n][c][dy][dx], columns 27..31 zeros.
+ *   in_channels other than 3: UNSUPPORTED.
+ * ofa_vqgan_quantize: out[r] = argmax_n (w[n] . h[r] + bias[n] + g[r][n]) without forming the logits.  h [N, K], w [n_embed, K], bias
+ *   [n_embed] of `dtype`; out int32 [N]; K a multiple of 32 in 32..512, n_embed a multiple of 32.  The lowest index wins a tie; a NaN
+ *   never wins (a row of NaNs gives 0).  seed < 0: g = 0.  Else g = -log(-log(u)) in fp32, u = ((word >> 8) + 0.5) * 2^-24, `word` the
+ *   word n % 4 of Philox4x32-10(counter = r * (n_embed / 4) + n / 4 in the low two counter words, key = seed): the noise of a row depends
+ *   on its index r in the call.  ws: workspace of ofa_vqgan_quantize_plan's bytes (16-byte aligned; may be NULL when that is 0).
+ *   ofa_vqgan_quantize_plan (host only): out4 = {row tile, code splits (grid y), workspace bytes, LDS bytes}. */
+int ofa_vqgan_downsample_plan(int C, int* out5);                          /* host only */
+int ofa_vqgan_downsample(const void* x, const void* w, const void* bias, void* y, int B, int H, int W, int Cin, int Cout, int dtype, void* stream);
+int ofa_vqgan_conv_in(const float* image, const void* w32, const void* bias, void* y, int B, int in_channels, int H, int W, int Cout, int dtype,
+                      void* stream);
+int ofa_vqgan_quantize_plan(int64_t N, int K, int n_embed, int64_t* out4);  /* host only */
+int ofa_vqgan_quantize(const void* h, const void* w, const void* bias, int* out, void* ws, int64_t ws_bytes, int64_t N, int K, int n_embed,
+                       int64_t seed, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2408,3 +2408,58 @@ def vqgan_conv_out(x, w, bias, scale, shift):
     out = torch.empty(B, w.shape[1], H, W, dtype=torch.float32, device=x.device)
     lib().call("ofa_vqgan_conv_out", ptr(x), ptr(w), ptr(bias), ptr(scale), ptr(shift), ptr(out), B, H, W, C, w.shape[1], dtype_code(x), stream())
     return out
+
+
+# ---------------------------------------------------------------------------------------------- the VQGAN image encoder (csrc/vqgan_encode.hip)
+def vqgan_downsample_plan(C):
+    """(output tile rows, output tile columns, Cin slice, output channels per workgroup, LDS bytes) of ofa_vqgan_downsample (host only)."""
+    out = (ctypes.c_int * 5)()
+    lib().call("ofa_vqgan_downsample_plan", int(C), ctypes.addressof(out))
+    return tuple(out)
+
+
+def vqgan_downsample(x, w, bias):
+    """One launch of ofa_vqgan_downsample.  x [B, H, W, C]; w [9, C, C] and bias [C] of x's dtype.  -> [B, H // 2, W // 2, C]."""
+    B, H, W, Cin = _vq_rows("vqgan_downsample", x)
+    if w.dim() != 3 or w.shape[0] != 9 or w.shape[2] != Cin or bias.numel() != w.shape[1] or w.dtype != x.dtype or bias.dtype != x.dtype \
+            or not w.is_contiguous() or not bias.is_contiguous():
+        raise OfaError(f"vqgan_downsample: w {tuple(w.shape)} must be a contiguous [9, Cout, Cin={Cin}] and bias [Cout] of x's dtype")
+    out = torch.empty(B, H // 2, W // 2, w.shape[1], dtype=x.dtype, device=x.device)
+    lib().call("ofa_vqgan_downsample", ptr(x), ptr(w), ptr(bias), ptr(out), B, H, W, Cin, w.shape[1], dtype_code(x), stream())
+    return out
+
+
+def vqgan_conv_in(image, w32, bias):
+    """One launch of ofa_vqgan_conv_in.  image fp32 NCHW [B, 3, H, W]; w32 [Cout, 32] (k = 3 tap + c, columns 27..31 zeros) and bias [Cout]
+    of the output's 16-bit dtype.  -> rows [B, H, W, Cout] of that dtype."""
+    if image.dim() != 4 or image.dtype != torch.float32 or not image.is_contiguous():
+        raise OfaError(f"vqgan_conv_in: image must be a contiguous fp32 NCHW [B, 3, H, W], got {image.dtype} {tuple(image.shape)}")
+    if w32.dim() != 2 or w32.shape[1] != 32 or bias.numel() != w32.shape[0] or bias.dtype != w32.dtype or not w32.is_contiguous() \
+            or not bias.is_contiguous():
+        raise OfaError(f"vqgan_conv_in: w32 {tuple(w32.shape)} must be a contiguous [Cout, 32] and bias [Cout] of one 16-bit dtype")
+    B, Cin, H, W = image.shape
+    out = torch.empty(B, H, W, w32.shape[0], dtype=w32.dtype, device=image.device)
+    lib().call("ofa_vqgan_conv_in", ptr(image), ptr(w32), ptr(bias), ptr(out), B, Cin, H, W, w32.shape[0], dtype_code(w32), stream())
+    return out
+
+
+def vqgan_quantize_plan(N, K, n_embed):
+    """(row tile, code splits, workspace bytes, LDS bytes) of ofa_vqgan_quantize for this shape (host only)."""
+    out = (ctypes.c_int64 * 4)()
+    lib().call("ofa_vqgan_quantize_plan", int(N), int(K), int(n_embed), ctypes.addressof(out))
+    return tuple(out)
+
+
+def vqgan_quantize(h, w, bias, seed=-1):
+    """ofa_vqgan_quantize: h [N, K], w [n_embed, K], bias [n_embed] of one 16-bit dtype.  -> int32 [N], the arg-max of w h + bias (+ Gumbel
+    noise drawn from Philox(seed) when seed >= 0) over the codes; the logits are never formed."""
+    if h.dim() != 2 or w.dim() != 2 or w.shape[1] != h.shape[1] or bias.numel() != w.shape[0] or w.dtype != h.dtype or bias.dtype != h.dtype \
+            or not (h.is_contiguous() and w.is_contiguous() and bias.is_contiguous()):
+        raise OfaError(f"vqgan_quantize: h {tuple(h.shape)}, w {tuple(w.shape)} and bias must be contiguous [N, K], [n_embed, K], [n_embed] of "
+                       "one dtype")
+    N, Kd, n_embed = h.shape[0], h.shape[1], w.shape[0]
+    ws_bytes = vqgan_quantize_plan(N, Kd, n_embed)[2]
+    ws = torch.empty(ws_bytes // 4, dtype=torch.int32, device=h.device) if ws_bytes else None
+    out = torch.empty(N, dtype=torch.int32, device=h.device)
+    lib().call("ofa_vqgan_quantize", ptr(h), ptr(w), ptr(bias), ptr(out), ptr(ws), ws_bytes, N, Kd, n_embed, int(seed), dtype_code(h), stream())
+    return out

@@ -3175,3 +3175,22 @@ def vqgan_conv3x3(x, w, bias, scale=None, shift=None, res=None, upsample=False):
 def vqgan_conv_out(x, w, bias, scale, shift):
     """norm + swish -> 3 x 3 convolution to <= 4 channels -> fp32 NCHW (kernels.vqgan_conv_out)."""
     return K.vqgan_conv_out(x, w, bias, scale, shift)
+
+
+# ---------------------------------------------------------------------------------------------- the VQGAN image encoder (inference only)
+def vqgan_conv_in(image, w, bias):
+    """The encoder's first layer: Conv2d(3, Cout, 3, padding 1) from the fp32 NCHW image to 16-bit NHWC rows in one launch
+    (kernels.vqgan_conv_in; csrc/vqgan_encode.hip).  w [Cout, 32]: see module.vqgan.conv_in_weight."""
+    return K.vqgan_conv_in(image, w, bias)
+
+
+def vqgan_downsample(x_rows, w9, bias):
+    """taming's Downsample: zero pad on the bottom and right, 3 x 3 convolution at stride 2 (kernels.vqgan_downsample)."""
+    return K.vqgan_downsample(x_rows, w9, bias)
+
+
+def vqgan_quantize(h_rows, w, bias, seed=None):
+    """The Gumbel quantizer's codes, int64 [N]: argmax_n (w h + bias + g)[n] with the projection, the noise and the arg-max in one sweep
+    (kernels.vqgan_quantize).  seed None: no noise (the plain arg-max, lowest index on a tie).  With a seed, g[r, n] comes from Philox
+    position r * n_embed + n: the noise of a row depends on its position r in the batch, so a sample alone draws other noise."""
+    return K.vqgan_quantize(h_rows, w, bias, -1 if seed is None else int(seed)).long()

@@ -6,7 +6,14 @@
   (c) one vq_conv3x3 launch at 256 x 256 x 128 -> 128 and at 32 x 32 x 512 -> 512 (B = 1, bf16) against F.conv2d, NCHW and channels_last.
 Times are device events around `inner` back-to-back calls after a warm-up, the arms alternated in one process, median / min / max over the
 runs; Gflop counts 2 x the multiply-adds of the convolutions and of the attention products.  Writes what it prints to
-profiles/vqgan_bench.txt (--out).  Usage: python tools/vqgan_bench.py"""
+profiles/vqgan_bench.txt (--out).  Usage: python tools/vqgan_bench.py
+
+`--arm encode` measures the encoder instead (csrc/vqgan_encode.hip through VQGANTokenizer(with_encoder=True)) and writes
+profiles/vqgan_encode_bench.txt:
+  (d) the f8 encoder, 256 x 256 images -> 32 x 32 codes, bf16 and fp16 at B = 1 and B = 8: `encode` with and without the Gumbel noise against
+      torch's device composite of tests/vqgan_encode_case.py (the restated Encoder, quant_conv, the proj convolution and, as the reference,
+      F.gumbel_softmax(hard) -> argmax);
+  (e) the quantize launch alone at N = 8192, K = 256, n_embed = 8192 against F.conv2d + argmax."""
 import argparse
 import os
 import statistics
@@ -135,12 +142,76 @@ def conv_speed(H, Cn, runs, inner):
     say(f"        F.conv2d, channels_last      : {spread(res['nhwc'])}; vq_conv3x3 / F.conv2d = {ours / statistics.median(res['nhwc']):.3f}")
 
 
+def alternate(arms, runs, inner):
+    for fn in arms.values():
+        timed(fn, 1)
+    res = {k: [] for k in arms}
+    for _ in range(runs):
+        for k, fn in arms.items():
+            res[k].append(timed(fn, inner))
+    return res
+
+
+def encoder_speed(name, dtype, B, runs, inner):
+    from ofasys_amd import VQGANTokenizer
+    from tests import vqgan_encode_case as E
+    tok = VQGANTokenizer(C.F8, None, dtype=dtype, with_encoder=True)
+    state = tok.vqgan.state_dict()
+    x = torch.randn(B, 3, 256, 256, generator=torch.Generator().manual_seed(B)).to(dtype).float().cuda()
+    xt, pw, pb = x.to(dtype), state["quantize.proj.weight"], state["quantize.proj.bias"]
+    arms = {"ours": lambda: tok.encode(x, seed=1), "plain": lambda: tok.encode(x, gumbel=False),
+            "torch": lambda: F.gumbel_softmax(F.conv2d(E.prequant(state, C.F8, xt), pw, pb), tau=1.0, dim=1, hard=True).argmax(1)}
+    diff = C.rel(tok.encode_to_prequant(x), E.prequant(state, C.F8, xt).float())
+    same = float((arms["plain"]() == F.conv2d(E.prequant(state, C.F8, xt), pw, pb).argmax(1).view(B, -1)).float().mean())
+    calls, stats = count_calls(arms["ours"])
+    res = alternate(arms, runs, inner)
+    ours, theirs = statistics.median(res["ours"]), statistics.median(res["torch"])
+    say(f"    {name}, B = {B}; {runs} alternated runs of {inner} encodes, ms per encode; relative difference of the two arms' pre-quant features {diff:.2e}, "
+        f"equal plain arg-max codes {100 * same:.1f} %")
+    say(f"        csrc/vqgan_encode.hip + vqgan.hip, {calls} calls ({calls + stats} kernels + the split fold), Gumbel noise: {spread(res['ours'])} = {ours / B:.3f} ms per image")
+    say(f"        the same without the noise                      : {spread(res['plain'])}")
+    say(f"        torch's device composite (F.gumbel_softmax hard): {spread(res['torch'])} = {theirs / B:.3f} ms per image")
+    say(f"        new path / torch = {ours / theirs:.3f} (medians; both include the host's launch work)")
+
+
+def quantize_speed(runs, inner):
+    from ofasys_amd import ops
+    N, Kd, n_embed, gen, dtype = 8192, 256, 8192, torch.Generator().manual_seed(0), torch.bfloat16
+    h, w = torch.randn(N, Kd, generator=gen).to(dtype).cuda(), (torch.randn(n_embed, Kd, generator=gen) / Kd ** 0.5).to(dtype).cuda()
+    b = (0.1 * torch.randn(n_embed, generator=gen)).to(dtype).cuda()
+    hn, w4 = h.view(8, 32, 32, Kd).permute(0, 3, 1, 2).contiguous(), w.view(n_embed, Kd, 1, 1)
+    arms = {"ours": lambda: ops.vqgan_quantize(h, w, b), "noise": lambda: ops.vqgan_quantize(h, w, b, 1), "torch": lambda: F.conv2d(hn, w4, b).argmax(1)}
+    same = float((arms["ours"]() == arms["torch"]().view(-1)).float().mean())
+    res = alternate(arms, runs, inner)
+    gf, ours = 2 * N * Kd * n_embed / 1e9, statistics.median(res["ours"])
+    say(f"    N = {N}, K = {Kd}, n_embed = {n_embed}, bf16 ({gf:.1f} Gflop); {runs} alternated runs of {inner} calls; codes equal to torch's {100 * same:.2f} % "
+        "(torch rounds the logits to bf16 before its arg-max)")
+    say(f"        vq_quantize + fold, no noise : {spread(res['ours'])} = {gf / ours:.1f} Tflop/s")
+    say(f"        vq_quantize + fold, noise    : {spread(res['noise'])}")
+    say(f"        F.conv2d + argmax            : {spread(res['torch'])}; vq_quantize / torch = {ours / statistics.median(res['torch']):.3f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "vqgan_bench.txt"))
+    ap.add_argument("--arm", choices=("decode", "encode"), default="decode")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.out = args.out or os.path.join(ROOT, "profiles", "vqgan_bench.txt" if args.arm == "decode" else "vqgan_encode_bench.txt")
     if not torch.cuda.is_available():
         raise SystemExit("tools/vqgan_bench.py needs a GPU: there is no fallback")
+    if args.arm == "encode":
+        say("tools/vqgan_bench.py --arm encode -- the VQGAN encoder of csrc/vqgan_encode.hip against torch's device composite in the same 16-bit dtype")
+        say(f"source_id {bench.source_id()}")
+        with torch.no_grad():
+            say("(d) the f8 Gumbel encoder (ch 128, ch_mult 1,1,2,4, two res blocks, attention at 32 x 32), 256 x 256 images -> 32 x 32 codes, seeded weights, device events")
+            for name, dtype in DTYPES:
+                encoder_speed(name, dtype, 1, runs=7, inner=3)
+                encoder_speed(name, dtype, 8, runs=5, inner=1)
+            say("(e) the quantizer alone against F.conv2d + argmax, device events, ms per call")
+            quantize_speed(runs=7, inner=10)
+        with open(args.out, "w") as f:
+            f.write("\n".join(LINES) + "\n")
+        return
     say("tools/vqgan_bench.py -- the VQGAN decoder of csrc/vqgan.hip against torch's device composite in the same 16-bit dtype")
     say(f"source_id {bench.source_id()}")
     with torch.no_grad():
