@@ -1199,6 +1199,34 @@ int ofa_vqgan_quantize_plan(int64_t N, int K, int n_embed, int64_t* out4);  /* h
 int ofa_vqgan_quantize(const void* h, const void* w, const void* bias, int* out, void* ws, int64_t ws_bytes, int64_t N, int K, int n_embed,
                        int64_t seed, int dtype, void* stream);
 
+/* ---- the Griffin-Lim vocoder (module/vocoder.py:29-151), csrc/griffin_lim.hip: fp32 throughout, no atomics (equal inputs give equal bits),
+ * nothing reads a length on the host.  N = n_fft (a power of two in 256..2048), M = N / 2, K = M + 1 bins, win <= N, 1 <= hop <= N; other
+ * shapes: UNSUPPORTED before any launch.  A batch holds T frames per utterance and hop (T - 1) samples; lens (int32 [B] on the device, or
+ * NULL: every utterance is full) gives utterance b its own frame count Tb = clamp(lens[b], 0, T) and its own length Lb = hop (Tb - 1):
+ * reflect padding, frame count and window-sum-square are those of Lb, samples from Lb on are written as zeros, and no utterance reads a
+ * neighbour's samples -- a ragged batch gives the bits of its utterances run alone.
+ *   window   [N]: the analysis = synthesis window padded to N, (N - win) / 2 zeros on the left (16-byte aligned)
+ *   twiddle  [M][2]: (cos, -sin)(2 pi j / N), j < M, computed in float64 and rounded once
+ *   wss      window-sum-square tables of N + hop (T' - 1) entries: row b (at b * wss_stride) is the table of T' = Tb frames; wss_stride = 0
+ *            shares one table of T frames (lens NULL only)
+ *   S        [B, T, K] magnitudes
+ * ofa_griffin_lim_project: one Griffin-Lim iteration, w_in [B, hop (T-1)] -> w_out (another buffer).  Per frame t < Tb: the windowed segment
+ *   of w_in at t hop - M (index reflected at 0 and Lb - 1), a real FFT, every bin X_k replaced by S[b, t, k] X_k / |X_k| ((1, 0) at X_k = 0;
+ *   normalised by max(|re|, |im|) before the square root), the Hermitian inverse (imaginary parts of DC and Nyquist ignored), the window
+ *   again; frames are overlap-added in ascending order, divided by wss where wss > 1.1754944e-38 and trimmed by M at both ends.  The caller
+ *   refuses utterances with Lb <= M (reflect padding is undefined there; the kernel then clamps the index and stays in bounds).
+ * ofa_griffin_lim_inverse: the same synthesis from supplied phases [B, T, K] (bin k of frame t is S (cos, sin)(phase)); iteration 0.
+ * ofa_griffin_lim_specgram: S[r, k] = max(0, sum_j pinv_t[j, k] exp(x[r, j])), x [rows, n_mels] of `dtype` (converted on load), pinv_t fp32
+ *   [n_mels, n_freq] (the pseudo-inverse of the mel filters, transposed); one fp32 fma chain in j order per output.  n_mels <= 128.
+ * ofa_griffin_lim_run (host only): the frames' worth of samples one workgroup owns (it recomputes the ceil(N / hop) - 1 frames that
+ *   overlap them from outside), 0 when the shape is not served. */
+int ofa_griffin_lim_run(int n_fft, int win, int hop);                    /* host only */
+int ofa_griffin_lim_project(const float* w_in, const float* S, const float* window, const float* twiddle, const float* wss, int64_t wss_stride,
+                            const int32_t* lens, float* w_out, int B, int T, int n_fft, int win, int hop, void* stream);
+int ofa_griffin_lim_inverse(const float* phase, const float* S, const float* window, const float* twiddle, const float* wss, int64_t wss_stride,
+                            const int32_t* lens, float* w_out, int B, int T, int n_fft, int win, int hop, void* stream);
+int ofa_griffin_lim_specgram(const void* x, const float* pinv_t, float* S, int64_t rows, int n_mels, int n_freq, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,7 @@ from .traverse import TraversePlan, TraverseTask  # noqa: E402,F401
 from .generator import (AutoRegressiveSpeechGenerator, DiffusionGenerator, DiverseBeamSearch, DiverseSiblingsSearch, Sampling,  # noqa: E402,F401
                         MotionOutput, SpeechGenerator, SpeechGeneratorOutput)
 from .module.hifigan import Generator as HiFiGANGenerator  # noqa: E402,F401
-from .module.vocoder import HiFiGANVocoder  # noqa: E402,F401
+from .module.vocoder import GriffinLimVocoder, HiFiGANVocoder  # noqa: E402,F401
 from .module.vqgan import VQGANDecoderModel, VQGANTokenizer  # noqa: E402,F401
 from .scst import CiderD, ScstRewardCriterion  # noqa: E402,F401
 from .engine import Trainer, TrainerConfig  # noqa: E402,F401
@@ -25,5 +25,5 @@ __all__ = ["Task", "TaskConfig", "TraverseTask", "TraversePlan", "Trainer", "Tra
            "GeneralistModel", "GeneralistModelConfig", "Slot", "ModalityType", "Dictionary", "register_config",
            "ConfigStore", "AdaptorOutput", "BaseAdaptor", "BaseAdaptorConfig", "OFAGeneralAdaptor", "Sampling", "CiderD",
            "ScstRewardCriterion", "DiverseBeamSearch", "DiverseSiblingsSearch", "SpeechGenerator", "AutoRegressiveSpeechGenerator",
-           "SpeechGeneratorOutput", "DiffusionGenerator", "MotionOutput", "HiFiGANVocoder", "HiFiGANGenerator", "VQGANTokenizer",
+           "SpeechGeneratorOutput", "DiffusionGenerator", "MotionOutput", "HiFiGANVocoder", "GriffinLimVocoder", "HiFiGANGenerator", "VQGANTokenizer",
            "VQGANDecoderModel"]

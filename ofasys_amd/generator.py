@@ -757,7 +757,7 @@ class AutoRegressiveSpeechGenerator(SpeechGenerator):
     postnet.  Semantics are the reference's: the finish test is strict, finished rows keep decoding (their later positions are padded
     keys of their own cache, their later frames are fed back and reach their kept frames through the postnet's window), rows that
     never finish keep max_iter.  Differences ("Speech generation"): `attn` holds every step's map, results are on
-    the CPU, a local statistics file.  vocoder (module/vocoder.py HiFiGANVocoder, or None): the batch's denormalised frames are vocoded
+    the CPU, a local statistics file.  vocoder (module/vocoder.py HiFiGANVocoder or GriffinLimVocoder, or None): the batch's denormalised frames are vocoded
     as ONE ragged batch on the device, its lengths read there, and every output carries its `waveform` (with `has_targ` also
     `targ_waveform`); without one nothing else runs and `waveform` stays None.  fused_step=False (or a shape the kernel does not serve) runs the step's policy as
     the unfused composition of the existing kernels; `fused` reports which ran."""
@@ -846,12 +846,13 @@ class AutoRegressiveSpeechGenerator(SpeechGenerator):
         return finalized
 
     def _vocode(self, feat, lens):
-        """feat [B, T, raw_dim] on the device, lens [B] (host) -> the B waveforms fp32 [hop * lens[b]] on the CPU; None without a vocoder."""
+        """feat [B, T, raw_dim] on the device, lens [B] (host) -> the B waveforms fp32 [vocoder.out_len(lens[b])] on the CPU (HiFi-GAN:
+        hop * lens[b]; Griffin-Lim: hop * (lens[b] - 1)); None without a vocoder."""
         if self.vocoder is None:
             return None
         voc = self.vocoder.to(feat.device)
         wav = voc(feat, lengths=lens)[:, 0].cpu()
-        return [wav[b, :voc.hop * l].clone() for b, l in enumerate(lens.tolist())]
+        return [wav[b, :voc.out_len(l)].clone() for b, l in enumerate(lens.tolist())]
 
 
 # ---------------------------------------------------------------------------------------------------------------- motion generation

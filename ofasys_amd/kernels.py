@@ -2334,6 +2334,54 @@ def vocoder_post(x, w, bias, lens=None, len_scale=1, slope=0.01):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- the Griffin-Lim vocoder (csrc/griffin_lim.hip)
+def griffin_lim_run(n_fft, win, hop):
+    """Frames' worth of samples a workgroup of the Griffin-Lim step owns; 0: the shape is not served (host only)."""
+    return int(lib().cdll.ofa_griffin_lim_run(int(n_fft), int(win), int(hop)))
+
+
+def _gl_step(name, src, S, window, twiddle, wss, lens, out, win, hop):
+    B, T, K = S.shape
+    n_fft, L = 2 * (K - 1), hop * (T - 1)
+    for what, t, shape in (("S", S, (B, T, K)), ("window", window, (n_fft,)), ("twiddle", twiddle, (n_fft // 2, 2)),
+                           ("src", src, (B, L) if name == "project" else (B, T, K))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise OfaError(f"griffin_lim_{name}: {what} must be a contiguous fp32 {shape}, got {t.dtype} {tuple(t.shape)}")
+    n = n_fft + L
+    if wss.dtype != torch.float32 or not wss.is_contiguous() or tuple(wss.shape) not in ((n,), (B, n)):
+        raise OfaError(f"griffin_lim_{name}: wss must be a contiguous fp32 [{n}] or [{B}, {n}]")
+    if lens is not None and (lens.dtype != torch.int32 or lens.numel() != B or not lens.is_contiguous() or wss.dim() != 2):
+        raise OfaError(f"griffin_lim_{name}: lens must be a contiguous int32 [B] on the device, with one wss row per utterance")
+    if out is None:
+        out = torch.empty(B, L, dtype=torch.float32, device=S.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, L) or not out.is_contiguous():
+        raise OfaError(f"griffin_lim_{name}: out must be a contiguous fp32 [{B}, {L}]")
+    lib().call("ofa_griffin_lim_" + name, ptr(src), ptr(S), ptr(window), ptr(twiddle), ptr(wss), n if wss.dim() == 2 else 0, ptr(lens), ptr(out),
+               B, T, n_fft, int(win), int(hop), stream())
+    return out
+
+
+def griffin_lim_project(w, S, window, twiddle, wss, win, hop, lens=None, out=None):
+    """One launch of ofa_griffin_lim_project: one Griffin-Lim iteration.  w fp32 [B, hop (T - 1)], S [B, T, n_fft / 2 + 1], window [n_fft],
+    twiddle [n_fft / 2, 2], wss [n_fft + hop (T - 1)] (or one such row per utterance: [B, ...], required with lens) -> out (not w)."""
+    return _gl_step("project", w, S, window, twiddle, wss, lens, out, win, hop)
+
+
+def griffin_lim_inverse(phase, S, window, twiddle, wss, win, hop, lens=None, out=None):
+    """One launch of ofa_griffin_lim_inverse: the synthesis from supplied phases [B, T, n_fft / 2 + 1]; the rest as griffin_lim_project."""
+    return _gl_step("inverse", phase, S, window, twiddle, wss, lens, out, win, hop)
+
+
+def griffin_lim_specgram(x, pinv_t):
+    """One launch of ofa_griffin_lim_specgram.  x [..., n_mels] log-mel rows (fp32 / bf16 / fp16), pinv_t fp32 [n_mels, K] -> fp32 [..., K]."""
+    if not x.is_contiguous() or pinv_t.dtype != torch.float32 or pinv_t.dim() != 2 or pinv_t.shape[0] != x.shape[-1] or not pinv_t.is_contiguous():
+        raise OfaError(f"griffin_lim_specgram: x {tuple(x.shape)} must be contiguous rows of n_mels and pinv_t a contiguous fp32 [n_mels, K]")
+    n_mels, K = pinv_t.shape
+    S = torch.empty(*x.shape[:-1], K, dtype=torch.float32, device=x.device)
+    lib().call("ofa_griffin_lim_specgram", ptr(x), ptr(pinv_t), ptr(S), x.numel() // n_mels, n_mels, K, dtype_code(x), stream())
+    return S
+
+
 # ---------------------------------------------------------------------------------------------- the VQGAN image decoder (csrc/vqgan.hip)
 def vqgan_conv_plan(Cin, Cout, upsample=False):
     """(tile side in pixels, Cin slice, output channels per workgroup, LDS bytes) of ofa_vqgan_conv3x3 for this shape (host only)."""

@@ -9,7 +9,7 @@ Generation: `Task.generator` / `Task.inference` run beam search (ofasys_amd/gene
 AUDIO targets, and the diffusion sampler (DiffusionGenerator) for MOTION targets.
 Validation: `Task.valid_batches` walks a split once, in order; `Trainer.validate` (engine.py) runs it through the step engine's
 forward-only `valid_step` -- loss, NLL and, with `cfg.criterion.report_accuracy`, token accuracy (task/base.py:680-703).
-What stays out: file / OSS readers, multi-worker prefetch, generation metrics, the image generator, the BVH conversion of generated motion, the Griffin-Lim vocoder, checkpoint state.  The
+What stays out: file / OSS readers, multi-worker prefetch, generation metrics, the image generator, the BVH conversion of generated motion, checkpoint state.  The
 batch iterator is a plain in-process loop over the bound dataset: micro-batches of `micro_batch_size` rows, each rank of a
 data-parallel job reading its own contiguous shard (io/reader/dataset.py:49-53), reshuffled per epoch with a seeded permutation.
 """
@@ -344,7 +344,10 @@ class Task:
         reference's default is a URL, which nothing here fetches).  `vocoder_config` (a local HiFi-GAN JSON configuration, or such a
         dict) with `vocoder_checkpoint` (a local checkpoint holding "generator") and `vocoder_dtype` ("float16", the default, or
         "bfloat16") -- as arguments or in cfg.evaluation.generator_args -- give the generator a HiFiGANVocoder: every output then
-        carries its `waveform`.  Without them nothing changes."""
+        carries its `waveform`.  `vocoder="griffin_lim"` gives it a GriffinLimVocoder instead, which needs no checkpoint: `vocoder_features`
+        (a dict with any of sample_rate, n_fft, win_length, hop_length, n_mels, f_min, f_max, window_fn; the defaults are the reference's
+        AudioPreprocessConfig: 22050, 1024, 1024, 256, 80, 0, 8000, "hann") and `spec_bwd_max_iter` (default 8, as there).  Without
+        those arguments nothing changes."""
         from .generator import AutoRegressiveSpeechGenerator
         if self.global_dict is None:
             raise ValueError(f"task {self.name}: initialize(global_dict) before building a generator")
@@ -353,7 +356,20 @@ class Task:
         extra = {k: gen_kwargs.pop(k) for k in ("use_graph", "fused_step", "graph_cap") if k in gen_kwargs}
         voc_cfg, voc_ckpt = gen_kwargs.pop("vocoder_config", None), gen_kwargs.pop("vocoder_checkpoint", None)
         voc_dtype = gen_kwargs.pop("vocoder_dtype", "float16")
-        if voc_cfg is not None:
+        voc_kind, voc_feat = gen_kwargs.pop("vocoder", None), gen_kwargs.pop("vocoder_features", None)
+        gl_iter = gen_kwargs.pop("spec_bwd_max_iter", 8)
+        if voc_kind == "griffin_lim":
+            from .module.vocoder import GriffinLimVocoder
+            f = dict(sample_rate=22050, n_fft=1024, win_length=1024, hop_length=256, n_mels=80, f_min=0, f_max=8000, window_fn="hann")
+            unknown = set(voc_feat or {}) - set(f)
+            if unknown:
+                raise ValueError(f"task {self.name}: vocoder_features has unknown keys {sorted(unknown)}")
+            f.update(voc_feat or {})
+            extra["vocoder"] = GriffinLimVocoder(f["sample_rate"], f["win_length"], f["hop_length"], f["n_fft"], f["n_mels"], f["f_min"], f["f_max"],
+                                                 f["window_fn"], spec_bwd_max_iter=gl_iter)
+        elif voc_kind not in (None, "hifigan"):
+            raise ValueError(f"task {self.name}: unknown vocoder {voc_kind!r} (hifigan or griffin_lim)")
+        elif voc_cfg is not None:
             from .module.vocoder import HiFiGANVocoder
             extra["vocoder"] = HiFiGANVocoder(voc_ckpt, voc_cfg, dtype=voc_dtype)
         elif voc_ckpt is not None:
