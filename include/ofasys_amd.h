@@ -1227,6 +1227,35 @@ int ofa_griffin_lim_inverse(const float* phase, const float* S, const float* win
                             const int32_t* lens, float* w_out, int B, int T, int n_fft, int win, int hop, void* stream);
 int ofa_griffin_lim_specgram(const void* x, const float* pinv_t, float* S, int64_t rows, int n_mels, int n_freq, int dtype, void* stream);
 
+/* ---- log-mel feature extraction and utterance CMVN (preprocessor/default/audio.py:297-328, 485-565), csrc/audio_features.hip: fp32
+ * throughout, no atomics (equal inputs give equal bits; an utterance gives the same bits alone and inside a ragged batch).
+ * ofa_logmel_fwd: wav [B, Lmax] on the int16 scale (16-byte aligned) -> out [B, Tmax, n_mels] in ONE launch.  lens (int32 [B] on the device,
+ *   or NULL: every utterance has Lmax samples) gives utterance b its own length Lb = clamp(lens[b], 0, Lmax) and frame count; rows from that
+ *   count on are written as zeros.  N = n_fft (a power of two in 256..2048), M = N / 2, win <= N, 1 <= shift <= N, n_mels <= 128; anything
+ *   else: UNSUPPORTED before any launch.
+ *     kind 0 (kaldi: torchaudio.compliance.kaldi.fbank at its defaults, dither 0): T = 1 + (L - win) / shift, 0 if L < win; frame t is
+ *       samples [t shift, t shift + win): minus their mean, pre-emphasis x[n] - 0.97 x[n-1] with x[-1] := x[0], times window[n], zero-padded
+ *       to N; the spectrum is |X_k|^2; the floor 1.1920929e-07
+ *     kind 1 (tts: extract_logmel_spectrogram): T = 1 + L / shift; frame t is samples [t shift - M, t shift + M), the index reflected at 0
+ *       and Lb - 1 (the caller refuses Lb <= M; the kernel then clamps the index and stays in bounds), times 2^-15 window[n]; the spectrum is
+ *       |X_k|; the floor 1e-5
+ *   window    [N] (kind 0 reads its first `win` entries)
+ *   twiddle   [M][2]: (cos, -sin)(2 pi j / N), j < M, computed in float64 and rounded once
+ *   the filter bank, compressed: filter m weighs bins filt_start[m] + j by filt_w[filt_off[m] + j], j < filt_off[m + 1] - filt_off[m]
+ *   (filt_start [n_mels], filt_off [n_mels + 1], filt_w [n_weights]; bins beyond M and weights beyond n_weights are not read).  A filter's
+ *   bins are summed in ascending order in one fp32 fma chain: E; out = log(max(E, floor)), then (out - cmvn_mean[m]) / cmvn_std[m] where the
+ *   two tables ([n_mels]) are given.  Tmax may not exceed the frame count of Lmax samples.
+ * ofa_logmel_run (host only): the consecutive frames one workgroup owns, 0 when the configuration is not served.
+ * ofa_utterance_cmvn: UtteranceCMVN in place on x [B, Tmax, n_feat] (n_feat <= 256), one workgroup per utterance: over the T =
+ *   clamp(frames[b], 0, Tmax) rows of utterance b (frames int32 [B] on the device, or NULL: Tmax), mean = sum x / T, var = sum x^2 / T - mean^2
+ *   (both sums in double, in a fixed order), std = sqrt(max(var, 1e-10)); x <- (x - mean) / std, either half switched by its flag.  Rows from
+ *   T on and utterances of 0 frames are not touched. */
+int ofa_logmel_run(int kind, int n_fft, int win, int shift);             /* host only */
+int ofa_logmel_fwd(const float* wav, const int32_t* lens, const float* window, const float* twiddle, const int32_t* filt_start,
+                   const int32_t* filt_off, const float* filt_w, const float* cmvn_mean, const float* cmvn_std, float* out, int B, int Lmax,
+                   int Tmax, int n_mels, int n_weights, int kind, int n_fft, int win, int shift, void* stream);
+int ofa_utterance_cmvn(float* x, const int32_t* frames, int B, int Tmax, int n_feat, int norm_means, int norm_vars, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

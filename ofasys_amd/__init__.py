@@ -17,6 +17,7 @@ from .generator import (AutoRegressiveSpeechGenerator, DiffusionGenerator, Diver
                         MotionOutput, SpeechGenerator, SpeechGeneratorOutput)
 from .module.hifigan import Generator as HiFiGANGenerator  # noqa: E402,F401
 from .module.vocoder import GriffinLimVocoder, HiFiGANVocoder  # noqa: E402,F401
+from .module.audio_features import LogMelExtractor  # noqa: E402,F401
 from .module.vqgan import VQGANDecoderModel, VQGANTokenizer  # noqa: E402,F401
 from .scst import CiderD, ScstRewardCriterion  # noqa: E402,F401
 from .engine import Trainer, TrainerConfig  # noqa: E402,F401
@@ -26,4 +27,4 @@ __all__ = ["Task", "TaskConfig", "TraverseTask", "TraversePlan", "Trainer", "Tra
            "ConfigStore", "AdaptorOutput", "BaseAdaptor", "BaseAdaptorConfig", "OFAGeneralAdaptor", "Sampling", "CiderD",
            "ScstRewardCriterion", "DiverseBeamSearch", "DiverseSiblingsSearch", "SpeechGenerator", "AutoRegressiveSpeechGenerator",
            "SpeechGeneratorOutput", "DiffusionGenerator", "MotionOutput", "HiFiGANVocoder", "GriffinLimVocoder", "HiFiGANGenerator", "VQGANTokenizer",
-           "VQGANDecoderModel"]
+           "VQGANDecoderModel", "LogMelExtractor"]

@@ -2382,6 +2382,46 @@ def griffin_lim_specgram(x, pinv_t):
     return S
 
 
+# ---------------------------------------------------------------------------------------------- log-mel features (csrc/audio_features.hip)
+LOGMEL_KINDS = {"kaldi": 0, "tts": 1}
+
+
+def logmel_run(kind, n_fft, win, shift):
+    """Consecutive frames a workgroup of ofa_logmel_fwd owns; 0: the configuration is not served (host only).  kind: "kaldi" or "tts"."""
+    return int(lib().cdll.ofa_logmel_run(LOGMEL_KINDS.get(kind, -1), int(n_fft), int(win), int(shift)))
+
+
+def logmel(wav, lens, window, twiddle, filt_start, filt_off, filt_w, kind, win, shift, n_frames, mean=None, std=None):
+    """One launch of ofa_logmel_fwd.  wav fp32 [B, Lmax] on the int16 scale; lens int32 [B] on the device or None; window fp32 [n_fft];
+    twiddle [n_fft / 2, 2]; the compressed filter bank (int32 [n_mels], int32 [n_mels + 1], fp32 [n_weights]); mean / std fp32 [n_mels]
+    or None.  -> fp32 [B, n_frames, n_mels], rows past an utterance's own frame count zero."""
+    n_fft, n_mels = window.numel(), filt_start.numel()
+    for what, t, dtype, shape in (("wav", wav, torch.float32, None), ("window", window, torch.float32, (n_fft,)),
+                                  ("twiddle", twiddle, torch.float32, (n_fft // 2, 2)), ("filt_start", filt_start, torch.int32, (n_mels,)),
+                                  ("filt_off", filt_off, torch.int32, (n_mels + 1,)), ("filt_w", filt_w, torch.float32, None),
+                                  ("lens", lens, torch.int32, (wav.shape[0],) if wav.dim() == 2 else None),
+                                  ("mean", mean, torch.float32, (n_mels,)), ("std", std, torch.float32, (n_mels,))):
+        if t is not None and (t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape)):
+            raise OfaError(f"logmel: {what} must be a contiguous {dtype} {shape or ''}, got {t.dtype} {tuple(t.shape)}")
+    if wav.dim() != 2 or filt_w.dim() != 1 or (mean is None) != (std is None):
+        raise OfaError(f"logmel: wav {tuple(wav.shape)} must be [B, Lmax], filt_w 1-D, and mean and std come together")
+    B, Lmax = wav.shape
+    out = torch.empty(B, int(n_frames), n_mels, dtype=torch.float32, device=wav.device)
+    lib().call("ofa_logmel_fwd", ptr(wav), ptr(lens), ptr(window), ptr(twiddle), ptr(filt_start), ptr(filt_off), ptr(filt_w), ptr(mean), ptr(std),
+               ptr(out), B, Lmax, int(n_frames), n_mels, filt_w.numel(), LOGMEL_KINDS.get(kind, -1), n_fft, int(win), int(shift), stream())
+    return out
+
+
+def utterance_cmvn(x, frames=None, norm_means=True, norm_vars=True):
+    """One launch of ofa_utterance_cmvn, in place.  x fp32 [B, Tmax, F]; frames int32 [B] on the device or None (every utterance has Tmax)."""
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise OfaError(f"utterance_cmvn: x must be a contiguous fp32 [B, Tmax, F], got {x.dtype} {tuple(x.shape)}")
+    if frames is not None and (frames.dtype != torch.int32 or frames.numel() != x.shape[0] or not frames.is_contiguous()):
+        raise OfaError("utterance_cmvn: frames must be a contiguous int32 [B] on the device")
+    lib().call("ofa_utterance_cmvn", ptr(x), ptr(frames), x.shape[0], x.shape[1], x.shape[2], int(bool(norm_means)), int(bool(norm_vars)), stream())
+    return x
+
+
 # ---------------------------------------------------------------------------------------------- the VQGAN image decoder (csrc/vqgan.hip)
 def vqgan_conv_plan(Cin, Cout, upsample=False):
     """(tile side in pixels, Cin slice, output channels per workgroup, LDS bytes) of ofa_vqgan_conv3x3 for this shape (host only)."""

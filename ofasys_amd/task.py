@@ -23,7 +23,7 @@ import torch
 
 from .preprocessor.collate import (BoxPreprocessConfig, DefaultBoxPreprocess, DefaultTextPreprocess, GeneralPreprocess,
                                    PreprocessConfig, TensorPreprocess, TextPreprocessConfig, default_preprocess)
-from .preprocessor.audio import FbankPreprocess
+from .preprocessor.audio import AudioPreprocessConfig, FbankPreprocess
 from .preprocessor.motion import Motion6dPreprocess
 from .preprocessor.instruction import Instruction, ModalityType, Slot
 
@@ -100,6 +100,7 @@ class TaskConfig:                                     # task/base.py:157-189
     text: TextPreprocessConfig = field(default_factory=TextPreprocessConfig)
     box: BoxPreprocessConfig = field(default_factory=BoxPreprocessConfig)
     image: ImagePreprocessConfig = field(default_factory=ImagePreprocessConfig)
+    audio: AudioPreprocessConfig = field(default_factory=AudioPreprocessConfig)
     max_src_length: int = 128
     max_tgt_length: int = 30
     constraint_range: Optional[str] = None
@@ -226,8 +227,9 @@ class Task:
         name2pre = {"text": DefaultTextPreprocess(global_dict, self.cfg.text), "box": DefaultBoxPreprocess(global_dict, self.cfg.box)}
         for name, mod in (("image", ModalityType.IMAGE), ("video", ModalityType.VIDEO)):
             name2pre[name] = ImageTensorPreprocess(global_dict, self.cfg.image, mod)
-        # (source-side and plain tensor values as TensorPreprocess; a target-side fbank slot collates as a text-to-speech target)
-        name2pre["audio"] = FbankPreprocess(global_dict, PreprocessConfig(), ModalityType.AUDIO)
+        # (plain tensor values as TensorPreprocess; a target-side fbank slot collates as a text-to-speech target; {"wav"} values become frames
+        # on the device as cfg.audio says)
+        name2pre["audio"] = FbankPreprocess(global_dict, self.cfg.audio, ModalityType.AUDIO)
         name2pre["table"] = name2pre["phone"] = name2pre["text"]     # STRUCT / PHONE columns arrive as token ids (text adaptor)
         name2pre["motion_6d"] = Motion6dPreprocess(global_dict)      # rot6d frames: a slot selects it with preprocess=motion_6d
         self.general_preprocess = GeneralPreprocess(global_dict, name2pre)
