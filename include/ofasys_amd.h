@@ -1256,6 +1256,32 @@ int ofa_logmel_fwd(const float* wav, const int32_t* lens, const float* window, c
                    int Tmax, int n_mels, int n_weights, int kind, int n_fft, int win, int shift, void* stream);
 int ofa_utterance_cmvn(float* x, const int32_t* frames, int B, int Tmax, int n_feat, int norm_means, int norm_vars, void* stream);
 
+/* ---- mel-cepstral distortion after dynamic time warping (task/text_to_speech.py:101-295), csrc/dtw.hip: fp32 only (`dtype` other than
+ * OFA_F32: UNSUPPORTED), no atomics, nothing is read on the host.
+ * ofa_dtw: the whole DP of a ragged batch in ONE launch, one workgroup per pair.  shapes (int32 [B, 2] on the device) gives pair b its
+ *   (M_b, N_b), clamped to (maxM, maxN).  cum[0][j] and cum[i][0] are running fp32 sums in index order; elsewhere cum[i][j] = d[i][j] +
+ *   min(cum[i][j-1], cum[i-1][j-1], cum[i-1][j]) with back pointer 0 = left, 1 = up-left, 2 = up, the lowest code on a tie; bp[0][j > 0] = 0,
+ *   bp[i][0] = 2.  The length of the chosen path is carried along: total[b] = cum[M_b-1][N_b-1], pathlen[b] = the number of cells on the path
+ *   (both 0 for an empty pair).  cumdist (fp32) and backptr (one byte a cell), both [B, maxM, maxN], are optional (NULL: not written); cells
+ *   outside [:M_b, :N_b] are left UNWRITTEN.
+ *     distance form (distance != NULL, x1 = x2 = NULL): d is read from distance [B, maxM, maxN]; maxM, maxN <= 4096.
+ *     features form (distance NULL): d is computed from x1 [B, maxM, ld] and x2 [B, maxN, ld], D <= 16 features a row (ld >= D floats between
+ *       rows): metric 0 (l2) sum_k (a_k - b_k)^2 in index order, metric 1 (rms) sqrtf(l2 / D); maxM, maxN <= 2048 (x1 stays in LDS).
+ *   strip: the columns a lane owns, 4, 8 or (distance form) 16, or 0: chosen here (ofa_dtw_strip: the smallest with 256 strips covering maxN).
+ * ofa_dtw_backtrace: backptr [B, maxM, maxN] + shapes -> path (int32 [B, maxM + maxN - 1, 2]: the (i, j) of the path from (0, 0) to
+ *   (M_b - 1, N_b - 1), front-aligned; entries past the count are not written) and count (int32 [B]).  One wave per pair; maxM, maxN <= 4096.
+ *   Pointers are clamped so that the walk stays inside the matrix whatever the bytes hold.
+ * ofa_mfcc_rows: power [rows, n_bins] (|X|^2) -> out [rows, 16]: columns < n_mfcc are sum_n dct[k][n] log(mel_n + 1e-6), the rest zeros.
+ *   The mel filter bank comes compressed as for ofa_logmel_fwd (a filter's bins summed in ascending order in one fp32 fma chain); dct is
+ *   [n_mfcc, n_mels], summed as four interleaved fma chains (n mod 4) in n order, (0 + 1) + (2 + 3).  n_mfcc <= 16, n_mels <= 128,
+ *   n_bins <= 2049. */
+int ofa_dtw_strip(int features, int maxN, int strip);                    /* host only; 0: not served */
+int ofa_dtw(const float* distance, const float* x1, const float* x2, const int32_t* shapes, float* total, int32_t* pathlen, float* cumdist,
+            uint8_t* backptr, int B, int maxM, int maxN, int D, int ld, int metric, int strip, int dtype, void* stream);
+int ofa_dtw_backtrace(const uint8_t* backptr, const int32_t* shapes, int32_t* path, int32_t* count, int B, int maxM, int maxN, void* stream);
+int ofa_mfcc_rows(const float* power, const int32_t* filt_start, const int32_t* filt_off, const float* filt_w, const float* dct, float* out,
+                  int64_t rows, int n_bins, int n_mels, int n_weights, int n_mfcc, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,8 @@ from .generator import (AutoRegressiveSpeechGenerator, DiffusionGenerator, Diver
 from .module.hifigan import Generator as HiFiGANGenerator  # noqa: E402,F401
 from .module.vocoder import GriffinLimVocoder, HiFiGANVocoder  # noqa: E402,F401
 from .module.audio_features import LogMelExtractor  # noqa: E402,F401
+from .mcd import (MFCC, batch_dtw_features, batch_dynamic_time_warping,  # noqa: E402,F401
+                  batch_mel_cepstral_distortion)
 from .module.vqgan import VQGANDecoderModel, VQGANTokenizer  # noqa: E402,F401
 from .scst import CiderD, ScstRewardCriterion  # noqa: E402,F401
 from .engine import Trainer, TrainerConfig  # noqa: E402,F401
@@ -27,4 +29,5 @@ __all__ = ["Task", "TaskConfig", "TraverseTask", "TraversePlan", "Trainer", "Tra
            "ConfigStore", "AdaptorOutput", "BaseAdaptor", "BaseAdaptorConfig", "OFAGeneralAdaptor", "Sampling", "CiderD",
            "ScstRewardCriterion", "DiverseBeamSearch", "DiverseSiblingsSearch", "SpeechGenerator", "AutoRegressiveSpeechGenerator",
            "SpeechGeneratorOutput", "DiffusionGenerator", "MotionOutput", "HiFiGANVocoder", "GriffinLimVocoder", "HiFiGANGenerator", "VQGANTokenizer",
-           "VQGANDecoderModel", "LogMelExtractor"]
+           "VQGANDecoderModel", "LogMelExtractor", "MFCC", "batch_dtw_features",
+           "batch_dynamic_time_warping", "batch_mel_cepstral_distortion"]

@@ -2422,6 +2422,96 @@ def utterance_cmvn(x, frames=None, norm_means=True, norm_vars=True):
     return x
 
 
+# ---------------------------------------------------------------------------------------------- MCD evaluation: DTW and MFCC rows (csrc/dtw.hip)
+DTW_METRICS = {"l2": 0, "rms": 1}
+DTW_FEATURES_MAX, DTW_DISTANCE_MAX, DTW_MAX_D = 2048, 4096, 16
+
+
+def dtw_strip(features, maxN, strip=0):
+    """The columns a lane of ofa_dtw owns for this width (host only); 0: not served."""
+    return int(lib().cdll.ofa_dtw_strip(int(bool(features)), int(maxN), int(strip)))
+
+
+def _dtw_shapes(who, shapes, B):
+    if shapes.dtype != torch.int32 or tuple(shapes.shape) != (B, 2) or not shapes.is_contiguous():
+        raise OfaError(f"{who}: shapes must be a contiguous int32 [B={B}, 2] on the device, got {shapes.dtype} {tuple(shapes.shape)}")
+
+
+def dtw(shapes, distance=None, x1=None, x2=None, D=None, metric="rms", want_cumdist=False, want_backptr=False, strip=0):
+    """One launch of ofa_dtw.  shapes int32 [B, 2] on the device.  Either distance fp32 [B, maxM, maxN], or x1 fp32 [B, maxM, ld] and x2
+    [B, maxN, ld] of which the first D columns (default: all ld) are the features.  -> (total fp32 [B], pathlen int32 [B], cumdist fp32
+    [B, maxM, maxN] or None, backptr uint8 [B, maxM, maxN] or None); cells outside a pair's own [:M_b, :N_b] are not written."""
+    feat = distance is None
+    ops_ = (x1, x2) if feat else (distance,)
+    if any(t is None or t.dim() != 3 or not t.is_contiguous() for t in ops_) or (not feat and (x1 is not None or x2 is not None)):
+        raise OfaError("dtw: give either a contiguous distance [B, maxM, maxN] or contiguous x1 [B, maxM, ld] and x2 [B, maxN, ld]")
+    first = ops_[0]
+    B, maxM = first.shape[0], first.shape[1]
+    code = dtype_code(first)
+    if any(t.dtype != first.dtype for t in ops_) or code != F32:
+        raise OfaError(f"dtw: fp32 only, got {[str(t.dtype) for t in ops_]}")
+    if feat:
+        maxN, ld = x2.shape[1], x1.shape[2]
+        D = ld if D is None else int(D)
+        if x2.shape[0] != B or x2.shape[2] != ld or not 1 <= D <= ld:
+            raise OfaError(f"dtw: x1 {tuple(x1.shape)} and x2 {tuple(x2.shape)} must share the batch and the row pitch, with 1 <= D={D} <= {ld}")
+        if D > DTW_MAX_D:
+            raise OfaError(f"dtw: D={D} features a row exceed the {DTW_MAX_D} the features form serves")
+        if metric not in DTW_METRICS:
+            raise OfaError(f"dtw: metric {metric!r} must be one of {sorted(DTW_METRICS)}")
+        if maxM > DTW_FEATURES_MAX or maxN > DTW_FEATURES_MAX:
+            raise OfaError(f"dtw: the features form serves M, N <= {DTW_FEATURES_MAX}, got maxM={maxM} maxN={maxN}")
+    else:
+        maxN, ld, D = distance.shape[2], 0, 0
+        if maxM > DTW_DISTANCE_MAX or maxN > DTW_DISTANCE_MAX:
+            raise OfaError(f"dtw: the distance form serves M, N <= {DTW_DISTANCE_MAX}, got maxM={maxM} maxN={maxN}")
+    _dtw_shapes("dtw", shapes, B)
+    dev = first.device
+    total = torch.empty(B, dtype=torch.float32, device=dev)
+    pathlen = torch.empty(B, dtype=torch.int32, device=dev)
+    cum = torch.empty(B, maxM, maxN, dtype=torch.float32, device=dev) if want_cumdist else None
+    bp = torch.empty(B, maxM, maxN, dtype=torch.uint8, device=dev) if want_backptr else None
+    lib().call("ofa_dtw", ptr(distance), ptr(x1), ptr(x2), ptr(shapes), ptr(total), ptr(pathlen), ptr(cum), ptr(bp), B, maxM, maxN, D, ld,
+               DTW_METRICS.get(metric, 0), int(strip), code, stream())
+    return total, pathlen, cum, bp
+
+
+def dtw_backtrace(backptr, shapes):
+    """One launch of ofa_dtw_backtrace.  backptr uint8 [B, maxM, maxN], shapes int32 [B, 2] -> (path int32 [B, maxM + maxN - 1, 2] from
+    (0, 0) to (M_b - 1, N_b - 1), front-aligned and zero behind the count; count int32 [B])."""
+    if backptr.dim() != 3 or backptr.dtype != torch.uint8 or not backptr.is_contiguous():
+        raise OfaError(f"dtw_backtrace: backptr must be a contiguous uint8 [B, maxM, maxN], got {backptr.dtype} {tuple(backptr.shape)}")
+    B, maxM, maxN = backptr.shape
+    if maxM > DTW_DISTANCE_MAX or maxN > DTW_DISTANCE_MAX:
+        raise OfaError(f"dtw_backtrace: serves M, N <= {DTW_DISTANCE_MAX}, got maxM={maxM} maxN={maxN}")
+    _dtw_shapes("dtw_backtrace", shapes, B)
+    path = torch.zeros(B, max(maxM + maxN - 1, 0), 2, dtype=torch.int32, device=backptr.device)
+    count = torch.zeros(B, dtype=torch.int32, device=backptr.device)
+    lib().call("ofa_dtw_backtrace", ptr(backptr), ptr(shapes), ptr(path), ptr(count), B, maxM, maxN, stream())
+    return path, count
+
+
+def mfcc_rows(power, filt_start, filt_off, filt_w, dct):
+    """One launch of ofa_mfcc_rows.  power fp32 [..., n_bins] (|X|^2); the compressed mel filter bank (int32 [n_mels], int32 [n_mels + 1],
+    fp32 [n_weights]); dct fp32 [n_mfcc, n_mels].  -> fp32 [..., 16]: the n_mfcc coefficients, then zeros."""
+    code = dtype_code(power)
+    if code != F32:
+        raise OfaError(f"mfcc_rows: fp32 only, got {power.dtype}")
+    n_mels = filt_start.numel()
+    for what, t, dtype, shape in (("power", power, torch.float32, None), ("filt_start", filt_start, torch.int32, (n_mels,)),
+                                  ("filt_off", filt_off, torch.int32, (n_mels + 1,)), ("filt_w", filt_w, torch.float32, None),
+                                  ("dct", dct, torch.float32, (dct.shape[0], n_mels))):
+        if t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+            raise OfaError(f"mfcc_rows: {what} must be a contiguous {dtype} {shape or ''}, got {t.dtype} {tuple(t.shape)}")
+    if power.dim() < 1 or filt_w.dim() != 1:
+        raise OfaError(f"mfcc_rows: power {tuple(power.shape)} must be [..., n_bins] and filt_w 1-D")
+    n_bins = power.shape[-1]
+    out = torch.empty(*power.shape[:-1], 16, dtype=torch.float32, device=power.device)
+    lib().call("ofa_mfcc_rows", ptr(power), ptr(filt_start), ptr(filt_off), ptr(filt_w), ptr(dct), ptr(out), power.numel() // max(n_bins, 1), n_bins,
+               n_mels, filt_w.numel(), dct.shape[0], code, stream())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- the VQGAN image decoder (csrc/vqgan.hip)
 def vqgan_conv_plan(Cin, Cout, upsample=False):
     """(tile side in pixels, Cin slice, output channels per workgroup, LDS bytes) of ofa_vqgan_conv3x3 for this shape (host only)."""

@@ -502,6 +502,29 @@ class Task:
                     hyp.text = pre.decode(hyp.tokens)
         return outputs
 
+    def valid_step_with_inference(self, model, sample, sample_rate: Optional[int] = None):
+        """The reference's TTS validation figures (task/text_to_speech.py:101-125): generate with the target present, vocode both, and
+        sum over the batch the mel-cepstral distortion after DTW between target and generated waveform (`mcd.batch_mel_cepstral_distortion`,
+        normalize_type=None).  -> (hypos, losses) with the reference's keys: mcd_loss, targ_frames, pred_frames (MFCC frames), nins, ndel.
+        sample_rate: of the vocoder's waveforms; default cfg.audio.target_sr."""
+        from .mcd import batch_mel_cepstral_distortion
+        if self.target_modality != ModalityType.AUDIO:
+            raise ValueError(f"task {self.name}: valid_step_with_inference scores speech; the target is {self.target_modality}")
+        if getattr(self.generator, "vocoder", None) is None:
+            raise ValueError(f"task {self.name}: valid_step_with_inference compares waveforms, and the speech generator has no vocoder "
+                             "(build_speech_generator: vocoder=\"griffin_lim\", or vocoder_config with vocoder_checkpoint)")
+        hypos = self.inference(model, sample, has_targ=True)
+        sr = int(sample_rate if sample_rate is not None else self.cfg.audio.target_sr)
+        rets = batch_mel_cepstral_distortion([h.targ_waveform for h in hypos], [h.waveform for h in hypos], sr, normalize_type=None)
+        losses = {"mcd_loss": 0.0, "targ_frames": 0.0, "pred_frames": 0.0, "nins": 0.0, "ndel": 0.0}
+        for d, (pathlen, m, n) in rets:
+            losses["mcd_loss"] += d
+            losses["targ_frames"] += m
+            losses["pred_frames"] += n
+            losses["nins"] += pathlen - m
+            losses["ndel"] += pathlen - n
+        return hypos, losses
+
 
 def collect_adaptor_name_from_tasks(tasks) -> Set[str]:
     names = set()
